@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: concurrent 48 kS/s DMR channels sustained end-to-end on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (one kernel: every channel's wavefront filters + slices its samples
@@ -11,23 +11,31 @@ configs[2], 16 384 DMR channels x 3.96 s of 48 kS/s audio per GPU, full chain in
 State (filter history, timing recovery, decoder phase) carries from step to step exactly as in a
 continuous stream; the input buffer is periodic so the stream is seamless.
 
-One process per GPU.  Started as plain `python bench.py --gpus N` with N > 1 it re-executes itself under
-`torch.distributed.run` with N ranks (and refuses when the box has fewer GPUs); a line whose n_gpus differs from
+One process per GPU.  Started as plain `python bench.py --gpus N` with N > 1 it runs itself under
+`torch.distributed.run` with N ranks as a child process (and refuses when the box has fewer GPUs); a line whose n_gpus differs from
 --gpus is never printed.  Channels shard by index, no collective on the data path: RCCL only carries the barrier
 and the MAX / SUM of the report.  `--scaling weak` (default): --channels per GPU; `--scaling strong`:
 --total-channels split over the ranks (BASELINE configs[4]: --workload mixed --scaling strong --total-channels 65536).
 
-One JSON line on rank 0: value = whole-job real-time 48 kS/s channels = samples/s / 48 000, plus
-`roofline` for the dominant kernel (timed with HIP events on its own stream inside the timed region),
-`cpu_baseline` (the oracle's scalar restatement of the reference pipe on this box's host cores, bounded sample,
-rank 0 at N = 1 only) and `other_configs`: the other single-GPU BASELINE configs timed on the same lease
-(N = 1 only, after the headline's timed region; --no-other-configs skips them).
+One JSON line on rank 0: value = whole-job real-time 48 kS/s channels = samples/s / 48 000, ms_per_step = the
+wall time of one timed step.  A plain run does nothing else: set-up, W warm-up steps, K timed steps, the line.
+
+--dump-outputs DIR writes what the timed engines computed in their last step (a fixed sample of channels,
+dump_outputs) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds, after the timed region: `roofline` for the dominant kernel (timed with HIP events on its own stream
+inside the timed region, against a streaming ceiling timed on this GPU), `verified` (the timed engines' last push
+against the oracle, --verify channels), `cpu_baseline` (the oracle's scalar restatement of the reference pipe on this
+box's host cores, bounded sample, rank 0 at N = 1 only) and `other_configs`: the other single-GPU BASELINE configs
+timed on the same lease (N = 1 only; --no-other-configs skips them).  The full record also goes to bench_detail.json
+and a `BENCH_DETAIL ` stdout line in front of the compact last line.
 """
 import argparse
 import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -311,7 +319,7 @@ def reference_fec_baseline(torch, ctx, seconds=1.5):
 
 
 def respawn_under_torchrun(args):
-    """`python bench.py --gpus N` (N > 1) outside torchrun: become N ranks, or fail loudly."""
+    """`python bench.py --gpus N` (N > 1) outside torchrun: run N ranks as a child process and exit with its status, or fail loudly."""
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < args.gpus:
@@ -323,7 +331,7 @@ def respawn_under_torchrun(args):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))          # a fresh process: this one has already opened the GPU runtime to count devices
 
 
 class Job:
@@ -732,6 +740,55 @@ def other_configs(torch, ctx, device, steps, warmup, verify):
     return out
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_CHANNELS = 256            # channels per engine in the sample, fewer where their rows would not fit DUMP_BYTES
+DUMP_SEED = 20240917
+
+
+def dump_outputs(job, out_dir, rank=0, world=1):
+    """--dump-outputs DIR: what the timed engines computed in their last push, for a fixed, seeded sample of every engine's
+    channels, as DIR/<name>.npy (float32; float64 where float32 would not hold the value exactly).  Names: `channels` (the
+    sampled indices), `symbols` + `symbol_count` (dibits), `frames` + `frame_count` (decoder bytes), `events_sym_index` +
+    `events` (type, a, b, len, 24 payload bytes) + `event_count` (decoder events), `filtered` (the RRC output, where the
+    workload keeps it).  Rows are zero beyond their count.  Prefixed with the protocol where a step has two engines
+    (mixed), suffixed with the rank where there are several.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // (len(job.parts) * world)
+    written = []
+    for p in job.parts:
+        eng, B = p["eng"], p["B"]
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_CHANNELS), replace=False))
+        arrays = {"channels": pick.astype(np.float64)}
+
+        def prefix(rows, counts, dtype, tail=()):
+            out = np.zeros((len(pick), int(counts.max()) if len(counts) else 0) + tail, dtype)
+            for j, c in enumerate(counts):
+                out[j, :c] = rows[j, :c]
+            return out
+        if eng.has_demod:
+            s, sc = eng.read_rows("symbols", pick)
+            arrays["symbols"], arrays["symbol_count"] = prefix(s, sc, np.float32), sc.astype(np.float64)
+        if eng.has_proto:
+            f, fc = eng.read_rows("frames", pick)
+            arrays["frames"], arrays["frame_count"] = prefix(f, fc, np.float32), fc.astype(np.float64)
+            e, ec = eng.read_rows("events", pick)
+            fields = np.concatenate([np.stack([e["type"], e["a"], e["b"], e["len"]], axis=-1), e["payload"]], axis=-1)
+            arrays["events_sym_index"] = prefix(e["sym_index"], ec, np.float64)
+            arrays["events"] = prefix(fields, ec, np.float32, (fields.shape[-1],))
+            arrays["event_count"] = ec.astype(np.float64)
+        if eng.keep_filtered:
+            arrays["filtered"] = np.ascontiguousarray(eng.read_rows("filtered", pick)[0][:, :p["T"]])
+        row_bytes = sum(a.nbytes for a in arrays.values()) / float(len(pick))
+        keep = max(1, min(len(pick), int(budget // row_bytes)))
+        pre = p["proto"] + "_" if len(job.parts) > 1 else ""
+        suf = "_rank%d" % rank if world > 1 else ""
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, pre + name + suf + ".npy"), np.ascontiguousarray(a[:keep]))
+            written.append(pre + name + suf)
+    return written
+
+
 MAX_LINE_BYTES = 4096          # the driver keeps an 8 KB tail of stdout and parses its last line: round 5's 20.7 KB line was lost
 
 
@@ -774,7 +831,8 @@ def compact_line(line, detail_path=None):
         r["co_limit"] = {"binds": "instruction issue", "valu_issue_frac": co.get("valu_issue_frac"), "mfma_busy_frac": co.get("mfma_busy_frac"),
                          "issue": pick(issue, ("vector", "scalar", "lds", "mfma", "branch", "vmem_read", "vmem_write", "lds_bank_conflict_cycles",
                                                "lds_active_cycles", "simd_cycles_per_run", "shader_clock_ghz"))}
-    out["roofline"] = r
+    if roof:
+        out["roofline"] = r
     cb = line.get("cpu_baseline")
     if isinstance(cb, dict):
         out["cpu_baseline"] = pick(cb, ("value", "unit", "msamples_per_s", "cores", "kind", "gpu_matches_baseline_outputs", "error"))
@@ -836,11 +894,14 @@ def main():
     ap.add_argument("--total-channels", type=int, default=65536, help="channels of the whole job (strong scaling)")
     ap.add_argument("--units", type=int, default=0, help="bursts (DMR, 30 ms) or frames (YSF, 100 ms) per step; 0 = ~4 s")
     ap.add_argument("--streams", type=int, default=1, help="mixed: 2 = the two engines on their own HIP streams; dmr_iq_full: 2 = the front-end of the next step on its own stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without other_configs")
     ap.add_argument("--split-stages", action="store_true", help="slicer and decoder as two kernels (per-stage timing)")
     ap.add_argument("--overlap", action="store_true", help="DH_FLAG_OVERLAP_PUSHES: pushes as two launches on the engine's own streams, joined at the end")
-    ap.add_argument("--verify", type=int, default=64, help="channels checked bit-exact against the oracle after the run")
+    ap.add_argument("--verify", type=int, default=64, help="--full: channels checked bit-exact against the oracle after the run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed engines computed in their last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline, stage timings, the oracle check, the CPU baseline and the other BASELINE configs (off: the headline only)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -874,14 +935,17 @@ def main():
     dt = job.timed(args.steps, args.warmup, barrier=shard.barrier)
     samples = job.samples_per_step * args.steps
     dt_max, samples_all = shard.reduce_report(dt, samples, device)
-    roof, stage = job.roofline(args.split_stages, step_ms=dt / args.steps * 1e3)
+    if args.dump_outputs:
+        dump_outputs(job, args.dump_outputs, rank, world)
 
     verified = None
-    if args.verify:
-        ok, verified = job.verify_timed(args.verify, args.steps + args.warmup)
-        if ok is None and not (job.kw["proto"] == "none" and not job.kw.get("keep_filtered")):
-            ok, verified = job.verify(ctx, args.verify)          # front-end workloads: a replay on a fresh small engine
-        assert ok is not False, "GPU output differs from the oracle"
+    if args.full:
+        roof, stage = job.roofline(args.split_stages, step_ms=dt / args.steps * 1e3)
+        if args.verify:
+            ok, verified = job.verify_timed(args.verify, args.steps + args.warmup)
+            if ok is None and not (job.kw["proto"] == "none" and not job.kw.get("keep_filtered")):
+                ok, verified = job.verify(ctx, args.verify)          # front-end workloads: a replay on a fresh small engine
+            assert ok is not False, "GPU output differs from the oracle"
 
     if rank == 0:
         rate = samples_all / dt_max
@@ -908,9 +972,12 @@ def main():
                        # the rows from this percentage on (engine.hip: go_chain / k_chain); "0" = one workgroup per channel
                        "tail_split_pct": os.environ.get("DH_TAIL_SPLIT", "80")},
             "msamples_per_s": rate / 1e6,
+        }
+    if rank == 0 and args.full:
+        line.update({
             "frac_step": job.step_algorithmic_bytes() * args.steps / dt / 1e9 / HBM_PEAK_GBS,      # this rank's whole step over its own period
             "roofline": roof, "stage_ms": stage, "verified": verified,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             x0 = job.parts[0]["x"]
 
@@ -939,7 +1006,7 @@ def main():
     del job
     if rank == 0:
         default_headline = args.workload == "dmr_full" and args.scaling == "weak" and args.channels == 16384
-        if world == 1 and default_headline and not args.no_other_configs:
+        if args.full and world == 1 and default_headline and not args.no_other_configs:
             torch.cuda.empty_cache()
             try:
                 line["other_configs"] = other_configs(torch, ctx, device, min(args.steps, 10), min(args.warmup, 2), args.verify)
@@ -957,6 +1024,9 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
+        if not args.full:
+            print(compact_line(line), flush=True)                   # the headline alone
+            return
         detail = None
         for cand in (os.environ.get("DH_BENCH_DETAIL"), os.path.join(ROOT, "bench_detail.json")):
             if not cand:
@@ -970,7 +1040,6 @@ def main():
                 continue
         print("BENCH_DETAIL " + json.dumps(line), flush=True)          # the full record (sources, notes, per-workload detail): NOT the line the driver parses
         print(compact_line(line, detail), flush=True)                  # the last line of stdout, after RCCL's own chatter: <= 4 KB
-
 
 if __name__ == "__main__":
     main()

@@ -83,3 +83,51 @@ def rel_err(a, ref):
     ref = ref.astype(np.float64)
     rms = np.sqrt(np.mean(ref ** 2)) + 1e-30
     return np.abs(a.astype(np.float64) - ref) / np.maximum(np.abs(ref), rms)
+
+
+def fec_digests(O, which):
+    """The FEC comparison of tests/test_oracle.py on fixed random inputs, one SHA-256 per part, for `which` = "oracle" or
+    "ref" (oracle/_ref).  Outputs count only where the decoder says ok.  tests/golden/ref_compare_hashes.json holds the
+    reference's digests (tests/golden/make_golden_ref_compare.py)."""
+    rng = np.random.default_rng(7)
+    out = {}
+    for code, bits in CODES:
+        w = rng.integers(0, 1 << bits, 50000)
+        cw, ok = O.block_decode(code, w, which)
+        out[code] = sha(np.asarray(cw, np.uint32), np.asarray(ok, np.uint8))
+    p = rng.integers(0, 256, (4000, 25), dtype=np.uint8)
+    o, k = O.bptc_196_96(p, which)
+    out["bptc_196_96"] = sha(np.asarray(k, np.uint8), o[k == 1])
+    for nd, nb in ((100, 25), (180, 45)):
+        x = rng.integers(0, 256, (500, nb), dtype=np.uint8)
+        o, m = O.trellis(x, nd, which)
+        out["trellis_%d" % nd] = sha(o, m)
+    return out
+
+
+def nxdn_digests(O, which):
+    """The NXDN element comparison of tests/test_nxdn.py (scrambler, LICH, SACCH, FACCH1 on 300 random dibit blocks),
+    one SHA-256 per element, for `which` = "oracle" or "ref"; decoded data count only where the CRC passed."""
+    import hashlib
+    rng = np.random.default_rng(7)
+    h = {k: hashlib.sha256() for k in ("scramble", "lich", "sacch", "facch1")}
+    for _ in range(300):
+        d = rng.integers(0, 4, 182).astype(np.uint8)
+        h["scramble"].update(np.ascontiguousarray(O.nxdn_scramble(d, which), np.uint8).tobytes())
+        h["lich"].update(repr(O.nxdn_lich(d[:8], which)).encode())
+        for name, n in (("sacch", 30), ("facch1", 72)):
+            ok, data = getattr(O, "nxdn_" + name)(d[:n], which)
+            h[name].update(bytes([bool(ok)]) + (np.ascontiguousarray(data, np.uint8).tobytes() if ok else b""))
+    return {k: v.hexdigest() for k, v in h.items()}
+
+
+def npz_digest(path):
+    """SHA-256 over every array of an .npz (names, dtypes, shapes and bytes, in name order)."""
+    import hashlib
+    h = hashlib.sha256()
+    with np.load(path) as z:
+        for name in sorted(z.files):
+            a = np.ascontiguousarray(z[name])
+            h.update(("%s %s %s" % (name, a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+    return h.hexdigest()

@@ -110,3 +110,59 @@ def test_final_line_stays_bounded_whatever_the_record_holds():
     full = _full_record()
     full["other_configs"] = {"error": "RuntimeError('x')"}
     assert json.loads(bench.compact_line(full))["other_configs"] == {"error": "RuntimeError('x')"}
+
+
+class _RowsEngine:
+    """Stands in for api.Engine in bench.dump_outputs: row b of every output holds values derived from b."""
+    has_demod = has_proto = keep_filtered = True
+
+    def __init__(self, B, T):
+        self.B, self.T = B, T
+
+    def read_rows(self, what, channels):
+        import numpy as np
+        from digiham_amd import api
+        ch = np.asarray(channels, np.int64)
+        if what == "filtered":
+            return (ch[:, None] + np.arange(self.T + 8)[None, :] * 0.5).astype(np.float32), None
+        counts = (ch % 7 + 1).astype(np.uint32)
+        if what == "events":
+            rows = np.zeros((len(ch), 9), api.EVENT_DTYPE)
+            rows["sym_index"] = ch[:, None] * 100000 + np.arange(9)
+            rows["type"], rows["payload"] = 3, (ch % 251)[:, None, None]
+            return rows, counts
+        return ((ch[:, None] + np.arange(9)[None, :]) % 4 if what == "symbols" else (ch[:, None] * 3) % 256).astype(np.uint8), counts
+
+
+class _RowsJob:
+    def __init__(self, parts):
+        self.parts = [{"proto": p, "eng": _RowsEngine(B, T), "B": B, "T": T} for p, B, T in parts]
+
+
+def test_dump_outputs_sample_is_fixed_bounded_and_exact(tmp_path, monkeypatch):
+    """--dump-outputs: the same seeded channels every time, float32 / float64 arrays only, rows zero beyond their count,
+    and never more than DUMP_BYTES in all -- a sample too large for the budget is cut to fewer channels."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    names = bench.dump_outputs(_RowsJob([("dmr", 16384, 1000), ("ysf", 100, 2000)]), str(tmp_path / "a"))
+    assert len(names) == len(set(names)) and all(n.startswith(("dmr_", "ysf_")) for n in names)
+    bench.dump_outputs(_RowsJob([("dmr", 16384, 1000), ("ysf", 100, 2000)]), str(tmp_path / "b"))
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy")))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and (a == b).all()
+        total += a.nbytes
+    assert total <= 1 << 20
+    d = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    ch = d["dmr_channels"].astype(np.int64)
+    assert 0 < len(ch) < bench.DUMP_CHANNELS and (np.diff(ch) > 0).all() and ch.max() < 16384      # cut to fit the budget
+    k = len(d["ysf_channels"])           # (a batch under DUMP_CHANNELS is sampled whole, then cut to the budget)
+    assert 0 < k < 100 and (d["ysf_channels"] == np.arange(k)).all() and d["ysf_filtered"].shape == (k, 2000)
+    for j, c in enumerate(ch):
+        n = c % 7 + 1
+        assert d["dmr_symbol_count"][j] == n and (d["dmr_symbols"][j, :n] == (c + np.arange(n)) % 4).all() and not d["dmr_symbols"][j, n:].any()
+        assert (d["dmr_events_sym_index"][j, :n] == c * 100000 + np.arange(n)).all() and not d["dmr_events_sym_index"][j, n:].any()
+        assert (d["dmr_events"][j, :n, 0] == 3).all() and (d["dmr_events"][j, :n, 4:] == c % 251).all()
+        assert d["dmr_filtered"].shape[1] == 1000 and d["dmr_filtered"][j, 2] == np.float32(c + 1.0)

@@ -5,13 +5,14 @@
   patterns of the NXDN "Common Air Interface Test" document quoted at nxdn_phase.cpp:73-98;
 * the engine (CPU wave emulation / MI355X) against the oracle: decoder on dibits, and the whole chain on audio.
 """
+import json
 import os
 
 import numpy as np
 import pytest
 
 from digiham_amd import api, synth, _taps
-from common import assert_matches_oracle, run_engine
+from common import assert_matches_oracle, nxdn_digests, run_engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,17 +40,12 @@ def test_oracle_frame_elements_match_the_reference_vectors(oracle, nx):
 
 
 def test_oracle_vs_compiled_reference_when_present(oracle):
-    if oracle.ref_nxdn() is None:
-        pytest.skip("oracle/_ref/libdigiham_ref_nxdn.so not built (no /root/reference)")
-    rng = np.random.default_rng(7)
-    for _ in range(300):
-        d = rng.integers(0, 4, 182).astype(np.uint8)
-        assert (oracle.nxdn_scramble(d) == oracle.nxdn_scramble(d, "ref")).all()
-        assert oracle.nxdn_lich(d[:8]) == oracle.nxdn_lich(d[:8], "ref")
-        a, b = oracle.nxdn_sacch(d[:30]), oracle.nxdn_sacch(d[:30], "ref")
-        assert a[0] == b[0] and (not a[0] or (a[1] == b[1]).all())
-        a, b = oracle.nxdn_facch1(d[:72]), oracle.nxdn_facch1(d[:72], "ref")
-        assert a[0] == b[0] and (not a[0] or (a[1] == b[1]).all())
+    """Scrambler, LICH, SACCH and FACCH1 of the oracle against the reference's classes on 300 random blocks: against the
+    reference's outputs stored as digests (tests/golden/ref_compare_hashes.json), and against oracle/_ref live where it is built."""
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_compare_hashes.json")))["nxdn"]
+    assert nxdn_digests(oracle, "oracle") == want
+    if oracle.ref_nxdn() is not None:
+        assert nxdn_digests(oracle, "ref") == want
 
 
 def test_cai_test_patterns_form_a_vcall_superframe(oracle, nx):

@@ -1,8 +1,11 @@
 """CPU tier: the oracle against the reference's own FEC code and the committed golden vectors."""
+import json
+import os
+
 import numpy as np
 import pytest
 
-from common import CODES, sha
+from common import CODES, fec_digests, sha
 
 
 def test_oracle_fec_matches_golden_hashes(oracle, golden):
@@ -39,24 +42,12 @@ def test_oracle_fec_matches_golden_vectors(oracle, golden):
 
 
 def test_oracle_fec_vs_compiled_reference(oracle):
-    """Direct comparison with oracle/_ref (the reference's C sources compiled in place), when present."""
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    rng = np.random.default_rng(7)
-    for code, bits in CODES:
-        w = rng.integers(0, 1 << bits, 50000)
-        a, ao = oracle.block_decode(code, w)
-        b, bo = oracle.block_decode(code, w, "ref")
-        assert (a == b).all() and (ao == bo).all(), code
-    p = rng.integers(0, 256, (4000, 25), dtype=np.uint8)
-    o1, k1 = oracle.bptc_196_96(p)
-    o2, k2 = oracle.bptc_196_96(p, "ref")
-    assert (k1 == k2).all() and (o1[k1 == 1] == o2[k2 == 1]).all()
-    for nd, nb in ((100, 25), (180, 45)):
-        x = rng.integers(0, 256, (500, nb), dtype=np.uint8)
-        o1, m1 = oracle.trellis(x, nd)
-        o2, m2 = oracle.trellis(x, nd, "ref")
-        assert (o1 == o2).all() and (m1 == m2).all()
+    """The oracle against the reference's C sources compiled in place (oracle/_ref) on the same random blocks: against the
+    reference's outputs stored as digests (tests/golden/ref_compare_hashes.json), and against oracle/_ref live where it is built."""
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_compare_hashes.json")))["fec"]
+    assert fec_digests(oracle, "oracle") == want
+    if oracle.ref() is not None:
+        assert fec_digests(oracle, "ref") == want
 
 
 def test_oracle_chain_golden(oracle, golden):

@@ -270,7 +270,7 @@ def test_bench_runs_its_distributed_path_on_one_gpu():
     env = dict(os.environ, DH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29517", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--channels", "2048", "--units", "20", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--channels", "2048", "--units", "20", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--no-other-configs", "--verify", "4"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -282,6 +282,45 @@ def test_bench_runs_its_distributed_path_on_one_gpu():
     assert last == lines[0] and len(last) <= 4096 and 0 < line["roofline"]["frac"] < 1 and line["roofline"]["avg_launch_ms"] > 0
     detail = [l for l in r.stdout.splitlines() if l.startswith("BENCH_DETAIL ")]
     assert len(detail) == 1 and json.loads(detail[0][len("BENCH_DETAIL "):])["roofline"]["peak_achievable_rates"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(oracle, tmp_path):
+    """A plain bench.py run prints the headline line alone; --dump-outputs writes what the timed engine computed in its
+    last step: the dibits, decoder bytes and events of the sampled channels equal the oracle's over the same stream."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from digiham_amd import api, synth_torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, units, steps, warmup = 64, 20, 2, 1
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--channels", str(B), "--units", str(units),
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "BENCH_DETAIL" not in r.stdout
+    line = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["unit"] == "channels" and "roofline" not in line and "verified" not in line
+    d = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert {"channels", "symbols", "symbol_count", "frames", "frame_count", "events", "events_sym_index", "event_count"} <= set(d)
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    pick = d["channels"].astype(np.int64)
+    assert len(pick) == B and (pick == np.arange(B)).all()               # (a batch under 256 channels is dumped whole)
+    x, info = synth_torch.make_batch(torch, torch.device("cuda", 0), "dmr", B, units, seed=1000, sps=10)      # bench.py's input, rank 0
+    pushes = steps + warmup
+    xs = x.cpu().numpy()
+    full = oracle.chain(np.tile(xs, (1, pushes)), proto=1, threads=8)
+    pre = oracle.chain(np.tile(xs, (1, pushes - 1)), proto=1, threads=8)
+    for j in range(B):
+        want = full["syms"][j, pre["sym_count"][j]:full["sym_count"][j]]
+        assert d["symbol_count"][j] == len(want) and (d["symbols"][j, :len(want)] == want).all() and not d["symbols"][j, len(want):].any()
+        wf = full["out"][j, pre["out_count"][j]:full["out_count"][j]]
+        assert d["frame_count"][j] == len(wf) and (d["frames"][j, :len(wf)] == wf).all()
+        we = full["events"][j, pre["event_count"][j]:full["event_count"][j]]
+        assert d["event_count"][j] == len(we) and (d["events_sym_index"][j, :len(we)] == we["sym_index"]).all()
+        assert (d["events"][j, :len(we), 4:] == we["payload"]).all() and (d["events"][j, :len(we), 0] == we["type"]).all()
 
 
 @pytest.mark.gpu

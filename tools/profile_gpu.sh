@@ -1,15 +1,15 @@
 #!/bin/bash
-# Run on the GPU box (via gpurun): kernel trace + PMC passes of the headline bench, summaries into gpurun_out/prof_$1
+# Run on the GPU box: kernel trace + PMC passes of the headline bench (`bench.py --full`), summaries into $PROF_OUT/prof_$1 (default prof_out/)
 #   tools/profile_gpu.sh <tag> [bench args...]
 set -u
 TAG=${1:-run}; shift || true
-OUT=gpurun_out/prof_$TAG
+OUT=${PROF_OUT:-prof_out}/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --verify 0 $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --verify 0 $*"
 # (the trace pass runs bench.py's own default step counts -- 2 warm-up + 10 timed launches -- so that its per-kernel average is over the same
 # launches the bench line's HIP events time; the first launches of a process are slower and weighed a 4-launch average down: r06_d 5.57 traced vs 5.04 live)
-TRACE_ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-other-configs --verify 0 $*"
+TRACE_ARGS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-other-configs --verify 0 $*"
 if [ -z "${SKIP_TRACE:-}" ]; then timeout 600 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python bench.py $TRACE_ARGS > $OUT/trace.log 2>&1; fi
 grep '^{' $OUT/trace.log > $OUT/bench_under_trace.json
 python tools/rocpd_summary.py $OUT/trace_results.db > $OUT/trace_summary.txt 2>&1
