@@ -82,6 +82,9 @@ void orc_demod_free(orc_demod*);
  * caller keeps the unread tail, exactly like a csdr ringbuffer reader) and
  * appends symbols to out (capacity cap); *n_out receives the count. */
 size_t orc_demod_process(orc_demod*, const float* in, size_t n, uint8_t* out, size_t cap, size_t* n_out);
+/* the timing recovery's counters since orc_demod_new (test bookkeeping, not in the reference):
+ * stats[0] variance blocks evaluated, [1] those with vmin > 5e6, [2] +1 steps, [3] -1 steps */
+void orc_demod_stats(const orc_demod*, uint32_t* stats);
 
 typedef struct orc_dvfilter orc_dvfilter;
 orc_dvfilter* orc_dvfilter_new(void);
@@ -198,6 +201,13 @@ int orc_chain_run(const orc_chain_cfg* cfg, const float* in, size_t n_channels, 
                   uint8_t* out, size_t out_stride, uint32_t* out_count,
                   orc_event* ev, size_t ev_stride, uint32_t* ev_count,
                   int n_threads);
+/* the same, also writing orc_demod_stats of every channel's demodulator to timing[n_channels][4] (when not NULL) */
+int orc_chain_run_stats(const orc_chain_cfg* cfg, const float* in, size_t n_channels, size_t stride, size_t n,
+                        float* filtered,
+                        uint8_t* syms, size_t sym_stride, uint32_t* sym_count,
+                        uint8_t* out, size_t out_stride, uint32_t* out_count,
+                        orc_event* ev, size_t ev_stride, uint32_t* ev_count,
+                        uint32_t* timing, int n_threads);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,9 @@ struct orc_demod {
     float volume_rb[VOLUME_RB_SIZE];
     unsigned volume_rb_pos;
     float min, max, center, umid, lmid;
+    /* bookkeeping for the tests (not in the reference): variance blocks evaluated, those whose vmin > 5e6,
+     * and the +1 / -1 timing steps taken */
+    uint32_t blocks, blocks_over, steps_up, steps_down;
 };
 
 /* gfsk_demodulator.cpp:6-12 / fsk_demodulator.cpp:6-13 */
@@ -153,6 +156,10 @@ static uint8_t demod_symbol(orc_demod* d, const float* input, size_t* advance) {
         } else if (vmin_pos >= d->sps / 2 && vmin_pos < d->sps - 1) {
             d->variance_offset = -1;
         }
+        d->blocks++;
+        if (vmin > 5000000) d->blocks_over++;
+        if (d->variance_offset > 0) d->steps_up++;
+        if (d->variance_offset < 0) d->steps_down++;
         d->variance_rb_pos %= d->variance_rb_size;
     }
 
@@ -183,6 +190,11 @@ size_t orc_demod_process(orc_demod* d, const float* in, size_t n, uint8_t* out, 
     }
     *n_out = w;
     return pos;
+}
+
+/* counters of the timing recovery since orc_demod_new: stats[4] = blocks, blocks with vmin > 5e6, +1 steps, -1 steps */
+void orc_demod_stats(const orc_demod* d, uint32_t* stats) {
+    stats[0] = d->blocks; stats[1] = d->blocks_over; stats[2] = d->steps_up; stats[3] = d->steps_down;
 }
 
 /* -------------------------------------------------- digital voice filter */

@@ -92,6 +92,8 @@ def _declare(L):
     L.orc_decoder_process.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t),
                                       vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.orc_chain_run.restype = C.c_int
+    L.orc_chain_run_stats.restype = C.c_int
+    L.orc_demod_stats.argtypes = [vp, vp]
     L.orc_bptc_196_96_encode.argtypes = [vp, vp]
     L.orc_trellis_encode.argtypes = [vp, C.c_int, vp]
     for name, rt in [("orc_hamming_7_4_encode", C.c_uint8), ("orc_hamming_13_9_encode", C.c_uint16),
@@ -303,7 +305,9 @@ class ChainCfg(C.Structure):
 
 
 def chain(x, rrc=1, levels=4, invert=False, sps=10, proto=1, slot_filter=3, threads=1, keep_filtered=False):
-    """Run the whole reference pipe over x[channels][n]; returns a dict of per-channel results."""
+    """Run the whole reference pipe over x[channels][n]; returns a dict of per-channel results.  Besides the outputs, the
+    timing recovery's counters per channel (bookkeeping, not in the reference): "timing_blocks" variance blocks evaluated,
+    "blocks_over" those whose smallest phase variance is above 5e6 (no step), "steps_up" / "steps_down" the +1 / -1 steps."""
     x = np.ascontiguousarray(x, np.float32)
     if x.ndim == 1:
         x = x[None, :]
@@ -319,15 +323,17 @@ def chain(x, rrc=1, levels=4, invert=False, sps=10, proto=1, slot_filter=3, thre
     ev_stride = sym_stride // 40 + 64
     ev = np.zeros((B, ev_stride), EVENT_DTYPE)
     ev_count = np.zeros(B, np.uint32)
-    rc = lib().orc_chain_run(C.byref(cfg), _p(x), C.c_size_t(B), C.c_size_t(n), C.c_size_t(n),
-                             _p(filt) if filt is not None else None,
-                             _p(syms), C.c_size_t(sym_stride), _p(sym_count),
-                             _p(out), C.c_size_t(out_stride), _p(out_count),
-                             _p(ev), C.c_size_t(ev_stride), _p(ev_count), C.c_int(threads))
+    timing = np.zeros((B, 4), np.uint32)
+    rc = lib().orc_chain_run_stats(C.byref(cfg), _p(x), C.c_size_t(B), C.c_size_t(n), C.c_size_t(n),
+                                   _p(filt) if filt is not None else None,
+                                   _p(syms), C.c_size_t(sym_stride), _p(sym_count),
+                                   _p(out), C.c_size_t(out_stride), _p(out_count),
+                                   _p(ev), C.c_size_t(ev_stride), _p(ev_count), _p(timing), C.c_int(threads))
     if rc != 0:
         raise RuntimeError("orc_chain_run failed: %d" % rc)
     return {"filtered": filt, "syms": syms, "sym_count": sym_count, "out": out, "out_count": out_count,
-            "events": ev, "event_count": ev_count}
+            "events": ev, "event_count": ev_count, "timing_blocks": timing[:, 0].copy(), "blocks_over": timing[:, 1].copy(),
+            "steps_up": timing[:, 2].copy(), "steps_down": timing[:, 3].copy()}
 
 
 # ------------------------------------------------------------------ NXDN frame elements

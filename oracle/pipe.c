@@ -18,6 +18,7 @@ typedef struct {
     uint8_t* syms; size_t sym_stride; uint32_t* sym_count;
     uint8_t* out; size_t out_stride; uint32_t* out_count;
     orc_event* ev; size_t ev_stride; uint32_t* ev_count;
+    uint32_t* timing;
     size_t next; pthread_mutex_t lock;
     int error;
 } job;
@@ -40,6 +41,7 @@ static int run_channel(job* j, size_t ch) {
         size_t ns = 0;
         orc_demod* d = orc_demod_new(cfg->sps, cfg->levels, cfg->invert);
         orc_demod_process(d, x, j->n, s, j->sym_stride, &ns);
+        if (j->timing) orc_demod_stats(d, j->timing + 4 * ch);
         orc_demod_free(d);
         if (j->sym_count) j->sym_count[ch] = (uint32_t) ns;
         if (cfg->proto) {
@@ -76,6 +78,16 @@ int orc_chain_run(const orc_chain_cfg* cfg, const float* in, size_t n_channels, 
                   uint8_t* out, size_t out_stride, uint32_t* out_count,
                   orc_event* ev, size_t ev_stride, uint32_t* ev_count,
                   int n_threads) {
+    return orc_chain_run_stats(cfg, in, n_channels, stride, n, filtered, syms, sym_stride, sym_count,
+                               out, out_stride, out_count, ev, ev_stride, ev_count, NULL, n_threads);
+}
+
+int orc_chain_run_stats(const orc_chain_cfg* cfg, const float* in, size_t n_channels, size_t stride, size_t n,
+                        float* filtered,
+                        uint8_t* syms, size_t sym_stride, uint32_t* sym_count,
+                        uint8_t* out, size_t out_stride, uint32_t* out_count,
+                        orc_event* ev, size_t ev_stride, uint32_t* ev_count,
+                        uint32_t* timing, int n_threads) {
     job j;
     memset(&j, 0, sizeof(j));
     j.cfg = cfg; j.in = in; j.n_channels = n_channels; j.stride = stride; j.n = n;
@@ -83,6 +95,7 @@ int orc_chain_run(const orc_chain_cfg* cfg, const float* in, size_t n_channels, 
     j.syms = syms; j.sym_stride = sym_stride; j.sym_count = sym_count;
     j.out = out; j.out_stride = out_stride; j.out_count = out_count;
     j.ev = ev; j.ev_stride = ev_stride; j.ev_count = ev_count;
+    j.timing = timing;
     if (cfg->levels && !syms) return -1;
     pthread_mutex_init(&j.lock, NULL);
     if (n_threads < 1) n_threads = 1;

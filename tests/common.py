@@ -85,6 +85,15 @@ def rel_err(a, ref):
     return np.abs(a.astype(np.float64) - ref) / np.maximum(np.abs(ref), rms)
 
 
+def rel_err_per_channel(a, ref):
+    """rel_err with the rms taken per channel (row of [B][n]): every channel is its own rrc_filter process, so a quiet
+    channel is held to the 1e-6 of BASELINE.md section 4 against its own level, not the loudest channel's."""
+    ref = np.atleast_2d(ref).astype(np.float64)
+    a = np.atleast_2d(a).astype(np.float64)
+    rms = np.sqrt(np.mean(ref ** 2, axis=1, keepdims=True)) + 1e-30
+    return np.abs(a - ref) / np.maximum(np.abs(ref), rms)
+
+
 def fec_digests(O, which):
     """The FEC comparison of tests/test_oracle.py on fixed random inputs, one SHA-256 per part, for `which` = "oracle" or
     "ref" (oracle/_ref).  Outputs count only where the decoder says ok.  tests/golden/ref_compare_hashes.json holds the

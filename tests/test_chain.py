@@ -7,7 +7,7 @@ mode and within 1e-6 in FAST_FIR mode.
 import numpy as np
 import pytest
 
-from common import assert_matches_oracle, make_channels, rel_err, run_engine, sha
+from common import assert_matches_oracle, make_channels, rel_err, rel_err_per_channel, run_engine, sha
 from digiham_amd import api, synth
 
 
@@ -64,12 +64,15 @@ def test_rrc_and_gfsk_in_one_launch(ctx, oracle, chunks):
     res = run_engine(ctx, x, "none", chunks, keep_filtered=True, one_launch=True)
     assert res["filtered"].shape == ref["filtered"].shape
     assert rel_err(res["filtered"], ref["filtered"]).max() <= 2.5e-6
+    assert rel_err_per_channel(res["filtered"], ref["filtered"]).max() <= 2.5e-6
     assert_matches_oracle(res, {"syms": ref["syms"], "sym_count": ref["sym_count"]}, x.shape[0], "one launch %s" % chunks[:2])
     if chunks[0] > 10 ** 6:
         full = oracle.chain(x, proto=1)
         res = run_engine(ctx, x, "dmr", [x.shape[1]], keep_filtered=True, one_launch=True)
         assert_matches_oracle(res, full, x.shape[0], "one launch + dmr")
         assert rel_err(res["filtered"], ref["filtered"]).max() <= 2.5e-6
+        assert rel_err_per_channel(res["filtered"], ref["filtered"]).max() <= 2.5e-6
+    assert rel_err_per_channel(res["filtered"], ref["filtered"]).max() <= 2.5e-6
 
 
 @pytest.mark.parametrize("chunks", [[10 ** 9], [3000, 17, 9000, 1, 4096]])
@@ -84,6 +87,7 @@ def test_rrc_and_gfsk_in_one_launch_within_1e6(ctx, oracle, chunks):
     res = run_engine(ctx, x, "none", chunks, keep_filtered=True, one_launch=True, fast_fir=True)
     assert res["filtered"].shape == ref["filtered"].shape
     assert rel_err(res["filtered"], ref["filtered"]).max() <= 1e-6
+    assert rel_err_per_channel(res["filtered"], ref["filtered"]).max() <= 1e-6
     assert_matches_oracle(res, {"syms": ref["syms"], "sym_count": ref["sym_count"]}, x.shape[0], "one launch, FMA floats %s" % chunks[:2])
 
 
@@ -93,6 +97,7 @@ def test_fast_fir_within_1e6(ctx, oracle):
     ref = oracle.chain(x, proto=0, keep_filtered=True)
     res = run_engine(ctx, x, "none", [x.shape[1]], keep_filtered=True, fast_fir=True)
     assert rel_err(res["filtered"], ref["filtered"]).max() <= 1e-6
+    assert rel_err_per_channel(res["filtered"], ref["filtered"]).max() <= 1e-6
     # dibits agree except (rarely) at threshold ties; on this input they agree exactly
     agree = np.mean([np.mean(res["syms"][b][:1000] == ref["syms"][b, :1000]) for b in range(2)])
     assert agree > 0.999
@@ -433,6 +438,7 @@ def test_ragged_pushes_every_channel_at_its_own_pace(ctx, oracle, kw, oproto):
         if kw.get("one_launch"):                    # (DH_FLAG_ONE_LAUNCH: the matrix-core FIR's floats, 2.5e-6; every sample of every push delivered)
             y = np.concatenate(filt[b])
             assert y.shape == ref["filtered"][b].shape and rel_err(y, ref["filtered"][b]).max() <= 2.5e-6, b
+            assert rel_err_per_channel(y, ref["filtered"][b]).max() <= 2.5e-6, b
         elif kw.get("keep_filtered"):
             assert (np.concatenate(filt[b]).view(np.uint32) == ref["filtered"][b].view(np.uint32)).all(), b
 

@@ -10,6 +10,8 @@ import hashlib
 import numpy as np
 import pytest
 
+from common import rel_err_per_channel
+
 pytestmark = pytest.mark.gpu
 
 
@@ -251,6 +253,7 @@ def test_config1_rrc_materialised_plus_gfsk_at_full_size(gpu_ctx, oracle, fast):
     if fast:
         rms = np.sqrt(np.mean(r.astype(np.float64) ** 2)) + 1e-30
         assert float(np.max(np.abs(yy.astype(np.float64) - r) / np.maximum(np.abs(r), rms))) <= 1e-6
+        assert float(rel_err_per_channel(yy, r).max()) <= 1e-6          # and against every channel's own level
     else:
         assert (yy.view(np.uint32) == r.view(np.uint32)).all()
     if fast is not True:
