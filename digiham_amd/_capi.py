@@ -25,6 +25,17 @@ class EngineConfig(C.Structure):
                 ("rrc_taps", C.POINTER(C.c_float)), ("rrc_nzeros", C.c_uint32), ("rrc_gain", C.c_double)]
 
 
+class ChannelizerConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
+                ("taps", C.POINTER(C.c_float)), ("n_taps", C.c_uint32), ("increments", C.POINTER(C.c_uint32)),
+                ("input_format", C.c_int32), ("output_mode", C.c_int32), ("dcblock", C.c_int32), ("max_input", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
+CZ_INPUT = {"cs16": 1, "cf32": 2}
+CZ_OUTPUT = {"iq": 1, "fm": 2}
+
+
 class DhError(RuntimeError):
     def __init__(self, code, what, detail=""):
         names = {-1: "DH_EINVAL", -2: "DH_ENOMEM", -3: "DH_EDEVICE", -4: "DH_ENODEV", -5: "DH_ECAPACITY"}
@@ -73,6 +84,10 @@ def declare(L, lenient=False):
         "dh_engine_timing_read_split": [vp, vp, vp, C.POINTER(u32)],
         "dh_engine_timing_stats": [vp, vp, vp],
         "dh_engine_debug_header": [vp, u32, vp],
+        "dh_channelizer_create": [C.POINTER(ChannelizerConfig), C.POINTER(vp)],
+        "dh_channelizer_reset": [vp], "dh_channelizer_retune": [vp, u32, u32],
+        "dh_channelizer_push": [vp, vp, sz, vp, sz, C.POINTER(sz)], "dh_channelizer_push_host": [vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "dh_channelizer_phasor": [vp, vp, sz],
     }
     for name, args in sig.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
@@ -82,6 +97,9 @@ def declare(L, lenient=False):
         fn.restype = C.c_int
     L.dh_engine_destroy.argtypes = [vp]
     L.dh_engine_destroy.restype = None
+    if hasattr(L, "dh_channelizer_destroy"):
+        L.dh_channelizer_destroy.argtypes = [vp]
+        L.dh_channelizer_destroy.restype = None
     return L
 
 
@@ -94,6 +112,8 @@ EXPORTED_SYMBOLS = [
     "dh_engine_filtered", "dh_engine_symbols", "dh_engine_frames", "dh_engine_events", "dh_engine_read_symbols",
     "dh_engine_read_frames", "dh_engine_read_events", "dh_engine_read_filtered", "dh_engine_sync",
     "dh_engine_timing_enable", "dh_engine_timing_read", "dh_engine_timing_read_split", "dh_engine_timing_stats", "dh_engine_debug_header",
+    "dh_channelizer_create", "dh_channelizer_destroy", "dh_channelizer_reset", "dh_channelizer_retune", "dh_channelizer_push",
+    "dh_channelizer_push_host", "dh_channelizer_phasor",
 ]
 
 _LIB = None

@@ -385,3 +385,95 @@ class Engine:
             if getter(self._h, C.byref(p), C.byref(stride), C.byref(cnt)) == 0:
                 out[name] = (p.value, stride.value, cnt.value)
         return out
+
+
+def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0):
+    """Real low-pass prototype for Channelizer: a Kaiser-windowed sinc with its cut-off halfway between the pass- and
+    stopband edges, the length and beta of Kaiser's estimates for `atten_db` of stopband attenuation, unity gain at DC.
+    (`decimation` is not part of the design; it is checked against the stopband: the output rate must hold it.)"""
+    if not 0 < passband_hz < stopband_hz:
+        raise ValueError("channel_taps: need 0 < passband < stopband")
+    if stopband_hz > input_rate / decimation:
+        raise ValueError("channel_taps: the stopband edge %.0f Hz aliases at the output rate %.0f Hz" % (stopband_hz, input_rate / decimation))
+    a = float(atten_db)
+    dw = 2.0 * np.pi * (stopband_hz - passband_hz) / input_rate
+    n = int(np.ceil((a - 7.95) / (2.285 * dw))) + 1
+    beta = 0.1102 * (a - 8.7) if a > 50 else (0.5842 * (a - 21) ** 0.4 + 0.07886 * (a - 21) if a >= 21 else 0.0)
+    fc = 0.5 * (passband_hz + stopband_hz) / input_rate
+    t = np.arange(n) - (n - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * t) * np.kaiser(n, beta)
+    return (h / h.sum()).astype(np.float32)
+
+
+def nco_increment(offset_hz, input_rate):
+    """uint32 NCO increment of a channel at `offset_hz` from the centre: offset / rate * 2^32 (two's complement below 0)."""
+    return int(round(float(offset_hz) / float(input_rate) * 2.0 ** 32)) & 0xFFFFFFFF
+
+
+class Channelizer:
+    """One wideband complex stream -> one row per channel at input_rate / decimation (dh_channelizer; the arithmetic is
+    specified in digiham_amd/csrc/channelizer_core.hpp).  input "cs16" (int16 I / Q pairs) or "cf32" (float32 pairs, or
+    complex64); output "fm" (discriminator audio for Engine.push, optionally DC-blocked) or "iq" (complex rows).
+    push(x) returns (rows, n_out): rows is the channelizer's own device array [B][max_input // D + 1] (x 2 for "iq"),
+    valid in [:, :n_out] until the next push."""
+
+    def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
+                 ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        lib, mem = self.ctx.lib, self.ctx.mem
+        self.rate, self.D, self.B = float(input_rate), int(decimation), len(freqs_hz)
+        self.input, self.output = input, output
+        t = np.ascontiguousarray(taps, np.float32).ravel()
+        inc = np.array([nco_increment(f, input_rate) for f in freqs_hz], np.uint32)
+        cfg = _capi.ChannelizerConfig(C.sizeof(_capi.ChannelizerConfig), getattr(mem, "index", 0), self.B, self.D,
+                                      t.ctypes.data_as(C.POINTER(C.c_float)), len(t), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      _capi.CZ_INPUT[input], _capi.CZ_OUTPUT[output], int(bool(dcblock) and output == "fm"),
+                                      int(max_input), mem.stream())
+        h = C.c_void_p()
+        _check(lib.dh_channelizer_create(C.byref(cfg), C.byref(h)), "dh_channelizer_create", lib)
+        self._h = h
+        self.max_input = int(max_input)
+        self.out_stride = self.max_input // self.D + 1
+        self.rows = mem.zeros((self.B, self.out_stride) if output == "fm" else (self.B, self.out_stride, 2), np.float32)
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx.lib.dh_channelizer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        _check(self.ctx.lib.dh_channelizer_reset(self._h), "dh_channelizer_reset", self.ctx.lib)
+
+    def retune(self, ch, hz):
+        _check(self.ctx.lib.dh_channelizer_retune(self._h, int(ch), nco_increment(hz, self.rate)), "dh_channelizer_retune", self.ctx.lib)
+
+    def push(self, x):
+        """x: numpy (host) or a device array: int16 [n][2] / [2 n] for "cs16", float32 [n][2] / [2 n] or complex64 [n] for
+        "cf32".  Returns (rows, n_out)."""
+        mem = self.ctx.mem
+        if isinstance(x, np.ndarray):
+            a = np.ascontiguousarray(x.view(np.float32) if x.dtype == np.complex64 else x, np.int16 if self.input == "cs16" else np.float32)
+            n = a.size // 2
+            dev = mem.is_device_array(a) and not hasattr(mem, "torch")
+        else:
+            want = mem.torch.int16 if self.input == "cs16" else mem.torch.float32
+            if x.dtype != want or not x.is_contiguous():
+                raise ValueError("Channelizer.push: need a contiguous %s device array, got %s" % (want, x.dtype))
+            a, n, dev = x, x.numel() // 2, True
+        cnt = C.c_size_t(0)
+        fn = self.ctx.lib.dh_channelizer_push if dev else self.ctx.lib.dh_channelizer_push_host
+        ptr = mem.ptr(a) if dev else a.ctypes.data_as(C.c_void_p)
+        self._keep = a              # asynchronous: the input stays alive until the next push
+        _check(fn(self._h, ptr, n, mem.ptr(self.rows), self.out_stride, C.byref(cnt)), "dh_channelizer_push", self.ctx.lib)
+        return self.rows, cnt.value
+
+    def phasor(self, phi):
+        """P(phi) of the specification for uint32 phase words (host arithmetic) -> complex128 array."""
+        p = np.ascontiguousarray(phi, np.uint32).ravel()
+        out = np.zeros((p.size, 2), np.float32)
+        _check(self.ctx.lib.dh_channelizer_phasor(p.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), p.size),
+               "dh_channelizer_phasor", self.ctx.lib)
+        return out[:, 0].astype(np.float64) + 1j * out[:, 1].astype(np.float64)

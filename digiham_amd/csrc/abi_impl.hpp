@@ -224,3 +224,165 @@ int dh_engine_sync(dh_engine* e) {
 }
 
 }  // extern "C"
+
+// ---- the channelizer (channelizer_core.hpp): host bookkeeping over the backend's memory and the dh_be_cz_* launches -----
+//   dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream);
+//   dh_be_cz_gemm(const DhCzParams& P, void* stream);
+//   dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream);
+// (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
+// window is the last H = T' - 1 samples of the previous one followed by the new samples.
+struct dh_channelizer {
+    DH_BACKEND be;
+    void* stream = nullptr;
+    uint32_t B = 0, D = 0, tpad = 0, ncols = 0, max_input = 0;
+    int cf32 = 0, fm = 0, dcblock = 0;
+    std::vector<float> taps;                            // h zero-padded to T'
+    std::vector<uint32_t> inc;
+    float* d_tables = nullptr;                          // coarse ++ fine
+    uint32_t* d_inc = nullptr;
+    float* d_bmat = nullptr;                            // [2 T'][ncols]
+    float* d_win[2] = { nullptr, nullptr };             // [T' - 1 + max_input][2] each
+    float* d_state = nullptr;                           // [B][DH_CZ_STATE_WORDS]
+    float* d_zbuf = nullptr;                            // FM: [max_input / D + 1][B][2]
+    void* d_stage = nullptr;                            // push_host's input
+    int cur = 0;
+    uint32_t prev_n = 0;
+    uint64_t n0 = 0;                                    // samples pushed since create / reset
+
+    void release() {
+        for (void* p : { (void*) d_tables, (void*) d_inc, (void*) d_bmat, (void*) d_win[0], (void*) d_win[1], (void*) d_state, (void*) d_zbuf, d_stage })
+            if (p) be.free(p);
+    }
+    size_t in_bytes() const { return cf32 ? 8u : 4u; }
+    size_t win_bytes() const { return sizeof(float) * 2 * ((size_t) tpad - 1 + max_input); }
+    int clear() {
+        cur = 0; prev_n = 0; n0 = 0;
+        if (be.zero(d_win[0], win_bytes()) || be.zero(d_win[1], win_bytes())) return DH_EDEVICE;
+        return be.zero(d_state, sizeof(float) * DH_CZ_STATE_WORDS * B) ? DH_EDEVICE : DH_OK;
+    }
+    int init(const dh_channelizer_config& c) {
+        B = c.n_channels; D = c.decimation; tpad = dh_cz_tpad(c.n_taps); ncols = dh_cz_ncols(B); max_input = c.max_input;
+        cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
+        taps.assign(tpad, 0.0f);
+        for (uint32_t k = 0; k < c.n_taps; k++) taps[k] = c.taps[k];
+        inc.assign(c.increments, c.increments + B);
+        const size_t bm = (size_t) 2 * tpad * ncols;
+        d_tables = (float*) be.alloc(sizeof(float) * 4 * 4096);
+        d_inc = (uint32_t*) be.alloc(sizeof(uint32_t) * B);
+        d_bmat = (float*) be.alloc(sizeof(float) * bm);
+        d_win[0] = (float*) be.alloc(win_bytes()); d_win[1] = (float*) be.alloc(win_bytes());
+        d_state = (float*) be.alloc(sizeof(float) * DH_CZ_STATE_WORDS * B);
+        if (fm) d_zbuf = (float*) be.alloc(sizeof(float) * 2 * ((size_t) max_input / D + 1) * B);
+        d_stage = be.alloc(in_bytes() * max_input);
+        if (!d_tables || !d_inc || !d_bmat || !d_win[0] || !d_win[1] || !d_state || (fm && !d_zbuf) || !d_stage) return DH_ENOMEM;
+        std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
+        for (uint32_t b = 0; b < B; b++) {
+            dh_cz_columns(taps.data(), tpad, inc[b], re.data(), im.data());
+            const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
+            for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bmat[r * ncols + cr] = re[r]; bmat[r * ncols + ci] = im[r]; }
+        }
+        if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_inc, inc.data(), sizeof(uint32_t) * B) ||
+            be.upload(d_bmat, bmat.data(), sizeof(float) * bm)) return DH_EDEVICE;
+        const int rc = clear();
+        if (rc != DH_OK) return rc;
+        return be.sync() ? DH_EDEVICE : DH_OK;           // (the host copies above are released on return)
+    }
+    int retune(uint32_t ch, uint32_t u) {
+        std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
+        inc[ch] = u;
+        dh_cz_columns(taps.data(), tpad, u, re.data(), im.data());
+        const size_t pitch = sizeof(float) * ncols;
+        if (be.upload2d(d_bmat + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
+            be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
+            be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || be.zero(d_state + (size_t) ch * DH_CZ_STATE_WORDS, sizeof(float) * DH_CZ_STATE_WORDS))
+            return DH_EDEVICE;
+        return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    int push(const void* in, size_t n_in, float* out, size_t out_stride, size_t* n_out, bool host) {
+        if (!n_out) return DH_EINVAL;
+        *n_out = 0;
+        if (n_in > max_input || (!in && n_in)) return DH_EINVAL;
+        const uint64_t no = (n0 + n_in) / D - n0 / D;
+        if (no && (!out || out_stride < no)) return DH_EINVAL;
+        if (!n_in) return DH_OK;
+        const void* src = in;
+        if (host) {
+            if (be.upload(d_stage, in, in_bytes() * n_in)) return DH_EDEVICE;
+            src = d_stage;
+        }
+        float* w = d_win[cur];
+        if (dh_be_cz_window(w, d_win[cur ^ 1], prev_n, src, cf32, tpad - 1, n_in, stream)) return DH_EDEVICE;
+        if (no) {
+            DhCzParams P;
+            P.win = w; P.bmat = d_bmat; P.coarse = d_tables; P.fine = d_tables + 8192; P.inc = d_inc;
+            P.out = out; P.out_stride = out_stride; P.zbuf = d_zbuf;
+            P.j0 = n0 / D; P.off0 = (uint32_t) (D - 1 - n0 % D);
+            P.D = D; P.tpad = tpad; P.B = B; P.ncols = ncols; P.n_out = (uint32_t) no; P.fm = fm;
+            if (dh_be_cz_gemm(P, stream)) return DH_EDEVICE;
+            if (fm && dh_be_cz_fm(d_zbuf, d_state, out, out_stride, B, (uint32_t) no, dcblock, stream)) return DH_EDEVICE;
+        }
+        if (host && be.sync()) return DH_EDEVICE;       // the staging buffer is the next push's
+        cur ^= 1; prev_n = (uint32_t) n_in; n0 += n_in;
+        *n_out = (size_t) no;
+        return DH_OK;
+    }
+};
+
+extern "C" {
+
+int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out) {
+    if (!cfg || !out) return DH_EINVAL;
+    *out = nullptr;
+    const dh_channelizer_config& c = *cfg;
+    if (c.struct_size < sizeof(dh_channelizer_config) || c.decimation < 1 || c.decimation > 1024 || c.n_taps < 1 || c.n_taps > 16384 ||
+        c.n_channels < 1 || c.n_channels > 65536 || c.max_input < 1 || c.max_input > (1u << 28) || !c.taps || !c.increments ||
+        (c.input_format != DH_CZ_CS16 && c.input_format != DH_CZ_CF32) || (c.output_mode != DH_CZ_IQ_F32 && c.output_mode != DH_CZ_FM) ||
+        (c.dcblock && c.output_mode != DH_CZ_FM))
+        return DH_EINVAL;
+    for (uint32_t k = 0; k < c.n_taps; k++)
+        if (!(c.taps[k] - c.taps[k] == 0.0f)) return DH_EINVAL;        // finite taps only
+    dh_channelizer* z = new (std::nothrow) dh_channelizer;
+    if (!z) return DH_ENOMEM;
+    int rc = z->be.open(c.device, c.stream);
+    if (rc == DH_OK) {
+        auto on_device = z->be.scope(); (void) on_device;
+        z->stream = c.stream;
+        rc = z->init(c);
+        if (rc != DH_OK) z->release();
+    }
+    if (rc != DH_OK) { delete z; return rc; }
+    *out = z;
+    return DH_OK;
+}
+
+void dh_channelizer_destroy(dh_channelizer* c) {
+    if (!c) return;
+    {
+        auto on_device = c->be.scope(); (void) on_device;
+        c->be.sync();
+        c->be.close();
+        c->release();
+    }
+    delete c;
+}
+
+int dh_channelizer_reset(dh_channelizer* c) { if (!c) return DH_EINVAL; auto on_device = c->be.scope(); (void) on_device; return c->clear(); }
+int dh_channelizer_retune(dh_channelizer* c, uint32_t ch, uint32_t u) { if (!c || ch >= c->B) return DH_EINVAL; auto on_device = c->be.scope(); (void) on_device; return c->retune(ch, u); }
+int dh_channelizer_push(dh_channelizer* c, const void* d_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
+    if (!c) return DH_EINVAL;
+    auto on_device = c->be.scope(); (void) on_device;
+    return c->push(d_in, n_in, d_out, out_stride, n_out, false);
+}
+int dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
+    if (!c) return DH_EINVAL;
+    auto on_device = c->be.scope(); (void) on_device;
+    return c->push(h_in, n_in, d_out, out_stride, n_out, true);
+}
+int dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n) {
+    if ((!h_phi || !h_out) && n) return DH_EINVAL;
+    const float* t = dh_cz_host_tables();
+    for (size_t i = 0; i < n; i++) dh_cz_phasor(h_phi[i], t, t + 8192, h_out[2 * i], h_out[2 * i + 1]);
+    return DH_OK;
+}
+
+}  // extern "C"

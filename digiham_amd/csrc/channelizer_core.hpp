@@ -1,0 +1,185 @@
+// channelizer_core.hpp -- dh_channelizer: one wideband complex stream -> B narrow channel rows at input_rate / D, a bank of
+// digital down-converters on the matrix cores.  Shared by the gfx950 kernels in engine.hip and by the CPU test harness (the
+// host bodies and the host dh_be_cz_* backends at the end of this file).  This is THIS project's own stage, so the arithmetic
+// below is its specification; tests/cz_restate.c restates it from this text alone.
+//
+//   Input     x[n], n = 0, 1, ... counted from create / reset, x[n < 0] = 0.  DH_CZ_CS16: interleaved int16 I / Q,
+//             x = (I * 2^-15, Q * 2^-15) (exact).  DH_CZ_CF32: interleaved float32, taken as is.
+//   Phasor    P(phi), phi a uint32 phase word (2^32 = one turn):  v = phi + 2^7 (mod 2^32), c = v >> 20, f = (v >> 8) & 4095,
+//             C[c] = ((float) cos(c * (2 pi / 4096)), (float) sin(...)),  F[f] = ((float) cos(f * (2 pi / 2^24)), (float) sin(...))
+//             (double angles, libm cos / sin, one rounding to float), P = (Cr Fr - Ci Fi, Cr Fi + Ci Fr), every product and
+//             sum rounded to float in that order.  |P(phi) - e^(2 pi i phi / 2^32)| <= 1e-6 (tested; ~3e-7 in fact).
+//   Channels  channel b has the uint32 increment u_b (offset / input_rate * 2^32, two's complement for negative offsets);
+//             phi_b(n) = u_b * n mod 2^32 in integer arithmetic.
+//   Filter    h[0..T-1] (the caller's table), zero-padded to T' = 16 ceil(T / 16) taps.  G_b[k] = (h[k] * Pr, h[k] * Pi),
+//             P = P(phi_b(k)), one rounding each.
+//   Output j  at input index n_j = j D + D - 1 (a push yields exactly the D-blocks it completes):
+//             y = sum_k G_b[k] x[n_j - k] as two fused chains over k = 0 .. T'-1 in increasing k, starting from +0:
+//               yr = fma(xi, -Gi[k], fma(xr, Gr[k], yr))      yi = fma(xi, Gr[k], fma(xr, Gi[k], yi))
+//             (x = x[n_j - k]; one chain per component, no split accumulators: v_mfma_f32_16x16x4_f32 is bit for bit this
+//             k-ordered fmaf chain, and the K order of the GEMM below is exactly k, then re before im)
+//             z_b[j] = P(-phi_b(n_j)) (x) y:  zr = (pr yr) - (pi yi),  zi = (pr yi) + (pi yr)   (products rounded, then the sum)
+//   IQ_F32    row b = z_b[j] interleaved (re, im).
+//   FM        w = z[j] conj(z[j-1]): wr = (zr pr') + (zi pi'),  wi = (zi pr') - (zr pi')  with z[j-1] = (pr', pi'), z[-1] = 0;
+//             out = dh_fe_atan2f_over_pi(wi, wr) -- the arctangent of the receiver front-end (frontend_core.hpp); (0, 0) -> 0.
+//   dcblock   (FM only) y = (x - x_prev) + 0.995f y_prev, the operations of dh_frontend_channel; x_prev = y_prev = 0 at the start.
+//   Retune    replaces u_b from the next push on, recomputes G_b and zeroes channel b's z[j-1], x_prev and y_prev; the input
+//             history and every other channel are untouched.
+//   Denormals are kept everywhere: the host rounds taps with IEEE floats, and the kernels run in hipcc's default f32 mode
+//             (float_denorm_mode_32 = 3: VALU and MFMA A / B keep subnormals, MFMA C / D never flush), which is what the
+//             host's IEEE fmaf does.  A test pushes input whose products and sums are subnormal and compares device, CPU
+//             emulation and the restatement byte for byte.
+//
+// Work per push (host code in abi_impl.hpp): (1) dh_cz_window_item -- the window [H = T'-1 history samples ++ the new ones]
+// as complex floats; (2) the GEMM + rotation, tiled over 128 output instants x 64 channels (k_cz_gemm; host body
+// dh_cz_output); FM mode then (3) dh_cz_fm_item, one output per lane, and (4) dh_cz_tail_channel, one channel per lane:
+// the DC blocker's recurrence and the carried z[j-1].
+#pragma once
+
+#include <math.h>
+
+#include "frontend_core.hpp"
+
+#define DH_CZ_TAP_STEP 16         // T' = a multiple of the K extent of one LDS chunk of the GEMM (16 taps = 32 real K)
+#define DH_CZ_TM 128              // output instants per GEMM workgroup tile
+#define DH_CZ_TNC 64              // channels per GEMM workgroup tile (128 real columns)
+#define DH_CZ_TBITS 12            // the two phasor tables: 4096 entries each
+#define DH_CZ_STATE_WORDS 4       // per channel: z[j-1] (re, im), x_prev, y_prev of the DC blocker
+
+// Column of the real GEMM for channel b, component c (0: the real output, 1: the imaginary one).  Sixteen channels' real
+// columns, then their sixteen imaginary ones: a 16 x 16 MFMA tile holds one component of sixteen channels, and the lane
+// that holds a channel's real part in tile 2t holds its imaginary part in tile 2t + 1 (no exchange between lanes).
+DH_HD uint32_t dh_cz_col(uint32_t b, uint32_t c) { return 32u * (b >> 4) + 16u * c + (b & 15u); }
+DH_HD uint32_t dh_cz_ncols(uint32_t B) { return 2u * DH_CZ_TNC * ((B + DH_CZ_TNC - 1) / DH_CZ_TNC); }
+DH_HD uint32_t dh_cz_tpad(uint32_t T) { return DH_CZ_TAP_STEP * ((T + DH_CZ_TAP_STEP - 1) / DH_CZ_TAP_STEP); }
+
+DH_HD void dh_cz_phasor(uint32_t phi, const float* coarse, const float* fine, float& pr, float& pi) {
+    const uint32_t v = phi + 128u, c = v >> 20, f = (v >> 8) & 4095u;
+    const float cr = coarse[2 * c], ci = coarse[2 * c + 1], fr = fine[2 * f], fi = fine[2 * f + 1];
+    const float a = cr * fr, b = ci * fi, d = cr * fi, e = ci * fr;
+    pr = a - b; pi = d + e;
+}
+
+struct DhCzParams {
+    const float* win;             // [H + n_in][2] window: x[N0 - H .. N0 + n_in) of this push, H = T' - 1
+    const float* bmat;            // [2 T'][ncols] the GEMM's B operand: row 2k (x real part) / 2k + 1 (x imaginary part)
+    const float* coarse;          // [4096][2]
+    const float* fine;            // [4096][2]
+    const uint32_t* inc;          // [B] u_b
+    float* out; size_t out_stride;        // output rows [B][out_stride] (complex pairs in IQ_F32 mode, floats in FM mode)
+    float* zbuf;                  // FM mode: z of this push, [n_out][B][2]
+    uint64_t j0;                  // index of the push's first output
+    uint32_t off0;                // window index of x[n_{j0}] minus H: D - 1 - (N0 mod D)
+    uint32_t D, tpad, B, ncols, n_out;
+    int fm;                       // 0: rotated z to the output rows, 1: to zbuf
+};
+
+// the rotation and the store of output `row` of channel b, y = the two chains
+DH_HD void dh_cz_emit(const DhCzParams& P, uint32_t row, uint32_t b, float yr, float yi) {
+    const uint32_t nj = (uint32_t) ((P.j0 + row) * (uint64_t) P.D + (P.D - 1u));         // n_j mod 2^32
+    float pr, pi;
+    dh_cz_phasor(0u - P.inc[b] * nj, P.coarse, P.fine, pr, pi);
+    const float a = pr * yr, c = pi * yi, d = pr * yi, e = pi * yr;
+    const float zr = a - c, zi = d + e;
+    float* q = P.fm ? P.zbuf + 2 * ((size_t) row * P.B + b) : P.out + 2 * ((size_t) b * P.out_stride + row);
+    q[0] = zr; q[1] = zi;
+}
+
+// Host body of the GEMM: the two chains of one output, in the MFMA's K order (row 2k, then 2k + 1, k = 0 .. T'-1)
+DH_HD void dh_cz_output(const DhCzParams& P, uint32_t row, uint32_t b) {
+    const uint32_t base = P.off0 + row * P.D + (P.tpad - 1u);
+    const float* cr = P.bmat + dh_cz_col(b, 0), * ci = P.bmat + dh_cz_col(b, 1);
+    float yr = 0.0f, yi = 0.0f;
+    for (uint32_t k = 0; k < P.tpad; k++) {
+        const float xr = P.win[2 * (size_t) (base - k)], xi = P.win[2 * (size_t) (base - k) + 1];
+        const size_t r0 = (size_t) (2 * k) * P.ncols, r1 = r0 + P.ncols;
+        yr = __builtin_fmaf(xr, cr[r0], yr); yr = __builtin_fmaf(xi, cr[r1], yr);
+        yi = __builtin_fmaf(xr, ci[r0], yi); yi = __builtin_fmaf(xi, ci[r1], yi);
+    }
+    dh_cz_emit(P, row, b, yr, yi);
+}
+
+// element e of this push's window: the last H samples of the previous window, then the new samples converted
+DH_HD void dh_cz_window_item(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t e) {
+    float re, im;
+    if (e < H) { re = prev[2 * (prev_n + e)]; im = prev[2 * (prev_n + e) + 1]; }
+    else if (cf32) { const float* s = (const float*) in + 2 * (e - H); re = s[0]; im = s[1]; }
+    else { const int16_t* s = (const int16_t*) in + 2 * (e - H); re = (float) s[0] * 0.000030517578125f; im = (float) s[1] * 0.000030517578125f; }
+    cur[2 * e] = re; cur[2 * e + 1] = im;
+}
+
+// FM discriminator of output j of channel b (FM mode): zbuf [n_out][B][2], z[j-1] of j = 0 from the channel's state
+DH_HD void dh_cz_fm_item(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t b, uint32_t j) {
+    const float* z = zbuf + 2 * ((size_t) j * B + b);
+    const float* p = j ? z - 2 * (size_t) B : state + (size_t) b * DH_CZ_STATE_WORDS;
+    const float zr = z[0], zi = z[1], pr = p[0], pi = p[1];
+    const float a = zr * pr, c = zi * pi, d = zi * pr, e = zr * pi;
+    const float wr = a + c, wi = d - e;
+    out[(size_t) b * out_stride + j] = dh_fe_atan2f_over_pi(wi, wr);
+}
+
+// the serial part of FM mode, one channel: DC blocker over the channel's n_out outputs in place, then the carried state
+DH_HD void dh_cz_tail_channel(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, uint32_t b) {
+    float* st = state + (size_t) b * DH_CZ_STATE_WORDS;
+    float* row = out + (size_t) b * out_stride;
+    if (dcblock) {
+        float xp = st[2], yp = st[3];
+        uint32_t j = 0;
+        for (; j + 8 <= n_out; j += 8) {          // eight loads in flight ahead of the recurrence
+            float v[8];
+            for (int e = 0; e < 8; e++) v[e] = row[j + e];
+            for (int e = 0; e < 8; e++) { const float d = v[e] - xp; const float f = 0.995f * yp; const float y = d + f; xp = v[e]; yp = y; v[e] = y; }
+            for (int e = 0; e < 8; e++) row[j + e] = v[e];
+        }
+        for (; j < n_out; j++) { const float x = row[j]; const float d = x - xp; const float f = 0.995f * yp; const float y = d + f; xp = x; yp = y; row[j] = y; }
+        st[2] = xp; st[3] = yp;
+    }
+    if (n_out) { const float* z = zbuf + 2 * ((size_t) (n_out - 1) * B + b); st[0] = z[0]; st[1] = z[1]; }
+}
+
+// ---- host side: the phasor tables and the rotated taps (computed once per create / retune, then uploaded) ---------------
+// coarse ++ fine, [2][4096][2] floats
+inline const float* dh_cz_host_tables() {
+    static const float* t = [] {
+        float* v = new float[4 * 4096];
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int i = 0; i < 4096; i++) {
+            const double ac = (double) i * (two_pi / 4096.0), af = (double) i * (two_pi / 16777216.0);
+            v[2 * i] = (float) cos(ac); v[2 * i + 1] = (float) sin(ac);
+            v[8192 + 2 * i] = (float) cos(af); v[8192 + 2 * i + 1] = (float) sin(af);
+        }
+        return (const float*) v;
+    }();
+    return t;
+}
+
+// the two GEMM columns of one channel: re_col / im_col [2 T'] (rows 2k, 2k + 1), h zero-padded to T'
+inline void dh_cz_columns(const float* h, uint32_t tpad, uint32_t u, float* re_col, float* im_col) {
+    const float* t = dh_cz_host_tables();
+    for (uint32_t k = 0; k < tpad; k++) {
+        float pr, pi;
+        dh_cz_phasor(u * k, t, t + 8192, pr, pi);
+        const float gr = h[k] * pr, gi = h[k] * pi;
+        re_col[2 * k] = gr; re_col[2 * k + 1] = -gi;
+        im_col[2 * k] = gi; im_col[2 * k + 1] = gr;
+    }
+}
+
+#if !DH_DEVICE_BUILD
+// ---- host backends of the CPU test harness (engine.hip defines the gfx950 ones) --------------------------------------
+static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void*) {
+    for (size_t e = 0; e < H + n_in; e++) dh_cz_window_item(cur, prev, prev_n, in, cf32, H, e);
+    return 0;
+}
+static int dh_be_cz_gemm(const DhCzParams& P, void*) {
+    for (uint32_t b = 0; b < P.B; b++)
+        for (uint32_t row = 0; row < P.n_out; row++) dh_cz_output(P, row, b);
+    return 0;
+}
+static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void*) {
+    for (uint32_t b = 0; b < B; b++)
+        for (uint32_t j = 0; j < n_out; j++) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
+    for (uint32_t b = 0; b < B; b++) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
+    return 0;
+}
+#endif

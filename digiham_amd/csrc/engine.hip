@@ -891,6 +891,111 @@ struct HipBackend {
     }
 };
 
+// ---------------------------------------------------------------------------------- channelizer (channelizer_core.hpp)
+__global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n) {
+    for (size_t e = blockIdx.x * (size_t) blockDim.x + threadIdx.x; e < n; e += (size_t) gridDim.x * blockDim.x)
+        dh_cz_window_item(cur, prev, prev_n, in, cf32, H, e);
+}
+
+// The channelizer's GEMM on v_mfma_f32_16x16x4_f32 (bit for bit the k-ordered fmaf chain of dh_cz_output).  A workgroup of
+// four wavefronts computes DH_CZ_TM = 128 output instants x 128 real columns (64 channels); wavefront w takes rows 64 (w & 1)
+// and columns 64 (w >> 1) onwards as 4 x 4 tiles of 16 x 16.  K runs over the taps in chunks of DH_CZ_TAP_STEP = 16 (32 real
+// K rows) staged through LDS, the next chunk's global loads issued before this chunk's 128 MFMAs per wavefront.
+//   As[row][kappa], kappa = 2 i + (0 re, 1 im) of tap k0 + i; row stride 36: the 16 rows x 4 K of one operand read hit 64 banks
+//   Bs[kappa][col], row stride 144: likewise for the 4 K x 16 columns
+//   MFMA operands: A lane (m = l & 15, q = l >> 4) = As[row m][4 s + q], B lane (n = l & 15, q) = Bs[4 s + q][col n];
+//   D lane (n, g = l >> 4), register r = (row 4 g + r, col n).  Column tile 2 c holds sixteen channels' real parts and tile
+//   2 c + 1 their imaginary parts (dh_cz_col), so each lane rotates and stores its own outputs.
+#define DH_CZ_AS 36
+#define DH_CZ_BS 144
+__global__ __launch_bounds__(256) void k_cz_gemm(const DhCzParams P) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ __attribute__((aligned(16))) float As[DH_CZ_TM * DH_CZ_AS];
+    __shared__ __attribute__((aligned(16))) float Bs[32 * DH_CZ_BS];
+    const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t row0 = blockIdx.x * DH_CZ_TM, col0 = blockIdx.y * (2u * DH_CZ_TNC);
+    // loaders: A -- row ar = tid >> 1, taps 8 ah .. 8 ah + 7 of the chunk (window indices descending); B -- float4 number
+    // tid + 256 i of the 32 x 128 slab
+    const uint32_t ar = (uint32_t) tid >> 1, ah = (uint32_t) tid & 1u;
+    const bool arow_ok = row0 + ar < P.n_out;
+    const uint32_t abase = P.off0 + (row0 + ar) * P.D + (P.tpad - 1u) - 8u * ah;
+    const float2* win = (const float2*) P.win;
+    const uint32_t nch = P.tpad / DH_CZ_TAP_STEP;
+    float2 ra[8];
+    float4 rb[4];
+    auto load = [&](uint32_t c) {
+        const uint32_t k0 = DH_CZ_TAP_STEP * c;
+#pragma unroll
+        for (int e = 0; e < 8; e++) ra[e] = arow_ok ? win[abase - k0 - (uint32_t) e] : make_float2(0.0f, 0.0f);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t q = (uint32_t) tid + 256u * i, r = q >> 5, c4 = q & 31u;
+            rb[i] = *(const float4*) (P.bmat + (size_t) (32u * c + r) * P.ncols + col0 + 4u * c4);
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int e = 0; e < 8; e++) *(float2*) (As + ar * DH_CZ_AS + 2u * (8u * ah + (uint32_t) e)) = ra[e];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t q = (uint32_t) tid + 256u * i, r = q >> 5, c4 = q & 31u;
+            *(float4*) (Bs + r * DH_CZ_BS + 4u * c4) = rb[i];
+        }
+    };
+    const int m = lane & 15, q = lane >> 4;
+    const float* ap = As + (64 * (w & 1) + m) * DH_CZ_AS + q;
+    const float* bp = Bs + q * DH_CZ_BS + 64 * (w >> 1) + m;
+    dh_f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] = dh_f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+    load(0);
+    stash();
+    __syncthreads();
+    for (uint32_t c = 0; c < nch; c++) {
+        if (c + 1 < nch) load(c + 1);
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            float a[4], b[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) { a[t] = ap[16 * t * DH_CZ_AS + 4 * s]; b[t] = bp[4 * s * DH_CZ_BS + 16 * t]; }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+        if (c + 1 < nch) stash();
+        __syncthreads();
+    }
+    const int g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const uint32_t row = row0 + 64u * (uint32_t) (w & 1) + 16u * i + 4u * (uint32_t) g + r;
+            if (row >= P.n_out) continue;
+#pragma unroll
+            for (int cg = 0; cg < 2; cg++) {
+                const uint32_t b = (col0 + 64u * (uint32_t) (w >> 1) + 32u * cg) / 2u + (uint32_t) m;
+                if (b < P.B) dh_cz_emit(P, row, b, acc[i][2 * cg][r], acc[i][2 * cg + 1][r]);
+            }
+        }
+#endif
+}
+
+__global__ __launch_bounds__(256) void k_cz_fm(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_out) return;
+    for (uint32_t b = blockIdx.y; b < B; b += gridDim.y) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_cz_tail(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock) {
+    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
+    if (b < B) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------- ABI hooks
@@ -1005,6 +1110,27 @@ static int dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* s
     }
     const unsigned grid = (unsigned) std::min<size_t>((n16 + 255) / 256, 2048);      // 256 CUs x 8 resident workgroups of 256
     hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(256), 0, (hipStream_t) stream, (const dh_u4s*) src, (dh_u4s*) dst, n16);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+
+static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream) {
+    const size_t n = H + n_in;
+    hipLaunchKernelGGL(k_cz_window, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, cur, prev, prev_n, in, cf32, H, n);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_cz_gemm(const DhCzParams& P, void* stream) {
+    if (!P.n_out) return DH_OK;
+    hipLaunchKernelGGL(k_cz_gemm, dim3((P.n_out + DH_CZ_TM - 1) / DH_CZ_TM, P.ncols / (2u * DH_CZ_TNC)), dim3(256), 0, (hipStream_t) stream, P);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream) {
+    if (!n_out) return DH_OK;
+    hipLaunchKernelGGL(k_cz_fm, dim3((n_out + 255) / 256, B < 65535u ? B : 65535u), dim3(256), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cz_tail, dim3((B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out, dcblock);
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }

@@ -21,9 +21,9 @@
 #include "../../include/digiham_amd.h"      // DH_FE_AUDIO_S16, DH_FE_IQ_S16
 #define DH_FE_STATE_WORDS 4            // per channel: x[n-1], y[n-1], I[n-1], Q[n-1] (the last two as floats holding int16 values)
 
-DH_HD float dh_fe_atan2_over_pi(int32_t im, int32_t re) {
-    if (re == 0 && im == 0) return 0.0f;
-    const float fre = (float) re, fim = (float) im;              // |values| < 2^31: one rounding each
+// the polynomial on float operands (the channelizer's FM discriminator feeds it float products); fre == fim == 0 -> 0
+DH_HD float dh_fe_atan2f_over_pi(float fim, float fre) {
+    if (fre == 0.0f && fim == 0.0f) return 0.0f;
     const float are = fre < 0.0f ? -fre : fre, aim = fim < 0.0f ? -fim : fim;
     const bool swap = aim > are;
     const float r = (swap ? are : aim) / (swap ? aim : are);
@@ -42,6 +42,10 @@ DH_HD float dh_fe_atan2_over_pi(int32_t im, int32_t re) {
     if (fre < 0.0f) a = 3.14159265358979323846f - a;
     if (fim < 0.0f) a = -a;
     return a * 0.31830988618379067154f;
+}
+
+DH_HD float dh_fe_atan2_over_pi(int32_t im, int32_t re) {
+    return dh_fe_atan2f_over_pi((float) im, (float) re);         // |values| < 2^31: one rounding each, and zero only for 0
 }
 
 // sample t of a channel before the DC blocker; (ip, qp) = the I / Q pair before it (from the state for t = 0)

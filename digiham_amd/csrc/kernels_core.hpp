@@ -5,6 +5,7 @@
 
 #include "dsp_core.hpp"
 #include "frontend_core.hpp"
+#include "channelizer_core.hpp"
 #include "decoder_core.hpp"
 
 // ---- engine state initialisation: what the reference's constructors leave behind ------------

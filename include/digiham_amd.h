@@ -267,6 +267,49 @@ int dh_frontend_s16(const int16_t* d_in, size_t in_stride, float* d_out, size_t 
                     size_t n_channels, size_t n, int mode, int dcblock, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Channelizer: ONE wideband complex stream -> n_channels rows at input_rate / decimation, a bank of digital down-converters
+ * (this library's own stage; the arithmetic, bit for bit, is specified in digiham_amd/csrc/channelizer_core.hpp).
+ * Channel b: NCO increment increments[b] = offset_b / input_rate * 2^32 (two's complement for negative offsets), the real
+ * low-pass taps[0..n_taps) rotated to the channel, output j at input index j * decimation + decimation - 1.
+ *   input_format  DH_CZ_CS16 interleaved int16 I / Q (scaled by 2^-15), DH_CZ_CF32 interleaved float32
+ *   output_mode   DH_CZ_IQ_F32 interleaved complex float rows, DH_CZ_FM arg(z[j] conj(z[j-1])) / pi (what dh_engine_push takes),
+ *                 dcblock != 0 (FM only): y = (x - x[-1]) + 0.995 y[-1] as in dh_frontend_s16
+ * Limits: 1 <= decimation <= 1024, 1 <= n_taps <= 16384 (finite), 1 <= n_channels <= 65536, 1 <= max_input <= 2^28.
+ * ---------------------------------------------------------------------- */
+enum { DH_CZ_CS16 = 1, DH_CZ_CF32 = 2 };
+enum { DH_CZ_IQ_F32 = 1, DH_CZ_FM = 2 };
+typedef struct dh_channelizer dh_channelizer;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(dh_channelizer_config) */
+    int32_t  device;
+    uint32_t n_channels;
+    uint32_t decimation;
+    const float* taps;             /* host, copied at create */
+    uint32_t n_taps;
+    const uint32_t* increments;    /* host [n_channels], copied at create */
+    int32_t  input_format;         /* DH_CZ_* */
+    int32_t  output_mode;          /* DH_CZ_* */
+    int32_t  dcblock;
+    uint32_t max_input;            /* complex samples per push */
+    void*    stream;               /* hipStream_t; NULL = default stream */
+} dh_channelizer_config;
+
+int  dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out);
+void dh_channelizer_destroy(dh_channelizer* c);
+/* back to sample 0: zero input history and channel states (taps and increments stay) */
+int  dh_channelizer_reset(dh_channelizer* c);
+/* channel `channel` takes `increment` from the next push on; its FM / DC-blocker state restarts, the input history stays */
+int  dh_channelizer_retune(dh_channelizer* c, uint32_t channel, uint32_t increment);
+/* n_in (<= max_input, any length, 0 included) complex samples; *n_out = outputs completed by this push, known without a
+ * sync.  d_out [n_channels][out_stride] (out_stride in output samples: complex pairs for IQ_F32, floats for FM, >= *n_out)
+ * receives them.  Asynchronous on the channelizer's stream. */
+int  dh_channelizer_push(dh_channelizer* c, const void* d_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out);
+/* the same from host memory (staged through a device buffer; returns once the input has been read) */
+int  dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out);
+/* the NCO phasor P(phi) of the specification for n host phase words -> h_out [n][2] (host arithmetic, for tests) */
+int  dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n);
+
+/* ------------------------------------------------------------------------
  * Diagnostics: the RRC output scaling `(float)((double)sum / gain)` of
  * src/rrc_filter/rrc_filter.cpp:33 exactly as the FIR kernels evaluate it
  * (reciprocal multiply + exact-division fallback near float rounding ties).
