@@ -3,7 +3,8 @@
 // CPU test harness (DH_BACKEND = lane-loop backend -> tests/host_harness/libdh_hostemu.so, never
 // shipped and never loaded by the digiham_amd package).
 //
-// Before inclusion the includer defines DH_BACKEND and these free functions:
+// Before inclusion the includer defines DH_BACKEND (the duck-typed interface listed in engine_impl.hpp; which instantiation
+// a launch_* runs is not the backend's to decide: launch_plan.hpp) and these free functions:
 //   int  dh_be_device_count();
 //   const char* dh_be_last_error();
 //   int  dh_be_alloc(int device, size_t bytes, void** out); int dh_be_free(void*);
@@ -14,6 +15,13 @@
 //   int  dh_be_crc16(const uint8_t* in, size_t stride, int count, uint16_t* out, size_t n, void* stream);
 //   int  dh_be_whitening(const uint8_t* in, uint8_t* out, size_t stride, int n_bits, size_t n, void* stream);
 //   int  dh_be_dvfilter(const int16_t* in, int16_t* out, float* state, size_t B, size_t stride, size_t n, void* stream);
+//   int  dh_be_div_gain(const float* in, float* out, size_t n, int narrow, void* stream);
+//   int  dh_be_div_const(const float* in, float* out, size_t n, unsigned divisor, void* stream);
+//   int  dh_be_frontend(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock, void* stream);
+//   int  dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, float* d, size_t tiles, void* stream);
+//   int  dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* stream);
+//   int  dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream);
+//   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_fm: the channelizer's launches, listed where they are used (below)
 #pragma once
 
 #include "engine_impl.hpp"

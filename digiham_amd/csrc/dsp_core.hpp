@@ -2026,7 +2026,7 @@ DH_COLD void dh_settle_doubts(const DhDspParams& P, DhDspShared& S, DhBoundState
 // push and appends its symbols behind the sym_base symbols the earlier parts produced (a part is a push: results do not
 // depend on where pushes end).
 // LV = 4 / 2: the number of levels is known where the kernel is instantiated (the chain kernels: 4 for DMR / YSF / NXDN, 2 for
-// D-Star; engine.hip checks P.levels against it) and the other slicer's selects, its invert mask and two scalar register
+// D-Star; dh_plan_chain, launch_plan.hpp, checks P.levels against it) and the other slicer's selects, its invert mask and two scalar register
 // pairs drop out of the slicing phase; 0 = taken from P.levels.
 // KEEPF (DH_FLAG_KEEP_FILTERED | DH_FLAG_ONE_LAUNCH): the run's filtered samples also leave, from where they stand in LDS -- 1: those of the
 // split-f16 product (2.5e-6 of the reference's); 2 (with DH_FLAG_FAST_FIR): the error-bounded kernel filters with the f32 FMA chain instead

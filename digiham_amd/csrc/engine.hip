@@ -18,6 +18,7 @@
 
 #include "../../include/digiham_amd.h"
 #include "kernels_core.hpp"
+#include "launch_plan.hpp"
 #include "fec_tables.hpp"
 #include "rrc_taps.h"
 
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
         while (part < last_part && bid >= P.split_pad) { part++; bid -= P.split_pad; }
         if (bid >= P.n_channels) return;                // padding between the parts of the grid
         part_lo = part == 0 ? 0u : part == 1 ? P.split_n0 : P.split_n1;
-        part_hi = part == 0 ? P.split_n0 : (part == 1 && P.split_n1) ? P.split_n1 : 0xFFFFFFFFu;
+        part_hi = part == 0 ? P.split_n0 : (part == 1 && P.split_n1) ? P.split_n1 : 0xFFFFFFFFu;       // (= dh_part_lo / dh_part_hi, launch_plan.hpp)
     }
     const uint32_t ch = bid + P.ch_base;
     // flag word: epoch of the push (24 bits) | parts written back << 24 | a later part gave up << 26 | XCC id << 28
@@ -133,7 +134,9 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
     }
     {
         DhDspShared L = dh_dsp_carve(dh_smem, SPS ? (uint32_t) SPS : P.sps, NZ);
-        dh_rrc_demod_channel<NZ, FAST, SPS, (PROTO == DH_PROTO_DSTAR ? 2 : 4)>(P, ch, L, part_lo, part_hi, sym_base);      // (launch_chain checked P.levels)
+        constexpr int LV = PROTO == DH_PROTO_DSTAR ? 2 : 4;
+        static_assert(LV == DhChainInst<NZ, FAST, PROTO, SPS>::LV, "the plan routes by these levels (launch_plan.hpp)");
+        dh_rrc_demod_channel<NZ, FAST, SPS, LV>(P, ch, L, part_lo, part_hi, sym_base);      // (dh_plan_chain checked P.levels)
     }
     // This wavefront's symbol / count stores are read back by its own decoder half below: a WORKGROUP-scope fence (part of
     // __syncthreads) orders them.  A device-scope __threadfence() here made every wavefront write back its XCD's L2 --
@@ -538,15 +541,9 @@ struct HipBackend {
         if (lds < 0) { g_last_error = "the device does not return unaligned 8 / 16-byte LDS reads whole (LDS alignment mode): the slicer kernels need it"; return DH_EDEVICE; }
         if (lds == 0) { g_last_error = why ? why : "the LDS alignment probe could not run"; return DH_EDEVICE; }
         if (!tail_split_probe()) tail_split_pct = 0;              // workgroup i does not run on XCD i mod 8 here (another part, a partitioned one): one workgroup per channel
-        if (const char* e = std::getenv("DH_TAIL_SPLIT_FORCE_FAIL")) tail_split_force_fail = (uint32_t) std::strtoul(e, nullptr, 10);     // tests: see DhDspParams
-        if (const char* e = std::getenv("DH_TAIL_SPLIT")) {       // "80" or "75,93" (percent of a push where the second / third workgroup of a channel starts), "0" = off
-            char* end = nullptr;
-            const long v = std::strtol(e, &end, 10), w = end && *end == ',' ? std::strtol(end + 1, nullptr, 10) : 0;
-            if (tail_split_pct) {                   // (the probe's verdict stands: the environment can only move the split point, or switch it off)
-                tail_split_pct = v > 0 && v < 100 ? (uint32_t) v : 0u;
-                tail_split_pct2 = tail_split_pct && w > v && w < 100 ? (uint32_t) w : 0u;
-            }
-        }
+        const DhTailSplitEnv env = dh_tail_split_env();          // DH_TAIL_SPLIT, DH_TAIL_SPLIT_FORCE_FAIL (launch_plan.hpp)
+        tail_split_force_fail = env.force_fail;
+        if (env.set && tail_split_pct) { tail_split_pct = env.pct; tail_split_pct2 = env.pct2; }     // (the probe's verdict stands: the environment can only move the split point, or switch it off)
         return DH_OK;
     }
     void drop_timing_events() {
@@ -758,19 +755,9 @@ struct HipBackend {
         hipLaunchKernelGGL((k_rrc_demod<NZ, FAST, SPS, KEEPF>), dim3(P.n_channels), dim3(DH_WAVE), lds, ms(), P);
         return launched("k_rrc_demod");
     }
+    // (which instantiation serves which configuration: launch_plan.hpp, for this backend and the CPU harness alike)
     int launch_rrc_demod(const DhDspParams& P, uint32_t nz, bool fast) {
-        // (engine_impl.hpp: only this pipe asks for it; `fast` here = the floats of the f32 FMA chain, dsp_core.hpp KEEPF = 2)
-        if (P.filt_out) return (P.sps == 10 && nz == 80) ? (fast ? go_rrc_demod<80, false, 10, 2>(P) : go_rrc_demod<80, false, 10, 1>(P)) : -1;
-        if (P.sps == 10) {                      // DMR / YSF: specialised symbol loops
-            if (nz == 0) return go_rrc_demod<0, false, 10>(P);
-            if (nz == 80) return fast ? go_rrc_demod<80, true, 10>(P) : go_rrc_demod<80, false, 10>(P);
-        }
-        if (nz == 0 && P.sps == 40) return go_rrc_demod<0, false, 40>(P);       // fsk_demodulator -s 40 (POCSAG): the generic code with the constant folded in
-        if (nz == 160 && P.sps == 20 && !fast) return go_rrc_demod<160, false, 20>(P);      // rrc_filter -n | gfsk_demodulator -s 20 (NXDN48)
-        if (nz == 0) return go_rrc_demod<0, false, 0>(P);
-        if (nz == 80) return fast ? go_rrc_demod<80, true, 0>(P) : go_rrc_demod<80, false, 0>(P);
-        if (nz == 160) return fast ? go_rrc_demod<160, true, 0>(P) : go_rrc_demod<160, false, 0>(P);
-        return -1;
+        return dh_plan_rrc_demod(P, nz, fast, [&](auto i) { using I = decltype(i); return go_rrc_demod<I::NZ, I::FAST, I::SPS, I::KEEPF>(P); });
     }
     template <int NZ, bool FAST, int PROTO, int SPS = 10, bool MAY_SPLIT = false> int go_chain(const DhDspParams& P, const DhDecParams& D) {
         size_t lds = dh_dsp_shared_bytes(SPS ? (uint32_t) SPS : P.sps, NZ);
@@ -808,8 +795,7 @@ struct HipBackend {
             // two prologues.
             if (tail_split_pct > 0 && P.n_channels >= DH_TAIL_SPLIT_MIN_CHANNELS && P.n >= DH_TAIL_SPLIT_MIN_SAMPLES) {
                 DhDspParams Q = P;
-                Q.split_n0 = (uint32_t) ((uint64_t) P.n * tail_split_pct / 100u);
-                Q.split_n1 = tail_split_pct2 > tail_split_pct ? (uint32_t) ((uint64_t) P.n * tail_split_pct2 / 100u) : 0u;
+                dh_tail_split_points(P.n, tail_split_pct, tail_split_pct2, Q.split_n0, Q.split_n1);
                 Q.split_pad = (P.n_channels + 7u) & ~7u;
                 part_epoch = (part_epoch % 0x00FFFFFEu) + 1u;
                 Q.part_epoch = part_epoch;
@@ -829,17 +815,7 @@ struct HipBackend {
     }
     // 1 = not available for this configuration (the caller launches the two stages separately), 0 = launched
     int launch_chain(const DhDspParams& P, const DhDecParams& D, uint32_t nz, bool fast, int proto) {
-        if (P.levels != (proto == DH_PROTO_DSTAR ? 2 : 4)) return 1;        // the chain kernels are built for their pipe's slicer (k_chain); anything else runs as two launches
-        if (proto == DH_PROTO_NXDN && nz == 160 && !fast && P.sps == 20) return go_chain<160, false, DH_PROTO_NXDN, 20, true>(P, D);   // rrc_filter -n | gfsk_demodulator -s 20 | nxdn_decoder
-        if (proto == DH_PROTO_NXDN && nz == 160 && !fast) return go_chain<160, false, DH_PROTO_NXDN, 0, true>(P, D);    // (any other samples-per-symbol)
-        // (POCSAG stays on two launches: measured 9.5 ms chained against 8.9 ms split at 16 384 channels)
-        if (P.sps != 10) return 1;
-        if (proto == DH_PROTO_DSTAR && nz == 0) return go_chain<0, false, DH_PROTO_DSTAR, 10, true>(P, D);    // fsk_demodulator -s 10 | dstar_decoder
-        if ((nz != 0 && nz != 80) || (proto != DH_PROTO_DMR && proto != DH_PROTO_YSF)) return 1;
-        const bool dmr = proto == DH_PROTO_DMR;
-        if (nz == 0) return dmr ? go_chain<0, false, DH_PROTO_DMR>(P, D) : go_chain<0, false, DH_PROTO_YSF>(P, D);
-        if (fast) return dmr ? go_chain<80, true, DH_PROTO_DMR>(P, D) : go_chain<80, true, DH_PROTO_YSF>(P, D);
-        return dmr ? go_chain<80, false, DH_PROTO_DMR, 10, true>(P, D) : go_chain<80, false, DH_PROTO_YSF, 10, true>(P, D);     // the headline pipes
+        return dh_plan_chain(P, nz, fast, proto, [&](auto i) { using I = decltype(i); return go_chain<I::NZ, I::FAST, I::PROTO, I::SPS, I::MAY_SPLIT>(P, D); });
     }
     template <int NZ, bool FAST> int go_rrc_tiles(const DhRrcParams& R) {
         const uint32_t tiles = (R.n + DH_FTILE - 1) / DH_FTILE;
@@ -855,9 +831,7 @@ struct HipBackend {
         return 0;
     }
     int launch_rrc_tiles(const DhRrcParams& R, uint32_t nz, bool fast) {
-        if (nz == 80) return fast ? go_rrc_tiles<80, true>(R) : go_rrc_tiles<80, false>(R);
-        if (nz == 160) return fast ? go_rrc_tiles<160, true>(R) : go_rrc_tiles<160, false>(R);
-        return -1;
+        return dh_plan_rrc_tiles(nz, fast, [&](auto i) { using I = decltype(i); return go_rrc_tiles<I::NZ, I::FAST>(R); });
     }
     int launch_rrc_generic(const DhRrcGenParams& G) {
         for (uint32_t b0 = 0; b0 < G.n_channels; b0 += 65535u) {      // channels on grid.y: at most 65 535 per launch

@@ -4,6 +4,8 @@
 // 64-iteration loop, DH_BARRIER a no-op, "device memory" is the host heap and a "kernel launch"
 // is a loop over workgroups.  It exports the same C ABI as libdigiham_amd.so so the CPU-only test
 // tier can run the engine's orchestration and the exact wave algorithms against the oracle.
+// Which instantiation serves which configuration comes from digiham_amd/csrc/launch_plan.hpp, as
+// on the device: every route the device chains or splits is chained or split here.
 // It is built into tests/host_harness/libdh_hostemu.so, is never installed, and the digiham_amd
 // package has no code path that loads it: the product fails loudly without the gfx950 library.
 #include <stdlib.h>
@@ -13,6 +15,7 @@
 
 #include "../../include/digiham_amd.h"
 #include "../../digiham_amd/csrc/kernels_core.hpp"
+#include "../../digiham_amd/csrc/launch_plan.hpp"
 #include "../../digiham_amd/csrc/fec_tables.hpp"
 #include "../../digiham_amd/csrc/rrc_taps.h"
 
@@ -49,35 +52,27 @@ struct HostBackend {
     int timing_read_split(float*, uint32_t*, uint32_t* n) { *n = 0; return 0; }
     bool overlap_pushes = false;                     // (a property of the GPU dispatcher; nothing to emulate)
 
-    template <int NZ, bool FAST, int SPS, int KEEPF = 0> static void run_rrc_demod(const DhDspParams& P) {
-        std::vector<float> lds(dh_dsp_shared_bytes(P.sps, NZ) / sizeof(float));     // exactly the device allocation
-        DhDspShared S = dh_dsp_carve(lds.data(), P.sps, NZ);
-        for (uint32_t ch = 0; ch < P.n_channels; ch++) dh_rrc_demod_channel<NZ, FAST, SPS, 0, KEEPF>(P, ch, S);
+    // Which instantiation serves which configuration is launch_plan.hpp's to say, for this backend as for the device's:
+    // the run_* below are what go_* are in engine.hip, one instantiation each.
+    template <class I> static int run_rrc_demod(const DhDspParams& P) {
+        std::vector<float> lds(dh_dsp_shared_bytes(P.sps, I::NZ) / sizeof(float));     // exactly the device allocation
+        DhDspShared S = dh_dsp_carve(lds.data(), P.sps, I::NZ);
+        for (uint32_t ch = 0; ch < P.n_channels; ch++) dh_rrc_demod_channel<I::NZ, I::FAST, I::SPS, 0, I::KEEPF>(P, ch, S);
+        return 0;
     }
     int launch_rrc_demod(const DhDspParams& P, uint32_t nz, bool fast) {
-        if (P.filt_out) { if (P.sps == 10 && nz == 80) { if (fast) run_rrc_demod<80, false, 10, 2>(P); else run_rrc_demod<80, false, 10, 1>(P); return 0; } return -1; }
-        if (P.sps == 10 && nz == 0) run_rrc_demod<0, false, 10>(P);
-        else if (P.sps == 10 && nz == 80) { if (fast) run_rrc_demod<80, true, 10>(P); else run_rrc_demod<80, false, 10>(P); }
-        else if (nz == 0 && P.sps == 40) run_rrc_demod<0, false, 40>(P);                 // the same instantiations as engine.hip
-        else if (nz == 160 && P.sps == 20 && !fast) run_rrc_demod<160, false, 20>(P);
-        else if (nz == 0) run_rrc_demod<0, false, 0>(P);
-        else if (nz == 80) { if (fast) run_rrc_demod<80, true, 0>(P); else run_rrc_demod<80, false, 0>(P); }
-        else if (nz == 160) { if (fast) run_rrc_demod<160, true, 0>(P); else run_rrc_demod<160, false, 0>(P); }
-        else return -1;
-        return 0;
+        return dh_plan_rrc_demod(P, nz, fast, [&](auto i) { return run_rrc_demod<decltype(i)>(P); });
     }
-    template <int NZ, bool FAST> static void run_rrc_tiles(const DhRrcParams& R) {
-        std::vector<float> lds(dh_dsp_shared_bytes(0, NZ) / sizeof(float));
-        DhDspShared S = dh_dsp_carve(lds.data(), 0, NZ);
+    template <class I> static int run_rrc_tiles(const DhRrcParams& R) {
+        std::vector<float> lds(dh_dsp_shared_bytes(0, I::NZ) / sizeof(float));
+        DhDspShared S = dh_dsp_carve(lds.data(), 0, I::NZ);
         const uint32_t tiles = (R.n + DH_FTILE - 1) / DH_FTILE;
         for (uint32_t ch = 0; ch < R.n_channels; ch++)
-            for (uint32_t t = 0; t < tiles; t++) dh_rrc_tile<NZ, FAST>(R, ch, t, S);
+            for (uint32_t t = 0; t < tiles; t++) dh_rrc_tile<I::NZ, I::FAST>(R, ch, t, S);
+        return 0;
     }
     int launch_rrc_tiles(const DhRrcParams& R, uint32_t nz, bool fast) {
-        if (nz == 80) { if (fast) run_rrc_tiles<80, true>(R); else run_rrc_tiles<80, false>(R); }
-        else if (nz == 160) { if (fast) run_rrc_tiles<160, true>(R); else run_rrc_tiles<160, false>(R); }
-        else return -1;
-        return 0;
+        return dh_plan_rrc_tiles(nz, fast, [&](auto i) { return run_rrc_tiles<decltype(i)>(R); });
     }
     int launch_rrc_generic(const DhRrcGenParams& G) {
         static float win[DH_GEN_WINDOW], taps[DH_MAX_NZ + 1];
@@ -90,51 +85,45 @@ struct HostBackend {
         for (uint32_t ch = 0; ch < B; ch++) dh_rrc_hist_channel(hist, in, in_stride, n, n_per, nz, ch, sh);
         return 0;
     }
+    // One chain instantiation, in the device kernel's order of work: channel by channel, slicer then decoder.
+    // The tail split of the device's chain launches (engine.hip, k_chain), on every route the device splits: DH_TAIL_SPLIT
+    // = percent of a push where the later parts start, in launch_plan.hpp's grammar and bounds.  The policy is this
+    // backend's own -- split whenever the variable is set and the push has two samples, the first part at least one (the
+    // tests are far below the device's thresholds).  Here the parts of a channel simply run one after the other: what
+    // is exercised is the part arithmetic of the kernel bodies (offsets into the rows, appended symbols / frames / events).
+    template <class I> static int run_chain(const DhDspParams& P, const DhDecParams& D) {
+        const uint32_t sps = I::SPS ? (uint32_t) I::SPS : P.sps;
+        std::vector<float> lds(dh_dsp_shared_bytes(sps, I::NZ) / sizeof(float));
+        DhDspShared S = dh_dsp_carve(lds.data(), sps, I::NZ);
+        DhDecShared* DS = new DhDecShared;
+        const DhTailSplitEnv env = dh_tail_split_env();
+        uint32_t n0 = 0, n1 = 0;
+        if (I::MAY_SPLIT && env.pct && P.n >= 2) {
+            dh_tail_split_points(P.n, env.pct, env.pct2, n0, n1);
+            n0 = std::max<uint32_t>(1u, n0);
+            n1 = env.pct2 ? std::max<uint32_t>(n0, n1) : 0u;
+        }
+        const uint32_t parts = n0 ? (n1 ? 3u : 2u) : 1u;
+        for (uint32_t ch = 0; ch < P.n_channels; ch++)
+            for (uint32_t part = 0; part < parts; part++) {
+                const uint32_t sym_base = part ? P.sym_count[ch] : 0u;
+                // DH_TAIL_SPLIT_FORCE_FAIL = k: the later parts of the channels with ch % k == 1 "fail" their hand-over, and what the
+                // device's fix-up launch does is done here -- the rest of the row in one piece behind the first part
+                const bool fixup = env.force_fail && ch % env.force_fail == 1u && part;
+                const uint32_t hi = parts == 1u || fixup ? 0xFFFFFFFFu : dh_part_hi(part, n0, n1);
+                dh_rrc_demod_channel<I::NZ, I::FAST, I::SPS, I::LV>(P, ch, S, dh_part_lo(part, n0, n1), hi, sym_base);
+                dh_decode_channel(I::PROTO, D, ch, *DS, sym_base, part != 0);
+                if (fixup) break;
+            }
+        delete DS;
+        return 0;
+    }
     int launch_chain(const DhDspParams& P, const DhDecParams& D, uint32_t nz, bool fast, int proto) {
-        // same order of work as the device kernel: channel by channel, slicer then decoder
-        if (P.sps != 10 || (nz != 0 && nz != 80) || (proto != DH_PROTO_DMR && proto != DH_PROTO_YSF)) return 1;
-        // the tail split of the device's chain launches (engine.hip, k_chain): DH_TAIL_SPLIT = percent of a push the first
-        // part takes.  Here the two parts of a channel simply run one after the other -- what is exercised is the part
-        // arithmetic of the kernel bodies (offsets into the rows, appended symbols / frames / events).
-        uint32_t pct = 0, pct2 = 0;
-        if (const char* e = getenv("DH_TAIL_SPLIT")) {
-            char* end = nullptr;
-            const long v = strtol(e, &end, 10), w = end && *end == ',' ? strtol(end + 1, nullptr, 10) : 0;
-            pct = v > 0 && v < 100 ? (uint32_t) v : 0u; pct2 = pct && w > v && w < 100 ? (uint32_t) w : 0u;
-        }
-        if (pct && nz == 80 && !fast && P.n >= 2) {
-            const uint32_t b0 = std::max<uint32_t>(1u, (uint32_t) ((uint64_t) P.n * pct / 100u));
-            const uint32_t b1 = pct2 ? std::max<uint32_t>(b0, (uint32_t) ((uint64_t) P.n * pct2 / 100u)) : 0u;
-            const uint32_t lo[3] = { 0u, b0, b1 }, hi[3] = { b0, b1 ? b1 : 0xFFFFFFFFu, 0xFFFFFFFFu };
-            std::vector<float> lds(dh_dsp_shared_bytes(P.sps, 80) / sizeof(float));
-            DhDspShared S = dh_dsp_carve(lds.data(), P.sps, 80);
-            DhDecShared* DS = new DhDecShared;
-            // DH_TAIL_SPLIT_FORCE_FAIL = k: the later parts of the channels with ch % k == 1 "fail" their hand-over, and what the
-            // device's fix-up launch does is done here -- the rest of the row in one piece behind the first part
-            const uint32_t force = getenv("DH_TAIL_SPLIT_FORCE_FAIL") ? (uint32_t) strtoul(getenv("DH_TAIL_SPLIT_FORCE_FAIL"), nullptr, 10) : 0u;
-            for (uint32_t ch = 0; ch < P.n_channels; ch++)
-                for (uint32_t part = 0; part < (b1 ? 3u : 2u); part++) {
-                    const uint32_t sym_base = part ? P.sym_count[ch] : 0u;
-                    if (force && ch % force == 1u && part) {
-                        dh_rrc_demod_channel<80, false, 10>(P, ch, S, lo[1], 0xFFFFFFFFu, sym_base);
-                        if (proto == DH_PROTO_DMR) dh_dmr_channel(D, ch, *DS, sym_base, true); else dh_ysf_channel(D, ch, *DS, sym_base, true);
-                        break;
-                    }
-                    dh_rrc_demod_channel<80, false, 10>(P, ch, S, lo[part], hi[part], sym_base);
-                    if (proto == DH_PROTO_DMR) dh_dmr_channel(D, ch, *DS, sym_base, part != 0); else dh_ysf_channel(D, ch, *DS, sym_base, part != 0);
-                }
-            delete DS;
-            return 0;
-        }
-        if (launch_rrc_demod(P, nz, fast)) return -1;
-        return launch_decoder(D, proto) ? -1 : 0;
+        return dh_plan_chain(P, nz, fast, proto, [&](auto i) { return run_chain<decltype(i)>(P, D); });
     }
     int launch_decoder(const DhDecParams& P, int proto) {
         DhDecShared* S = new DhDecShared;
-        for (uint32_t ch = 0; ch < P.n_channels; ch++) {
-            if (proto == DH_PROTO_DMR) dh_dmr_channel(P, ch, *S); else if (proto == DH_PROTO_YSF) dh_ysf_channel(P, ch, *S); else if (proto == DH_PROTO_NXDN) dh_nxdn_channel(P, ch, *S);
-            else if (proto == DH_PROTO_POCSAG) dh_pocsag_channel(P, ch, *S); else dh_dstar_channel(P, ch, *S);
-        }
+        for (uint32_t ch = 0; ch < P.n_channels; ch++) dh_decode_channel(proto, P, ch, *S);
         delete S;
         return 0;
     }

@@ -3,8 +3,9 @@
 A launch of one workgroup per channel drains for about one workgroup's duration; the chain kernels therefore hand the
 last part of every row to a second workgroup of the same launch, which starts from the state the first one wrote back and
 appends its symbols, frames and events.  A part is a push, so nothing may change: these tests compare split launches with
-whole ones and with the oracle -- on the CPU tier through the wave emulation (tests/host_harness/harness.cpp runs the two
-parts of a channel one after the other: the part arithmetic of the kernel bodies), on the GPU at a size where the
+whole ones and with the oracle -- on the CPU tier through the wave emulation (tests/host_harness/harness.cpp runs the
+parts of a channel one after the other, on every route the device splits -- DMR, YSF, NXDN, D-Star, taken from the same
+launch_plan.hpp: the part arithmetic of the kernel bodies), on the GPU at a size where the
 engine really splits (>= 8192 channels, >= 65536 samples per push), with a channel count that is not a multiple of 8
 (the grid is padded), ragged counts on both sides of the split point and a short push (not split) in between.
 """
@@ -14,7 +15,26 @@ import numpy as np
 import pytest
 
 from common import make_channels
-from digiham_amd import api
+from digiham_amd import api, synth, _taps
+
+# engine and oracle arguments of the pipes whose chain launch the device splits (launch_plan.hpp: MAY_SPLIT)
+PIPES = {"dmr": ({}, {}), "ysf": ({}, {}),
+         "nxdn": (dict(rrc="narrow", sps=20), dict(rrc=2, sps=20)),
+         "dstar": (dict(rrc="none", demod="fsk", sps=10), dict(rrc=0, levels=2, sps=10))}
+
+
+def _channels(proto, seeds):
+    if proto in ("dmr", "ysf"):
+        return make_channels(proto, seeds, 10)
+    chans = []
+    for i, seed in enumerate(seeds):                # (the signals of test_nxdn.py / test_dstar.py)
+        if proto == "nxdn":
+            x = synth.shape(synth.nxdn_stream(seed, 14), sps=20, taps=_taps.narrow())
+        else:
+            x = synth.fsk_shape(synth.dstar_stream(seed, 3)[0], sps=10)
+        chans.append(synth.impair(x, seed, snr_db=[None, 22, 16, 20][i % 4], dc=[0, 0.1, -0.2, 0.05][i % 4], delay=7 * i, gain=[1, 0.5, 1.7, 0.6][i % 4]))
+    n = min(len(c) for c in chans)
+    return np.stack([c[:n] for c in chans])
 
 
 def _collect(eng, B, acc):
@@ -23,18 +43,19 @@ def _collect(eng, B, acc):
             acc[k][b].append(rows[b, :counts[b]].copy())
 
 
-@pytest.mark.parametrize("proto,oproto", [("dmr", 1), ("ysf", 2)])
+@pytest.mark.parametrize("proto,oproto", [("dmr", 1), ("ysf", 2), ("nxdn", 3), ("dstar", 5)])
 @pytest.mark.parametrize("pct", ["1", "37", "75", "99", "40,90", "80,81", "75:fail", "40,90:fail"])
 def test_split_pushes_on_the_wave_emulation(emu_ctx, oracle, monkeypatch, proto, oproto, pct):
-    x = make_channels(proto, [31, 32, 33, 34], 10)
+    kw, okw = PIPES[proto]
+    x = _channels(proto, [31, 32, 33, 34])
     B, n = x.shape
-    ref = oracle.chain(x, proto=oproto)
+    ref = oracle.chain(x, proto=oproto, **okw)
     if pct.endswith(":fail"):                   # channels 1 and 3 lose their hand-over: the rest of the row in one piece (the fix-up launch's arithmetic)
         pct = pct[:-5]
         monkeypatch.setenv("DH_TAIL_SPLIT_FORCE_FAIL", "2")
     monkeypatch.setenv("DH_TAIL_SPLIT", str(pct))
     cap = 20000
-    eng = api.Engine(B, cap, proto=proto, ctx=emu_ctx)
+    eng = api.Engine(B, cap, proto=proto, ctx=emu_ctx, **kw)
     rng = np.random.default_rng(len(pct) + int(pct.split(",")[0]))
     acc = [[[] for _ in range(B)] for _ in range(3)]
     pos = np.zeros(B, np.int64)
