@@ -32,6 +32,12 @@ class ChannelizerConfig(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class ChannelizerPowerConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_uint32), ("open_level", C.c_float), ("close_level", C.c_float),
+                ("hang_blocks", C.c_uint32), ("d_power", C.c_void_p), ("d_gate", C.c_void_p), ("d_counts", C.c_void_p),
+                ("stride", C.c_size_t)]
+
+
 CZ_INPUT = {"cs16": 1, "cf32": 2}
 CZ_OUTPUT = {"iq": 1, "fm": 2}
 
@@ -88,6 +94,9 @@ def declare(L, lenient=False):
         "dh_channelizer_reset": [vp], "dh_channelizer_retune": [vp, u32, u32],
         "dh_channelizer_push": [vp, vp, sz, vp, sz, C.POINTER(sz)], "dh_channelizer_push_host": [vp, vp, sz, vp, sz, C.POINTER(sz)],
         "dh_channelizer_phasor": [vp, vp, sz],
+        "dh_channelizer_power_enable": [vp, C.POINTER(ChannelizerPowerConfig)],
+        "dh_channelizer_set_squelch": [vp, C.c_float, C.c_float, u32],
+        "dh_channelizer_power_last": [vp, C.POINTER(C.c_uint64), C.POINTER(sz)],
     }
     for name, args in sig.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
@@ -113,7 +122,8 @@ EXPORTED_SYMBOLS = [
     "dh_engine_read_frames", "dh_engine_read_events", "dh_engine_read_filtered", "dh_engine_sync",
     "dh_engine_timing_enable", "dh_engine_timing_read", "dh_engine_timing_read_split", "dh_engine_timing_stats", "dh_engine_debug_header",
     "dh_channelizer_create", "dh_channelizer_destroy", "dh_channelizer_reset", "dh_channelizer_retune", "dh_channelizer_push",
-    "dh_channelizer_push_host", "dh_channelizer_phasor",
+    "dh_channelizer_push_host", "dh_channelizer_phasor", "dh_channelizer_power_enable", "dh_channelizer_set_squelch",
+    "dh_channelizer_power_last",
 ]
 
 _LIB = None

@@ -415,7 +415,9 @@ class Channelizer:
     specified in digiham_amd/csrc/channelizer_core.hpp).  input "cs16" (int16 I / Q pairs) or "cf32" (float32 pairs, or
     complex64); output "fm" (discriminator audio for Engine.push, optionally DC-blocked) or "iq" (complex rows).
     push(x) returns (rows, n_out): rows is the channelizer's own device array [B][max_input // D + 1] (x 2 for "iq"),
-    valid in [:, :n_out] until the next push."""
+    valid in [:, :n_out] until the next push.
+    enable_power(...) adds per-channel block power and a squelch gate: after every push `counts` (device uint32 [B]) is what
+    Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed."""
 
     def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
                  ctx=None, device=0):
@@ -436,6 +438,36 @@ class Channelizer:
         self.out_stride = self.max_input // self.D + 1
         self.rows = mem.zeros((self.B, self.out_stride) if output == "fm" else (self.B, self.out_stride, 2), np.float32)
         self._keep = None
+        self.block, self.power, self.gate, self.counts = 0, None, None, None
+
+    @staticmethod
+    def _level(db):
+        return 0.0 if db is None else float(10.0 ** (float(db) / 10.0))
+
+    def enable_power(self, block=480, open_db=None, close_db=None, hang_blocks=0):
+        """Block power over `block` outputs and the squelch gate (before the first push, or right after reset()).  Levels in dB
+        relative to |z|^2 = 1 -- a full-scale CS16 tone through unity-gain taps is 0 dB; None: level 0.0 (with both None
+        every channel passes: power only)."""
+        mem, block = self.ctx.mem, int(block)
+        if block < 1:
+            raise DhError(_capi.DH_EINVAL, "dh_channelizer_power_enable", "block < 1")
+        stride = self.out_stride // block + 1
+        power, gate = mem.zeros((self.B, stride), np.float32), mem.zeros((self.B, stride), np.uint8)
+        counts = mem.zeros((self.B,), np.uint32)
+        cfg = _capi.ChannelizerPowerConfig(C.sizeof(_capi.ChannelizerPowerConfig), block, self._level(open_db), self._level(close_db),
+                                           int(hang_blocks), mem.ptr(power), mem.ptr(gate), mem.ptr(counts), stride)
+        _check(self.ctx.lib.dh_channelizer_power_enable(self._h, C.byref(cfg)), "dh_channelizer_power_enable", self.ctx.lib)
+        self.block, self.power, self.gate, self.counts = block, power, gate, counts
+
+    def set_squelch(self, open_db, close_db, hang_blocks):
+        _check(self.ctx.lib.dh_channelizer_set_squelch(self._h, self._level(open_db), self._level(close_db), int(hang_blocks)),
+               "dh_channelizer_set_squelch", self.ctx.lib)
+
+    def power_blocks(self):
+        """(power[:, :n], gate[:, :n], first_block) of the last push, device arrays: column i is block first_block + i."""
+        first, n = C.c_uint64(0), C.c_size_t(0)
+        _check(self.ctx.lib.dh_channelizer_power_last(self._h, C.byref(first), C.byref(n)), "dh_channelizer_power_last", self.ctx.lib)
+        return self.power[:, :n.value], self.gate[:, :n.value], first.value
 
     def close(self):
         if getattr(self, "_h", None):

@@ -237,6 +237,7 @@ int dh_engine_sync(dh_engine* e) {
 //   dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream);
 //   dh_be_cz_gemm(const DhCzParams& P, void* stream);
 //   dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream);
+//   dh_be_cz_power(const DhCzPowerParams& P, void* stream);      (only with power enabled: block power, then the gate and the counts)
 // (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
 // window is the last H = T' - 1 samples of the previous one followed by the new samples.
 struct dh_channelizer {
@@ -256,16 +257,24 @@ struct dh_channelizer {
     int cur = 0;
     uint32_t prev_n = 0;
     uint64_t n0 = 0;                                    // samples pushed since create / reset
+    // block power and gate (dh_channelizer_power_enable); pw_L = 0: off, nothing allocated and nothing launched
+    uint32_t pw_L = 0, pw_hang = 0;
+    float pw_inv = 0.0f, pw_open = 0.0f, pw_close = 0.0f;
+    float* pw_power = nullptr; uint8_t* pw_gate = nullptr; uint32_t* pw_counts = nullptr;      // the caller's
+    size_t pw_stride = 0;
+    uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
+    uint64_t pw_first = 0; size_t pw_n = 0;             // blocks completed by the last push
 
     void release() {
-        for (void* p : { (void*) d_tables, (void*) d_inc, (void*) d_bmat, (void*) d_win[0], (void*) d_win[1], (void*) d_state, (void*) d_zbuf, d_stage })
+        for (void* p : { (void*) d_tables, (void*) d_inc, (void*) d_bmat, (void*) d_win[0], (void*) d_win[1], (void*) d_state, (void*) d_zbuf, d_stage, (void*) d_pstate })
             if (p) be.free(p);
     }
     size_t in_bytes() const { return cf32 ? 8u : 4u; }
     size_t win_bytes() const { return sizeof(float) * 2 * ((size_t) tpad - 1 + max_input); }
     int clear() {
-        cur = 0; prev_n = 0; n0 = 0;
+        cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
         if (be.zero(d_win[0], win_bytes()) || be.zero(d_win[1], win_bytes())) return DH_EDEVICE;
+        if (d_pstate && be.zero(d_pstate, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B)) return DH_EDEVICE;
         return be.zero(d_state, sizeof(float) * DH_CZ_STATE_WORDS * B) ? DH_EDEVICE : DH_OK;
     }
     int init(const dh_channelizer_config& c) {
@@ -304,7 +313,39 @@ struct dh_channelizer {
             be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
             be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || be.zero(d_state + (size_t) ch * DH_CZ_STATE_WORDS, sizeof(float) * DH_CZ_STATE_WORDS))
             return DH_EDEVICE;
+        if (d_pstate && be.zero(d_pstate + (size_t) ch * DH_CZ_PSTATE_WORDS, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS)) return DH_EDEVICE;
         return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    static bool level_ok(float v) { return v - v == 0.0f && v >= 0.0f; }       // finite and not negative
+    int set_squelch(float open_level, float close_level, uint32_t hang) {
+        if (!level_ok(open_level) || !level_ok(close_level) || close_level > open_level || hang > 65535u) return DH_EINVAL;
+        pw_open = open_level; pw_close = close_level; pw_hang = hang;
+        return DH_OK;
+    }
+    int power_enable(const dh_channelizer_power_config& c) {
+        if (c.struct_size < sizeof(dh_channelizer_power_config) || c.block < 1 || c.block > 65536 || !c.d_power || !c.d_gate || !c.d_counts ||
+            c.stride < ((size_t) max_input / D + 1) / c.block + 1 || n0 != 0)
+            return DH_EINVAL;
+        const int rc = set_squelch(c.open_level, c.close_level, c.hang_blocks);
+        if (rc != DH_OK) return rc;
+        if (!d_pstate && !(d_pstate = (uint32_t*) be.alloc(sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B))) return DH_ENOMEM;
+        if (be.zero(d_pstate, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B)) return DH_EDEVICE;
+        pw_L = c.block; pw_inv = (float) (1.0 / (double) c.block);
+        pw_power = c.d_power; pw_gate = c.d_gate; pw_counts = c.d_counts; pw_stride = c.stride;
+        pw_first = 0; pw_n = 0;
+        return DH_OK;
+    }
+    // block power of the push's no outputs (j0 the first), the gate and the counts; no = 0: the counts are zeros
+    int power(const float* out, size_t out_stride, uint64_t j0, uint32_t no) {
+        DhCzPowerParams P;
+        P.z = fm ? d_zbuf : out; P.z_stride = out_stride; P.pstate = d_pstate;
+        P.power = pw_power; P.gate = pw_gate; P.counts = pw_counts; P.stride = pw_stride;
+        P.pos0 = (uint32_t) (j0 % pw_L); P.n_out = no; P.B = B; P.L = pw_L; P.fm = fm;
+        P.n_blocks = (uint32_t) ((j0 + no) / pw_L - j0 / pw_L);
+        P.nseg = no ? (uint32_t) (((uint64_t) P.pos0 + no + pw_L - 1) / pw_L) : 0u;
+        P.inv = pw_inv; P.open_level = pw_open; P.close_level = pw_close; P.hang = pw_hang;
+        pw_first = j0 / pw_L; pw_n = P.n_blocks;
+        return dh_be_cz_power(P, stream) ? DH_EDEVICE : DH_OK;
     }
     int push(const void* in, size_t n_in, float* out, size_t out_stride, size_t* n_out, bool host) {
         if (!n_out) return DH_EINVAL;
@@ -312,7 +353,7 @@ struct dh_channelizer {
         if (n_in > max_input || (!in && n_in)) return DH_EINVAL;
         const uint64_t no = (n0 + n_in) / D - n0 / D;
         if (no && (!out || out_stride < no)) return DH_EINVAL;
-        if (!n_in) return DH_OK;
+        if (!n_in) return pw_L ? power(out, out_stride, n0 / D, 0) : DH_OK;
         const void* src = in;
         if (host) {
             if (be.upload(d_stage, in, in_bytes() * n_in)) return DH_EDEVICE;
@@ -329,6 +370,7 @@ struct dh_channelizer {
             if (dh_be_cz_gemm(P, stream)) return DH_EDEVICE;
             if (fm && dh_be_cz_fm(d_zbuf, d_state, out, out_stride, B, (uint32_t) no, dcblock, stream)) return DH_EDEVICE;
         }
+        if (pw_L) { const int rc = power(out, out_stride, n0 / D, (uint32_t) no); if (rc != DH_OK) return rc; }
         if (host && be.sync()) return DH_EDEVICE;       // the staging buffer is the next push's
         cur ^= 1; prev_n = (uint32_t) n_in; n0 += n_in;
         *n_out = (size_t) no;
@@ -385,6 +427,20 @@ int dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, f
     if (!c) return DH_EINVAL;
     auto on_device = c->be.scope(); (void) on_device;
     return c->push(h_in, n_in, d_out, out_stride, n_out, true);
+}
+int dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg) {
+    if (!c || !cfg) return DH_EINVAL;
+    auto on_device = c->be.scope(); (void) on_device;
+    return c->power_enable(*cfg);
+}
+int dh_channelizer_set_squelch(dh_channelizer* c, float open_level, float close_level, uint32_t hang_blocks) {
+    if (!c || !c->pw_L) return DH_EINVAL;
+    return c->set_squelch(open_level, close_level, hang_blocks);
+}
+int dh_channelizer_power_last(dh_channelizer* c, uint64_t* first_block, size_t* n_blocks) {
+    if (!c || !c->pw_L || !first_block || !n_blocks) return DH_EINVAL;
+    *first_block = c->pw_first; *n_blocks = c->pw_n;
+    return DH_OK;
 }
 int dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n) {
     if ((!h_phi || !h_out) && n) return DH_EINVAL;

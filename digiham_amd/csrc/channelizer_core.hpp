@@ -30,6 +30,42 @@
 //             host's IEEE fmaf does.  A test pushes input whose products and sums are subnormal and compares device, CPU
 //             emulation and the restatement byte for byte.
 //
+// ---- Block power and the squelch gate (optional; dh_channelizer_power_enable).  The specification; tests/cz_power_restate.c
+// restates it from this text alone. ----
+//   Blocks    enabled once per channelizer with a block length L, 1 <= L <= 65536 outputs (L = 480: 10 ms at 48 kS/s).  j is
+//             the global output index since create / reset (the j of n_j above).  Block m of a channel covers the outputs
+//             j in [m L, (m + 1) L).  Push boundaries do not move block boundaries.
+//   q         z_b[j] is the rotated output above -- the same value in both output modes: what IQ_F32 stores and what FM
+//             feeds to the discriminator.  q = (zr zr) + (zi zi): both products rounded, then the sum.
+//   S         starts at +0 at the beginning of every block; S = S + q[j] in increasing j: ONE chain, no split accumulators,
+//             no tree.  When output (m + 1) L - 1 has been added: power[b][m] = S inv, inv = (float) (1.0 / (double) L)
+//             computed on the host, the multiply rounded once.  A push that ends inside a block leaves S in the channel's
+//             state and the next push continues the same chain; the position inside the block follows from j alone.
+//             Infinities and NaN propagate as IEEE arithmetic has them.
+//   Gate      per channel (open in {0, 1}, quiet: an unsigned counter), both 0 at create / reset.  Parameters: two finite
+//             floats open_level >= close_level >= 0 and hang <= 65535 blocks.  For each completed block in order, p its power:
+//               closed:  if (p >= open_level) { open = 1; quiet = 0; }
+//               open:    if (p >= close_level) quiet = 0; else if (++quiet > hang) { open = 0; quiet = 0; }
+//               gate[b][m] = open after the update.
+//             A NaN power never opens a gate and counts as quiet; hang = 0 closes on the first quiet block;
+//             open_level = close_level = 0 is "power only": every channel opens with its first block that is not NaN.
+//   Counts    for a push that completes n_out outputs: counts[b] = n_out if channel b's gate was open when the push began
+//             or if any gate byte this push wrote for b is 1, else 0; a push with n_out = 0 writes zeros.  That is the
+//             d_counts argument of dh_engine_push_ragged.  Gating acts on whole pushes: the push in which a gate opens
+//             passes completely (the pre-roll), and so does the push in which it closes.  A transmission that starts
+//             inside the last, unfinished block of a push loses at most L - 1 outputs (that push is not passed; the block
+//             completes in the next one, which is).
+//   Retune    of channel b zeroes its S, open and quiet together with the state it zeroes anyway.  The block in progress
+//             keeps its index; its value is the chain over the outputs after the retune, times inv.
+//   Reset     zeroes all of it; the power configuration stays.  Enabling is only legal while no sample has been pushed
+//             since create / reset (block alignment would be ambiguous otherwise).  Levels and hang may change between
+//             any two pushes; the state is kept.
+//   Off       a channelizer on which power was never enabled allocates nothing for it and launches exactly the kernels above.
+// Work per push with power on, after the steps below: (5) dh_cz_power_segment, one lane per (channel, block segment of this
+// push) -- a segment is the continuation of the carried block, a whole block, or the unfinished tail; the lane adds its
+// segment in order and writes either a power value or the carried S; (6) dh_cz_gate_channel, one channel per lane: the
+// recurrence over the blocks this push completed, the gate bytes, counts[b] and the state.
+//
 // Work per push (host code in abi_impl.hpp): (1) dh_cz_window_item -- the window [H = T'-1 history samples ++ the new ones]
 // as complex floats; (2) the GEMM + rotation, tiled over 128 output instants x 64 channels (k_cz_gemm; host body
 // dh_cz_output); FM mode then (3) dh_cz_fm_item, one output per lane, and (4) dh_cz_tail_channel, one channel per lane:
@@ -45,6 +81,7 @@
 #define DH_CZ_TNC 64              // channels per GEMM workgroup tile (128 real columns)
 #define DH_CZ_TBITS 12            // the two phasor tables: 4096 entries each
 #define DH_CZ_STATE_WORDS 4       // per channel: z[j-1] (re, im), x_prev, y_prev of the DC blocker
+#define DH_CZ_PSTATE_WORDS 4      // per channel, only with power enabled (an array of its own): S (float bits), open, quiet, S of this push
 
 // Column of the real GEMM for channel b, component c (0: the real output, 1: the imaginary one).  Sixteen channels' real
 // columns, then their sixteen imaginary ones: a 16 x 16 MFMA tile holds one component of sixteen channels, and the lane
@@ -137,6 +174,94 @@ DH_HD void dh_cz_tail_channel(const float* zbuf, float* state, float* out, size_
     if (n_out) { const float* z = zbuf + 2 * ((size_t) (n_out - 1) * B + b); st[0] = z[0]; st[1] = z[1]; }
 }
 
+// ---- block power and gate (the specification in the header comment) ------------------------------------------------------
+struct alignas(8) DhCzF2 { float v[2]; };               // one output: an 8-byte load
+struct alignas(16) DhCzF4 { float v[4]; };              // two outputs of an IQ row: a 16-byte load
+
+struct DhCzPowerParams {
+    const float* z;               // FM mode: zbuf [n_out][B][2]; IQ mode: the caller's output rows [B][z_stride][2]
+    size_t z_stride;
+    uint32_t* pstate;             // [B][DH_CZ_PSTATE_WORDS]
+    float* power; uint8_t* gate;  // [B][stride]: column i = block first + i of this push
+    uint32_t* counts;             // [B]
+    size_t stride;
+    uint32_t pos0;                // j0 mod L: outputs the block in progress already holds
+    uint32_t n_out, n_blocks, nseg, B, L;
+    int fm;
+    float inv, open_level, close_level;
+    uint32_t hang;
+};
+
+DH_HD float dh_cz_q(float zr, float zi) { const float a = zr * zr, c = zi * zi; return a + c; }
+DH_HD float dh_cz_bits_f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
+DH_HD uint32_t dh_cz_f_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+
+// segment s of channel b: the outputs of block (j0 / L + s) that this push holds, rows [r0, r1) of the push
+DH_HD void dh_cz_power_segment(const DhCzPowerParams& P, uint32_t b, uint32_t s) {
+    const uint32_t end = (s + 1u) * P.L - P.pos0;                       // row after the block's last output
+    const uint32_t r0 = s ? s * P.L - P.pos0 : 0u, r1 = dh_min(end, P.n_out);
+    uint32_t* st = P.pstate + (size_t) b * DH_CZ_PSTATE_WORDS;
+    float S = (s == 0u && P.pos0) ? dh_cz_bits_f(st[0]) : 0.0f;
+    uint32_t r = r0;
+    if (P.fm) {                   // lanes on consecutive channels: 8-byte loads, 512 contiguous bytes per wave instruction
+        const size_t step = 2 * (size_t) P.B;
+        const float* p = P.z + 2 * ((size_t) r0 * P.B + b);
+        for (; r + 8 <= r1; r += 8, p += 8 * step) {                    // eight loads in flight ahead of the chain
+            DhCzF2 v[8];
+            for (int e = 0; e < 8; e++) v[e] = *(const DhCzF2*) (p + e * step);
+            for (int e = 0; e < 8; e++) S = S + dh_cz_q(v[e].v[0], v[e].v[1]);
+        }
+        for (; r < r1; r++, p += step) { const DhCzF2 v = *(const DhCzF2*) p; S = S + dh_cz_q(v.v[0], v.v[1]); }
+    } else {                      // each lane along its own contiguous segment of its row
+        const float* p = P.z + 2 * ((size_t) b * P.z_stride + r0);
+        if (((uintptr_t) p & 7u) == 0) {
+            if (((uintptr_t) p & 8u) && r < r1) { const DhCzF2 v = *(const DhCzF2*) p; S = S + dh_cz_q(v.v[0], v.v[1]); r++; p += 2; }
+            for (; r + 16 <= r1; r += 16, p += 32) {                    // eight 16-byte loads in flight: one 128-byte line
+                DhCzF4 v[8];
+                for (int e = 0; e < 8; e++) v[e] = *(const DhCzF4*) (p + 4 * e);
+                for (int e = 0; e < 8; e++) { S = S + dh_cz_q(v[e].v[0], v[e].v[1]); S = S + dh_cz_q(v[e].v[2], v[e].v[3]); }
+            }
+            for (; r + 2 <= r1; r += 2, p += 4) { const DhCzF4 v = *(const DhCzF4*) p; S = S + dh_cz_q(v.v[0], v.v[1]); S = S + dh_cz_q(v.v[2], v.v[3]); }
+        }
+        for (; r < r1; r++, p += 2) S = S + dh_cz_q(p[0], p[1]);        // the last output, or rows that are only 4-byte aligned
+    }
+    const bool complete = end <= P.n_out;
+    if (complete) { const float pw = S * P.inv; P.power[(size_t) b * P.stride + s] = pw; }
+    // The carried S goes to word 3, not to word 0: the lane of segment 0 reads word 0 in this same launch, and nothing orders
+    // the two lanes.  dh_cz_gate_channel, which runs after every lane of this launch, moves it to word 0.
+    if (s + 1u == P.nseg) st[3] = complete ? 0u : dh_cz_f_bits(S);
+}
+
+// the gate recurrence of channel b over the n_blocks blocks this push completed; counts[b]; the carried (open, quiet)
+DH_HD void dh_cz_gate_channel(const DhCzPowerParams& P, uint32_t b) {
+    uint32_t* st = P.pstate + (size_t) b * DH_CZ_PSTATE_WORDS;
+    uint32_t open = st[1], quiet = st[2], any = open;
+    const float* pw = P.power + (size_t) b * P.stride;
+    uint8_t* g = P.gate + (size_t) b * P.stride;
+    uint32_t i = 0;
+    for (; i + 8 <= P.n_blocks; i += 8) {                               // eight loads in flight ahead of the recurrence
+        float v[8]; uint8_t o[8];
+        for (int e = 0; e < 8; e++) v[e] = pw[i + e];
+        for (int e = 0; e < 8; e++) {
+            if (!open) { if (v[e] >= P.open_level) { open = 1u; quiet = 0u; } }
+            else if (v[e] >= P.close_level) quiet = 0u;
+            else if (++quiet > P.hang) { open = 0u; quiet = 0u; }
+            o[e] = (uint8_t) open; any |= open;
+        }
+        for (int e = 0; e < 8; e++) g[i + e] = o[e];
+    }
+    for (; i < P.n_blocks; i++) {
+        const float p = pw[i];
+        if (!open) { if (p >= P.open_level) { open = 1u; quiet = 0u; } }
+        else if (p >= P.close_level) quiet = 0u;
+        else if (++quiet > P.hang) { open = 0u; quiet = 0u; }
+        g[i] = (uint8_t) open; any |= open;
+    }
+    st[1] = open; st[2] = quiet;
+    if (P.nseg) st[0] = st[3];                                          // the carried S of this push (dh_cz_power_segment)
+    P.counts[b] = any ? P.n_out : 0u;
+}
+
 // ---- host side: the phasor tables and the rotated taps (computed once per create / retune, then uploaded) ---------------
 // coarse ++ fine, [2][4096][2] floats
 inline const float* dh_cz_host_tables() {
@@ -180,6 +305,12 @@ static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_s
     for (uint32_t b = 0; b < B; b++)
         for (uint32_t j = 0; j < n_out; j++) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
     for (uint32_t b = 0; b < B; b++) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
+    return 0;
+}
+static int dh_be_cz_power(const DhCzPowerParams& P, void*) {
+    for (uint32_t s = P.nseg; s-- > 0;)                                 // last segment first: the lanes of a launch have no order
+        for (uint32_t b = 0; b < P.B; b++) dh_cz_power_segment(P, b, s);
+    for (uint32_t b = 0; b < P.B; b++) dh_cz_gate_channel(P, b);
     return 0;
 }
 #endif

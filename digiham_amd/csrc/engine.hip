@@ -970,6 +970,21 @@ __global__ __launch_bounds__(DH_WAVE) void k_cz_tail(const float* zbuf, float* s
     if (b < B) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
 }
 
+// Block power (channelizer_core.hpp): one lane per (channel, block segment of this push).  FM mode: lanes on consecutive
+// channels of zbuf [n_out][B][2]; IQ mode: lanes on consecutive segments of one channel's row.
+__global__ __launch_bounds__(256) void k_cz_power(const DhCzPowerParams P) {
+    const size_t n = (size_t) P.B * P.nseg;
+    for (size_t t = (size_t) blockIdx.x * 256u + threadIdx.x; t < n; t += (size_t) gridDim.x * 256u) {
+        const uint32_t b = (uint32_t) (P.fm ? t % P.B : t / P.nseg), s = (uint32_t) (P.fm ? t / P.B : t % P.nseg);
+        dh_cz_power_segment(P, b, s);
+    }
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_cz_gate(const DhCzPowerParams P) {
+    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
+    if (b < P.B) dh_cz_gate_channel(P, b);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------- ABI hooks
@@ -1105,6 +1120,15 @@ static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_s
     hipLaunchKernelGGL(k_cz_fm, dim3((n_out + 255) / 256, B < 65535u ? B : 65535u), dim3(256), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_cz_tail, dim3((B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out, dcblock);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_cz_power(const DhCzPowerParams& P, void* stream) {
+    if (P.nseg) {
+        hipLaunchKernelGGL(k_cz_power, dim3(grid_for((size_t) P.B * P.nseg, 256)), dim3(256), 0, (hipStream_t) stream, P);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cz_gate, dim3((P.B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, P);
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }

@@ -31,11 +31,12 @@ def ysf_audio(seed, n_frames=30):
     return synth.shape(synth.ysf_stream(seed, n_frames))
 
 
-def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak=0.9):
+def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak=0.9, keying=None):
     """carriers: list of (offset_hz, level_db, audio48) -- each FM-modulated at 48 kS/s x decimation (audio linearly
     interpolated), level relative to the strongest; the sum is scaled so that it never clips, complex Gaussian noise of
-    `noise_lsb` rms per component is added, and the result rounded to int16.  Returns int16 [n][2] (a numpy array, or a
-    torch tensor on `device` when that is not the CPU)."""
+    `noise_lsb` rms per component is added, and the result rounded to int16.  `keying`: per carrier None (always on) or
+    (start_s, stop_s) -- the carrier's amplitude is 0 outside [start, stop) and its audio begins at start.  Returns
+    int16 [n][2] (a numpy array, or a torch tensor on `device` when that is not the CPU)."""
     import torch
     rate = AUDIO_RATE * decimation
     dev = torch.device(device)
@@ -43,16 +44,22 @@ def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak
     acc = torch.zeros(n, dtype=torch.complex128, device=dev)
     amps = [10.0 ** (lv / 20.0) for _, lv, _ in carriers]
     scale = peak * 32767.0 / max(sum(amps), 1e-9)
-    for (off, lv, audio), a in zip(carriers, amps):
+    for c, ((off, lv, audio), a) in enumerate(zip(carriers, amps)):
+        key = keying[c] if keying is not None else None
         au = torch.from_numpy(np.asarray(audio, np.float64)).to(dev)
-        idx = t_out.clamp(max=len(audio) - 1.0)
+        idx = t_out.clamp(max=len(audio) - 1.0) if key is None else (t_out - key[0] * AUDIO_RATE).clamp(min=0.0, max=len(audio) - 1.0)
         i0 = idx.floor().long()
         i1 = (i0 + 1).clamp(max=len(audio) - 1)
         fr = idx - i0.double()
         a_t = au[i0] * (1.0 - fr) + au[i1] * fr
         f = off + DEVIATION_HZ * a_t
         ph = torch.cumsum(f, 0) * (2.0 * np.pi / rate)
-        acc += scale * a * torch.polar(torch.ones_like(ph), ph)
+        if key is None:
+            acc += scale * a * torch.polar(torch.ones_like(ph), ph)
+        else:
+            t_s = t_out / AUDIO_RATE
+            on = ((t_s >= key[0]) & (t_s < key[1])).double()
+            acc += scale * a * torch.polar(on, ph)
     g = torch.Generator(device=dev).manual_seed(seed)
     noise = torch.randn((n, 2), generator=g, dtype=torch.float64, device=dev) * noise_lsb
     iq = torch.stack((acc.real, acc.imag), 1) + noise

@@ -302,10 +302,38 @@ int  dh_channelizer_reset(dh_channelizer* c);
 int  dh_channelizer_retune(dh_channelizer* c, uint32_t channel, uint32_t increment);
 /* n_in (<= max_input, any length, 0 included) complex samples; *n_out = outputs completed by this push, known without a
  * sync.  d_out [n_channels][out_stride] (out_stride in output samples: complex pairs for IQ_F32, floats for FM, >= *n_out)
- * receives them.  Asynchronous on the channelizer's stream. */
+ * receives them.  Asynchronous on the channelizer's stream.  With block power enabled every push writes d_counts, so even
+ * a push of n_in = 0 launches one small kernel. */
 int  dh_channelizer_push(dh_channelizer* c, const void* d_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out);
 /* the same from host memory (staged through a device buffer; returns once the input has been read) */
 int  dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out);
+/* Block power and squelch gate (optional; bit for bit specified in channelizer_core.hpp).  Block m of a channel covers the
+ * outputs [m block, (m + 1) block) counted from create / reset, whatever the push lengths; power = the in-order sum of |z|^2
+ * over the block times (float) (1 / block), z the rotated output (the same in both output modes).  The gate of a channel opens
+ * with a block >= open_level and closes after more than hang_blocks consecutive blocks < close_level.  After every push
+ * d_counts[b] = n_out if the gate of channel b was open when the push began or in any block the push completed, else 0:
+ * the d_counts argument of dh_engine_push_ragged.  Whole pushes pass or do not; a transmission that begins inside the last,
+ * unfinished block of a push loses at most block - 1 outputs.  The three arrays are the caller's device memory, like push's
+ * d_out, and are written by every push from the enable on.  Legal only while no sample has been pushed since create / reset.
+ * A retune zeroes the channel's sum and gate; a reset zeroes all of them and keeps this configuration.
+ * DH_EINVAL: null pointers, block 0 or > 65536, stride too small, levels not finite or negative, close_level > open_level,
+ * hang_blocks > 65535, samples already pushed. */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(dh_channelizer_power_config) */
+    uint32_t block;                /* L: outputs per block, 1 .. 65536 (480 = 10 ms at 48 kS/s) */
+    float    open_level, close_level;      /* |z|^2 units: a full-scale CS16 tone through unity-gain taps is 1.0 */
+    uint32_t hang_blocks;
+    float*    d_power;             /* [n_channels][stride] */
+    uint8_t*  d_gate;              /* [n_channels][stride] */
+    uint32_t* d_counts;            /* [n_channels] */
+    size_t   stride;               /* >= (max_input / decimation + 1) / block + 1 */
+} dh_channelizer_power_config;
+int  dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg);
+/* new levels and hang from the next push on; the gates' state is kept.  DH_EINVAL before the enable */
+int  dh_channelizer_set_squelch(dh_channelizer* c, float open_level, float close_level, uint32_t hang_blocks);
+/* blocks completed by the last push: the index of the first one and how many (host arithmetic, no sync).  Column i of
+ * d_power / d_gate holds block *first_block + i. */
+int  dh_channelizer_power_last(dh_channelizer* c, uint64_t* first_block, size_t* n_blocks);
 /* the NCO phasor P(phi) of the specification for n host phase words -> h_out [n][2] (host arithmetic, for tests) */
 int  dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n);
 

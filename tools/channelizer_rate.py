@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""tools/channelizer_rate.py [--out FILE] [--pushes K] [--config a|b|all]: throughput of dh_channelizer on cuda:0.
+"""tools/channelizer_rate.py [--out FILE] [--pushes K] [--config a|b|all] [--power L] [--lib PATH --tag NAME]: throughput of
+dh_channelizer on cuda:0.
 
 Configurations, taps = api.channel_taps(rate, D, 6.5 kHz, 12 kHz, 60 dB):
   (a) 2.4 MS/s CS16, D = 50, 192 channels on a 12.5 kHz raster, 10 s of input per push;
@@ -7,7 +8,9 @@ Configurations, taps = api.channel_taps(rate, D, 6.5 kHz
 Each push is timed with HIP events (torch.cuda.Event on the channelizer's stream) in "iq" mode (window + GEMM / rotation)
 and in "fm" + DC-blocker mode (+ the discriminator and the recurrence).  Reported per push: ms, ms per second of input,
 the real-time factor, and the GEMM's TFLOP/s counted as 8 B T' n_out over the whole push, with its fraction of the
-157.3 TF f32 matrix peak.  One JSON line per (config, mode)."""
+157.3 TF f32 matrix peak.  One JSON line per (config, mode).  --power L adds the modes "iq+power" and "fm+power": the same
+with block power over L outputs and the gate enabled (k_cz_power reads 8 bytes per output and channel once more; k_cz_gate).
+--lib PATH times another build of the library (tools/build_variant.sh) instead of the package's, --tag labels its lines."""
 import argparse
 import json
 import os
@@ -20,15 +23,18 @@ CONFIGS = {"a": dict(rate=2.4e6, D=50, B=192, seconds=10.0), "b": dict(rate=9.6e
 PEAK_TF = 157.3
 
 
-def run(name, c, mode, pushes, warmup=2):
+def run(name, c, mode, pushes, warmup=2, power=0, ctx=None, tag=None):
     import torch
     from digiham_amd import api
+    label, mode = mode, mode.split("+")[0]
     rate, D, B = c["rate"], c["D"], c["B"]
     n = int(c["seconds"] * rate)
     h = api.channel_taps(rate, D, 6500.0, 12000.0, 60.0)
     tpad = 16 * ((len(h) + 15) // 16)
     freqs = [(b - B // 2) * 12500.0 for b in range(B)]
-    cz = api.Channelizer(rate, D, freqs, h, input="cs16", output=mode, dcblock=(mode == "fm"), max_input=n)
+    cz = api.Channelizer(rate, D, freqs, h, input="cs16", output=mode, dcblock=(mode == "fm"), max_input=n, ctx=ctx)
+    if label.endswith("+power"):
+        cz.enable_power(block=power, open_db=-40.0, close_db=-43.0, hang_blocks=2)
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randint(-2000, 2000, (n, 2), generator=g, device="cuda", dtype=torch.int32).to(torch.int16)
     times = []
@@ -44,7 +50,10 @@ def run(name, c, mode, pushes, warmup=2):
     ms = sorted(times)[len(times) // 2]
     flop = 8.0 * B * tpad * n_out
     tf = flop / (ms * 1e-3) / 1e12
-    return {"config": name, "mode": mode, "rate": rate, "D": D, "B": B, "taps": len(h), "tpad": tpad, "n_in": n, "n_out": n_out,
+    extra = {"tag": tag} if tag else {}
+    if label.endswith("+power"):
+        extra.update(block=power, power_read_mb=round(8.0 * B * n_out / 1e6, 1))
+    return {**extra, "config": name, "mode": label, "rate": rate, "D": D, "B": B, "taps": len(h), "tpad": tpad, "n_in": n, "n_out": n_out,
             "ms_per_push": round(ms, 3), "ms_min": round(min(times), 3), "ms_per_s_input": round(ms / c["seconds"], 3),
             "realtime_factor": round(c["seconds"] * 1e3 / ms, 1), "gemm_tflops": round(tf, 2), "fraction_of_peak": round(tf / PEAK_TF, 3),
             "pushes": pushes}
@@ -56,15 +65,23 @@ def main():
     ap.add_argument("--pushes", type=int, default=5)
     ap.add_argument("--config", default="all")
     ap.add_argument("--modes", default="iq,fm")
+    ap.add_argument("--power", type=int, default=0)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--tag", default=None)
     a = ap.parse_args()
     rows = []
+    ctx = None
+    if a.lib:
+        from digiham_amd import _capi, api
+        ctx = api.Context(lib=_capi.load(a.lib))
+    modes = [m for m in a.modes.split(",") if m] + (["iq+power", "fm+power"] if a.power else [])
     for name in (["a", "b"] if a.config == "all" else [a.config]):
-        for mode in a.modes.split(","):
-            r = run(name, CONFIGS[name], mode, a.pushes)
+        for mode in modes:
+            r = run(name, CONFIGS[name], mode, a.pushes, power=a.power, ctx=ctx, tag=a.tag)
             print(json.dumps(r), flush=True)
             rows.append(r)
     if a.out:
-        with open(a.out, "w") as f:
+        with open(a.out, "a" if a.tag else "w") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
 
