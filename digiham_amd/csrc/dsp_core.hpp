@@ -29,7 +29,7 @@
 #define DH_PF_SINK 512               // word offset inside the window block where the L2-touch loads drop their dwords (64 words)
 #define DH_MAX_NZ 160
 #define DH_MAX_SPS 40
-// raw samples kept BEHIND the read position by the error-bounded kernels (see DH_BOUNDED_FIR): the 100 symbols of the
+// raw samples kept BEHIND the read position by the error-bounded kernels (see "Error-bounded FIR"): the 100 symbols of the
 // rings + slack; and the most the tail carries between pushes: history + the last nz inputs + not yet consumed ones
 DH_HD uint32_t dh_history(uint32_t sps) { return DH_VARIANCE_SYMBOLS * (sps > 10u ? sps : 10u) + 152u; }
 DH_HD uint32_t dh_tail_max(uint32_t sps) { return 256u + dh_history(sps); }
@@ -128,9 +128,8 @@ struct DhDspShared {
 };
 
 #define DH_TAP_LEAD 15                                 // zeros in front of (and behind) the wide filter's tap table
-#define DH_LDS_CLK_WORDS 0u
 // words in front of the variance ring (a multiple of 4: keeps var_rb 16-byte aligned)
-DH_HD uint32_t dh_lds_fixed_words(uint32_t nz) { return nz > 80u ? 352u + 16u : 384u + DH_LDS_CLK_WORDS; }
+DH_HD uint32_t dh_lds_fixed_words(uint32_t nz) { return nz > 80u ? 352u + 16u : 384u; }
 DH_HD uint32_t dh_dsp_xf_words(uint32_t nz) {
     const uint32_t padded = DH_XPAD(DH_FTILE + nz) + 1u, with_sums = DH_FTILE + 4u + DH_SCAN_N;
     return ((padded > with_sums ? padded : with_sums) + 3u) & ~3u;
@@ -519,7 +518,7 @@ __device__ __forceinline__ void dh_fir_lane(const float* taps, double gain, doub
     } else dh_fir_finish<FAST>(acc, gain, rgain, inv_gain, out16, nonfinite);
 }
 #else
-template <int NZ, bool FAST>
+template <int NZ, bool FAST, bool SG = false, bool SAFE = false>         // (SG, SAFE: how the device form gets and waits for its operands)
 inline void dh_fir_lane(const float* taps, double gain, double rgain, float inv_gain, const float* xs_all, int lane, float* out16, bool* nonfinite = nullptr) {
     const float* xs = xs_all + (DH_FIR_L + 1) * lane;
 #define DH_XL(e) xs[DH_XLOFF(e)]
@@ -546,8 +545,6 @@ inline void dh_fir_lane(const float* taps, double gain, double rgain, float inv_
 struct __attribute__((aligned(4))) dh_f4 { float x, y, z, w; };
 struct alignas(16) dh_f4a { float x, y, z, w; };     // 16-byte aligned: one ds_read_b128
 DH_HD dh_f4 dh_load4_unaligned(const float* p) { dh_f4 v; __builtin_memcpy(&v, p, sizeof(v)); return v; }
-// the same for the one-touch input stream: DH_NT_INPUT=1 marks the loads non-temporal (A/B: see DESIGN.md section 5)
-DH_HD dh_f4 dh_load4_stream(const float* p) { return dh_load4_unaligned(p); }
 DH_HD void dh_store4(float* q, const dh_f4& v) { q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
 DH_HD void dh_store4_unaligned(float* q, const dh_f4& v) { __builtin_memcpy(q, &v, sizeof(v)); }   // global_store_dwordx4
 
@@ -571,7 +568,6 @@ DH_HD void dh_store4_unaligned(float* q, const dh_f4& v) { __builtin_memcpy(q, &
 // slice s + 4 of the even one: 28 window reads serve the 48 MFMAs of a tile pair.  Results go back unpadded (sample o at
 // word o): sixteen ds_write_b32 at compile-time offsets from one per-lane base (2-way bank conflicts, which a 4-byte
 // store hides behind its own issue time).
-#define DH_MFMA_FIR 1
 #define DH_MF_OUT(T, r, g, n) (128u * (uint32_t) (g) + (uint32_t) (n) + 32u * (uint32_t) (r) + 16u * ((uint32_t) (T) & 1u) + 512u * ((uint32_t) (T) >> 1))
 #if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
 typedef float dh_f32x4 __attribute__((ext_vector_type(4)));
@@ -612,7 +608,7 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// The fused FIR as a SPLIT-f16 product on the matrix cores (DH_FIR_F16; the error-bounded wide-filter kernels).
+// The fused FIR as a SPLIT-f16 product on the matrix cores (the error-bounded kernels).
 //
 // f32 arithmetic -- v_pk_fma_f32 and v_mfma_f32_16x16x4_f32 alike -- runs at 64 flop / clock / SIMD, and an f32 MFMA keeps
 // the vector ALU as busy as the packed FMAs it replaces (tools/microbench/mfma_valu_overlap.hip: MFMA wave + VALU wave on one
@@ -641,11 +637,7 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 //   B: lane (n = l & 15, q = l >> 4) holds g[32 s + 8 q + j - n]: per-lane fragments precomputed on the host (6 x 1 KiB,
 //      dh_f16_tap_fragments), fetched with the samples
 //   D: lane (n, g), register r holds y[256 T + 16 b(4 g + r) + n] = y[DH_F16_OUT(T, r, g, n)]
-#define DH_FIR_F16 1
-#define DH_PLAN_FAST 1                       // sps-10 kernels: the run planning of a whole-block run in three compares
 #define DH_EXACT_BATCH 2                     // exact evaluations of the 81-tap kernels: this many products at a time, their LDS reads in flight together (the 161-tap ones: 8)
-#define DH_PF_REG 1                          // split-f16 kernels: the next window is fetched into registers behind P3 and split into halves in P7
-#define DH_F16_EDGE_WINDOWS 1                // split-f16 kernels: the first / last windows of a push take the split-f16 FIR too (0: the reference-order FIR, as before)
 // K = taps + 15 rounded up to whole MFMAs of 32: three for the wide filter (96), six for the narrow one (192; taps beyond the
 // response are zeros in the fragments, and the halves beyond the window are stored as zeros)
 #define DH_F16_KSTEPS_OF(nz) (((nz) + 16 + 31) / 32)
@@ -891,6 +883,9 @@ DH_HD float dh_sqrt_upper(float x) {
 }
 DH_HD float dh_fmin_(float a, float b) { return b < a ? b : a; }
 DH_HD float dh_fmax_(float a, float b) { return b > a ? b : a; }
+// the extremes of a lane's two symbols 2 l, 2 l + 1 (device: what the scan hands to the slicing phase in registers; the
+// harness's scan leaves its results in S.mn / S.mx only)
+struct DhAgcPair { float mn0, mx0, mn1, mx1; };
 
 #if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
 // v_min_f32 / v_max_f32 return the operand that is not NaN -- exactly what `if (v < min) min = v` does with a
@@ -949,7 +944,6 @@ __device__ __forceinline__ float dh_wave_prev(float v, float first) {
 // backwards (lane l takes slots 126-2l and 127-2l), handed back to the owning lanes -- lane 63 - l -- by four ds_bpermute
 // (until round 5 through S.mn / S.mx: four stores, a barrier, four loads, a barrier -- one LDS round trip more).  The lane's
 // results (slots 2l and 2l+1) are also returned: the slicing phase of a run that starts its block takes them from there.
-struct DhAgcPair { float mn0, mx0, mn1, mx1; };
 __device__ __forceinline__ DhAgcPair dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1) {
     const int lane = dh_fresh_lane_id_();
     const uint32_t e0 = 2u * (uint32_t) lane, e1 = e0 + 1u;
@@ -1010,7 +1004,7 @@ __device__ __forceinline__ float dh_row_min_to_lane15(float v) {
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// Error-bounded FIR (DH_BOUNDED_FIR; the exact wide-filter kernels at sps 10, i.e. the DMR / YSF pipes).
+// Error-bounded FIR (the exact wide-filter kernels at sps 10, i.e. the DMR / YSF pipes).
 //
 // The reference's dibits and timing steps depend on the filtered samples only through comparisons.  The kernel therefore
 // filters with the fused multiply-add FIR (half the vector instructions of the rounded-product chain), carries a proven
@@ -1032,10 +1026,9 @@ __device__ __forceinline__ float dh_row_min_to_lane15(float v) {
 // an average and a threshold computed from values with radii <= e differ from the reference's difference by at most
 // (1 + 2.25) 167/240 e + 62/240 e < 2.53 e; a comparison is DECIDED when they are further apart than T = 3.5 e.
 // e of a ring entry is the e of the run that produced it: kept as two maxima over >= 100-symbol buckets (DH_ST_E_*).
-#define DH_BOUNDED_FIR 1
-#define DH_BOUNDED_NARROW 1                 // the same for the narrow filter at a run-time samples-per-symbol (the NXDN pipe)
+// The same scheme serves the narrow filter at a run-time samples-per-symbol (the NXDN pipe).
 template <int NZ, bool FAST, int SPS> struct DhIsBounded {
-    static constexpr bool value = DH_BOUNDED_FIR && !FAST && ((NZ == 80 && SPS == 10) || (DH_BOUNDED_NARROW && NZ == 160 && SPS != 10));
+    static constexpr bool value = !FAST && ((NZ == 80 && SPS == 10) || (NZ == 160 && SPS != 10));
 };
 // Diagnostic builds only (tools/phase_budget.sh): -DDH_STOP_AFTER=n leaves out the phases after Pn of every run (the
 // results are then wrong; the instruction counters of such builds, subtracted from each other, give the per-phase budget)
@@ -1097,6 +1090,14 @@ __device__ __forceinline__ float dh_wave_max(float v) {
 __device__ __forceinline__ float dh_max3_abs(float a, float b, float c) {
     float r; asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
 }
+#define DH_WAVE_MAX(a) dh_wave_max((a)[0])             // of a DH_LANE_ARRAY(float, a, 1)
+#else
+inline float dh_wave_max_lanes(const float (&a)[DH_WAVE][1]) {
+    float m = 0.0f;
+    for (int l = 0; l < DH_WAVE; l++) m = __builtin_fmaxf(m, a[l][0]);
+    return m;
+}
+#define DH_WAVE_MAX(a) dh_wave_max_lanes(a)
 #endif
 
 // The rare paths of the error-bounded kernels (inlined: as real calls they would force the kernel's argument block into
@@ -1331,18 +1332,13 @@ DH_COLD void dh_exact_var_ring_staged(const DhExactCtx& C, DhDspShared& S, uint3
 
 // the rounded-product FIR over the staged window (runs the bound does not cover): outputs into fo[16] per lane
 template <int NZ>
-DH_COLD void dh_exact_fir_pass(const DhDspParams& P, DhDspShared& S, uint32_t need, float (*fo_all)[DH_FIR_L], float* fo_dev) {
+DH_COLD void dh_exact_fir_pass(const DhDspParams& P, DhDspShared& S, uint32_t need, DH_LANE_ARRAY(float, (&fo), DH_FIR_L)) {
     float tv[NZ / 2 + 1];
     for (int i = 0; i <= NZ / 2; i++) tv[i] = S.tapsf[i];
     DH_FOR_LANES_FRESH(lane) {
         if ((uint32_t) (lane * DH_FIR_L) < need) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            (void) fo_all;
-            dh_fir_lane<NZ, false, false, DH_FIR_F16 != 0>(tv, P.gain, P.rgain, P.inv_gain, S.xf, lane, fo_dev);      // (a rare path next to the split-f16 FIR: loads waited for where they are issued)
-#else
-            (void) fo_dev;
-            dh_fir_lane<NZ, false>(tv, P.gain, P.rgain, P.inv_gain, S.xf, lane, fo_all[lane]);
-#endif
+            // (device: a rare path next to the split-f16 FIR, loads waited for where they are issued)
+            dh_fir_lane<NZ, false, false, true>(tv, P.gain, P.rgain, P.inv_gain, S.xf, lane, DH_LA(fo, lane));
         }
     }
 }
@@ -1934,9 +1930,6 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
 // `out`: where symbol 0 of the run goes; `agc` (device): the scan's own results for the lane's two symbols, used when the run starts its
 // block.  Doubtful symbols are not stored; their votes come back in vote_a (symbols 2 l) and vote_b (2 l + 1).
 struct DhSliceSetup { bool four_levels, e_pos, width_pow2, pair_store; float T_eff, inv_width; };
-#if !(DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__))
-struct DhAgcPair { float mn0, mx0, mn1, mx1; };          // (harness: the scan leaves its results in S.mn / S.mx only)
-#endif
 template <int SPS, int LV, bool BOUNDED>
 DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, const DhAgcPair agc, uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
                             const DhSliceSetup& U, uint64_t& vote_a, uint64_t& vote_b) {
@@ -2018,6 +2011,164 @@ DH_COLD void dh_settle_doubts(const DhDspParams& P, DhDspShared& S, DhBoundState
 }
 
 // ---------------------------------------------------------------------------------------------
+// ---- P1 / P2 / P7: what staging a run's raw window and putting its filtered samples back are made of, each stated once.
+// Staging itself (P1), the FIR with its store-back layouts (P2) and the P7 half of the fetch ahead are written out in
+// dh_rrc_demod_channel: moved behind a call -- a function or an always_inline lambda, arguments by value or by reference --
+// every slicer kernel comes out of the compiler with other registers.
+// the last window of a push: zeros beyond the input (`w` holds the elements e .. e + 3 of a window with `have` samples)
+DH_HD dh_f4 dh_zero_beyond(dh_f4 w, uint32_t e, uint32_t have) {
+    w.x = e + 0u < have ? w.x : 0.0f; w.y = e + 1u < have ? w.y : 0.0f;
+    w.z = e + 2u < have ? w.z : 0.0f; w.w = e + 3u < have ? w.w : 0.0f;
+    return w;
+}
+// raw-sample window layout: padded one word per 16 for the FIR's lane-strided reads; plain without an RRC stage
+// (the samples are then used where they were staged, and the window sums sit right behind them)
+#define DH_XP(e) (NZ > 0 ? DH_XPAD(e) : (e))
+// the window V[p .. p + DH_FTILE + NZ) sample by sample out of the carried tail and the input, zeros beyond the stream
+template <int NZ>
+DH_HD void dh_gather_window(DhDspShared& S, const float* tail, uint32_t tc, const float* in, uint32_t nv, uint32_t p) {
+    DH_FOR_LANES_FRESH(lane) {
+        for (uint32_t e = lane; e < DH_FTILE + NZ; e += DH_WAVE)
+            S.xf[DH_XP(e)] = p + e < nv ? dh_virtual_sample(tail, tc, in, p + e) : 0.0f;
+    }
+}
+// A window of DH_FTILE + NZ samples as DH_PF_N groups of 16 bytes per lane: group r holds the elements 4 lane + 256 r ...
+// Only the last group is partial: LAST_LANES of its lanes lie inside the window.  GSTEP: words between two groups of a lane
+// in the (padded) window block.  STORE_LANES: lanes of the last group that the arrays of halves of the split-f16 FIR reach
+// (they are as long as the last block's K range).
+template <int NZ> struct DhWindowGroups {
+    static constexpr uint32_t GSTEP = NZ > 0 ? DH_XPAD(4u * DH_WAVE) : 4u * DH_WAVE;
+    static constexpr uint32_t LAST_LANES = (DH_FTILE + NZ - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;
+    static constexpr uint32_t STORE_LANES = (DH_F16_HALVES_OF(NZ) - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;
+    static_assert((DH_FTILE + NZ) % 4u == 0 && (DH_FTILE + NZ) >= 4u * DH_WAVE * (DH_PF_N - 1) && LAST_LANES <= DH_WAVE, "four full groups + a partial one cover the window");
+    static_assert(STORE_LANES >= LAST_LANES && STORE_LANES <= DH_WAVE, "the partial group covers the padded arrays");
+};
+// a lane's 16 consecutive filtered samples back into the window block, unpadded: four 16-byte stores
+// (a macro: as a function the error-bounded sps-10 kernels came out with other registers)
+#define DH_STORE_FIR_OUT(xf, lane, fo) do { \
+        dh_f4a* dst_ = reinterpret_cast<dh_f4a*>((xf) + DH_FIR_L * (lane)); \
+        _Pragma("unroll") for (int j_ = 0; j_ < DH_FIR_L / 4; j_++) { \
+            dh_f4a v_; v_.x = DH_LA(fo, lane)[4 * j_]; v_.y = DH_LA(fo, lane)[4 * j_ + 1]; \
+            v_.z = DH_LA(fo, lane)[4 * j_ + 2]; v_.w = DH_LA(fo, lane)[4 * j_ + 3]; \
+            dst_[j_] = v_; \
+        } } while (0)
+// split-f16 FIR: the window held in `varr` (five 16-byte groups per lane, as loaded) -> zeros beyond `have`, max |x| of the
+// wavefront, the power-of-two scale that puts it into [0.5, 1), the two arrays of halves in the window block.  Returns
+// false (nothing stored) when max |x| is outside the range the bound covers.
+template <int NZ>
+DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f4, (&varr), DH_PF_N), uint32_t have, float& e_out, float& k1_out, float& k2_out) {
+    constexpr uint32_t LAST_LANES = DhWindowGroups<NZ>::LAST_LANES, STORE_LANES = DhWindowGroups<NZ>::STORE_LANES;
+    DH_LANE_ARRAY(float, xm, 1);
+    DH_FOR_LANES_FRESH(lane) {
+        const uint32_t l4 = 4u * (uint32_t) lane;
+        if (DH_UNLIKELY(have < DH_FTILE + NZ)) {   // the last window of the push: zeros beyond the input
+#pragma unroll
+            for (int r = 0; r < DH_PF_N; r++) {
+                const uint32_t e = l4 + 4u * DH_WAVE * (uint32_t) r;
+                DH_LA(varr, lane)[r] = dh_zero_beyond(DH_LA(varr, lane)[r], e, have);
+            }
+        }
+        float mx = 0.0f;                            // (a NaN is skipped here and caught behind the FIR)
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+        {
+            // ten v_max3_f32 in ONE statement (as ten statements the compiler put an s_nop behind each)
+            static_assert(DH_PF_N == 5, "five groups of four");
+            const dh_f4 w0 = varr[0], w1 = varr[1], w2 = varr[2], w3 = varr[3], w4 = varr[4];
+            asm("v_max3_f32 %0, |%1|, |%2|, 0\n\tv_max3_f32 %0, |%3|, |%4|, %0\n\tv_max3_f32 %0, |%5|, |%6|, %0\n\tv_max3_f32 %0, |%7|, |%8|, %0\n\t"
+                "v_max3_f32 %0, |%9|, |%10|, %0\n\tv_max3_f32 %0, |%11|, |%12|, %0\n\tv_max3_f32 %0, |%13|, |%14|, %0\n\tv_max3_f32 %0, |%15|, |%16|, %0\n\t"
+                "v_max3_f32 %0, |%17|, |%18|, %0\n\tv_max3_f32 %0, |%19|, |%20|, %0"
+                : "=&v"(mx) : "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w),
+                              "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w));
+        }
+#else
+#pragma unroll
+        for (int r = 0; r < DH_PF_N; r++) {
+            const dh_f4 w = DH_LA(varr, lane)[r];
+            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.x), __builtin_fabsf(w.y)));
+            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.z), __builtin_fabsf(w.w)));
+        }
+#endif
+        DH_LA(xm, lane)[0] = mx;
+    }
+    const float xmax = DH_WAVE_MAX(xm);
+    float scale = 1.0f;
+    if (xmax == 0.0f) { e_out = 0.0f; k1_out = P.inv_gain; }                       // all zeros in, all zeros out
+    else if (xmax >= DH_BOUND_XMAX_LO && xmax <= DH_BOUND_XMAX_HI) {
+        union { float f; uint32_t u; } b; b.f = xmax;
+        const uint32_t ex = b.u >> 23;                                              // xmax in [2^(ex - 127), 2^(ex - 126))
+        b.u = (253u - ex) << 23; scale = b.f;                                       // 2^(126 - ex)
+        b.u = (ex + 1u) << 23; k1_out = P.inv_gain * b.f;                           // fl32(1 / gain) 2^(ex - 126): exact scaling
+        e_out = P.err_coef_f16 * xmax;
+    } else return false;                                                            // tiny, huge or infinite samples: outside the bound's assumptions
+    k2_out = k1_out * 0.00048828125f;                                               // 2^-11
+    // (the arrays are as long as the last block's K range reaches: the halves behind the window, under zero taps, must be
+    // finite -- the lanes of the last group beyond the window store zeros there)
+    DH_FOR_LANES_FRESH(lane) {
+        const bool in_last = (uint32_t) lane < LAST_LANES, in_store = (uint32_t) lane < STORE_LANES;
+        if (STORE_LANES > LAST_LANES && !in_last) { dh_f4 z; z.x = 0.0f; z.y = 0.0f; z.z = 0.0f; z.w = 0.0f; DH_LA(varr, lane)[DH_PF_N - 1] = z; }
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+        dh_h4* d1 = reinterpret_cast<dh_h4*>(S.xf) + lane;                          // halves 4 lane .. 4 lane + 3 of group 0; group r is 256 halves on
+        dh_h4* d2 = reinterpret_cast<dh_h4*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + lane;
+#pragma unroll
+        for (int r = 0; r < DH_PF_N; r++) {
+            dh_h4 a, b;
+            dh_f16_split4(varr[r], scale, a, b);
+            if (r < DH_PF_N - 1 || in_store) { d1[DH_WAVE * r] = a; d2[DH_WAVE * r] = b; }
+        }
+#else
+        uint16_t* d1 = reinterpret_cast<uint16_t*>(S.xf) + 4 * lane;
+        uint16_t* d2 = reinterpret_cast<uint16_t*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + 4 * lane;
+        for (int r = 0; r < DH_PF_N; r++)
+            if (r < DH_PF_N - 1 || in_store) dh_f16_split4(varr[lane][r], scale, d1 + 4 * DH_WAVE * r, d2 + 4 * DH_WAVE * r);
+#endif
+    }
+    return true;
+}
+
+// ---- the fetch ahead: the raw window of the NEXT run.  Its start is already known (the timing decision of this
+// block only moves symbols 1.. of the next one), the window block is idle from here to the end of the
+// iteration, and P4-P6 are latency-bound with few live registers: the HBM latency of these loads hides
+// behind them.  Five 16-byte loads per lane, parked in registers until P7.
+// (arguments by reference, as the lambda this used to be captured them: by value the PF_REG kernels come out with other registers)
+template <int NZ, bool PF_REG>
+DH_HD void dh_issue_next_window(DhDspShared& S, const float* const& in, const uint32_t& tc, const uint32_t& p_next, const bool& pf_plain, const bool& pf_reg, DH_LANE_ARRAY(dh_f4, (&pfr), PF_REG ? DH_PF_N : 1)) {
+    (void) S; (void) pfr;
+    if (DH_LIKELY(pf_reg)) {
+        // The split-f16 FIR leaves registers free where the packed-FMA FIR had none: the next window's five 16-byte loads
+        // per lane are issued here, straight from HBM, land while P4 - P6 run, and P7 turns them into the two arrays of
+        // halves -- the next iteration starts at the matrix cores.
+        constexpr uint32_t LAST_LANES = DhWindowGroups<NZ>::LAST_LANES;
+        const float* src = in + (p_next - tc);
+        DH_FOR_LANES_FRESH(lane) {
+            const float* lsrc = src + 4u * (uint32_t) lane;
+            const bool in_last = (uint32_t) lane < LAST_LANES;
+#pragma unroll
+            for (int r = 0; r < DH_PF_N - 1; r++) DH_LA(pfr, lane)[PF_REG ? r : 0] = dh_load4_unaligned(lsrc + 4 * DH_WAVE * r);
+            if constexpr (LAST_LANES > 0) DH_LA(pfr, lane)[PF_REG ? DH_PF_N - 1 : 0] = dh_load4_unaligned(lsrc + (in_last ? 4 * DH_WAVE * (DH_PF_N - 1) : 0));
+            else (void) in_last;
+        }
+    } else {
+        // Register-free variant: one dword per 128-byte line of the next window is requested now, which pulls the
+        // lines into L2; the next iteration's P1 then stages from L2 instead of HBM.  The dwords themselves are not
+        // wanted: global_load_lds_dword drops them (lane l -> m0 + 4 l) into a part of the window block that is dead
+        // until the next staging, so no vector register is tied to a load the compiler does not know about.  They
+        // have landed before the next P1 stores anything there (its own, younger loads are waited for first), and
+        // an explicit s_waitcnt follows the loop for the last one.
+        if (pf_plain) {
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+            const uint32_t pf_lane = (uint32_t) dh_fresh_lane_id_();       // not loop-invariant: a hoisted address is spilled
+            const float* line = in + (p_next - tc) + 32u * pf_lane;
+            const uint32_t sink = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) (S.xf + DH_PF_SINK);
+            uint32_t keep_m0;
+            if (32u * pf_lane < DH_FTILE + NZ)
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep_m0) : "s"(sink), "v"(line) : "memory");
+#endif
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // One channel, one push.  `S` is this wavefront's LDS block.  Called by all 64 lanes (device) or
 // once (host harness; the DH_FOR_LANES loops then iterate the lanes).
 // SPS = 10 bakes the DMR / YSF samples-per-symbol (and its evaluation window 3..6) into the code so the
@@ -2035,7 +2186,7 @@ template <int NZ, bool FAST, int SPS, int LV = 0, int KEEPF = 0>
 DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& S, uint32_t part_lo = 0, uint32_t part_hi = 0xFFFFFFFFu, uint32_t sym_base = 0) {
     static_assert(SPS == 0 || SPS == 10 || SPS == 20 || SPS == 40, "0 = run-time samples per symbol; 10 has its own window and timing code, 20 / 40 are the generic code with the constant folded in");
     constexpr bool BOUNDED = DhIsBounded<NZ, FAST, SPS>::value;                      // see "Error-bounded FIR" above
-    constexpr bool MF16 = DH_FIR_F16 && BOUNDED && (NZ == 80 || NZ == 160) && KEEPF != 2;           // its fused FIR as a split-f16 product on the matrix cores
+    constexpr bool MF16 = BOUNDED && (NZ == 80 || NZ == 160) && KEEPF != 2;           // its fused FIR as a split-f16 product on the matrix cores
     DhBoundState* const BS = DH_BOUND_STATE(S);
     float* st = P.state + (size_t) ch * P.state_stride;
     uint32_t* sth = (uint32_t*) st;
@@ -2047,9 +2198,6 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     uint8_t* syms = P.syms + (size_t) ch * P.sym_stride;
     const float* in_end = P.in + (size_t) (P.n_channels - 1u) * P.in_stride + P.n;    // end of the readable input
 
-    // raw-sample window layout: padded one word per 16 for the FIR's lane-strided reads; plain without an RRC stage
-    // (the samples are then used where they were staged, and the window sums sit right behind them)
-#define DH_XP(e) (NZ > 0 ? DH_XPAD(e) : (e))
     DH_PHASE_MARK_BEGIN();
     // ---- load carried state
     uint32_t k0 = sth[DH_ST_K];
@@ -2087,7 +2235,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         if (lane < 2) S.stats[lane] = 0;
     }
 
-    // error-bounded mode (see DH_BOUNDED_FIR above): the tail then starts with DH_ST_P0 samples of HISTORY, so that the
+    // error-bounded mode (see "Error-bounded FIR" above): the tail then starts with DH_ST_P0 samples of HISTORY, so that the
     // raw samples behind every entry of the 100-symbol rings are still at hand when a comparison has to be settled exactly
     uint32_t p = BOUNDED ? sth[DH_ST_P0] : 0u;          // read position in the filtered stream
     bool staged = false; uint32_t staged_p = 0;         // the LDS window already holds V[staged_p ...) (prefetch)
@@ -2095,91 +2243,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     // halves, with the constants of its run below) and the kernels without an RRC stage (as it is: they have the registers, and staged
     // from L2 at the start of the next run every run waited out an L2 round trip: POCSAG slicer 4.86 -> 4.34 ms, D-Star chain 3.94 -> 3.65,
     // r05_a_ab_logs.txt pf1)
-    constexpr bool PF_PLAIN = DH_PF_REG && NZ == 0 && !BOUNDED && !KEEPF;
-    constexpr bool PF_REG = (MF16 && DH_PF_REG) || PF_PLAIN;
+    const DhStreamView V = { tail, tc, in, nv, sps_rcp };
+    constexpr bool PF_PLAIN = NZ == 0 && !BOUNDED && !KEEPF;
+    constexpr bool PF_REG = MF16 || PF_PLAIN;
     float st_e_run = 0.0f, st_k1 = 0.0f, st_k2 = 0.0f;
-    // split-f16 FIR: the window held in `varr` (five 16-byte groups per lane, as loaded) -> zeros beyond `have`, max |x| of the
-    // wavefront, the power-of-two scale that puts it into [0.5, 1), the two arrays of halves in the window block.  Returns
-    // false (nothing stored) when max |x| is outside the range the bound covers.
-    auto stage_f16 = [&](auto& varr, uint32_t have, float& e_out, float& k1_out, float& k2_out) __attribute__((always_inline)) -> bool {
-        constexpr uint32_t LAST_LANES = (DH_FTILE + NZ - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;
-        DH_LANE_ARRAY(float, xm, 1);
-        DH_FOR_LANES_FRESH(lane) {
-            const uint32_t l4 = 4u * (uint32_t) lane;
-            if (DH_UNLIKELY(have < DH_FTILE + NZ)) {   // the last window of the push: zeros beyond the input
-#pragma unroll
-                for (int r = 0; r < DH_PF_N; r++) {
-                    const uint32_t e = l4 + 4u * DH_WAVE * (uint32_t) r;
-                    dh_f4 w = DH_LA(varr, lane)[r];
-                    w.x = e + 0u < have ? w.x : 0.0f; w.y = e + 1u < have ? w.y : 0.0f;
-                    w.z = e + 2u < have ? w.z : 0.0f; w.w = e + 3u < have ? w.w : 0.0f;
-                    DH_LA(varr, lane)[r] = w;
-                }
-            }
-            float mx = 0.0f;                            // (a NaN is skipped here and caught behind the FIR)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            {
-                // ten v_max3_f32 in ONE statement (as ten statements the compiler put an s_nop behind each)
-                static_assert(DH_PF_N == 5, "five groups of four");
-                const dh_f4 w0 = varr[0], w1 = varr[1], w2 = varr[2], w3 = varr[3], w4 = varr[4];
-                asm("v_max3_f32 %0, |%1|, |%2|, 0\n\tv_max3_f32 %0, |%3|, |%4|, %0\n\tv_max3_f32 %0, |%5|, |%6|, %0\n\tv_max3_f32 %0, |%7|, |%8|, %0\n\t"
-                    "v_max3_f32 %0, |%9|, |%10|, %0\n\tv_max3_f32 %0, |%11|, |%12|, %0\n\tv_max3_f32 %0, |%13|, |%14|, %0\n\tv_max3_f32 %0, |%15|, |%16|, %0\n\t"
-                    "v_max3_f32 %0, |%17|, |%18|, %0\n\tv_max3_f32 %0, |%19|, |%20|, %0"
-                    : "=&v"(mx) : "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w),
-                                  "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w));
-            }
-#else
-#pragma unroll
-            for (int r = 0; r < DH_PF_N; r++) {
-                const dh_f4 w = DH_LA(varr, lane)[r];
-                mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.x), __builtin_fabsf(w.y)));
-                mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.z), __builtin_fabsf(w.w)));
-            }
-#endif
-            DH_LA(xm, lane)[0] = mx;
-        }
-        float xmax;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        xmax = dh_wave_max(xm[0]);
-#else
-        xmax = 0.0f;
-        for (int l = 0; l < DH_WAVE; l++) xmax = __builtin_fmaxf(xmax, xm[l][0]);
-#endif
-        float scale = 1.0f;
-        if (xmax == 0.0f) { e_out = 0.0f; k1_out = P.inv_gain; }                       // all zeros in, all zeros out
-        else if (xmax >= DH_BOUND_XMAX_LO && xmax <= DH_BOUND_XMAX_HI) {
-            union { float f; uint32_t u; } b; b.f = xmax;
-            const uint32_t ex = b.u >> 23;                                              // xmax in [2^(ex - 127), 2^(ex - 126))
-            b.u = (253u - ex) << 23; scale = b.f;                                       // 2^(126 - ex)
-            b.u = (ex + 1u) << 23; k1_out = P.inv_gain * b.f;                           // fl32(1 / gain) 2^(ex - 126): exact scaling
-            e_out = P.err_coef_f16 * xmax;
-        } else return false;                                                            // tiny, huge or infinite samples: outside the bound's assumptions
-        k2_out = k1_out * 0.00048828125f;                                               // 2^-11
-        // (the arrays are as long as the last block's K range reaches: the halves behind the window, under zero taps, must be
-        // finite -- the lanes of the last group beyond the window store zeros there)
-        constexpr uint32_t STORE_LANES = (DH_F16_HALVES_OF(NZ) - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;
-        static_assert(STORE_LANES >= LAST_LANES && STORE_LANES <= DH_WAVE, "the partial group covers the padded arrays");
-        DH_FOR_LANES_FRESH(lane) {
-            const bool in_last = (uint32_t) lane < LAST_LANES, in_store = (uint32_t) lane < STORE_LANES;
-            if (STORE_LANES > LAST_LANES && !in_last) { dh_f4 z; z.x = 0.0f; z.y = 0.0f; z.z = 0.0f; z.w = 0.0f; DH_LA(varr, lane)[DH_PF_N - 1] = z; }
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            dh_h4* d1 = reinterpret_cast<dh_h4*>(S.xf) + lane;                          // halves 4 lane .. 4 lane + 3 of group 0; group r is 256 halves on
-            dh_h4* d2 = reinterpret_cast<dh_h4*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + lane;
-#pragma unroll
-            for (int r = 0; r < DH_PF_N; r++) {
-                dh_h4 a, b;
-                dh_f16_split4(varr[r], scale, a, b);
-                if (r < DH_PF_N - 1 || in_store) { d1[DH_WAVE * r] = a; d2[DH_WAVE * r] = b; }
-            }
-#else
-            uint16_t* d1 = reinterpret_cast<uint16_t*>(S.xf) + 4 * lane;
-            uint16_t* d2 = reinterpret_cast<uint16_t*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + 4 * lane;
-            for (int r = 0; r < DH_PF_N; r++)
-                if (r < DH_PF_N - 1 || in_store) dh_f16_split4(varr[lane][r], scale, d1 + 4 * DH_WAVE * r, d2 + 4 * DH_WAVE * r);
-#endif
-        }
-        return true;
-    };
     uint32_t nsym = sym_base;                           // symbols of this push so far (a later part of a split push starts behind the earlier ones')
     bool overflow = false;
     const uint32_t max_run = (DH_FTILE - 2) / sps;      // symbols whose windows fit one FIR pass
@@ -2203,6 +2270,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 #define DH_TAPFRAG_SETTLE() do { if constexpr (MF16) { _Pragma("unroll") for (int f_ = 0; f_ < 2 * DH_F16_KSTEPS_OF(NZ > 0 ? NZ : 80); f_++) \
         asm volatile("" :: "v"(tapfrag_regs[f_])); } } while (0)
 #else
+    const uint32_t (* const tapfrag_regs)[DH_WAVE][4] = reinterpret_cast<const uint32_t (*)[DH_WAVE][4]>(P.tapfrag);     // (harness: the table itself)
 #define DH_TAPFRAG_LOAD() ((void) 0)
 #define DH_TAPFRAG_SETTLE() ((void) 0)
 #endif
@@ -2212,7 +2280,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         // s_0 = p, s_q = p + q*sps + step_off for q >= 1.
         const int32_t step_off = (k0 == 0) ? off : 0;   // applied after the first symbol of a block
         uint32_t m = 0;
-        if (DH_PLAN_FAST && SPS == 10 && DH_LIKELY(k0 == 0 && (int32_t) p <= fast_p_end && (int32_t) nsym <= fast_sym_end)) {
+        if (SPS == 10 && DH_LIKELY(k0 == 0 && (int32_t) p <= fast_p_end && (int32_t) nsym <= fast_sym_end)) {
             // the usual run: it starts a variance block and holds all of it -- the stream has the samples whatever the pending step
             // is (nf - p >= 1003 >= 1002 + step_off) and the symbol buffer the room: what the general form below comes to, in three
             // compares instead of forty-five scalar instructions and a load of the symbol capacity from the argument block
@@ -2267,9 +2335,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             // the load) and DH_XP(4 lane + 256 r) = DH_XP(4 lane) + 272 r words further in the padded window -- written
             // out, because the compiler otherwise rebuilds every address from the lane id (6 VALU per group).  Only the
             // last group is partial (elements < DH_FTILE + NZ): its lanes beyond the window re-read group 0.
-            constexpr uint32_t GSTEP = NZ > 0 ? DH_XPAD(4u * DH_WAVE) : 4u * DH_WAVE;
-            constexpr uint32_t LAST_LANES = (DH_FTILE + NZ - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;     // lanes of the last group inside the window
-            static_assert((DH_FTILE + NZ) % 4u == 0 && (DH_FTILE + NZ) >= 4u * DH_WAVE * (DH_PF_N - 1) && LAST_LANES <= DH_WAVE, "four full groups + a partial one cover the window");
+            constexpr uint32_t GSTEP = DhWindowGroups<NZ>::GSTEP, LAST_LANES = DhWindowGroups<NZ>::LAST_LANES;
             DH_LANE_ARRAY(dh_f4, v, DH_PF_N);
             DH_FOR_LANES_FRESH(lane) {
                 const uint32_t l4 = 4u * (uint32_t) lane;
@@ -2284,10 +2350,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 #pragma unroll
                         for (int r = 0; r < DH_PF_N; r++) {
                             const uint32_t e = l4 + 4u * DH_WAVE * (uint32_t) r;
-                            dh_f4 w = DH_LA(v, lane)[r];
-                            w.x = e + 0u < have ? w.x : 0.0f; w.y = e + 1u < have ? w.y : 0.0f;
-                            w.z = e + 2u < have ? w.z : 0.0f; w.w = e + 3u < have ? w.w : 0.0f;
-                            DH_LA(v, lane)[r] = w;
+                            DH_LA(v, lane)[r] = dh_zero_beyond(DH_LA(v, lane)[r], e, have);
                         }
                     }
                     if (BOUNDED) {                     // max |x| of the window (a NaN is skipped here and caught behind the FIR)
@@ -2307,9 +2370,9 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 }
             }
             if (MF16 && !use_exact) {
-                // split-f16 FIR: the window goes to LDS as two arrays of halves (stage_f16)
+                // split-f16 FIR: the window goes to LDS as two arrays of halves (dh_stage_f16)
                 xmax_done = true;
-                if (stage_f16(v, have, e_run, k1, k2)) f16_staged = true; else use_exact = true;
+                if (dh_stage_f16<NZ>(P, S, v, have, e_run, k1, k2)) f16_staged = true; else use_exact = true;
             }
             if (!f16_staged) {
                 DH_FOR_LANES_FRESH(lane) {
@@ -2323,7 +2386,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                     dh_lds_stores_done();
                 }
             }
-        } else if (MF16 && !use_exact && DH_F16_EDGE_WINDOWS) {
+        } else if (MF16 && !use_exact) {
             // The first window of a push (it starts in the carried tail) and the last ones (they end within DH_FTILE + NZ of
             // the input buffer's end): gathered sample by sample, then the same two arrays of halves as everywhere else.  These
             // runs used to go through the reference-order FIR -- one or two of every push, which is most of a push of a few
@@ -2343,13 +2406,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 }
             }
             xmax_done = true;
-            if (stage_f16(v, have, e_run, k1, k2)) f16_staged = true;
+            if (dh_stage_f16<NZ>(P, S, v, have, e_run, k1, k2)) f16_staged = true;
             else {
                 use_exact = true;
-                DH_FOR_LANES_FRESH(lane) {
-                    for (uint32_t e = lane; e < DH_FTILE + NZ; e += DH_WAVE)
-                        S.xf[DH_XP(e)] = p + e < nv ? dh_virtual_sample(tail, tc, in, p + e) : 0.0f;
-                }
+                dh_gather_window<NZ>(S, tail, tc, in, nv, p);
             }
         } else if (p >= tc) {
             use_exact = BOUNDED;
@@ -2368,20 +2428,11 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             }
         } else {
             use_exact = BOUNDED;
-            DH_FOR_LANES_FRESH(lane) {
-                for (uint32_t e = lane; e < DH_FTILE + NZ; e += DH_WAVE)
-                    S.xf[DH_XP(e)] = p + e < nv ? dh_virtual_sample(tail, tc, in, p + e) : 0.0f;
-            }
+            dh_gather_window<NZ>(S, tail, tc, in, nv, p);
         }
         DH_BARRIER();
         if (BOUNDED && !use_exact && !xmax_done) {
-            float xmax;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            xmax = dh_wave_max(xmax_lane[0]);
-#else
-            xmax = 0.0f;
-            for (int l = 0; l < DH_WAVE; l++) xmax = __builtin_fmaxf(xmax, xmax_lane[l][0]);
-#endif
+            const float xmax = DH_WAVE_MAX(xmax_lane);
             if (xmax == 0.0f) e_run = 0.0f;             // all zeros in, all zeros out of either FIR
             else if (xmax >= DH_BOUND_XMAX_LO && xmax <= DH_BOUND_XMAX_HI) e_run = P.err_coef * xmax;
             else use_exact = true;                      // tiny, huge or infinite samples: outside the bound's assumptions
@@ -2398,7 +2449,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             DH_COMPILER_FENCE();                        // forces the tap loads below to stay inside this pass
             // (taps from the LDS copy into vector registers: as scalar operands they free 40 VGPRs but cost this kernel 5 %,
             // see DhFirBatch)
-            constexpr bool MFMA = DH_MFMA_FIR && NZ > 0 && NZ <= 80 && (BOUNDED || FAST) && !MF16;      // the fused FIR as f32 MFMAs (dh_fir_mfma)
+            constexpr bool MFMA = NZ > 0 && NZ <= 80 && (BOUNDED || FAST) && !MF16;      // the fused FIR as f32 MFMAs (dh_fir_mfma)
             int mf_layout = 0;                          // fo[] holds a matrix-core output layout: 1 = DH_MF_OUT, 2 = DH_F16_OUT
             if (BOUNDED) {
                 uint64_t vote_bad = 0;
@@ -2407,11 +2458,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                         // (f16_staged holds: every staging path that does not fill the two arrays of halves sets use_exact)
                         DH_FOR_LANES_FRESH(lane) {
                             float t = 0.0f;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-                            dh_fir_f16<MF16 ? NZ : 80>(S.xf, tapfrag_regs, lane, k1, k2, fo);
-#else
-                            dh_fir_f16<MF16 ? NZ : 80>(S.xf, reinterpret_cast<const uint32_t (*)[DH_WAVE][4]>(P.tapfrag), lane, k1, k2, fo[lane]);
-#endif
+                            dh_fir_f16<MF16 ? NZ : 80>(S.xf, tapfrag_regs, lane, k1, k2, DH_LA(fo, lane));
 #pragma unroll
                             for (int j = 0; j < DH_FIR_L; j++) t = __builtin_fmaf(DH_LA(fo, lane)[j], 0.0f, t);       // NaN or infinity anywhere: 0 * y is NaN
                             DH_BALLOT_ACC(vote_bad, !(t == 0.0f), lane);
@@ -2426,33 +2473,16 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                             DH_BALLOT_ACC(vote_bad, bad, lane);
                         }
                         mf_layout = 1;
-                    } else {
-                        float tv[NZ / 2 + 1];
-#pragma unroll
-                        for (int i = 0; i <= NZ / 2; i++) tv[i] = S.tapsf[i];
-                        DH_FOR_LANES_FRESH(lane) {
-                            bool bad = false;
-                            if ((uint32_t) (lane * DH_FIR_L) < need_fir)
-                                dh_fir_lane<NZ, true>(tv, P.gain, P.rgain, P.inv_gain, S.xf, lane, DH_LA(fo, lane), &bad);
-                            DH_BALLOT_ACC(vote_bad, bad, lane);
-                        }
-                    }
+                    } else static_assert(!BOUNDED, "every error-bounded kernel filters on the matrix cores (launch_plan.hpp instantiates none without MF16 or MFMA)");
                 }
                 if (DH_UNLIKELY(use_exact || vote_bad)) {            // a NaN / infinity among the samples: the reference's arithmetic decides
                     use_exact = true; e_run = 0.0f; BS->n_exact_runs++; mf_layout = 0;
                     if (MF16 && f16_staged) {           // the window block holds halves: the reference's FIR wants the raw samples back
                         DH_BARRIER();
-                        DH_FOR_LANES_FRESH(lane) {
-                            for (uint32_t e = lane; e < DH_FTILE + NZ; e += DH_WAVE)
-                                S.xf[DH_XP(e)] = p + e < nv ? dh_virtual_sample(tail, tc, in, p + e) : 0.0f;
-                        }
+                        dh_gather_window<NZ>(S, tail, tc, in, nv, p);
                         DH_BARRIER();
                     }
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-                    dh_exact_fir_pass<NZ>(P, S, need_fir, nullptr, fo);
-#else
-                    dh_exact_fir_pass<NZ>(P, S, need_fir, fo, nullptr);
-#endif
+                    dh_exact_fir_pass<NZ>(P, S, need_fir, fo);
                 }
             } else if constexpr (MFMA) {
                 DH_FOR_LANES_FRESH(lane) {
@@ -2490,15 +2520,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 }
             } else {
                 DH_FOR_LANES_FRESH(lane) {
-                    if ((uint32_t) (lane * DH_FIR_L) < need_fir) {
-                        dh_f4a* dst = reinterpret_cast<dh_f4a*>(S.xf + DH_FIR_L * lane);
-#pragma unroll
-                        for (int j = 0; j < DH_FIR_L / 4; j++) {
-                            dh_f4a v; v.x = DH_LA(fo, lane)[4 * j]; v.y = DH_LA(fo, lane)[4 * j + 1];
-                            v.z = DH_LA(fo, lane)[4 * j + 2]; v.w = DH_LA(fo, lane)[4 * j + 3];
-                            dst[j] = v;
-                        }
-                    }
+                    if ((uint32_t) (lane * DH_FIR_L) < need_fir) DH_STORE_FIR_OUT(S.xf, lane, fo);
                 }
             }
             DH_BARRIER();
@@ -2507,10 +2529,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         DH_PHASE_MARK(1);
         const float* fbuf = S.xf;
 
-        // ---- prefetch: the raw window of the NEXT run.  Its start is already known (the timing decision of this
-        // block only moves symbols 1.. of the next one), the window block is idle from here to the end of the
-        // iteration, and P4-P6 are latency-bound with few live registers: the HBM latency of these loads hides
-        // behind them.  Five 16-byte loads per lane, parked in registers until P7.
+        // ---- the raw window of the NEXT run: planned here, fetched behind P3 (dh_issue_next_window), stored in P7 (dh_store_next_window)
         const uint32_t p_next = last_start + sps + ((k0 == 0 && m == 1) ? (uint32_t) step_off : 0u);
         const bool pf_ok = p_next >= tc && p_next < nv;
         const uint32_t pf_have = pf_ok ? dh_min<uint32_t>(DH_FTILE + NZ, nv - p_next) : 0u;
@@ -2532,41 +2551,6 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 for (uint32_t e = s0 + (uint32_t) lane; e < s1; e += DH_WAVE) orow[e] = fbuf[e];
             }
         }
-        auto issue_next_window = [&]() __attribute__((always_inline)) {
-        if (DH_LIKELY(pf_reg)) {
-            // The split-f16 FIR leaves registers free where the packed-FMA FIR had none: the next window's five 16-byte loads
-            // per lane are issued here, straight from HBM, land while P4 - P6 run, and P7 turns them into the two arrays of
-            // halves -- the next iteration starts at the matrix cores.
-            constexpr uint32_t LAST_LANES = (DH_FTILE + NZ - 4u * DH_WAVE * (DH_PF_N - 1)) / 4u;
-            const float* src = in + (p_next - tc);
-            DH_FOR_LANES_FRESH(lane) {
-                const float* lsrc = src + 4u * (uint32_t) lane;
-                const bool in_last = (uint32_t) lane < LAST_LANES;
-#pragma unroll
-                for (int r = 0; r < DH_PF_N - 1; r++) DH_LA(pfr, lane)[PF_REG ? r : 0] = dh_load4_stream(lsrc + 4 * DH_WAVE * r);
-                if constexpr (LAST_LANES > 0) DH_LA(pfr, lane)[PF_REG ? DH_PF_N - 1 : 0] = dh_load4_stream(lsrc + (in_last ? 4 * DH_WAVE * (DH_PF_N - 1) : 0));
-                else (void) in_last;
-            }
-        } else {
-        // Register-free variant: one dword per 128-byte line of the next window is requested now, which pulls the
-        // lines into L2; the next iteration's P1 then stages from L2 instead of HBM.  The dwords themselves are not
-        // wanted: global_load_lds_dword drops them (lane l -> m0 + 4 l) into a part of the window block that is dead
-        // until the next staging, so no vector register is tied to a load the compiler does not know about.  They
-        // have landed before the next P1 stores anything there (its own, younger loads are waited for first), and
-        // an explicit s_waitcnt follows the loop for the last one.
-        if (pf_plain) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            const uint32_t pf_lane = (uint32_t) dh_fresh_lane_id_();       // not loop-invariant: a hoisted address is spilled
-            const float* line = in + (p_next - tc) + 32u * pf_lane;
-            const uint32_t sink = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) (S.xf + DH_PF_SINK);
-            uint32_t keep_m0;
-            if (32u * pf_lane < DH_FTILE + NZ)
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep_m0) : "s"(sink), "v"(line) : "memory");
-#endif
-        }
-        }
-        };
 
         DH_COMPILER_FENCE();                            // the bookkeeping in LDS is read here, not carried across the FIR
         float e_blk = 0.0f;
@@ -2592,7 +2576,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         DH_BARRIER();
         DH_PHASE_MARK(2);
 
-        issue_next_window();
+        dh_issue_next_window<NZ, PF_REG>(S, in, tc, p_next, pf_plain, pf_reg, pfr);
 
         // ---- P4: sliding AGC min/max as two wave scans
         DhAgcPair agc = { 0.0f, 0.0f, 0.0f, 0.0f };
@@ -2610,7 +2594,6 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             dh_slice_symbols<SPS, LV, BOUNDED>(P, S, agc, syms + nsym, k0, m, ev_lo, ev_hi, U, vote_a, vote_b);
         }
         if (BOUNDED && DH_UNLIKELY((vote_a | vote_b) != 0)) {
-            const DhStreamView V = { tail, tc, in, nv, sps_rcp };
             dh_settle_doubts<NZ>(P, S, BS, V, syms + nsym, k0, e_eff, sps, ev_lo, ev_hi, vote_a, vote_b);
         }
 
@@ -2619,7 +2602,6 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         int32_t new_off = 0;
         const bool block_done = (k0 + m == DH_VARIANCE_SYMBOLS);
         if (block_done && DH_STOP_AFTER >= 6) {
-            const DhStreamView V = { tail, tc, in, nv, sps_rcp };
             new_off = dh_timing_decision<NZ, SPS, BOUNDED>(P, S, BS, V, sps, k0, e_blk);
         }
 
@@ -2635,7 +2617,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         }
         staged = false;
         if (DH_LIKELY(pf_reg)) {
-            if constexpr (PF_REG && MF16) { staged = stage_f16(pfr, pf_have, st_e_run, st_k1, st_k2); staged_p = p_next; }
+            if constexpr (PF_REG && MF16) { staged = dh_stage_f16<NZ>(P, S, pfr, pf_have, st_e_run, st_k1, st_k2); staged_p = p_next; }
             else if constexpr (PF_PLAIN) {
                 // no RRC stage: the window is the 1 024 samples themselves (four groups of four per lane, unpadded), zeros beyond the stream's end
                 static_assert(!PF_PLAIN || (DH_FTILE == 4u * DH_WAVE * (DH_PF_N - 1)), "four full groups cover the window");
@@ -2645,11 +2627,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 #pragma unroll
                     for (int r = 0; r < DH_PF_N - 1; r++) {
                         dh_f4 w = DH_LA(pfr, lane)[PF_REG ? r : 0];
-                        if (DH_UNLIKELY(pf_have < DH_FTILE)) {
-                            const uint32_t e = l4 + 4u * DH_WAVE * (uint32_t) r;
-                            w.x = e + 0u < pf_have ? w.x : 0.0f; w.y = e + 1u < pf_have ? w.y : 0.0f;
-                            w.z = e + 2u < pf_have ? w.z : 0.0f; w.w = e + 3u < pf_have ? w.w : 0.0f;
-                        }
+                        if (DH_UNLIKELY(pf_have < DH_FTILE)) w = dh_zero_beyond(w, l4 + 4u * DH_WAVE * (uint32_t) r, pf_have);
                         dh_store4(ldst + 4 * DH_WAVE * r, w);
                     }
                 }
@@ -2823,15 +2801,7 @@ DH_HD void dh_rrc_tile(const DhRrcParams& R, uint32_t ch, uint32_t tile, DhDspSh
     }
     DH_BARRIER();                                       // every lane has read its window
     DH_FOR_LANES(lane) {
-        if ((uint32_t) lane * DH_FIR_L < cnt) {
-            dh_f4a* dst = reinterpret_cast<dh_f4a*>(S.xf + DH_FIR_L * lane);
-#pragma unroll
-            for (int q = 0; q < DH_FIR_L / 4; q++) {
-                dh_f4a v; v.x = DH_LA(fo, lane)[4 * q]; v.y = DH_LA(fo, lane)[4 * q + 1];
-                v.z = DH_LA(fo, lane)[4 * q + 2]; v.w = DH_LA(fo, lane)[4 * q + 3];
-                dst[q] = v;
-            }
-        }
+        if ((uint32_t) lane * DH_FIR_L < cnt) DH_STORE_FIR_OUT(S.xf, lane, fo);
     }
     DH_BARRIER();
     DH_FOR_LANES(lane) {

@@ -45,6 +45,13 @@ int hip_fail(hipError_t e, const char* what) {
 #ifndef DH_LB
 #define DH_LB 4          // minimum waves per SIMD the wide-filter kernels are register-budgeted for (128 VGPRs)
 #endif
+// The hand-over flag word of a split push (DH_ST_PART of a channel's state; k_chain below):
+// epoch of the push (24 bits) | parts written back << 24 | a later part gave up << 26 | XCC id << 28
+#define DH_PF_GAVE_UP (1u << 26)
+__device__ __forceinline__ bool dh_pf_of_push(uint32_t v, uint32_t epoch) { return (v & 0x00FFFFFFu) == epoch; }
+__device__ __forceinline__ uint32_t dh_pf_done(uint32_t v) { return (v >> 24) & 3u; }
+__device__ __forceinline__ uint32_t dh_pf_xcc(uint32_t v) { return v >> 28; }
+__device__ __forceinline__ uint32_t dh_xcc_id() { return __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u; }      // HW_REG_XCC_ID
 // ---------------------------------------------------------------------------------- kernels
 // second launch-bounds argument = minimum waves per SIMD: caps the VGPR budget at 128 (wide) / 256 (narrow)
 // KEEPF: the launch also delivers the filtered samples (DhDspParams::filt_out; BASELINE configs[1] in one kernel)
@@ -86,7 +93,6 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
         part_hi = part == 0 ? P.split_n0 : (part == 1 && P.split_n1) ? P.split_n1 : 0xFFFFFFFFu;       // (= dh_part_lo / dh_part_hi, launch_plan.hpp)
     }
     const uint32_t ch = bid + P.ch_base;
-    // flag word: epoch of the push (24 bits) | parts written back << 24 | a later part gave up << 26 | XCC id << 28
     uint32_t* const part_flag = reinterpret_cast<uint32_t*>(P.state) + (size_t) ch * P.state_stride + DH_ST_PART;
     if (P.split_n0 && P.split_fixup) {
         // The launch behind a split launch (HipBackend::go_chain), one workgroup per channel.  The kernel boundary in front of
@@ -94,20 +100,20 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
         // back -- every channel, unless a hand-over failed -- is left alone.  Otherwise the rest of the row is done here in
         // one piece, starting behind the last part that was completed.
         const uint32_t v = dh_uniform(__hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const uint32_t done = (v & 0x00FFFFFFu) == P.part_epoch ? ((v >> 24) & 3u) : 0u;
+        const uint32_t done = dh_pf_of_push(v, P.part_epoch) ? dh_pf_done(v) : 0u;
         if (done > last_part) return;
         part = done;
         part_lo = part == 0 ? 0u : part == 1 ? P.split_n0 : P.split_n1;
         if (part) sym_base = dh_uniform(__hip_atomic_load(P.sym_count + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     } else if (part) {
-        const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u;      // HW_REG_XCC_ID
+        const uint32_t xcc = dh_xcc_id();
         bool ok = false, told = false;
         const bool forced = P.split_force_fail && part == 1u && ch % P.split_force_fail == 1u;     // (tests: this hand-over "fails"; a third part then has to notice)
         for (uint32_t spin = 0; spin < (1u << 16) && !forced; spin++) {                 // (a first part takes ~1.5 ms; 2^16 x ~2 us)
             const uint32_t v = dh_uniform(__hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if ((v & 0x00FFFFFFu) == P.part_epoch) {
-                if (v & (1u << 26)) { told = true; break; }                              // the part in front of this one gave up
-                if (((v >> 24) & 3u) >= part) { ok = (v >> 28) == xcc; break; }
+            if (dh_pf_of_push(v, P.part_epoch)) {
+                if (v & DH_PF_GAVE_UP) { told = true; break; }                              // the part in front of this one gave up
+                if (dh_pf_done(v) >= part) { ok = dh_pf_xcc(v) == xcc; break; }
             }
             __builtin_amdgcn_s_sleep(64);
         }
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
                 // own push) -- the part behind this one would then spin through its whole patience instead of leaving at once
                 uint32_t seen = __hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 for (;;) {
-                    const uint32_t want = ((seen & 0x00FFFFFFu) == P.part_epoch ? seen : P.part_epoch) | (1u << 26);
+                    const uint32_t want = (dh_pf_of_push(seen, P.part_epoch) ? seen : P.part_epoch) | DH_PF_GAVE_UP;
                     if (__hip_atomic_compare_exchange_strong(part_flag, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
                 }
                 if (P.overflow) __hip_atomic_fetch_add(P.overflow + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (a statistic: dh_engine_debug_header(202))
@@ -164,10 +170,10 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
         if (threadIdx.x == 0) {
             // (a later part that has given up meanwhile set bit 26 with a fetch_or: a plain store would wipe it out and leave the part
             // behind that one spinning through its whole patience -- compare-and-swap keeps the bit when the word is of this push)
-            const uint32_t mine = P.part_epoch | (part_end + 1u) << 24 | (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) << 28;
+            const uint32_t mine = P.part_epoch | (part_end + 1u) << 24 | dh_xcc_id() << 28;
             uint32_t seen = __hip_atomic_load(flag_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             for (;;) {
-                const uint32_t want = mine | (((seen & 0x00FFFFFFu) == P.part_epoch) ? (seen & (1u << 26)) : 0u);
+                const uint32_t want = mine | (dh_pf_of_push(seen, P.part_epoch) ? (seen & DH_PF_GAVE_UP) : 0u);
                 if (__hip_atomic_compare_exchange_strong(flag_end, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
             }
         }
@@ -223,7 +229,7 @@ __global__ __launch_bounds__(DH_WAVE, DH_DSTAR_LB) void k_dstar(const DhDecParam
 
 // which XCD workgroup i of a launch runs on (HipBackend::tail_split_probe)
 __global__ __launch_bounds__(DH_WAVE) void k_xcc_probe(uint32_t* out) {
-    if (threadIdx.x == 0) out[blockIdx.x] = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u;       // HW_REG_XCC_ID
+    if (threadIdx.x == 0) out[blockIdx.x] = dh_xcc_id();
 }
 
 // what the window phases of the slicer rest on (dsp_core.hpp, P3): eight / sixteen bytes read from LDS at an address that is only four-byte

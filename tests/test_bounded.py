@@ -1,4 +1,4 @@
-"""The error-bounded FIR of the wide-filter sps-10 kernels (dsp_core.hpp: DH_BOUNDED_FIR): FMA filtering + a proven
+"""The error-bounded FIR of the wide-filter sps-10 kernels (dsp_core.hpp: "Error-bounded FIR"): FMA filtering + a proven
 error radius decide what they can, the reference's arithmetic decides the rest.  Whatever the split, dibits, frames and
 events must be the oracle's, bit for bit:
 

@@ -130,9 +130,9 @@ def _blocks(lines):
 def test_exact_kernels_keep_their_two_firs_apart_and_the_hot_one_in_registers(kernels):
     """The exact chain kernels (DMR, YSF, NXDN) carry two FIR bodies (dsp_core.hpp, "Error-bounded FIR"):
     * the reference's arithmetic -- packed multiplies and packed adds, rounded one by one: NOTHING fused in that block;
-    * the error-bounded one, which runs in (nearly) every pass: no scratch access in that block.  For the wide filter
-      (DMR, YSF) it is the split-f16 product on the matrix cores: 36 v_mfma_f32_16x16x32_f16 per pass and no f32 FIR
-      arithmetic beside them; for the narrow filter (NXDN) packed FMAs.
+    * the error-bounded one, which runs in (nearly) every pass: no scratch access in that block.  It is the split-f16
+      product on the matrix cores with no f32 FIR arithmetic beside it: 36 v_mfma_f32_16x16x32_f16 per pass for the wide
+      filter (DMR, YSF), 72 for the narrow one (NXDN).
     A handful of spills elsewhere (rare paths, the YSF decoder half) is what a fourth wavefront per SIMD costs."""
     exact = [n for n in kernels if "k_chain" in n and ("ILi80ELb0E" in n or "ILi160ELb0E" in n)]
     assert len(exact) == 8                    # DMR, YSF, NXDN (161 taps) at sps 20 and at a run-time sps, each as launch PART 0 and PART 1 (DH_FLAG_OVERLAP_PUSHES)

@@ -88,7 +88,7 @@ def test_division_by_ten_all_floats(gpu_ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# The split-f16 FIR on the matrix cores (dsp_core.hpp, "DH_FIR_F16").  Its error radius is computed from (a) the split of
+# The split-f16 FIR on the matrix cores (dsp_core.hpp, "The fused FIR as a SPLIT-f16 product").  Its error radius is computed from (a) the split of
 # samples and taps into two halves each and (b) assumption (H1) about v_mfma_f32_16x16x32_f16:
 #     |D - (C + sum a b)| <= 41 u mu,  u = 2^-24,  mu >= every addend and partial sum  (here: mu = |C| + sum |a b|)
 # These tests pin both on the device (and run against the harness's stand-in on the CPU tier).
