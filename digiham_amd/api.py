@@ -235,6 +235,9 @@ class Engine:
         if self._inflight:
             self.sync()                          # the reset joined the streams; inputs are released once it has run
 
+    def reset_channel(self, ch):
+        _check(self.ctx.lib.dh_engine_reset_channel(self._h, ch), "dh_engine_reset_channel", self.ctx.lib)
+
     def set_slot_filter(self, f):
         _check(self.ctx.lib.dh_engine_set_slot_filter(self._h, f), "dh_engine_set_slot_filter", self.ctx.lib)
 

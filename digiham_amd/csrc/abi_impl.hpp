@@ -28,7 +28,13 @@
 
 static_assert(sizeof(dh_event) == 32, "dh_event layout");
 
-struct dh_engine { dh::Engine<DH_BACKEND> impl; };
+struct dh_engine {
+    dh::Engine<DH_BACKEND> impl;
+    auto scope() const { return impl.be.scope(); }      // (as dh_channelizer::scope: DH_ON_DEVICE takes either handle)
+};
+// every entry that touches the device runs on its handle's device (an engine's, a channelizer's) whatever the calling
+// thread's current device is (HipBackend::Scope)
+#define DH_ON_DEVICE(h) auto dh_on_device_ = (h)->scope(); (void) dh_on_device_
 
 enum { DH_CODE_H74 = 0, DH_CODE_H139, DH_CODE_H1511, DH_CODE_H1611, DH_CODE_QR, DH_CODE_G208, DH_CODE_G2412, DH_CODE_BCH3121 };
 
@@ -109,7 +115,7 @@ int dh_engine_create(const dh_engine_config* cfg, dh_engine** out) {
     dh_engine* e = new (std::nothrow) dh_engine;
     if (!e) return DH_ENOMEM;
     int rc = e->impl.be.open(cfg->device, cfg->stream);
-    if (rc == DH_OK) { auto on_device = e->impl.be.scope(); (void) on_device; rc = e->impl.init(*cfg); if (rc != DH_OK) e->impl.destroy(); }
+    if (rc == DH_OK) { DH_ON_DEVICE(e); rc = e->impl.init(*cfg); if (rc != DH_OK) e->impl.destroy(); }
     if (rc != DH_OK) { delete e; return rc; }
     *out = e;
     return DH_OK;
@@ -118,7 +124,7 @@ int dh_engine_create(const dh_engine_config* cfg, dh_engine** out) {
 void dh_engine_destroy(dh_engine* e) {
     if (!e) return;
     {
-        auto on_device = e->impl.be.scope(); (void) on_device;
+        DH_ON_DEVICE(e);
         e->impl.be.sync();
         e->impl.be.close();
         e->impl.destroy();
@@ -126,8 +132,6 @@ void dh_engine_destroy(dh_engine* e) {
     delete e;
 }
 
-// every entry below runs on the engine's device whatever the calling thread's current device is (HipBackend::Scope)
-#define DH_ON_DEVICE(e) auto dh_on_device_ = (e)->impl.be.scope(); (void) dh_on_device_
 int dh_engine_reset(dh_engine* e) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset(); }
 int dh_engine_set_slot_filter(dh_engine* e, uint32_t f) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.set_slot_filter(f); }
 int dh_engine_reset_channel(dh_engine* e, uint32_t ch) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset_channel(ch); }
@@ -199,19 +203,9 @@ int dh_engine_read_events(dh_engine* e, uint32_t ch, dh_event* h, size_t* n) {
     return e->impl.read_row(e->impl.events, sizeof(dh_event) * e->impl.L.ev_cap, ch, e->impl.ev_count, sizeof(dh_event), h, n);
 }
 int dh_engine_read_filtered(dh_engine* e, uint32_t ch, float* h, size_t* n) {
-    if (!e || !e->impl.filtered || !n || ch >= e->impl.L.B) return DH_EINVAL;
+    if (!e) return DH_EINVAL;
     DH_ON_DEVICE(e);
-    size_t cnt = e->impl.last_n;
-    const size_t cap = *n;
-    if (e->impl.last_counts) {                   // a ragged push: this channel's own count
-        uint32_t c = 0;
-        if (e->impl.be.download(&c, e->impl.last_counts + ch, sizeof(c))) return DH_EDEVICE;
-        if (c < cnt) cnt = c;
-    }
-    *n = cnt;
-    if (cnt > cap) return DH_ECAPACITY;
-    if (cnt && h && e->impl.be.download(h, e->impl.filtered + (size_t) ch * e->impl.L.max_samples, sizeof(float) * cnt)) return DH_EDEVICE;
-    return DH_OK;
+    return e->impl.read_filtered(ch, h, n);
 }
 int dh_engine_timing_enable(dh_engine* e, uint32_t max_pushes) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.be.timing_enable(max_pushes); }
 int dh_engine_timing_read_split(dh_engine* e, float* first_ms, uint32_t* first_channels, uint32_t* n) {
@@ -242,6 +236,7 @@ int dh_engine_sync(dh_engine* e) {
 // window is the last H = T' - 1 samples of the previous one followed by the new samples.
 struct dh_channelizer {
     DH_BACKEND be;
+    dh::DeviceBuffers<DH_BACKEND> bufs{ be };           // release(), clear() and retune() act on what init() and power_enable() declare
     void* stream = nullptr;
     uint32_t B = 0, D = 0, tpad = 0, ncols = 0, max_input = 0;
     int cf32 = 0, fm = 0, dcblock = 0;
@@ -253,29 +248,22 @@ struct dh_channelizer {
     float* d_win[2] = { nullptr, nullptr };             // [T' - 1 + max_input][2] each
     float* d_state = nullptr;                           // [B][DH_CZ_STATE_WORDS]
     float* d_zbuf = nullptr;                            // FM: [max_input / D + 1][B][2]
-    void* d_stage = nullptr;                            // push_host's input
+    uint8_t* d_stage = nullptr;                         // push_host's input
     int cur = 0;
     uint32_t prev_n = 0;
     uint64_t n0 = 0;                                    // samples pushed since create / reset
-    // block power and gate (dh_channelizer_power_enable); pw_L = 0: off, nothing allocated and nothing launched
-    uint32_t pw_L = 0, pw_hang = 0;
-    float pw_inv = 0.0f, pw_open = 0.0f, pw_close = 0.0f;
-    float* pw_power = nullptr; uint8_t* pw_gate = nullptr; uint32_t* pw_counts = nullptr;      // the caller's
-    size_t pw_stride = 0;
+    DhCzParams gemm{};                                  // what init() fixes; a push adds its window, its output rows and its position
+    // block power and gate (dh_channelizer_power_enable); pw.L = 0: off, nothing allocated and nothing launched
+    DhCzPowerParams pw{};                               // what power_enable() and set_squelch() fix; a push adds its outputs and its position
     uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
     uint64_t pw_first = 0; size_t pw_n = 0;             // blocks completed by the last push
 
-    void release() {
-        for (void* p : { (void*) d_tables, (void*) d_inc, (void*) d_bmat, (void*) d_win[0], (void*) d_win[1], (void*) d_state, (void*) d_zbuf, d_stage, (void*) d_pstate })
-            if (p) be.free(p);
-    }
+    auto scope() const { return be.scope(); }
+    void release() { bufs.free_all(); }
     size_t in_bytes() const { return cf32 ? 8u : 4u; }
-    size_t win_bytes() const { return sizeof(float) * 2 * ((size_t) tpad - 1 + max_input); }
     int clear() {
         cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
-        if (be.zero(d_win[0], win_bytes()) || be.zero(d_win[1], win_bytes())) return DH_EDEVICE;
-        if (d_pstate && be.zero(d_pstate, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B)) return DH_EDEVICE;
-        return be.zero(d_state, sizeof(float) * DH_CZ_STATE_WORDS * B) ? DH_EDEVICE : DH_OK;
+        return bufs.zero_all() ? DH_EDEVICE : DH_OK;
     }
     int init(const dh_channelizer_config& c) {
         B = c.n_channels; D = c.decimation; tpad = dh_cz_tpad(c.n_taps); ncols = dh_cz_ncols(B); max_input = c.max_input;
@@ -283,15 +271,18 @@ struct dh_channelizer {
         taps.assign(tpad, 0.0f);
         for (uint32_t k = 0; k < c.n_taps; k++) taps[k] = c.taps[k];
         inc.assign(c.increments, c.increments + B);
-        const size_t bm = (size_t) 2 * tpad * ncols;
-        d_tables = (float*) be.alloc(sizeof(float) * 4 * 4096);
-        d_inc = (uint32_t*) be.alloc(sizeof(uint32_t) * B);
-        d_bmat = (float*) be.alloc(sizeof(float) * bm);
-        d_win[0] = (float*) be.alloc(win_bytes()); d_win[1] = (float*) be.alloc(win_bytes());
-        d_state = (float*) be.alloc(sizeof(float) * DH_CZ_STATE_WORDS * B);
-        if (fm) d_zbuf = (float*) be.alloc(sizeof(float) * 2 * ((size_t) max_input / D + 1) * B);
-        d_stage = be.alloc(in_bytes() * max_input);
-        if (!d_tables || !d_inc || !d_bmat || !d_win[0] || !d_win[1] || !d_state || (fm && !d_zbuf) || !d_stage) return DH_ENOMEM;
+        const size_t bm = (size_t) 2 * tpad * ncols, win = 2 * ((size_t) tpad - 1 + max_input);
+        bool ok = bufs.alloc(d_tables, 4 * 4096);
+        ok &= bufs.alloc(d_inc, B);
+        ok &= bufs.alloc(d_bmat, bm);
+        ok &= bufs.alloc(d_win[0], win, dh::ZERO_ON_RESET);
+        ok &= bufs.alloc(d_win[1], win, dh::ZERO_ON_RESET);
+        ok &= bufs.alloc(d_state, (size_t) DH_CZ_STATE_WORDS * B, dh::ZERO_PER_CHANNEL);
+        if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) max_input / D + 1) * B);
+        ok &= bufs.alloc(d_stage, in_bytes() * max_input);
+        if (!ok) return DH_ENOMEM;
+        gemm.bmat = d_bmat; gemm.coarse = d_tables; gemm.fine = d_tables + 8192; gemm.inc = d_inc; gemm.zbuf = d_zbuf;
+        gemm.D = D; gemm.tpad = tpad; gemm.B = B; gemm.ncols = ncols; gemm.fm = fm;
         std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
         for (uint32_t b = 0; b < B; b++) {
             dh_cz_columns(taps.data(), tpad, inc[b], re.data(), im.data());
@@ -311,15 +302,14 @@ struct dh_channelizer {
         const size_t pitch = sizeof(float) * ncols;
         if (be.upload2d(d_bmat + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
             be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
-            be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || be.zero(d_state + (size_t) ch * DH_CZ_STATE_WORDS, sizeof(float) * DH_CZ_STATE_WORDS))
+            be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B))
             return DH_EDEVICE;
-        if (d_pstate && be.zero(d_pstate + (size_t) ch * DH_CZ_PSTATE_WORDS, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS)) return DH_EDEVICE;
         return be.sync() ? DH_EDEVICE : DH_OK;
     }
     static bool level_ok(float v) { return v - v == 0.0f && v >= 0.0f; }       // finite and not negative
     int set_squelch(float open_level, float close_level, uint32_t hang) {
         if (!level_ok(open_level) || !level_ok(close_level) || close_level > open_level || hang > 65535u) return DH_EINVAL;
-        pw_open = open_level; pw_close = close_level; pw_hang = hang;
+        pw.open_level = open_level; pw.close_level = close_level; pw.hang = hang;
         return DH_OK;
     }
     int power_enable(const dh_channelizer_power_config& c) {
@@ -328,24 +318,22 @@ struct dh_channelizer {
             return DH_EINVAL;
         const int rc = set_squelch(c.open_level, c.close_level, c.hang_blocks);
         if (rc != DH_OK) return rc;
-        if (!d_pstate && !(d_pstate = (uint32_t*) be.alloc(sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B))) return DH_ENOMEM;
-        if (be.zero(d_pstate, sizeof(uint32_t) * DH_CZ_PSTATE_WORDS * B)) return DH_EDEVICE;
-        pw_L = c.block; pw_inv = (float) (1.0 / (double) c.block);
-        pw_power = c.d_power; pw_gate = c.d_gate; pw_counts = c.d_counts; pw_stride = c.stride;
+        const size_t words = (size_t) DH_CZ_PSTATE_WORDS * B;
+        if (!d_pstate && !bufs.alloc(d_pstate, words, dh::ZERO_PER_CHANNEL)) return DH_ENOMEM;
+        if (be.zero(d_pstate, sizeof(uint32_t) * words)) return DH_EDEVICE;
+        pw.pstate = d_pstate; pw.power = c.d_power; pw.gate = c.d_gate; pw.counts = c.d_counts; pw.stride = c.stride;
+        pw.B = B; pw.L = c.block; pw.fm = fm; pw.inv = (float) (1.0 / (double) c.block);
         pw_first = 0; pw_n = 0;
         return DH_OK;
     }
     // block power of the push's no outputs (j0 the first), the gate and the counts; no = 0: the counts are zeros
     int power(const float* out, size_t out_stride, uint64_t j0, uint32_t no) {
-        DhCzPowerParams P;
-        P.z = fm ? d_zbuf : out; P.z_stride = out_stride; P.pstate = d_pstate;
-        P.power = pw_power; P.gate = pw_gate; P.counts = pw_counts; P.stride = pw_stride;
-        P.pos0 = (uint32_t) (j0 % pw_L); P.n_out = no; P.B = B; P.L = pw_L; P.fm = fm;
-        P.n_blocks = (uint32_t) ((j0 + no) / pw_L - j0 / pw_L);
-        P.nseg = no ? (uint32_t) (((uint64_t) P.pos0 + no + pw_L - 1) / pw_L) : 0u;
-        P.inv = pw_inv; P.open_level = pw_open; P.close_level = pw_close; P.hang = pw_hang;
-        pw_first = j0 / pw_L; pw_n = P.n_blocks;
-        return dh_be_cz_power(P, stream) ? DH_EDEVICE : DH_OK;
+        pw.z = fm ? d_zbuf : out; pw.z_stride = out_stride;
+        pw.pos0 = (uint32_t) (j0 % pw.L); pw.n_out = no;
+        pw.n_blocks = (uint32_t) ((j0 + no) / pw.L - j0 / pw.L);
+        pw.nseg = no ? (uint32_t) (((uint64_t) pw.pos0 + no + pw.L - 1) / pw.L) : 0u;
+        pw_first = j0 / pw.L; pw_n = pw.n_blocks;
+        return dh_be_cz_power(pw, stream) ? DH_EDEVICE : DH_OK;
     }
     int push(const void* in, size_t n_in, float* out, size_t out_stride, size_t* n_out, bool host) {
         if (!n_out) return DH_EINVAL;
@@ -353,7 +341,7 @@ struct dh_channelizer {
         if (n_in > max_input || (!in && n_in)) return DH_EINVAL;
         const uint64_t no = (n0 + n_in) / D - n0 / D;
         if (no && (!out || out_stride < no)) return DH_EINVAL;
-        if (!n_in) return pw_L ? power(out, out_stride, n0 / D, 0) : DH_OK;
+        if (!n_in) return pw.L ? power(out, out_stride, n0 / D, 0) : DH_OK;
         const void* src = in;
         if (host) {
             if (be.upload(d_stage, in, in_bytes() * n_in)) return DH_EDEVICE;
@@ -362,15 +350,12 @@ struct dh_channelizer {
         float* w = d_win[cur];
         if (dh_be_cz_window(w, d_win[cur ^ 1], prev_n, src, cf32, tpad - 1, n_in, stream)) return DH_EDEVICE;
         if (no) {
-            DhCzParams P;
-            P.win = w; P.bmat = d_bmat; P.coarse = d_tables; P.fine = d_tables + 8192; P.inc = d_inc;
-            P.out = out; P.out_stride = out_stride; P.zbuf = d_zbuf;
-            P.j0 = n0 / D; P.off0 = (uint32_t) (D - 1 - n0 % D);
-            P.D = D; P.tpad = tpad; P.B = B; P.ncols = ncols; P.n_out = (uint32_t) no; P.fm = fm;
-            if (dh_be_cz_gemm(P, stream)) return DH_EDEVICE;
+            gemm.win = w; gemm.out = out; gemm.out_stride = out_stride;
+            gemm.j0 = n0 / D; gemm.off0 = (uint32_t) (D - 1 - n0 % D); gemm.n_out = (uint32_t) no;
+            if (dh_be_cz_gemm(gemm, stream)) return DH_EDEVICE;
             if (fm && dh_be_cz_fm(d_zbuf, d_state, out, out_stride, B, (uint32_t) no, dcblock, stream)) return DH_EDEVICE;
         }
-        if (pw_L) { const int rc = power(out, out_stride, n0 / D, (uint32_t) no); if (rc != DH_OK) return rc; }
+        if (pw.L) { const int rc = power(out, out_stride, n0 / D, (uint32_t) no); if (rc != DH_OK) return rc; }
         if (host && be.sync()) return DH_EDEVICE;       // the staging buffer is the next push's
         cur ^= 1; prev_n = (uint32_t) n_in; n0 += n_in;
         *n_out = (size_t) no;
@@ -395,7 +380,7 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
     if (!z) return DH_ENOMEM;
     int rc = z->be.open(c.device, c.stream);
     if (rc == DH_OK) {
-        auto on_device = z->be.scope(); (void) on_device;
+        DH_ON_DEVICE(z);
         z->stream = c.stream;
         rc = z->init(c);
         if (rc != DH_OK) z->release();
@@ -408,7 +393,7 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
 void dh_channelizer_destroy(dh_channelizer* c) {
     if (!c) return;
     {
-        auto on_device = c->be.scope(); (void) on_device;
+        DH_ON_DEVICE(c);
         c->be.sync();
         c->be.close();
         c->release();
@@ -416,29 +401,29 @@ void dh_channelizer_destroy(dh_channelizer* c) {
     delete c;
 }
 
-int dh_channelizer_reset(dh_channelizer* c) { if (!c) return DH_EINVAL; auto on_device = c->be.scope(); (void) on_device; return c->clear(); }
-int dh_channelizer_retune(dh_channelizer* c, uint32_t ch, uint32_t u) { if (!c || ch >= c->B) return DH_EINVAL; auto on_device = c->be.scope(); (void) on_device; return c->retune(ch, u); }
+int dh_channelizer_reset(dh_channelizer* c) { if (!c) return DH_EINVAL; DH_ON_DEVICE(c); return c->clear(); }
+int dh_channelizer_retune(dh_channelizer* c, uint32_t ch, uint32_t u) { if (!c || ch >= c->B) return DH_EINVAL; DH_ON_DEVICE(c); return c->retune(ch, u); }
 int dh_channelizer_push(dh_channelizer* c, const void* d_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
     if (!c) return DH_EINVAL;
-    auto on_device = c->be.scope(); (void) on_device;
+    DH_ON_DEVICE(c);
     return c->push(d_in, n_in, d_out, out_stride, n_out, false);
 }
 int dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
     if (!c) return DH_EINVAL;
-    auto on_device = c->be.scope(); (void) on_device;
+    DH_ON_DEVICE(c);
     return c->push(h_in, n_in, d_out, out_stride, n_out, true);
 }
 int dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg) {
     if (!c || !cfg) return DH_EINVAL;
-    auto on_device = c->be.scope(); (void) on_device;
+    DH_ON_DEVICE(c);
     return c->power_enable(*cfg);
 }
 int dh_channelizer_set_squelch(dh_channelizer* c, float open_level, float close_level, uint32_t hang_blocks) {
-    if (!c || !c->pw_L) return DH_EINVAL;
+    if (!c || !c->pw.L) return DH_EINVAL;
     return c->set_squelch(open_level, close_level, hang_blocks);
 }
 int dh_channelizer_power_last(dh_channelizer* c, uint64_t* first_block, size_t* n_blocks) {
-    if (!c || !c->pw_L || !first_block || !n_blocks) return DH_EINVAL;
+    if (!c || !c->pw.L || !first_block || !n_blocks) return DH_EINVAL;
     *first_block = c->pw_first; *n_blocks = c->pw_n;
     return DH_OK;
 }

@@ -82,9 +82,9 @@ struct DhDspParams {
     // stopped; every other workgroup leaves at once.  split_force_fail = k > 0 (tests: DH_TAIL_SPLIT_FORCE_FAIL): the SECOND parts
     // of the channels with ch % k == 1 give up without looking.
     uint32_t split_fixup, split_force_fail;
-    // DH_FLAG_KEEP_FILTERED | DH_FLAG_ONE_LAUNCH on the wide filter at sps 10 (without DH_FLAG_FAST_FIR): the error-bounded slicer also delivers
-    // the filtered samples of the push it has in LDS anyway -- filt_out[ch][t] for every new sample t -- in ONE launch.  They are the split-f16
-    // FIR's: within 2.5e-6 of the reference's (measured 1.0e-6), NOT the 1e-6 of DH_FLAG_FAST_FIR / BASELINE configs[1]
+    // DH_FLAG_KEEP_FILTERED | DH_FLAG_ONE_LAUNCH on the wide filter at sps 10 (else null): the error-bounded slicer also delivers the filtered
+    // samples of the push it has in LDS anyway -- filt_out[ch][t] for every new sample t -- in ONE launch.  Without DH_FLAG_FAST_FIR (KEEPF = 1) the
+    // split-f16 FIR's: within 2.5e-6 of the reference's (measured 1.0e-6); with it (KEEPF = 2) the f32 FMA chain's: the 1e-6 of BASELINE configs[1]
     float* filt_out; size_t filt_stride;
 };
 

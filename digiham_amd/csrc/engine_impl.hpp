@@ -17,6 +17,7 @@
 
 #include <string.h>
 #include <new>
+#include <vector>
 
 #include "../../include/digiham_amd.h"
 #include "dsp_core.hpp"
@@ -80,37 +81,76 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
     return DH_OK;
 }
 
-inline void fill_taps(int rrc, float* half, double* gain) {
+// the built-in filter of a kernel's arguments (DhDspParams, DhRrcParams): first half of the taps and the gain in its three forms
+template <class P>
+inline void fill_taps(int rrc, P& p) {
     float full[DH_RRC_MAX_TAPS];
     const int narrow = rrc == DH_RRC_NARROW;
     dh_rrc_expand_taps(narrow, full);
     const int nz = narrow ? DH_RRC_NARROW_NZEROS : DH_RRC_WIDE_NZEROS;
-    for (int i = 0; i <= nz / 2; i++) half[i] = full[i];
-    *gain = narrow ? DH_RRC_NARROW_GAIN : DH_RRC_WIDE_GAIN;
+    for (int i = 0; i <= nz / 2; i++) p.taps[i] = full[i];
+    p.gain = narrow ? DH_RRC_NARROW_GAIN : DH_RRC_WIDE_GAIN; p.rgain = 1.0 / p.gain; p.inv_gain = (float) p.rgain;
 }
 
-// Backend interface (duck-typed):
+// Backend interface (duck-typed; HostBackend in tests/host_harness/harness.cpp is the shortest complete one):
+//   int open(int device, void* stream); void close();      // engine creation / teardown
+//   Scope scope() const;                                    // makes the engine's device current while the value lives
 //   void* alloc(size_t bytes); void free(void*);
 //   int zero(void* p, size_t bytes);                       // async on the engine stream
 //   int upload(void* dst, const void* src, size_t bytes);  // host -> device, async
 //   int copy_device(void* dst, const void* src, size_t bytes);  // device -> device, async on the engine stream
 //   int download2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows);  // synchronous
-//   int launch_chain(const DhDspParams&, const DhDecParams&, uint32_t nz, bool fast, int proto);   // 1 = unavailable
 //   int upload2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows);
 //   int download(void* dst, const void* src, size_t bytes);// device -> host, synchronous
 //   int sync();
-//   int launch_rrc_demod(const DhDspParams&, uint32_t nz, bool fast);
-//   int launch_rrc_tiles(const DhRrcParams&, uint32_t nz, bool fast);
-//   int launch_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, uint32_t nz, uint32_t B);
-//   int launch_decoder(const DhDecParams&, int proto);
-//   int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
-//   int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B);
 //   void timing_mark(int k); void timing_next();            // optional per-push stage timestamps (k = 0..3)
 //   int timing_enable(uint32_t max_pushes); int timing_read(float* rrc, float* slicer, float* decoder, uint32_t* n);
 //   int timing_read_split(float* first_ms, uint32_t* first_channels, uint32_t* n); bool overlap_pushes;
+//   int launch_rrc_demod(const DhDspParams&, uint32_t nz, bool fast);
+//   int launch_rrc_tiles(const DhRrcParams&, uint32_t nz, bool fast);
+//   int launch_rrc_generic(const DhRrcGenParams&);
+//   int launch_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B);
+//   int launch_chain(const DhDspParams&, const DhDecParams&, uint32_t nz, bool fast, int proto);   // 1 = unavailable
+//   int launch_decoder(const DhDecParams&, int proto);
+//   int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
+//   int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B);
+
+// The device buffers of one handle (an engine, a channelizer).  Every buffer is allocated through alloc() and stated
+// nowhere else: free_all() frees what was allocated, zero_all() and zero_row() clear what was declared as state.
+enum Zeroed { ZERO_NEVER,          // outputs of a push, staging, tables, taps
+              ZERO_ON_RESET,       // zeroed whole by a reset of the handle
+              ZERO_PER_CHANNEL };  // [B][...] state of the channels: ... and one row of it by the reset of one channel
+template <class BE>
+struct DeviceBuffers {
+    struct Buf { void* p; size_t bytes; Zeroed zeroed; };
+    BE& be;
+    std::vector<Buf> list;
+
+    template <class T> bool alloc(T*& ptr, size_t count, Zeroed zeroed = ZERO_NEVER) {
+        ptr = (T*) be.alloc(sizeof(T) * count);
+        if (ptr) list.push_back({ ptr, sizeof(T) * count, zeroed });
+        return ptr != nullptr;
+    }
+    void free_all() {
+        for (const Buf& b : list) be.free(b.p);
+        list.clear();
+    }
+    int zero_all() {
+        int rc = 0;
+        for (const Buf& b : list) if (b.zeroed != ZERO_NEVER) rc |= be.zero(b.p, b.bytes);
+        return rc;
+    }
+    int zero_row(uint32_t ch, uint32_t B) {
+        int rc = 0;
+        for (const Buf& b : list) if (b.zeroed == ZERO_PER_CHANNEL) rc |= be.zero((char*) b.p + ch * (b.bytes / B), b.bytes / B);
+        return rc;
+    }
+};
+
 template <class BE>
 struct Engine {
     BE be;
+    DeviceBuffers<BE> bufs{ be };
     Layout L;
     uint32_t slot_filter;
     // device buffers
@@ -128,11 +168,12 @@ struct Engine {
     uint32_t* counts_copy = nullptr;     // the counts of the last ragged push of an engine that keeps its filtered samples
     const uint32_t* last_counts = nullptr;       // per-channel sample counts of the last push (device), or null
     DhFecTables* tables = nullptr;
-    uint32_t* zero_counts = nullptr;
     uint32_t last_n = 0;
-    DhDspParams dsp{}; DhRrcParams rrcp{}; DhDecParams dec{};
-    float* custom_taps = nullptr; double custom_gain = 0.0;      // DH_RRC_CUSTOM: device copy of the caller's table
-    uint32_t* tapfrag = nullptr; float err_coef_f16 = 0.0f;      // split-f16 FIR of the wide filter: per-lane tap fragments (dh_f16_tap_fragments)
+    // kernel arguments: what the configuration fixes is filled once (configure()), a push adds its input and its counts
+    DhDspParams dsp{}; DhRrcParams rrcp{}; DhRrcGenParams gen{}; DhDecParams dec{};
+    bool fast = false;                                           // DH_FLAG_FAST_FIR (with fused_keep: which floats the one launch delivers)
+    float* custom_taps = nullptr;                                // DH_RRC_CUSTOM: device copy of the caller's table
+    uint32_t* tapfrag = nullptr;                                 // split-f16 FIR of the wide filter: per-lane tap fragments (dh_f16_tap_fragments)
 
     int init(const dh_engine_config& c) {
         int rc = make_layout(c, L);
@@ -140,19 +181,27 @@ struct Engine {
         be.overlap_pushes = (L.flags & DH_FLAG_OVERLAP_PUSHES) != 0;
         slot_filter = c.slot_filter;
         const size_t B = L.B;
-#define DH_ALLOC(ptr, type, count) do { ptr = (type*) be.alloc(sizeof(type) * (size_t) (count)); if (!ptr) return DH_ENOMEM; } while (0)
-        DH_ALLOC(overflow, uint32_t, 16);
-        DH_ALLOC(sym_count, uint32_t, B);
-        if (L.demod) DH_ALLOC(dsp_state, uint32_t, B * L.state_words);
-        if (L.demod) DH_ALLOC(syms, uint8_t, B * L.sym_stride);
+        bool ok = bufs.alloc(overflow, 16, ZERO_ON_RESET);
+        ok &= bufs.alloc(sym_count, B, ZERO_PER_CHANNEL);
+        if (L.demod) ok &= bufs.alloc(dsp_state, B * L.state_words, ZERO_PER_CHANNEL);
+        if (L.demod) ok &= bufs.alloc(syms, B * L.sym_stride, ZERO_PER_CHANNEL);
         if (L.proto) {
-            DH_ALLOC(dec_state, uint32_t, B * DH_DEC_STATE_WORDS);
-            DH_ALLOC(sym_carry, uint8_t, B * dh_carry_max(L.proto));
-            DH_ALLOC(frames, uint8_t, B * (size_t) L.out_cap);
-            DH_ALLOC(frame_count, uint32_t, B);
-            DH_ALLOC(ev_count, uint32_t, B);
-            if (!(L.flags & DH_FLAG_NO_EVENTS)) DH_ALLOC(events, dh_event, B * (size_t) L.ev_cap);
-            DH_ALLOC(tables, DhFecTables, 1);
+            ok &= bufs.alloc(dec_state, B * DH_DEC_STATE_WORDS, ZERO_PER_CHANNEL);
+            ok &= bufs.alloc(sym_carry, B * dh_carry_max(L.proto), ZERO_PER_CHANNEL);
+            ok &= bufs.alloc(frames, B * (size_t) L.out_cap);
+            ok &= bufs.alloc(frame_count, B, ZERO_PER_CHANNEL);
+            ok &= bufs.alloc(ev_count, B, ZERO_PER_CHANNEL);
+            if (!(L.flags & DH_FLAG_NO_EVENTS)) ok &= bufs.alloc(events, B * (size_t) L.ev_cap);
+            ok &= bufs.alloc(tables, 1);
+        }
+        if (L.rrc && (!L.fused || L.fused_keep)) ok &= bufs.alloc(filtered, B * (size_t) L.max_samples);
+        if (L.rrc && !L.fused) ok &= bufs.alloc(rrc_hist, B * (size_t) L.nz, ZERO_PER_CHANNEL);
+        if (L.rrc == DH_RRC_CUSTOM) ok &= bufs.alloc(custom_taps, L.nz + 1);
+        if (L.fused && (L.nz == 80 || L.nz == 160)) ok &= bufs.alloc(tapfrag, sizeof(DhF16Taps::frag) / sizeof(uint32_t));
+        if (!ok) return DH_ENOMEM;
+        configure(c.rrc_gain);
+        // the tables the kernels read; the host copies (and the caller's table) may go away once the uploads have run
+        if (L.proto) {
             DhFecTables* host = new (std::nothrow) DhFecTables;
             if (!host) return DH_ENOMEM;
             build_fec_tables(*host);
@@ -161,46 +210,61 @@ struct Engine {
             delete host;
             if (rc) return rc;
         }
-        if (L.rrc && (!L.fused || L.fused_keep)) DH_ALLOC(filtered, float, B * (size_t) L.max_samples);
-        if (L.rrc && !L.fused) DH_ALLOC(rrc_hist, float, B * (size_t) L.nz);
-        if (L.rrc == DH_RRC_CUSTOM) {
-            DH_ALLOC(custom_taps, float, L.nz + 1);
-            custom_gain = c.rrc_gain;
-            if (be.upload(custom_taps, c.rrc_taps, sizeof(float) * (L.nz + 1)) || be.sync()) return DH_EDEVICE;   // the caller's table may go away
-        }
-        if (L.fused && (L.nz == 80 || L.nz == 160)) {
+        if (L.rrc == DH_RRC_CUSTOM && (be.upload(custom_taps, c.rrc_taps, sizeof(float) * (L.nz + 1)) || be.sync())) return DH_EDEVICE;
+        if (tapfrag) {
             DhF16Taps* F = new (std::nothrow) DhF16Taps;
             if (!F) return DH_ENOMEM;
-            float half[DH_MAX_NZ / 2 + 1]; double gain;
-            fill_taps(L.rrc, half, &gain);
-            dh_f16_tap_fragments(half, L.nz, *F);
-            err_coef_f16 = dh_f16_error_coefficient(*F, L.nz, gain);
-            tapfrag = (uint32_t*) be.alloc(sizeof(F->frag));
-            rc = tapfrag ? be.upload(tapfrag, F->frag, sizeof(F->frag)) : DH_ENOMEM;       // (the first 2 KS fragments are the ones a kernel reads)
-            if (!rc) rc = be.sync();
+            dh_f16_tap_fragments(dsp.taps, L.nz, *F);
+            dsp.err_coef_f16 = dh_f16_error_coefficient(*F, L.nz, dsp.gain);
+            rc = be.upload(tapfrag, F->frag, sizeof(F->frag)) || be.sync();       // (the first 2 KS fragments are the ones a kernel reads)
             delete F;
-            if (rc) return rc == DH_ENOMEM ? rc : DH_EDEVICE;
+            if (rc) return DH_EDEVICE;
         }
-#undef DH_ALLOC
         return reset();
     }
 
-    void destroy() {
-        void* ptrs[] = { dsp_state, syms, sym_count, sym_carry, dec_state, frames, frame_count, events, ev_count,
-                         overflow, filtered, rrc_hist, staging, staging_counts, counts_copy, tables, custom_taps, tapfrag };
-        for (void* p : ptrs) if (p) be.free(p);
+    // Every kernel argument that the configuration fixes for the engine's lifetime.  What a push brings -- its input rows and
+    // its sample counts, or its symbol rows -- is all that push() and push_symbols() add.
+    void configure(double custom_gain) {
+        fast = (L.flags & DH_FLAG_FAST_FIR) != 0;
+        const bool own_rrc = L.rrc && !L.fused;                   // the RRC stage is a launch of its own and the slicer reads `filtered`
+        if (L.rrc == DH_RRC_CUSTOM) {
+            gen.out = filtered; gen.out_stride = L.max_samples; gen.hist = rrc_hist; gen.taps = custom_taps;
+            gen.n_channels = L.B; gen.nz = L.nz; gen.gain = custom_gain;
+        } else if (own_rrc) {
+            rrcp.out = filtered; rrcp.out_stride = L.max_samples; rrcp.hist = rrc_hist;
+            rrcp.n_channels = L.B; rrcp.nz = L.nz; rrcp.fast = fast;
+            fill_taps(L.rrc, rrcp);
+        }
+        if (L.demod) {
+            if (own_rrc) { dsp.in = filtered; dsp.in_stride = L.max_samples; }
+            dsp.state = (float*) dsp_state; dsp.state_stride = L.state_words;
+            dsp.syms = syms; dsp.sym_stride = L.sym_stride;
+            dsp.sym_count = sym_count; dsp.sym_cap = L.sym_cap; dsp.overflow = overflow; dsp.n_channels = L.B;
+            dsp.sps = L.sps; dsp.lo = L.lo; dsp.hi = L.hi;
+            dsp.levels = L.demod; dsp.invert = (L.flags & DH_FLAG_FSK_INVERT) ? 1 : 0;
+            dsp.nz = L.fused ? L.nz : 0; dsp.fast = fast && !L.fused_keep;       // (fused_keep = 2 is an error-bounded kernel: exact dibits)
+            dsp.ordered_timing = (L.flags & DH_FLAG_ORDERED_TIMING) ? 1 : 0;
+            dsp.exact_mode = (L.flags & DH_FLAG_EXACT_FIR) ? 2 : (L.flags & DH_FLAG_EXACT_SYMBOLS) ? 1 : 0;
+            if (L.fused) {
+                fill_taps(L.rrc, dsp);
+                dsp.err_coef = dh_fir_error_coefficient(dsp.taps, L.nz, dsp.gain);
+                dsp.tapfrag = tapfrag;                                           // (err_coef_f16: with the fragments, init())
+            }
+            dsp.filt_out = L.fused_keep ? filtered : nullptr; dsp.filt_stride = L.max_samples;
+        }
+        dec.syms = syms; dec.sym_stride = L.sym_stride; dec.sym_count = sym_count;          // (decoder-only engines: the caller's, push_symbols)
+        dec.carry = sym_carry; dec.carry_stride = dh_carry_max(L.proto);
+        dec.state = dec_state; dec.state_stride = DH_DEC_STATE_WORDS;
+        dec.out = frames; dec.out_stride = L.out_cap; dec.out_cap = L.out_cap; dec.out_count = frame_count;
+        dec.events = events; dec.ev_stride = L.ev_cap; dec.ev_cap = L.ev_cap; dec.ev_count = ev_count;
+        dec.overflow = overflow; dec.T = tables; dec.n_channels = L.B;
     }
 
+    void destroy() { bufs.free_all(); }
+
     int reset() {
-        int rc = be.zero(overflow, sizeof(uint32_t) * 16);
-        rc |= be.zero(sym_count, sizeof(uint32_t) * L.B);
-        if (sym_carry) rc |= be.zero(sym_carry, (size_t) L.B * dh_carry_max(L.proto));
-        if (dsp_state) rc |= be.zero(dsp_state, sizeof(uint32_t) * L.B * L.state_words);
-        if (syms) rc |= be.zero(syms, L.B * L.sym_stride);
-        if (dec_state) rc |= be.zero(dec_state, sizeof(uint32_t) * L.B * DH_DEC_STATE_WORDS);
-        if (frame_count) rc |= be.zero(frame_count, sizeof(uint32_t) * L.B);
-        if (ev_count) rc |= be.zero(ev_count, sizeof(uint32_t) * L.B);
-        if (rrc_hist) rc |= be.zero(rrc_hist, sizeof(float) * L.B * L.nz);
+        int rc = bufs.zero_all();
         // the fused slicer starts with nz zero samples of history in its tail (RrcFilter's delay line)
         rc |= be.launch_init_state(dsp_state, L.state_words, L.fused ? L.nz : 0u, dec_state, slot_filter, L.B);
         last_n = 0;
@@ -220,26 +284,10 @@ struct Engine {
     // back to the freshly-constructed state of ONE channel (the others keep streaming)
     int reset_channel(uint32_t ch) {
         if (ch >= L.B) return DH_EINVAL;
-        int rc = be.zero(sym_count + ch, sizeof(uint32_t));
-        if (sym_carry) rc |= be.zero(sym_carry + (size_t) ch * dh_carry_max(L.proto), dh_carry_max(L.proto));
-        if (dsp_state) rc |= be.zero(dsp_state + (size_t) ch * L.state_words, sizeof(uint32_t) * L.state_words);
-        if (syms) rc |= be.zero(syms + (size_t) ch * L.sym_stride, L.sym_stride);
-        if (dec_state) rc |= be.zero(dec_state + (size_t) ch * DH_DEC_STATE_WORDS, sizeof(uint32_t) * DH_DEC_STATE_WORDS);
-        if (frame_count) rc |= be.zero(frame_count + ch, sizeof(uint32_t));
-        if (ev_count) rc |= be.zero(ev_count + ch, sizeof(uint32_t));
-        if (rrc_hist) rc |= be.zero(rrc_hist + (size_t) ch * L.nz, sizeof(float) * L.nz);
+        int rc = bufs.zero_row(ch, L.B);
         rc |= be.launch_init_state(dsp_state ? dsp_state + (size_t) ch * L.state_words : nullptr, L.state_words, L.fused ? L.nz : 0u,
                                    dec_state ? dec_state + (size_t) ch * DH_DEC_STATE_WORDS : nullptr, slot_filter, 1);
         return rc ? DH_EDEVICE : DH_OK;
-    }
-
-    void fill_dec_params(const uint8_t* d_syms, size_t stride, const uint32_t* d_count) {
-        dec.syms = d_syms; dec.sym_stride = stride; dec.sym_count = d_count;
-        dec.carry = sym_carry; dec.carry_stride = dh_carry_max(L.proto);
-        dec.state = dec_state; dec.state_stride = DH_DEC_STATE_WORDS;
-        dec.out = frames; dec.out_stride = L.out_cap; dec.out_cap = L.out_cap; dec.out_count = frame_count;
-        dec.events = events; dec.ev_stride = L.ev_cap; dec.ev_cap = L.ev_cap; dec.ev_count = ev_count;
-        dec.overflow = overflow; dec.T = tables; dec.n_channels = L.B;
     }
 
     // d_counts (device, [B], or null): ragged push -- channel b brings d_counts[b] <= n samples of its row
@@ -247,11 +295,11 @@ struct Engine {
         if ((!d_in && n) || n > L.max_samples || stride < n) return DH_EINVAL;
         if (d_counts && L.rrc == DH_RRC_CUSTOM) return DH_EINVAL;          // (the generic FIR takes whole pushes only)
         if (!L.rrc && !L.demod) return DH_EINVAL;
-        // what dh_engine_read_filtered needs to know later is kept in a buffer of the engine's own: the caller's counts only
+        // what read_filtered needs to know later is kept in a buffer of the engine's own: the caller's counts only
         // have to live as long as the sample rows (until the push has run)
         last_counts = nullptr;
         if (d_counts && filtered) {
-            if (!counts_copy) { counts_copy = (uint32_t*) be.alloc(sizeof(uint32_t) * L.B); if (!counts_copy) return DH_ENOMEM; }
+            if (!counts_copy && !bufs.alloc(counts_copy, L.B)) return DH_ENOMEM;
             if (be.copy_device(counts_copy, d_counts, sizeof(uint32_t) * L.B)) return DH_EDEVICE;
             last_counts = counts_copy;
         }
@@ -260,47 +308,25 @@ struct Engine {
         if (!d_in) d_in = reinterpret_cast<const float*>(overflow);
         last_n = (uint32_t) n;
         int rc = 0;
-        const float* demod_in = d_in; size_t demod_stride = stride;
-        const bool fast = (L.flags & DH_FLAG_FAST_FIR) != 0;                        // (with fused_keep: which floats the one launch delivers)
         bool decoder_done = false;
         be.timing_mark(0);
         if (L.rrc == DH_RRC_CUSTOM) {
-            DhRrcGenParams G{};
-            G.in = d_in; G.in_stride = stride; G.out = filtered; G.out_stride = L.max_samples; G.hist = rrc_hist; G.taps = custom_taps;
-            G.n = (uint32_t) n; G.n_channels = L.B; G.nz = L.nz; G.gain = custom_gain;
-            if (n) rc |= be.launch_rrc_generic(G);
+            gen.in = d_in; gen.in_stride = stride; gen.n = (uint32_t) n;
+            if (n) rc |= be.launch_rrc_generic(gen);
             if (n) rc |= be.launch_rrc_hist(rrc_hist, d_in, stride, (uint32_t) n, nullptr, L.nz, L.B);
-            demod_in = filtered; demod_stride = L.max_samples;
         } else if (L.rrc && !L.fused) {
-            rrcp.in = d_in; rrcp.in_stride = stride; rrcp.out = filtered; rrcp.out_stride = L.max_samples;
-            rrcp.hist = rrc_hist; rrcp.n = (uint32_t) n; rrcp.n_per = d_counts; rrcp.n_channels = L.B; rrcp.nz = L.nz; rrcp.fast = fast;
-            fill_taps(L.rrc, rrcp.taps, &rrcp.gain); rrcp.rgain = 1.0 / rrcp.gain; rrcp.inv_gain = (float) rrcp.rgain;
+            rrcp.in = d_in; rrcp.in_stride = stride; rrcp.n = (uint32_t) n; rrcp.n_per = d_counts;
             if (n) rc |= be.launch_rrc_tiles(rrcp, L.nz, fast);
             if (n) rc |= be.launch_rrc_hist(rrc_hist, d_in, stride, (uint32_t) n, d_counts, L.nz, L.B);
-            demod_in = filtered; demod_stride = L.max_samples;
         }
         be.timing_mark(1);
         if (L.demod) {
-            dsp.in = demod_in; dsp.in_stride = demod_stride; dsp.n = (uint32_t) n; dsp.n_per = d_counts;
-            dsp.state = (float*) dsp_state; dsp.state_stride = L.state_words;
-            dsp.syms = syms; dsp.sym_stride = L.sym_stride;
-            dsp.sym_count = sym_count; dsp.sym_cap = L.sym_cap; dsp.overflow = overflow; dsp.n_channels = L.B;
-            dsp.sps = L.sps; dsp.lo = L.lo; dsp.hi = L.hi;
-            dsp.levels = L.demod; dsp.invert = (L.flags & DH_FLAG_FSK_INVERT) ? 1 : 0;
-            dsp.nz = L.fused ? L.nz : 0; dsp.fast = fast && !L.fused_keep;       // (fused_keep = 2 is an error-bounded kernel: exact dibits)
-            dsp.ordered_timing = (L.flags & DH_FLAG_ORDERED_TIMING) ? 1 : 0;
-            dsp.exact_mode = (L.flags & DH_FLAG_EXACT_FIR) ? 2 : (L.flags & DH_FLAG_EXACT_SYMBOLS) ? 1 : 0;
-            if (L.fused) {
-                fill_taps(L.rrc, dsp.taps, &dsp.gain); dsp.rgain = 1.0 / dsp.gain; dsp.inv_gain = (float) dsp.rgain;
-                dsp.err_coef = dh_fir_error_coefficient(dsp.taps, L.nz, dsp.gain);
-                dsp.tapfrag = tapfrag; dsp.err_coef_f16 = err_coef_f16;
-            }
-            dsp.filt_out = L.fused_keep ? filtered : nullptr; dsp.filt_stride = L.max_samples;
+            if (!L.rrc || L.fused) { dsp.in = d_in; dsp.in_stride = stride; }      // (behind an RRC stage of its own: `filtered`, configure())
+            dsp.n = (uint32_t) n; dsp.n_per = d_counts;
             // slicer and decoder of a channel in one wavefront where the backend has that kernel (sps 10, wide or
             // no RRC); DH_FLAG_SPLIT_STAGES keeps the two launches (per-stage timing, A/B measurements)
             int chained = 1;
             if (L.proto && !(L.flags & DH_FLAG_SPLIT_STAGES) && !L.fused_keep) {
-                fill_dec_params(syms, L.sym_stride, sym_count);
                 chained = be.launch_chain(dsp, dec, dsp.nz, fast, L.proto);
                 if (chained < 0) rc |= chained;
             }
@@ -308,10 +334,7 @@ struct Engine {
             decoder_done = chained == 0;
         }
         be.timing_mark(2);
-        if (L.proto && L.demod && !decoder_done) {
-            fill_dec_params(syms, L.sym_stride, sym_count);
-            rc |= be.launch_decoder(dec, L.proto);
-        }
+        if (L.proto && L.demod && !decoder_done) rc |= be.launch_decoder(dec, L.proto);
         be.timing_mark(3);
         be.timing_next();
         return rc ? DH_EDEVICE : DH_OK;
@@ -319,11 +342,11 @@ struct Engine {
 
     int push_host(const float* h_in, size_t stride, size_t n, const uint32_t* h_counts = nullptr) {
         if (!h_in || n > L.max_samples || stride < n) return DH_EINVAL;
-        if (!staging) { staging = (float*) be.alloc(sizeof(float) * (size_t) L.B * L.max_samples); if (!staging) return DH_ENOMEM; }
+        if (!staging && !bufs.alloc(staging, (size_t) L.B * L.max_samples)) return DH_ENOMEM;
         // one strided copy for the whole batch (rows of n floats, host pitch `stride`, device pitch max_samples)
         if (be.upload2d(staging, sizeof(float) * L.max_samples, h_in, sizeof(float) * stride, sizeof(float) * n, L.B)) return DH_EDEVICE;
         if (h_counts) {
-            if (!staging_counts) { staging_counts = (uint32_t*) be.alloc(sizeof(uint32_t) * L.B); if (!staging_counts) return DH_ENOMEM; }
+            if (!staging_counts && !bufs.alloc(staging_counts, L.B)) return DH_ENOMEM;
             for (uint32_t b = 0; b < L.B; b++) if (h_counts[b] > n) return DH_EINVAL;
             if (be.upload(staging_counts, h_counts, sizeof(uint32_t) * L.B)) return DH_EDEVICE;
         }
@@ -334,7 +357,7 @@ struct Engine {
     int push_symbols(const uint8_t* d_syms, size_t stride, const uint32_t* d_count) {
         if (!L.proto || L.demod || !d_syms || !d_count) return DH_EINVAL;
         last_counts = nullptr;
-        fill_dec_params(d_syms, stride, d_count);
+        dec.syms = d_syms; dec.sym_stride = stride; dec.sym_count = d_count;
         return be.launch_decoder(dec, L.proto) ? DH_EDEVICE : DH_OK;
     }
 
@@ -371,15 +394,21 @@ struct Engine {
         return be.download2d(h_out, sizeof(uint32_t), dsp_state + word, sizeof(uint32_t) * L.state_words, sizeof(uint32_t), L.B) ? DH_EDEVICE : DH_OK;
     }
 
-    int read_row(const void* base, size_t row_bytes, uint32_t channel, const uint32_t* counts, size_t elem, void* h_out, size_t* n) {
+    // row `channel` of an output: counts[channel] elements of it (counts null: all the same), `most` at most
+    int read_row(const void* base, size_t row_bytes, uint32_t channel, const uint32_t* counts, size_t elem, void* h_out, size_t* n, uint32_t most = ~0u) {
         if (channel >= L.B || !n || !base) return DH_EINVAL;
-        uint32_t cnt = 0; const uint32_t off = 0;
-        if (be.download(&cnt, counts + channel, sizeof(cnt))) return DH_EDEVICE;
+        uint32_t cnt = most;
+        if (counts && be.download(&cnt, counts + channel, sizeof(cnt))) return DH_EDEVICE;
+        if (cnt > most) cnt = most;
         const size_t cap = *n;
         *n = cnt;
         if (cnt > cap) return DH_ECAPACITY;
-        if (cnt && h_out && be.download(h_out, (const char*) base + row_bytes * channel + (size_t) off * elem, cnt * elem)) return DH_EDEVICE;
+        if (cnt && h_out && be.download(h_out, (const char*) base + row_bytes * channel, cnt * elem)) return DH_EDEVICE;
         return DH_OK;
+    }
+    // the filtered samples of the last push: last_n of them, or this channel's own count where the push was ragged
+    int read_filtered(uint32_t channel, float* h_out, size_t* n) {
+        return read_row(filtered, sizeof(float) * L.max_samples, channel, last_counts, sizeof(float), h_out, n, last_n);
     }
 };
 

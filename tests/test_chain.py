@@ -453,3 +453,48 @@ def test_decoder_behind_the_other_slicer_runs_as_two_launches(ctx, oracle, proto
     ref = oracle.chain(x, proto=oproto, rrc=0, levels=levels)
     res = run_engine(ctx, x, proto, [x.shape[1] // 2, x.shape[1] - x.shape[1] // 2], **kw)
     assert_matches_oracle(res, ref, 2, "%s behind %s" % (proto, demod))
+
+
+def _last_push(eng, b, n):
+    """What the engine's last push (of n samples) left in channel b's rows, as bytes per kind of output."""
+    out = {}
+    if eng.has_demod:
+        s, sc = eng.symbols()
+        out["syms"] = s[b, :sc[b]].tobytes()
+    if eng.has_proto:
+        f, fc = eng.frames()
+        e, ec = eng.events()
+        out["frames"], out["events"] = f[b, :fc[b]].tobytes(), e[b, :ec[b]].tobytes()
+    if eng.keep_filtered:
+        out["filtered"] = eng.filtered()[b, :n].tobytes()
+    return out
+
+
+@pytest.mark.parametrize("kw", [dict(proto="dmr"), dict(proto="ysf"), dict(proto="none", keep_filtered=True), dict(proto="dmr", split_stages=True)],
+                         ids=["dmr", "ysf", "unfused", "dmr-split"])
+def test_reset_channel_resets_that_channel_only(ctx, kw):
+    """dh_engine_reset_channel between two pushes: the channel's second push is what a fresh engine makes of it -- slicer
+    rings and timing state, symbol carry, decoder phase, the counts and (unfused) the filter's history all start over --
+    while the other channels stream on as in an engine that was never reset."""
+    x = make_channels("ysf" if kw["proto"] == "ysf" else "dmr", [5, 6, 7, 8], 12)
+    B, n = x.shape
+    cut = n // 2 + 7
+    first, second = np.ascontiguousarray(x[:, :cut]), np.ascontiguousarray(x[:, cut:])
+    engines = {}
+    for name in ("reset", "continued", "fresh"):
+        eng = engines[name] = api.Engine(B, cut, ctx=ctx, **kw)
+        if name != "fresh":
+            eng.push(first)
+            eng.sync()
+        if name == "reset":
+            eng.reset_channel(2)
+        eng.push(second)
+    got = {name: [_last_push(eng, b, n - cut) for b in range(B)] for name, eng in engines.items()}
+    for eng in engines.values():
+        eng.sync()
+        eng.close()
+    assert got["reset"][2] == got["fresh"][2]
+    for b in (0, 1, 3):
+        assert got["reset"][b] == got["continued"][b], b
+    for kind in got["fresh"][2]:          # ... and the reset had something to undo in every kind of output
+        assert got["fresh"][2][kind] != got["continued"][2][kind], kind
