@@ -29,7 +29,7 @@ class ChannelizerConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
                 ("taps", C.POINTER(C.c_float)), ("n_taps", C.c_uint32), ("increments", C.POINTER(C.c_uint32)),
                 ("input_format", C.c_int32), ("output_mode", C.c_int32), ("dcblock", C.c_int32), ("max_input", C.c_uint32),
-                ("stream", C.c_void_p)]
+                ("stream", C.c_void_p), ("interpolation", C.c_uint32)]
 
 
 class ChannelizerPowerConfig(C.Structure):

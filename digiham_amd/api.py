@@ -390,14 +390,22 @@ class Engine:
         return out
 
 
-def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0):
+def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0, interpolation=1):
     """Real low-pass prototype for Channelizer: a Kaiser-windowed sinc with its cut-off halfway between the pass- and
     stopband edges, the length and beta of Kaiser's estimates for `atten_db` of stopband attenuation, unity gain at DC.
-    (`decimation` is not part of the design; it is checked against the stopband: the output rate must hold it.)"""
+    (`decimation` is not part of the design; it is checked against the stopband: the output rate must hold it.)
+    With interpolation = L > 1 the design is at the virtual rate L * input_rate and the sum is L: each of the L phases
+    h[r::L] that Channelizer applies to the input has a DC gain of 1 to within the stopband level, so 0 dB stays a
+    full-scale tone."""
+    L = int(interpolation)
+    out_rate = input_rate * L / decimation
+    if L < 1:
+        raise ValueError("channel_taps: interpolation < 1")
     if not 0 < passband_hz < stopband_hz:
         raise ValueError("channel_taps: need 0 < passband < stopband")
-    if stopband_hz > input_rate / decimation:
-        raise ValueError("channel_taps: the stopband edge %.0f Hz aliases at the output rate %.0f Hz" % (stopband_hz, input_rate / decimation))
+    if stopband_hz > out_rate:
+        raise ValueError("channel_taps: the stopband edge %.0f Hz aliases at the output rate %.0f Hz" % (stopband_hz, out_rate))
+    input_rate = input_rate * L
     a = float(atten_db)
     dw = 2.0 * np.pi * (stopband_hz - passband_hz) / input_rate
     n = int(np.ceil((a - 7.95) / (2.285 * dw))) + 1
@@ -405,7 +413,7 @@ def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0
     fc = 0.5 * (passband_hz + stopband_hz) / input_rate
     t = np.arange(n) - (n - 1) / 2.0
     h = 2.0 * fc * np.sinc(2.0 * fc * t) * np.kaiser(n, beta)
-    return (h / h.sum()).astype(np.float32)
+    return (h * (L / h.sum())).astype(np.float32)
 
 
 def nco_increment(offset_hz, input_rate):
@@ -413,32 +421,51 @@ def nco_increment(offset_hz, input_rate):
     return int(round(float(offset_hz) / float(input_rate) * 2.0 ** 32)) & 0xFFFFFFFF
 
 
+CZ_MAX_INTERPOLATION, CZ_MAX_DECIMATION = 64, 1024
+
+
+def resample_ratio(input_rate, output_rate=48000.0):
+    """(L, M), the reduced ratio output_rate / input_rate = L / M: Channelizer's interpolation and decimation for a capture
+    rate that is no multiple of the output rate (2.048 MS/s -> 48 kS/s: (3, 128)).  ValueError outside L <= 64, M <= 1024,
+    L <= M."""
+    from fractions import Fraction
+    f = Fraction(output_rate).limit_denominator(10 ** 6) / Fraction(input_rate).limit_denominator(10 ** 6)
+    L, M = f.numerator, f.denominator
+    if not (1 <= L <= CZ_MAX_INTERPOLATION and L <= M <= CZ_MAX_DECIMATION):
+        raise ValueError("resample_ratio: %g -> %g Hz is %d / %d, outside interpolation <= %d, decimation <= %d, ratio <= 1"
+                         % (input_rate, output_rate, L, M, CZ_MAX_INTERPOLATION, CZ_MAX_DECIMATION))
+    return L, M
+
+
 class Channelizer:
-    """One wideband complex stream -> one row per channel at input_rate / decimation (dh_channelizer; the arithmetic is
-    specified in digiham_amd/csrc/channelizer_core.hpp).  input "cs16" (int16 I / Q pairs) or "cf32" (float32 pairs, or
+    """One wideband complex stream -> one row per channel at input_rate * interpolation / decimation (dh_channelizer; the
+    arithmetic is specified in digiham_amd/csrc/channelizer_core.hpp).  interpolation is 1 unless the capture rate is no
+    multiple of the output rate; resample_ratio gives the pair, and `taps` is then channel_taps(..., interpolation=L).
+    input "cs16" (int16 I / Q pairs) or "cf32" (float32 pairs, or
     complex64); output "fm" (discriminator audio for Engine.push, optionally DC-blocked) or "iq" (complex rows).
-    push(x) returns (rows, n_out): rows is the channelizer's own device array [B][max_input // D + 1] (x 2 for "iq"),
+    push(x) returns (rows, n_out): rows is the channelizer's own device array [B][max_input * L // D + 1] (x 2 for "iq"),
     valid in [:, :n_out] until the next push.
     enable_power(...) adds per-channel block power and a squelch gate: after every push `counts` (device uint32 [B]) is what
     Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed."""
 
     def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
-                 ctx=None, device=0):
+                 ctx=None, device=0, interpolation=1):
         self.ctx = ctx if ctx is not None else Context(device=device)
         lib, mem = self.ctx.lib, self.ctx.mem
         self.rate, self.D, self.B = float(input_rate), int(decimation), len(freqs_hz)
+        self.L = max(int(interpolation), 1)
         self.input, self.output = input, output
         t = np.ascontiguousarray(taps, np.float32).ravel()
         inc = np.array([nco_increment(f, input_rate) for f in freqs_hz], np.uint32)
         cfg = _capi.ChannelizerConfig(C.sizeof(_capi.ChannelizerConfig), getattr(mem, "index", 0), self.B, self.D,
                                       t.ctypes.data_as(C.POINTER(C.c_float)), len(t), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
                                       _capi.CZ_INPUT[input], _capi.CZ_OUTPUT[output], int(bool(dcblock) and output == "fm"),
-                                      int(max_input), mem.stream())
+                                      int(max_input), mem.stream(), int(interpolation))
         h = C.c_void_p()
         _check(lib.dh_channelizer_create(C.byref(cfg), C.byref(h)), "dh_channelizer_create", lib)
         self._h = h
         self.max_input = int(max_input)
-        self.out_stride = self.max_input // self.D + 1
+        self.out_stride = self.max_input * self.L // self.D + 1
         self.rows = mem.zeros((self.B, self.out_stride) if output == "fm" else (self.B, self.out_stride, 2), np.float32)
         self._keep = None
         self.block, self.power, self.gate, self.counts = 0, None, None, None

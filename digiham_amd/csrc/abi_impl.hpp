@@ -24,6 +24,9 @@
 //   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_fm: the channelizer's launches, listed where they are used (below)
 #pragma once
 
+#include <cstddef>
+#include <numeric>
+
 #include "engine_impl.hpp"
 
 static_assert(sizeof(dh_event) == 32, "dh_event layout");
@@ -230,6 +233,7 @@ int dh_engine_sync(dh_engine* e) {
 // ---- the channelizer (channelizer_core.hpp): host bookkeeping over the backend's memory and the dh_be_cz_* launches -----
 //   dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream);
 //   dh_be_cz_gemm(const DhCzParams& P, void* stream);
+//   dh_be_cz_gemm_rat(const DhCzRatParams& R, void* stream);      (interpolation L > 1: one converter bank per phase)
 //   dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream);
 //   dh_be_cz_power(const DhCzPowerParams& P, void* stream);      (only with power enabled: block power, then the gate and the counts)
 // (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
@@ -238,21 +242,22 @@ struct dh_channelizer {
     DH_BACKEND be;
     dh::DeviceBuffers<DH_BACKEND> bufs{ be };           // release(), clear() and retune() act on what init() and power_enable() declare
     void* stream = nullptr;
-    uint32_t B = 0, D = 0, tpad = 0, ncols = 0, max_input = 0;
+    uint32_t B = 0, D = 0, L = 1, tpad = 0, ncols = 0, max_input = 0;      // rate = input L / D
     int cf32 = 0, fm = 0, dcblock = 0;
-    std::vector<float> taps;                            // h zero-padded to T'
+    std::vector<float> taps;                            // [L][T']: the phases h_p of h, each zero-padded to T'
     std::vector<uint32_t> inc;
     float* d_tables = nullptr;                          // coarse ++ fine
     uint32_t* d_inc = nullptr;
-    float* d_bmat = nullptr;                            // [2 T'][ncols]
+    float* d_bmat = nullptr;                            // [L][2 T'][ncols]
     float* d_win[2] = { nullptr, nullptr };             // [T' - 1 + max_input][2] each
     float* d_state = nullptr;                           // [B][DH_CZ_STATE_WORDS]
-    float* d_zbuf = nullptr;                            // FM: [max_input / D + 1][B][2]
+    float* d_zbuf = nullptr;                            // FM: [max_input L / D + 1][B][2]
     uint8_t* d_stage = nullptr;                         // push_host's input
     int cur = 0;
     uint32_t prev_n = 0;
     uint64_t n0 = 0;                                    // samples pushed since create / reset
-    DhCzParams gemm{};                                  // what init() fixes; a push adds its window, its output rows and its position
+    DhCzRatParams rat{};                                // rat.g: what init() fixes; a push adds its window, its output rows and its
+                                                        // position (L = 1), or its slots (L > 1)
     // block power and gate (dh_channelizer_power_enable); pw.L = 0: off, nothing allocated and nothing launched
     DhCzPowerParams pw{};                               // what power_enable() and set_squelch() fix; a push adds its outputs and its position
     uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
@@ -261,34 +266,41 @@ struct dh_channelizer {
     auto scope() const { return be.scope(); }
     void release() { bufs.free_all(); }
     size_t in_bytes() const { return cf32 ? 8u : 4u; }
+    uint64_t outputs(uint64_t n) const { return (uint64_t) L * n / D; }         // outputs that exist after n input samples
+    size_t bank() const { return (size_t) 2 * tpad * ncols; }
     int clear() {
         cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
         return bufs.zero_all() ? DH_EDEVICE : DH_OK;
     }
-    int init(const dh_channelizer_config& c) {
-        B = c.n_channels; D = c.decimation; tpad = dh_cz_tpad(c.n_taps); ncols = dh_cz_ncols(B); max_input = c.max_input;
+    int init(const dh_channelizer_config& c, uint32_t interp) {
+        B = c.n_channels; D = c.decimation; L = interp; tpad = dh_cz_tpad_rat(c.n_taps, L); ncols = dh_cz_ncols(B); max_input = c.max_input;
         cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
-        taps.assign(tpad, 0.0f);
-        for (uint32_t k = 0; k < c.n_taps; k++) taps[k] = c.taps[k];
+        taps.assign((size_t) L * tpad, 0.0f);
+        for (uint32_t p = 0; p < L; p++) {
+            const uint32_t r = (uint32_t) (((uint64_t) p * D + D - 1u) % L);
+            for (uint32_t k = 0; r + (uint64_t) k * L < c.n_taps; k++) taps[(size_t) p * tpad + k] = c.taps[r + k * L];
+        }
         inc.assign(c.increments, c.increments + B);
-        const size_t bm = (size_t) 2 * tpad * ncols, win = 2 * ((size_t) tpad - 1 + max_input);
+        const size_t bm = L * bank(), win = 2 * ((size_t) tpad - 1 + max_input);
         bool ok = bufs.alloc(d_tables, 4 * 4096);
         ok &= bufs.alloc(d_inc, B);
         ok &= bufs.alloc(d_bmat, bm);
         ok &= bufs.alloc(d_win[0], win, dh::ZERO_ON_RESET);
         ok &= bufs.alloc(d_win[1], win, dh::ZERO_ON_RESET);
         ok &= bufs.alloc(d_state, (size_t) DH_CZ_STATE_WORDS * B, dh::ZERO_PER_CHANNEL);
-        if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) max_input / D + 1) * B);
+        if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) outputs(max_input) + 1) * B);
         ok &= bufs.alloc(d_stage, in_bytes() * max_input);
         if (!ok) return DH_ENOMEM;
-        gemm.bmat = d_bmat; gemm.coarse = d_tables; gemm.fine = d_tables + 8192; gemm.inc = d_inc; gemm.zbuf = d_zbuf;
-        gemm.D = D; gemm.tpad = tpad; gemm.B = B; gemm.ncols = ncols; gemm.fm = fm;
+        rat.g.bmat = d_bmat; rat.g.coarse = d_tables; rat.g.fine = d_tables + 8192; rat.g.inc = d_inc; rat.g.zbuf = d_zbuf;
+        rat.g.D = D; rat.g.tpad = tpad; rat.g.B = B; rat.g.ncols = ncols; rat.g.fm = fm; rat.L = L;
         std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
-        for (uint32_t b = 0; b < B; b++) {
-            dh_cz_columns(taps.data(), tpad, inc[b], re.data(), im.data());
-            const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
-            for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bmat[r * ncols + cr] = re[r]; bmat[r * ncols + ci] = im[r]; }
-        }
+        for (uint32_t p = 0; p < L; p++)
+            for (uint32_t b = 0; b < B; b++) {
+                dh_cz_columns(taps.data() + (size_t) p * tpad, tpad, inc[b], re.data(), im.data());
+                float* bank_p = bmat.data() + p * bank();
+                const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
+                for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bank_p[r * ncols + cr] = re[r]; bank_p[r * ncols + ci] = im[r]; }
+            }
         if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_inc, inc.data(), sizeof(uint32_t) * B) ||
             be.upload(d_bmat, bmat.data(), sizeof(float) * bm)) return DH_EDEVICE;
         const int rc = clear();
@@ -298,12 +310,14 @@ struct dh_channelizer {
     int retune(uint32_t ch, uint32_t u) {
         std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
         inc[ch] = u;
-        dh_cz_columns(taps.data(), tpad, u, re.data(), im.data());
         const size_t pitch = sizeof(float) * ncols;
-        if (be.upload2d(d_bmat + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
-            be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
-            be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B))
-            return DH_EDEVICE;
+        for (uint32_t p = 0; p < L; p++) {
+            dh_cz_columns(taps.data() + (size_t) p * tpad, tpad, u, re.data(), im.data());
+            if (be.upload2d(d_bmat + p * bank() + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
+                be.upload2d(d_bmat + p * bank() + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()))
+                return DH_EDEVICE;
+        }
+        if (be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B)) return DH_EDEVICE;
         return be.sync() ? DH_EDEVICE : DH_OK;
     }
     static bool level_ok(float v) { return v - v == 0.0f && v >= 0.0f; }       // finite and not negative
@@ -314,7 +328,7 @@ struct dh_channelizer {
     }
     int power_enable(const dh_channelizer_power_config& c) {
         if (c.struct_size < sizeof(dh_channelizer_power_config) || c.block < 1 || c.block > 65536 || !c.d_power || !c.d_gate || !c.d_counts ||
-            c.stride < ((size_t) max_input / D + 1) / c.block + 1 || n0 != 0)
+            c.stride < ((size_t) outputs(max_input) + 1) / c.block + 1 || n0 != 0)
             return DH_EINVAL;
         const int rc = set_squelch(c.open_level, c.close_level, c.hang_blocks);
         if (rc != DH_OK) return rc;
@@ -339,9 +353,9 @@ struct dh_channelizer {
         if (!n_out) return DH_EINVAL;
         *n_out = 0;
         if (n_in > max_input || (!in && n_in)) return DH_EINVAL;
-        const uint64_t no = (n0 + n_in) / D - n0 / D;
+        const uint64_t j0 = outputs(n0), no = outputs(n0 + n_in) - j0;
         if (no && (!out || out_stride < no)) return DH_EINVAL;
-        if (!n_in) return pw.L ? power(out, out_stride, n0 / D, 0) : DH_OK;
+        if (!n_in) return pw.L ? power(out, out_stride, j0, 0) : DH_OK;
         const void* src = in;
         if (host) {
             if (be.upload(d_stage, in, in_bytes() * n_in)) return DH_EDEVICE;
@@ -350,12 +364,17 @@ struct dh_channelizer {
         float* w = d_win[cur];
         if (dh_be_cz_window(w, d_win[cur ^ 1], prev_n, src, cf32, tpad - 1, n_in, stream)) return DH_EDEVICE;
         if (no) {
-            gemm.win = w; gemm.out = out; gemm.out_stride = out_stride;
-            gemm.j0 = n0 / D; gemm.off0 = (uint32_t) (D - 1 - n0 % D); gemm.n_out = (uint32_t) no;
-            if (dh_be_cz_gemm(gemm, stream)) return DH_EDEVICE;
+            rat.g.win = w; rat.g.out = out; rat.g.out_stride = out_stride;
+            if (L == 1) {
+                rat.g.j0 = j0; rat.g.off0 = (uint32_t) (D - 1 - n0 % D); rat.g.n_out = (uint32_t) no;
+                if (dh_be_cz_gemm(rat.g, stream)) return DH_EDEVICE;
+            } else {
+                dh_cz_plan_rat(rat, n0, n_in);
+                if (dh_be_cz_gemm_rat(rat, stream)) return DH_EDEVICE;
+            }
             if (fm && dh_be_cz_fm(d_zbuf, d_state, out, out_stride, B, (uint32_t) no, dcblock, stream)) return DH_EDEVICE;
         }
-        if (pw.L) { const int rc = power(out, out_stride, n0 / D, (uint32_t) no); if (rc != DH_OK) return rc; }
+        if (pw.L) { const int rc = power(out, out_stride, j0, (uint32_t) no); if (rc != DH_OK) return rc; }
         if (host && be.sync()) return DH_EDEVICE;       // the staging buffer is the next push's
         cur ^= 1; prev_n = (uint32_t) n_in; n0 += n_in;
         *n_out = (size_t) no;
@@ -369,7 +388,11 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
     if (!cfg || !out) return DH_EINVAL;
     *out = nullptr;
     const dh_channelizer_config& c = *cfg;
-    if (c.struct_size < sizeof(dh_channelizer_config) || c.decimation < 1 || c.decimation > 1024 || c.n_taps < 1 || c.n_taps > 16384 ||
+    // interpolation was appended to the struct: a caller built against the older header passes the older size and means L = 1
+    const bool has_interp = c.struct_size >= offsetof(dh_channelizer_config, interpolation) + sizeof(c.interpolation);
+    const uint32_t L = has_interp && c.interpolation ? c.interpolation : 1u;
+    if (c.struct_size < offsetof(dh_channelizer_config, interpolation) || c.decimation < 1 || c.decimation > 1024 ||
+        L > DH_CZ_MAX_L || L > c.decimation || std::gcd(L, c.decimation) != 1u || c.n_taps < 1 || c.n_taps > 16384u * L ||
         c.n_channels < 1 || c.n_channels > 65536 || c.max_input < 1 || c.max_input > (1u << 28) || !c.taps || !c.increments ||
         (c.input_format != DH_CZ_CS16 && c.input_format != DH_CZ_CF32) || (c.output_mode != DH_CZ_IQ_F32 && c.output_mode != DH_CZ_FM) ||
         (c.dcblock && c.output_mode != DH_CZ_FM))
@@ -382,7 +405,7 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
     if (rc == DH_OK) {
         DH_ON_DEVICE(z);
         z->stream = c.stream;
-        rc = z->init(c);
+        rc = z->init(c, L);
         if (rc != DH_OK) z->release();
     }
     if (rc != DH_OK) { delete z; return rc; }

@@ -30,6 +30,30 @@
 //             host's IEEE fmaf does.  A test pushes input whose products and sums are subnormal and compares device, CPU
 //             emulation and the restatement byte for byte.
 //
+// ---- Rational rates (interpolation L > 1): output rate = input_rate L / M, M = decimation.  The specification;
+// tests/cz_rational_restate.c restates it from this text alone.  Everything not mentioned is as above (input formats, P(phi),
+// u_b, FM, dcblock, the power blocks / gate / counts in terms of the output index j, denormals, reset). ----
+//   Ratio     1 <= L <= 64, 1 <= M <= 1024, L <= M, gcd(L, M) = 1.  L = 1 is the channelizer above, bit for bit and launch
+//             for launch.
+//   Prototype h[0..T) is the caller's real low-pass at the virtual rate L input_rate, 1 <= T <= 16384 L.
+//   Output j  sits at the virtual index v_j = j M + M - 1: input index n_j = floor(v_j / L), tap phase r_j = v_j mod L.  With
+//             p = j mod L both depend on p only: r_p = (p M + M - 1) mod L, n_j = floor(j / L) M + floor((p M + M - 1) / L).
+//             Phase p's taps are h_p[k] = h[r_p + k L] for r_p + k L < T, zero-padded to the common
+//             T' = 16 ceil(ceil(T / L) / 16); a phase with r_p >= T is all zeros.
+//   Rotated   G_{b,p}[k] = (h_p[k] * Pr, h_p[k] * Pi), P = P(phi_b(k)), phi_b(n) = u_b n mod 2^32: n counts INPUT samples.
+//   Chains    the two fused chains above over k = 0 .. T'-1 in increasing k, from +0, with x = x[n_j - k] and G = G_{b,p}.
+//             The zero-stuffed virtual samples are skipped, not added (fma(0, g, y) can turn a -0 into +0); the padded
+//             taps are added, as above.
+//   Rotation  z_b[j] = P(-phi_b(n_j)) (x) y with n_j mod 2^32.
+//   Complete  output j completes when x[n_j] has been pushed: after N input samples in total exactly floor(L N / M) outputs
+//             exist, a push yields floor(L (N0 + n_in) / M) - floor(L N0 / M), and the results do not depend on how the
+//             stream is cut into pushes.  The history is T' - 1 input samples.
+//   Retune    of channel b recomputes G_{b,p} for all L phases and otherwise does what it does above.
+//   Work      the GEMM's B operand is L banks [2 T'][ncols].  A push's outputs are split by phase: slot s < min(L, n_out)
+//             holds the rows s, s + L, s + 2 L, ... of the push (phase p = (j0 + s) mod L), a decimate-by-M converter bank
+//             of its own: DhCzPhase has its row count, the window index of its first row and that row's n_j.  A GEMM
+//             workgroup tile belongs to one slot (k_cz_gemm_rat; host body dh_cz_output_rat).
+//
 // ---- Block power and the squelch gate (optional; dh_channelizer_power_enable).  The specification; tests/cz_power_restate.c
 // restates it from this text alone. ----
 //   Blocks    enabled once per channelizer with a block length L, 1 <= L <= 65536 outputs (L = 480: 10 ms at 48 kS/s).  j is
@@ -82,6 +106,7 @@
 #define DH_CZ_TBITS 12            // the two phasor tables: 4096 entries each
 #define DH_CZ_STATE_WORDS 4       // per channel: z[j-1] (re, im), x_prev, y_prev of the DC blocker
 #define DH_CZ_PSTATE_WORDS 4      // per channel, only with power enabled (an array of its own): S (float bits), open, quiet, S of this push
+#define DH_CZ_MAX_L 64            // interpolation: phases of a rational rate
 
 // Column of the real GEMM for channel b, component c (0: the real output, 1: the imaginary one).  Sixteen channels' real
 // columns, then their sixteen imaginary ones: a 16 x 16 MFMA tile holds one component of sixteen channels, and the lane
@@ -111,9 +136,8 @@ struct DhCzParams {
     int fm;                       // 0: rotated z to the output rows, 1: to zbuf
 };
 
-// the rotation and the store of output `row` of channel b, y = the two chains
-DH_HD void dh_cz_emit(const DhCzParams& P, uint32_t row, uint32_t b, float yr, float yi) {
-    const uint32_t nj = (uint32_t) ((P.j0 + row) * (uint64_t) P.D + (P.D - 1u));         // n_j mod 2^32
+// the rotation and the store of output `row` of channel b at input index nj (mod 2^32), y = the two chains
+DH_HD void dh_cz_emit_at(const DhCzParams& P, uint32_t row, uint32_t b, uint32_t nj, float yr, float yi) {
     float pr, pi;
     dh_cz_phasor(0u - P.inc[b] * nj, P.coarse, P.fine, pr, pi);
     const float a = pr * yr, c = pi * yi, d = pr * yi, e = pi * yr;
@@ -121,19 +145,65 @@ DH_HD void dh_cz_emit(const DhCzParams& P, uint32_t row, uint32_t b, float yr, f
     float* q = P.fm ? P.zbuf + 2 * ((size_t) row * P.B + b) : P.out + 2 * ((size_t) b * P.out_stride + row);
     q[0] = zr; q[1] = zi;
 }
+DH_HD void dh_cz_emit(const DhCzParams& P, uint32_t row, uint32_t b, float yr, float yi) {
+    dh_cz_emit_at(P, row, b, (uint32_t) ((P.j0 + row) * (uint64_t) P.D + (P.D - 1u)), yr, yi);         // n_j mod 2^32
+}
 
-// Host body of the GEMM: the two chains of one output, in the MFMA's K order (row 2k, then 2k + 1, k = 0 .. T'-1)
-DH_HD void dh_cz_output(const DhCzParams& P, uint32_t row, uint32_t b) {
-    const uint32_t base = P.off0 + row * P.D + (P.tpad - 1u);
-    const float* cr = P.bmat + dh_cz_col(b, 0), * ci = P.bmat + dh_cz_col(b, 1);
-    float yr = 0.0f, yi = 0.0f;
+// The two chains of one output in the MFMA's K order (row 2k, then 2k + 1, k = 0 .. T'-1): bmat the B operand (bank),
+// base the window index of x[n_j]
+DH_HD void dh_cz_chains(const DhCzParams& P, const float* bmat, uint32_t base, uint32_t b, float& yr, float& yi) {
+    const float* cr = bmat + dh_cz_col(b, 0), * ci = bmat + dh_cz_col(b, 1);
+    yr = 0.0f; yi = 0.0f;
     for (uint32_t k = 0; k < P.tpad; k++) {
         const float xr = P.win[2 * (size_t) (base - k)], xi = P.win[2 * (size_t) (base - k) + 1];
         const size_t r0 = (size_t) (2 * k) * P.ncols, r1 = r0 + P.ncols;
         yr = __builtin_fmaf(xr, cr[r0], yr); yr = __builtin_fmaf(xi, cr[r1], yr);
         yi = __builtin_fmaf(xr, ci[r0], yi); yi = __builtin_fmaf(xi, ci[r1], yi);
     }
+}
+
+// Host body of the GEMM
+DH_HD void dh_cz_output(const DhCzParams& P, uint32_t row, uint32_t b) {
+    float yr, yi;
+    dh_cz_chains(P, P.bmat, P.off0 + row * P.D + (P.tpad - 1u), b, yr, yi);
     dh_cz_emit(P, row, b, yr, yi);
+}
+
+// ---- rational rates: the slots of a push (the header comment) -------------------------------------------------------------
+struct DhCzPhase {
+    uint32_t count;               // outputs of this slot in the push: rows s + L i, i < count
+    uint32_t wbase;               // window index of x[n_j] of its first row (row i: wbase + i M)
+    uint32_t nj0;                 // that n_j mod 2^32 (row i: nj0 + i M)
+    uint32_t bank;                // p = (j0 + s) mod L: the B operand is bmat + p * 2 T' ncols
+};
+struct DhCzRatParams {
+    DhCzParams g;                 // as for L = 1 (D = M; j0 and off0 unused)
+    uint32_t L, nslots;           // nslots = min(L, n_out)
+    DhCzPhase ph[DH_CZ_MAX_L];
+};
+DH_HD uint32_t dh_cz_tpad_rat(uint32_t T, uint32_t L) { return dh_cz_tpad((T + L - 1u) / L); }
+DH_HD const float* dh_cz_bank(const DhCzParams& P, uint32_t p) { return P.bmat + (size_t) p * 2u * P.tpad * P.ncols; }
+
+// the slots of the push of n_in samples after N0: fills R.g.n_out, R.nslots and R.ph (host arithmetic)
+inline void dh_cz_plan_rat(DhCzRatParams& R, uint64_t N0, uint64_t n_in) {
+    const uint64_t L = R.L, M = R.g.D, j0 = L * N0 / M, no = L * (N0 + n_in) / M - j0;
+    R.g.n_out = (uint32_t) no;
+    R.nslots = (uint32_t) (no < L ? no : L);
+    for (uint32_t s = 0; s < R.nslots; s++) {
+        const uint64_t j = j0 + s, p = j % L, nj = j / L * M + (p * M + M - 1u) / L;
+        R.ph[s].count = (uint32_t) ((no - s + L - 1u) / L);
+        R.ph[s].wbase = (uint32_t) (R.g.tpad - 1u + (nj - N0));
+        R.ph[s].nj0 = (uint32_t) nj;
+        R.ph[s].bank = (uint32_t) p;
+    }
+}
+
+// Host body of the rational GEMM: row i of slot s
+DH_HD void dh_cz_output_rat(const DhCzRatParams& R, uint32_t s, uint32_t i, uint32_t b) {
+    const DhCzPhase& ph = R.ph[s];
+    float yr, yi;
+    dh_cz_chains(R.g, dh_cz_bank(R.g, ph.bank), ph.wbase + i * R.g.D, b, yr, yi);
+    dh_cz_emit_at(R.g, s + R.L * i, b, ph.nj0 + i * R.g.D, yr, yi);
 }
 
 // element e of this push's window: the last H samples of the previous window, then the new samples converted
@@ -299,6 +369,12 @@ static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const
 static int dh_be_cz_gemm(const DhCzParams& P, void*) {
     for (uint32_t b = 0; b < P.B; b++)
         for (uint32_t row = 0; row < P.n_out; row++) dh_cz_output(P, row, b);
+    return 0;
+}
+static int dh_be_cz_gemm_rat(const DhCzRatParams& R, void*) {
+    for (uint32_t s = 0; s < R.nslots; s++)
+        for (uint32_t b = 0; b < R.g.B; b++)
+            for (uint32_t i = 0; i < R.ph[s].count; i++) dh_cz_output_rat(R, s, i, b);
     return 0;
 }
 static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void*) {

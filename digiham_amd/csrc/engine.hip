@@ -886,19 +886,24 @@ __global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev
 //   MFMA operands: A lane (m = l & 15, q = l >> 4) = As[row m][4 s + q], B lane (n = l & 15, q) = Bs[4 s + q][col n];
 //   D lane (n, g = l >> 4), register r = (row 4 g + r, col n).  Column tile 2 c holds sixteen channels' real parts and tile
 //   2 c + 1 their imaginary parts (dh_cz_col), so each lane rotates and stores its own outputs.
+// One tile of a decimating converter bank: rows row0 .. row0 + 127 of nrows, row i reading the window at wbase + i step - k
+// against the B operand bmat; emit(i, b, yr, yi) gets each finished pair of chains.  k_cz_gemm (L = 1) and k_cz_gemm_rat (one
+// phase of a rational rate) are its two instantiations.
 #define DH_CZ_AS 36
 #define DH_CZ_BS 144
-__global__ __launch_bounds__(256) void k_cz_gemm(const DhCzParams P) {
+template <class Emit>
+__device__ __forceinline__ void dh_cz_gemm_tile(const DhCzParams& P, const float* bmat, uint32_t wbase, uint32_t step, uint32_t row0,
+                                                uint32_t nrows, Emit emit) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) float As[DH_CZ_TM * DH_CZ_AS];
     __shared__ __attribute__((aligned(16))) float Bs[32 * DH_CZ_BS];
     const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t row0 = blockIdx.x * DH_CZ_TM, col0 = blockIdx.y * (2u * DH_CZ_TNC);
+    const uint32_t col0 = blockIdx.y * (2u * DH_CZ_TNC);
     // loaders: A -- row ar = tid >> 1, taps 8 ah .. 8 ah + 7 of the chunk (window indices descending); B -- float4 number
     // tid + 256 i of the 32 x 128 slab
     const uint32_t ar = (uint32_t) tid >> 1, ah = (uint32_t) tid & 1u;
-    const bool arow_ok = row0 + ar < P.n_out;
-    const uint32_t abase = P.off0 + (row0 + ar) * P.D + (P.tpad - 1u) - 8u * ah;
+    const bool arow_ok = row0 + ar < nrows;
+    const uint32_t abase = wbase + (row0 + ar) * step - 8u * ah;
     const float2* win = (const float2*) P.win;
     const uint32_t nch = P.tpad / DH_CZ_TAP_STEP;
     float2 ra[8];
@@ -910,7 +915,7 @@ __global__ __launch_bounds__(256) void k_cz_gemm(const DhCzParams P) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t q = (uint32_t) tid + 256u * i, r = q >> 5, c4 = q & 31u;
-            rb[i] = *(const float4*) (P.bmat + (size_t) (32u * c + r) * P.ncols + col0 + 4u * c4);
+            rb[i] = *(const float4*) (bmat + (size_t) (32u * c + r) * P.ncols + col0 + 4u * c4);
         }
     };
     auto stash = [&]() {
@@ -955,14 +960,29 @@ __global__ __launch_bounds__(256) void k_cz_gemm(const DhCzParams P) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const uint32_t row = row0 + 64u * (uint32_t) (w & 1) + 16u * i + 4u * (uint32_t) g + r;
-            if (row >= P.n_out) continue;
+            if (row >= nrows) continue;
 #pragma unroll
             for (int cg = 0; cg < 2; cg++) {
                 const uint32_t b = (col0 + 64u * (uint32_t) (w >> 1) + 32u * cg) / 2u + (uint32_t) m;
-                if (b < P.B) dh_cz_emit(P, row, b, acc[i][2 * cg][r], acc[i][2 * cg + 1][r]);
+                if (b < P.B) emit(row, b, acc[i][2 * cg][r], acc[i][2 * cg + 1][r]);
             }
         }
 #endif
+}
+
+__global__ __launch_bounds__(256) void k_cz_gemm(const DhCzParams P) {
+    dh_cz_gemm_tile(P, P.bmat, P.off0 + (P.tpad - 1u), P.D, blockIdx.x * DH_CZ_TM, P.n_out,
+                    [&](uint32_t row, uint32_t b, float yr, float yi) { dh_cz_emit(P, row, b, yr, yi); });
+}
+
+// Rational rates: blockIdx.z is the slot (one phase of the push, channelizer_core.hpp), blockIdx.x its 128-row tiles.  The
+// slots of a push differ by at most one row, so at most one workgroup per slot and column tile finds nothing to do.
+__global__ __launch_bounds__(256) void k_cz_gemm_rat(const DhCzRatParams R) {
+    const uint32_t s = blockIdx.z, row0 = blockIdx.x * DH_CZ_TM;
+    const DhCzPhase ph = R.ph[s];
+    if (row0 >= ph.count) return;
+    dh_cz_gemm_tile(R.g, dh_cz_bank(R.g, ph.bank), ph.wbase, R.g.D, row0, ph.count,
+                    [&](uint32_t i, uint32_t b, float yr, float yi) { dh_cz_emit_at(R.g, s + R.L * i, b, ph.nj0 + i * R.g.D, yr, yi); });
 }
 
 __global__ __launch_bounds__(256) void k_cz_fm(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out) {
@@ -1121,6 +1141,14 @@ static int dh_be_cz_gemm(const DhCzParams& P, void* stream) {
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }
+static int dh_be_cz_gemm_rat(const DhCzRatParams& R, void* stream) {
+    if (!R.nslots) return DH_OK;
+    hipLaunchKernelGGL(k_cz_gemm_rat, dim3((R.ph[0].count + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC), R.nslots), dim3(256), 0,
+                       (hipStream_t) stream, R);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+
 static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream) {
     if (!n_out) return DH_OK;
     hipLaunchKernelGGL(k_cz_fm, dim3((n_out + 255) / 256, B < 65535u ? B : 65535u), dim3(256), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out);

@@ -275,6 +275,11 @@ int dh_frontend_s16(const int16_t* d_in, size_t in_stride, float* d_out, size_t 
  *   output_mode   DH_CZ_IQ_F32 interleaved complex float rows, DH_CZ_FM arg(z[j] conj(z[j-1])) / pi (what dh_engine_push takes),
  *                 dcblock != 0 (FM only): y = (x - x[-1]) + 0.995 y[-1] as in dh_frontend_s16
  * Limits: 1 <= decimation <= 1024, 1 <= n_taps <= 16384 (finite), 1 <= n_channels <= 65536, 1 <= max_input <= 2^28.
+ * Rational rates: interpolation = L > 1 gives rows at input_rate * L / decimation (2.048 MS/s -> 48 kS/s is 3 / 128).  taps is
+ * then the low-pass at the virtual rate L * input_rate, with about L at DC for unity gain; output j sits at input index
+ * floor((j * decimation + decimation - 1) / L), and after N input samples exactly floor(L N / decimation) outputs exist.
+ * Limits: L <= 64, L <= decimation, gcd(L, decimation) = 1, n_taps <= 16384 L.  Wherever "max_input / decimation" sizes
+ * something below, read max_input * L / decimation.
  * ---------------------------------------------------------------------- */
 enum { DH_CZ_CS16 = 1, DH_CZ_CF32 = 2 };
 enum { DH_CZ_IQ_F32 = 1, DH_CZ_FM = 2 };
@@ -292,6 +297,7 @@ typedef struct {
     int32_t  dcblock;
     uint32_t max_input;            /* complex samples per push */
     void*    stream;               /* hipStream_t; NULL = default stream */
+    uint32_t interpolation;        /* L of a rational rate; 0 and 1 (and a struct_size that ends before this field): L = 1 */
 } dh_channelizer_config;
 
 int  dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out);
@@ -326,7 +332,7 @@ typedef struct {
     float*    d_power;             /* [n_channels][stride] */
     uint8_t*  d_gate;              /* [n_channels][stride] */
     uint32_t* d_counts;            /* [n_channels] */
-    size_t   stride;               /* >= (max_input / decimation + 1) / block + 1 */
+    size_t   stride;               /* >= (max_input * L / decimation + 1) / block + 1 */
 } dh_channelizer_power_config;
 int  dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg);
 /* new levels and hang from the next push on; the gates' state is kept.  DH_EINVAL before the enable */

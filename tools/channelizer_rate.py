@@ -1,10 +1,20 @@
 #!/usr/bin/env python3
-"""tools/channelizer_rate.py [--out FILE] [--pushes K] [--config a|b|all] [--power L] [--lib PATH --tag NAME]: throughput of
-dh_channelizer on cuda:0.
+"""tools/channelizer_rate.py [--out FILE] [--pushes K] [--config a|b|c|c-short|all] [--interpolation L] [--power L]
+[--lib PATH --tag NAME]: throughput of dh_channelizer on cuda:0.
 
 Configurations, taps = api.channel_taps(rate, D, 6.5 kHz, 12 kHz, 60 dB):
   (a) 2.4 MS/s CS16, D = 50, 192 channels on a 12.5 kHz raster, 10 s of input per push;
-  (b) 9.6 MS/s CS16, D = 200, 768 channels, 1 s of input per push.
+  (b) 9.6 MS/s CS16, D = 200, 768 channels, 1 s of input per push;
+  (c) 2.048 MS/s CS16, L / M = 3 / 128 (a rational rate: taps designed with interpolation = 3), 160 channels, 10 s of input
+      per push; (c-short) the same in 20 ms pushes: 960 outputs, 320 per phase, so every phase's last 128-row tile is half
+      empty.  "all" is (a) and (b).
+--interpolation L replaces the configuration's L (1 for a and b, 3 for c and c-short); it must share no factor with D.
+The lines of profiles/channelizer_rational_rate.jsonl ("Rational rates measured"), in this order in
+one run on one device, variants/lib_parent.so being the parent commit built by tools/build_variant.sh:
+  --config a --out F --lib variants/lib_parent.so --tag parent_1          --config a --out F --lib digiham_amd/libdigiham_amd.so --tag new_1
+  --config a --out F --lib variants/lib_parent.so --tag parent_2          --config a --out F --lib digiham_amd/libdigiham_amd.so --tag new_2
+  --config c --out F --tag rational                                       --config c-short --pushes 50 --out F --tag rational
+and the kernel trace: rocprofv3 --kernel-trace --stats -- python tools/channelizer_rate.py --config c, in a run of its own.
 Each push is timed with HIP events (torch.cuda.Event on the channelizer's stream) in "iq" mode (window + GEMM / rotation)
 and in "fm" + DC-blocker mode (+ the discriminator and the recurrence).  Reported per push: ms, ms per second of input,
 the real-time factor, and the GEMM's TFLOP/s counted as 8 B T' n_out over the whole push, with its fraction of the
@@ -19,7 +29,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CONFIGS = {"a": dict(rate=2.4e6, D=50, B=192, seconds=10.0), "b": dict(rate=9.6e6, D=200, B=768, seconds=1.0)}
+CONFIGS = {"a": dict(rate=2.4e6, D=50, B=192, seconds=10.0), "b": dict(rate=9.6e6, D=200, B=768, seconds=1.0),
+           "c": dict(rate=2.048e6, D=128, L=3, B=160, seconds=10.0), "c-short": dict(rate=2.048e6, D=128, L=3, B=160, seconds=0.02)}
 PEAK_TF = 157.3
 
 
@@ -27,12 +38,13 @@ def run(name, c, mode, pushes, warmup=2, power=0, ctx=None, tag=None):
     import torch
     from digiham_amd import api
     label, mode = mode, mode.split("+")[0]
-    rate, D, B = c["rate"], c["D"], c["B"]
+    rate, D, B, L = c["rate"], c["D"], c["B"], c.get("L", 1)
     n = int(c["seconds"] * rate)
-    h = api.channel_taps(rate, D, 6500.0, 12000.0, 60.0)
-    tpad = 16 * ((len(h) + 15) // 16)
+    rational = dict(interpolation=L) if L > 1 else {}          # (an older build given with --lib has no such argument)
+    h = api.channel_taps(rate, D, 6500.0, 12000.0, 60.0, **rational)
+    tpad = 16 * ((-(-len(h) // L) + 15) // 16)
     freqs = [(b - B // 2) * 12500.0 for b in range(B)]
-    cz = api.Channelizer(rate, D, freqs, h, input="cs16", output=mode, dcblock=(mode == "fm"), max_input=n, ctx=ctx)
+    cz = api.Channelizer(rate, D, freqs, h, input="cs16", output=mode, dcblock=(mode == "fm"), max_input=n, ctx=ctx, **rational)
     if label.endswith("+power"):
         cz.enable_power(block=power, open_db=-40.0, close_db=-43.0, hang_blocks=2)
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -53,9 +65,11 @@ def run(name, c, mode, pushes, warmup=2, power=0, ctx=None, tag=None):
     extra = {"tag": tag} if tag else {}
     if label.endswith("+power"):
         extra.update(block=power, power_read_mb=round(8.0 * B * n_out / 1e6, 1))
+    if L > 1:
+        extra.update(L=L)
     return {**extra, "config": name, "mode": label, "rate": rate, "D": D, "B": B, "taps": len(h), "tpad": tpad, "n_in": n, "n_out": n_out,
             "ms_per_push": round(ms, 3), "ms_min": round(min(times), 3), "ms_per_s_input": round(ms / c["seconds"], 3),
-            "realtime_factor": round(c["seconds"] * 1e3 / ms, 1), "gemm_tflops": round(tf, 2), "fraction_of_peak": round(tf / PEAK_TF, 3),
+            "realtime_factor": round(c["seconds"] * 1e3 / ms, 1 if c["seconds"] >= 1 else 2), "gemm_tflops": round(tf, 2), "fraction_of_peak": round(tf / PEAK_TF, 3),
             "pushes": pushes}
 
 
@@ -66,6 +80,7 @@ def main():
     ap.add_argument("--config", default="all")
     ap.add_argument("--modes", default="iq,fm")
     ap.add_argument("--power", type=int, default=0)
+    ap.add_argument("--interpolation", type=int, default=0)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--tag", default=None)
     a = ap.parse_args()
@@ -77,7 +92,8 @@ def main():
     modes = [m for m in a.modes.split(",") if m] + (["iq+power", "fm+power"] if a.power else [])
     for name in (["a", "b"] if a.config == "all" else [a.config]):
         for mode in modes:
-            r = run(name, CONFIGS[name], mode, a.pushes, power=a.power, ctx=ctx, tag=a.tag)
+            cfg = dict(CONFIGS[name], L=a.interpolation) if a.interpolation else CONFIGS[name]
+            r = run(name, cfg, mode, a.pushes, power=a.power, ctx=ctx, tag=a.tag)
             print(json.dumps(r), flush=True)
             rows.append(r)
     if a.out:
