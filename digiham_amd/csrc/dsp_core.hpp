@@ -1101,16 +1101,19 @@ inline float dh_wave_max_lanes(const float (&a)[DH_WAVE][1]) {
 #endif
 
 // The rare paths of the error-bounded kernels (inlined: as real calls they would force the kernel's argument block into
-// scratch memory).  What they need to know lives in LDS between runs (DhBoundState), not in registers: every scalar that
-// stays live across the FIR -- where all 128 registers are taken -- is a spill in the hot loop.
+// scratch memory).  What they need to know lives in LDS between runs (DhBoundState), not in vector registers: all 128 are
+// taken across the FIR, and a value parked there is a spill in the hot loop.  (The seven words the run loop itself reads and
+// writes in every run fit the scalar file without one -- tools/asm_census.py -- and are carried there, see the struct.)
 #define DH_COLD DH_HD
 
 // bookkeeping of the error-bounded kernels between runs, in LDS (words 48.. of the tap block: the wide filter uses 41)
 struct DhBoundState {
     int32_t cur_start, cur_off, prev_start, prev_off;   // filtered positions of symbol 0 of the current / previous variance block, their offsets
     uint32_t blk_flags;                                 // bit 0: the current block's start is known, bit 1: the previous block's
-    uint32_t e_count, n_uncertain, n_exact_runs, n_exact_blocks;
-    float e_cur, e_prev, e_blk;                         // error radii: current / previous >= 100-symbol bucket, current variance block
+    uint32_t n_uncertain, n_exact_runs, n_exact_blocks;
+    // (what only the run loop itself reads and writes in every run -- the error radii of the current variance block and of the current /
+    // previous >= 100-symbol bucket, the bucket's symbol count, and its own copies of blk_flags, cur_start and cur_off -- is carried in
+    // scalar registers there: dh_rrc_demod_channel)
 };
 #define DH_BOUND_STATE(S) (reinterpret_cast<DhBoundState*>((S).bound))
 DH_HD float dh_uniform_f(float x) { union { float f; uint32_t u; } b; b.f = x; b.u = dh_uniform(b.u); return b.f; }
@@ -2218,11 +2221,19 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 
     // FIR taps are parked in LDS and pulled into VGPRs at the start of every FIR pass (see P2): their live range
     // must end with the FIR, or they pin ~80 registers through the latency-bound phases where the prefetch lives.
+    // (error radii of the current variance block and of the current / previous >= 100-symbol bucket, the current bucket's symbols, the
+    // block flags and the current block's start: wave-uniform, and read and written by every run -- carried in scalar registers across
+    // the loop, as k0, off, p and nsym are: read back from LDS they cost every run a ds_read, a wait and a v_readfirstlane each;
+    // blk_flags, cur_start and cur_off are also written through to DhBoundState, where the rare paths read them)
+    uint32_t blk_flags = 0, e_count = 0; float e_cur = 0.0f, e_prev = 0.0f, e_blk_run = 0.0f;
+    int32_t cur_start = 0, cur_off = 0;
     if (BOUNDED) {
-        BS->cur_start = (int32_t) sth[DH_ST_CUR_START]; BS->cur_off = (int32_t) sth[DH_ST_CUR_OFF];
+        cur_start = (int32_t) dh_uniform(sth[DH_ST_CUR_START]); cur_off = (int32_t) dh_uniform(sth[DH_ST_CUR_OFF]);
+        BS->cur_start = cur_start; BS->cur_off = cur_off;
         BS->prev_start = (int32_t) sth[DH_ST_PREV_START]; BS->prev_off = (int32_t) sth[DH_ST_PREV_OFF];
-        BS->blk_flags = sth[DH_ST_BLOCK_FLAGS]; BS->e_count = sth[DH_ST_E_COUNT]; BS->n_uncertain = 0; BS->n_exact_runs = 0; BS->n_exact_blocks = 0;
-        BS->e_cur = st[DH_ST_E_CUR]; BS->e_prev = st[DH_ST_E_PREV]; BS->e_blk = st[DH_ST_E_BLOCK];
+        blk_flags = dh_uniform(sth[DH_ST_BLOCK_FLAGS]); e_count = dh_uniform(sth[DH_ST_E_COUNT]);
+        e_cur = dh_uniform_f(st[DH_ST_E_CUR]); e_prev = dh_uniform_f(st[DH_ST_E_PREV]); e_blk_run = dh_uniform_f(st[DH_ST_E_BLOCK]);
+        BS->blk_flags = blk_flags; BS->n_uncertain = 0; BS->n_exact_runs = 0; BS->n_exact_blocks = 0;
     }
     DH_FOR_LANES(lane) {
         if (NZ > 80) { for (int i = lane; i <= NZ / 2; i += DH_WAVE) S.tapsf[i] = P.taps[i]; }
@@ -2311,8 +2322,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         const uint32_t last_start = p + (m - 1) * sps + (m > 1 ? (uint32_t) step_off : 0u);
         const uint32_t need = last_start + sps - p;     // filtered samples [p, p+need) feed this run
         const uint32_t need_fir = KEEPF ? (uint32_t) DH_FTILE : need;      // (a kernel that also delivers the filtered samples wants the whole pass)
-        // (bits 2.. of blk_flags, ring-less kernels: 4 = some run of the current block had a non-zero window, bits 8..15 = runs the block has been cut into)
-        if (BOUNDED && k0 == 0) { BS->cur_start = (int32_t) p; BS->cur_off = step_off; BS->blk_flags = (BS->blk_flags & 3u) | 1u; BS->e_blk = 0.0f; }   // symbol k of this block sits at cur_start + k sps + (k ? cur_off : 0)
+        if (BOUNDED && k0 == 0) { cur_start = (int32_t) p; cur_off = step_off; BS->cur_start = cur_start; BS->cur_off = cur_off; blk_flags = (blk_flags & 3u) | 1u; BS->blk_flags = blk_flags; e_blk_run = 0.0f; }   // symbol k of this block sits at cur_start + k sps + (k ? cur_off : 0)
         bool use_exact = BOUNDED && P.exact_mode == 2;  // this run through the exact FIR (odd samples, odd staging path)
         DH_LANE_ARRAY(float, xmax_lane, 1);
         float e_run = 0.0f;                             // error radius of this run's filtered samples (0: exact)
@@ -2552,10 +2562,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             }
         }
 
-        DH_COMPILER_FENCE();                            // the bookkeeping in LDS is read here, not carried across the FIR
+        DH_COMPILER_FENCE();                            // what the slicing phases read from LDS is read here, not hoisted across the FIR (the run's own bookkeeping is in scalar registers, see above)
         float e_blk = 0.0f;
-        if (BOUNDED) { e_blk = dh_uniform_f(__builtin_fmaxf(BS->e_blk, e_run)); BS->e_blk = e_blk; }
-        const float e_eff = BOUNDED ? dh_uniform_f(__builtin_fmaxf(e_run, __builtin_fmaxf(BS->e_cur, BS->e_prev))) : 0.0f;
+        if (BOUNDED) { e_blk = dh_uniform_f(__builtin_fmaxf(e_blk_run, e_run)); e_blk_run = e_blk; }
+        const float e_eff = BOUNDED ? dh_uniform_f(__builtin_fmaxf(e_run, __builtin_fmaxf(e_cur, e_prev))) : 0.0f;
         const float T = DH_BOUND_T_FACTOR * e_eff;
         uint64_t vote_a = 0, vote_b = 0;                // doubtful symbols of the run: bit l of vote_a = symbol 2 l, of vote_b = symbol 2 l + 1
         // Straight-line per half of the run (m <= 100 symbols: lanes 0..63, then 0..35): every lane computes, a predicate
@@ -2642,11 +2652,11 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         if (block_done) { k0 = 0; off = new_off; }
         if (BOUNDED) {
             // radii of the ring entries: the last 100 symbols always lie inside the current bucket + the one before it
-            const float ec = __builtin_fmaxf(BS->e_cur, e_run);
-            const uint32_t cnt = dh_uniform(BS->e_count) + m;
-            if (cnt >= DH_VOLUME_RB_SIZE) { BS->e_prev = ec; BS->e_cur = 0.0f; BS->e_count = 0; }
-            else { BS->e_cur = ec; BS->e_count = cnt; }
-            if (block_done) { BS->prev_start = BS->cur_start; BS->prev_off = BS->cur_off; BS->blk_flags = (BS->blk_flags & 1u) ? 2u : 0u; }
+            const float ec = dh_uniform_f(__builtin_fmaxf(e_cur, e_run));
+            const uint32_t cnt = e_count + m;
+            if (cnt >= DH_VOLUME_RB_SIZE) { e_prev = ec; e_cur = 0.0f; e_count = 0; }
+            else { e_cur = ec; e_count = cnt; }
+            if (block_done) { BS->prev_start = cur_start; BS->prev_off = cur_off; blk_flags = (blk_flags & 1u) ? 2u : 0u; BS->blk_flags = blk_flags; }
         }
         DH_TAPFRAG_LOAD();                              // for the next run
         DH_PHASE_MARK(6);
@@ -2700,10 +2710,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             sth[DH_ST_NSYM] += produced;
             if (BOUNDED) {
                 sth[DH_ST_P0] = keep;
-                sth[DH_ST_CUR_START] = (uint32_t) (BS->cur_start - (int32_t) base); sth[DH_ST_CUR_OFF] = (uint32_t) BS->cur_off;
+                sth[DH_ST_CUR_START] = (uint32_t) (cur_start - (int32_t) base); sth[DH_ST_CUR_OFF] = (uint32_t) cur_off;
                 sth[DH_ST_PREV_START] = (uint32_t) (BS->prev_start - (int32_t) base); sth[DH_ST_PREV_OFF] = (uint32_t) BS->prev_off;
-                sth[DH_ST_BLOCK_FLAGS] = BS->blk_flags; sth[DH_ST_E_COUNT] = BS->e_count;
-                st[DH_ST_E_CUR] = BS->e_cur; st[DH_ST_E_PREV] = BS->e_prev; st[DH_ST_E_BLOCK] = BS->e_blk;
+                sth[DH_ST_BLOCK_FLAGS] = blk_flags; sth[DH_ST_E_COUNT] = e_count;
+                st[DH_ST_E_CUR] = e_cur; st[DH_ST_E_PREV] = e_prev; st[DH_ST_E_BLOCK] = e_blk_run;
                 sth[DH_ST_UNCERTAIN] += BS->n_uncertain; sth[DH_ST_EXACT_RUNS] += BS->n_exact_runs; sth[DH_ST_EXACT_BLOCKS] += BS->n_exact_blocks;
             }
 
