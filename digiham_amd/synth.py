@@ -401,6 +401,109 @@ def nxdn_stream(seed, n_frames, lead_in=29, src=None, dst=None):
     return np.array(out, np.uint8)
 
 
+def nxdn_mixed_stream(seed, n_frames, accept=None, lead_in=29, loss=None, err=0.0, voice_only=False):
+    """Frames that walk the decoder's frame machine (nxdn_phase.cpp:43-170) instead of one call shape: every frame draws
+    its RF channel type (RCCH included: frame body skipped), its functional channel (UDCH: skipped; with and without the
+    superframe SACCH) and its option (which blocks are FACCH1), and some frames carry
+
+    * a TX_RELEASE in block 0 only or in block 1 only.  The decoder falls back to its sync search WITHOUT consuming the
+      released block, so the search runs through the rest of the frame: after a release in block 0 the other block's place
+      holds a few random dibits and then the next frame, sync word first.  Some releasing payloads are searched until
+      the released block ITSELF, as transmitted, holds a sync word (at most two wrong bits) followed by a LICH of right
+      parity: a decoder that counted the released block as consumed would not see that frame start;
+    * a sync word with 1..4 wrong bits (more than two count against the sync), or a LICH with broken parity (the previous
+      LICH then governs the frame).
+
+    `accept(dibits72) -> bool` says whether the decoder under test accepts a FACCH1 block (the reference's channel decoder
+    rejects two clean blocks in three): payloads are drawn again until it does.  `loss` =
+    (first frame, frames): that many frames from that index on are random dibits (signal lost).  `err`: share of wrong
+    dibits scattered over the result.  `voice_only`: every frame is a voice frame of a call (LICH 0x56), nothing special.
+    Returns (dibits, start offset of every frame -- lost frames included, the shortened release frames too --, offsets of
+    the sync words inside released blocks)."""
+    rng = np.random.default_rng(seed)
+
+    pn = np.array(nxdn_scramble([0] * 182), np.uint8)
+    sync_bits = np.unpackbits(np.array(NXDN_SYNC, np.uint8)[:, None], axis=1)[:, 6:].reshape(-1)
+
+    def frame_start_inside(d, blk):
+        """offset of a sync word (<= 2 wrong bits) + LICH of right parity inside block `blk` as transmitted, or -1"""
+        tx = np.array(d, np.uint8) ^ pn[38 + 72 * blk:110 + 72 * blk]
+        bits = np.unpackbits(tx[:, None], axis=1)[:, 6:].reshape(-1)
+        for k in range(72 - 18 + 1):
+            if int((bits[2 * k:2 * k + 20] ^ sync_bits).sum()) <= 2:
+                lb = (tx[k + 10:k + 18] ^ pn[:8]) >> 1
+                if (int(lb[0]) ^ int(lb[1]) ^ int(lb[2]) ^ int(lb[3])) == int(lb[7]):
+                    return k
+        return -1
+
+    def facch1(msg_type, inside=None):
+        while True:
+            info = _bits_of(int(rng.integers(0, 4)), 2) + _bits_of(msg_type, 6) + [int(b) for b in rng.integers(0, 2, 72)]
+            d = nxdn_facch1_dibits(info)
+            if inside is not None and frame_start_inside(d, inside) < 0:
+                continue
+            if accept is None or accept(np.array(d, np.uint8)):
+                return d
+
+    def other_type():
+        t = int(rng.integers(0, 63))
+        return t + 1 if t >= 0x08 else t                  # anything but TX_RELEASE
+
+    out = [int(d) for d in rng.integers(0, 4, lead_in)]
+    starts, inside = [], []
+    s, t = int(rng.integers(1, 65535)), int(rng.integers(1, 65535))
+    vcall = nxdn_vcall_bits(1 if s & 1 else 4, s, t)
+    ran = int(rng.integers(0, 64))
+    sidx = 0
+    for n in range(n_frames):
+        starts.append(len(out))
+        if loss is not None and loss[0] <= n < loss[0] + loss[1]:
+            out += [int(d) for d in rng.integers(0, 4, 192)]
+            continue
+        rf = int(rng.choice(4, p=[0.08, 0.32, 0.3, 0.3]))
+        fc = int(rng.choice(4, p=[0.15, 0.08, 0.65, 0.12]))
+        option = int(rng.integers(0, 4))
+        special = None if voice_only else rng.choice(["rel0", "rel1", "sync", "lich", None], p=[0.05, 0.05, 0.07, 0.07, 0.76])
+        searched = special in ("rel0", "rel1") and rng.random() < 0.12
+        if voice_only:
+            rf, fc, option = 2, 2, 3
+        if special in ("rel0", "rel1"):
+            rf, fc = max(rf, 1), fc if fc != 1 else 2
+            option = int(rng.choice([0, 1] if special == "rel0" else [0, 2]))     # the other block: a FACCH1 that is no release, or voice
+        lich = (rf << 5) | (fc << 3) | (option << 1) | int(rng.integers(0, 2))
+        sac = nxdn_sacch_dibits(sidx & 3, ran, vcall[18 * (sidx & 3):18 * (sidx & 3) + 18])
+        if rf != 0 and fc == 2:
+            sidx += 1
+        blocks = []
+        for i in (0, 1):
+            if (option >> (1 - i)) & 1:
+                blocks.append([int(d) for d in rng.integers(0, 4, 72)])
+            else:
+                release = special == "rel%d" % i
+                blocks.append(facch1(0x08 if release else other_type(), i if release and searched else None))
+                if release and searched:
+                    inside.append(len(out) + 48 + 72 * i + frame_start_inside(blocks[-1], i))
+        ldib = nxdn_lich_dibits(lich)
+        if special == "lich":
+            ldib[int(rng.integers(0, 8))] ^= 2
+        frame = nxdn_frame(rng, lich, sac, blocks)
+        frame[10:18] = nxdn_scramble(ldib + [0] * 174)[:8]
+        if special == "sync":
+            for bp in rng.choice(20, int(rng.integers(1, 5)), replace=False):
+                frame[bp // 2] ^= 2 >> (bp % 2)
+        if special == "rel0" and option == 1:
+            frame = frame[:120] + [int(d) for d in rng.integers(0, 4, int(rng.integers(0, 40)))]
+        elif special == "rel1" and rng.random() < 0.5:
+            frame += [int(d) for d in rng.integers(0, 4, int(rng.integers(1, 30)))]
+        out += frame
+    out += [int(d) for d in rng.integers(0, 4, int(rng.integers(15, 60)))]
+    a = np.array(out, np.uint8)
+    if err:
+        hit = rng.random(len(a)) < err
+        a[hit] ^= rng.integers(1, 4, int(hit.sum())).astype(np.uint8)
+    return a, np.array(starts), np.array(inside, np.int64)
+
+
 # ----------------------------------------------------------------------------- POCSAG
 POCSAG_SYNC = 0x7CD215D8          # decoder: pocsag_phase.hpp:15
 POCSAG_IDLE = 0x7A89C197          # decoder: codeword.hpp:23

@@ -176,3 +176,108 @@ def test_decoder_only_rows_at_odd_addresses(ctx, oracle):
         out, ev = oracle.Decoder("dstar").process(streams[b][:n])
         go, ge = np.concatenate(got_o[b]), np.concatenate(got_e[b])
         assert len(out) > 0 and len(go) == len(out) and (go == out).all() and ge.tobytes() == ev.tobytes()
+
+
+# ------------------------------------------------------------------ the five-frame fast path of the voice phase, by construction
+VOICE_AT = 64 + 15 + 660                       # dstar_transmission: bit sync, frame sync, header; then 96-bit frames
+
+
+def _decode_rows(ctx, rows, sizes, pitch=None):
+    """rows [B][n] through a decoder-only engine in pushes of the given sizes (cycled); pitch = row pitch of the pushed buffer"""
+    B, n = rows.shape
+    pitch = max(max(sizes), 64) if pitch is None else pitch
+    eng = api.Engine(B, pitch, rrc="none", demod="none", proto="dstar", ctx=ctx)
+    o, e, lo, k = [[] for _ in range(B)], [[] for _ in range(B)], 0, 0
+    while lo < n:
+        m = min(sizes[k % len(sizes)], n - lo); k += 1
+        part = np.zeros((B, pitch), np.uint8); part[:, :m] = rows[:, lo:lo + m]
+        eng.push_symbols(part, np.full(B, m, np.uint32))
+        lo += m
+        f, fc = eng.frames(); ev, ec = eng.events()
+        for b in range(B):
+            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
+    eng.close()
+    return [np.concatenate(x) for x in o], [np.concatenate(x) for x in e]
+
+
+def _assert_rows_match(ctx, oracle, rows, pushes, pitch=None):
+    want = [oracle.Decoder("dstar").process(r) for r in rows]
+    for sizes in pushes:
+        out, ev = _decode_rows(ctx, rows, sizes, pitch)
+        for b, (wo, we) in enumerate(want):
+            assert len(out[b]) == len(wo) and (out[b] == wo).all(), (sizes[:2], b)
+            assert ev[b].tobytes() == we.tobytes(), (sizes[:2], b)
+    return want
+
+
+def _stack(rows):
+    n = max(len(r) for r in rows)
+    return np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows]).astype(np.uint8)
+
+
+def test_end_pattern_at_every_frame_of_the_fast_path(ctx, oracle):
+    """The end pattern, and its second half alone (dstar_phase.cpp:92-96), in the data frame of frame 1..20 of a superframe:
+    each of the five positions of a fast-path batch, in each of the four batches.  The batch has to stop in front of that
+    frame.  Four channels of ten transmissions; after each end the search has to find the next header."""
+    rng = np.random.default_rng(60)
+    term = np.array(synth.DSTAR_TERMINATOR, np.uint8)
+    rows = [[rng.integers(0, 2, 30 + c).astype(np.uint8)] for c in range(4)]
+    for k, (idx, half) in enumerate((i, h) for h in (False, True) for i in range(1, 21)):
+        b, _, _ = synth.dstar_transmission(rng, my="T%02d" % idx, message="end in frame %d" % idx, n_superframes=2)
+        at = VOICE_AT + 96 * (21 + idx) + 72
+        tail = term[24:] if half else term
+        rows[k % 4] += [b[:at], tail, rng.integers(0, 2, int(rng.integers(150, 400))).astype(np.uint8)]
+    rows = _stack([np.concatenate(r) for r in rows])
+    want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [4096], [997]))
+    ev = np.concatenate([e for _, e in want])
+    assert ((ev["type"] == EV_META_RESET) & (ev["b"] == 0)).sum() >= 40 and (ev["type"] == EV_MESSAGE).sum() >= 40
+
+
+def test_symbols_with_bit_1_set_in_every_byte_lane_of_a_batch(ctx, oracle):
+    """A symbol 2 or 3 in each of the 60 eight-symbol lanes of a batch (frames 1..5 of a superframe, and one more in frames
+    11..15): the batch must go frame by frame, where the reference compares whole symbols (a difference in a sync or end
+    pattern) and packs bit 0."""
+    rng = np.random.default_rng(61)
+    rows = []
+    for c in range(4):
+        b, _, _ = synth.dstar_transmission(rng, my="ODD%d" % c, n_superframes=16, simple=synth.dstar_dprs_sentence("X>APDPRS:!4916.45N/01131.00E>"))
+        b = b.copy()
+        for k in range(1, 16):
+            lane = 15 * c + k - 1
+            b[VOICE_AT + 96 * (21 * k + 1) + 8 * lane + lane % 8] |= 2
+            b[VOICE_AT + 96 * (21 * k + 11) + 8 * (lane * 7 % 60) + 7 - lane % 8] |= 2
+        rows.append(np.concatenate([rng.integers(0, 2, 40 + c).astype(np.uint8), b, rng.integers(0, 2, 300).astype(np.uint8)]))
+    rows = _stack(rows)
+    assert (rows > 1).sum() == 4 * 30
+    want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [5000]))
+    assert all(len(o) // 9 >= 16 * 21 - 2 for o, _ in want)                 # the calls went through to their ends
+
+
+def test_fast_path_at_the_end_of_a_push_at_every_row_misalignment(ctx, oracle):
+    """A batch needs 516 symbols of the push from its (aligned) first word: pushes of 515..518 + 96 k symbols put the last
+    batch of a push on both sides of that limit, and four rows at a pitch of 4 m + 3 bytes give every misalignment."""
+    rng = np.random.default_rng(62)
+    rows = []
+    for c in range(4):
+        b, _, _ = synth.dstar_transmission(rng, my="MIS%d" % c, n_superframes=9, message="misaligned row %d" % c)
+        rows.append(np.concatenate([rng.integers(0, 2, 33 + 5 * c).astype(np.uint8), b, rng.integers(0, 2, 200).astype(np.uint8)]))
+    sizes = [515 + d + 96 * k for k in range(3) for d in range(4)]
+    want = _assert_rows_match(ctx, oracle, _stack(rows), (sizes, sizes[::-1], [s + 96 for s in sizes[5:] + sizes[:5]]), pitch=811)
+    assert all(len(o) // 9 >= 9 * 21 - 2 and (e["type"] == EV_MESSAGE).sum() >= 4 for o, e in want)
+
+
+def test_superframe_that_begins_without_sync_collects_slow_data_only(ctx, oracle):
+    """Late entry: the voice phase starts at a data-frame sync with a sync count of 0.  Until the next sync frame no voice
+    bytes are written, but the slow data of that superframe is collected and its message comes out at that sync frame
+    (dstar_phase.cpp:60-70, :81-86, :122-129)."""
+    rng = np.random.default_rng(63)
+    rows = []
+    for c in range(2):
+        b, _, voice = synth.dstar_transmission(rng, my="LATE%d" % c, message="late entry %d" % c, n_superframes=3, with_header=False, inline_header=False)
+        rows.append(np.concatenate([np.zeros(50 + 3 * c, np.uint8), b, rng.integers(0, 2, 300).astype(np.uint8)]))
+    rows = _stack(rows)
+    want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [1000], [97]))
+    for o, e in want:
+        start = e[e["type"] == EV_VOICE_START]
+        assert len(start) >= 1 and start[0]["b"] == 0                      # entered at a voice sync, not behind a header
+        assert (e["type"] == EV_MESSAGE).sum() == 3 and 9 * 42 <= len(o) <= 9 * 44      # three superframes' messages, two superframes' voice

@@ -3,7 +3,11 @@
 * the oracle's frame elements (scrambler, LICH, SACCH, FACCH1, trellis) against tests/golden/nxdn_ref.npz, whose
   expected values come from the reference's own classes compiled in place (PINNED), incl. the four SACCH
   patterns of the NXDN "Common Air Interface Test" document quoted at nxdn_phase.cpp:73-98;
-* the engine (CPU wave emulation / MI355X) against the oracle: decoder on dibits, and the whole chain on audio.
+* the engine (CPU wave emulation / MI355X) against the oracle: decoder on dibits, and the whole chain on audio -- on the
+  calls of synth.nxdn_stream and on synth.nxdn_mixed_stream, whose frames walk the whole frame machine (every LICH class,
+  releases in either block, damaged sync words and LICHs, sync loss at every frame index); what those streams reach is
+  asserted on the oracle's events.  The frame elements through the product against the reference's vectors:
+  tests/test_nxdn_elements.py.
 """
 import json
 import os
@@ -89,6 +93,103 @@ def test_decoder_on_dibits_matches_oracle(ctx, oracle, seed):
             go, ge = _decode_symbols(ctx, stream, chunk)
             assert len(go) == len(out) and (go == out).all()
             assert ge.tobytes() == ev.tobytes()
+
+
+def _decode_rows(ctx, rows, chunk):
+    B, n = rows.shape
+    eng = api.Engine(B, max(min(chunk, n), 16), rrc="none", demod="none", proto="nxdn", ctx=ctx)
+    o, e = [[] for _ in range(B)], [[] for _ in range(B)]
+    for lo in range(0, n, chunk):
+        part = np.ascontiguousarray(rows[:, lo:lo + chunk])
+        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
+        f, fc = eng.frames(); ev, ec = eng.events()
+        for b in range(B):
+            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
+    eng.close()
+    return [np.concatenate(x) for x in o], [np.concatenate(x) for x in e]
+
+
+@pytest.fixture(scope="module")
+def mixed(oracle):
+    """36 channels of synth.nxdn_mixed_stream with what oracle.Decoder("nxdn") makes of them.  Channels 0..23: frames of
+    every RF type / functional channel / option, FACCH1 payloads the decoder accepts, releases in either block, damaged
+    sync words, broken LICH parity; channel c loses its signal from frame c on for 1 + c % 9 frames; the odd channels
+    have 0.5 % wrong dibits.  Channels 24..35: a voice call (SACCHs decoded four frames ahead) that loses its signal from
+    frame 6 + k on (k = 0..11: every residue of the ahead group) for 1 + 2 k % 9 frames."""
+    accept = lambda d: oracle.nxdn_facch1(d)[0]
+    rows, starts, loss, inside = [], [], [], []
+    for c in range(24):
+        loss.append((c, 1 + c % 9))
+        s, st, ins = synth.nxdn_mixed_stream(500 + c, 44, accept, lead_in=20 + c, loss=loss[-1], err=0.005 * (c & 1))
+        rows.append(s); starts.append(st); inside.append(ins)
+    for k in range(12):
+        loss.append((6 + k, 1 + 2 * k % 9))
+        s, st, _ = synth.nxdn_mixed_stream(600 + k, 30, accept, lead_in=20 + k, loss=loss[-1], voice_only=True)
+        rows.append(s); starts.append(st)
+    n = max(len(r) for r in rows)
+    rows = np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows])
+    want = [oracle.Decoder("nxdn").process(r) for r in rows]
+    return rows, starts, loss, inside, want
+
+
+def test_mixed_streams_walk_the_whole_frame_machine(mixed):
+    """What the comparison below rests on, read off the ORACLE's output alone: both FACCH1 positions, releases in either
+    block, sync losses (the drop right after the count reached 0, and the seven-frame run-down from 6), SACCH superframes,
+    every option, and both kinds of LICH whose frame body is skipped."""
+    rows, starts, loss, inside, want = mixed
+    ev = np.concatenate([e for _, e in want[:24]])
+    fa = ev[ev["type"] == 36]
+    rel = fa[(fa["payload"][:, 0] & 0x3F) == 0x08]
+    for blk in (0, 1):
+        assert (fa["a"] == blk).sum() >= 20 and (rel["a"] == blk).sum() >= 10
+    assert ((ev["type"] == 37) & (ev["b"] == 0)).sum() >= 10 and ((ev["type"] == 37) & (ev["b"] == 1)).sum() == len(rel)
+    assert (ev["type"] == 34).sum() >= 5
+    # frame starts INSIDE a released block (it is not consumed: the search resumes at its first dibit) that the decoder took
+    taken = sum(int(((e["type"] == 32) & (e["sym_index"] == p)).any()) for ins, (_, e) in zip(inside, want) for p in ins)
+    assert taken >= 4, taken
+    lich = ev[ev["type"] == 32]["payload"][:, 0]
+    assert set((lich >> 1) & 3) == {0, 1, 2, 3} and set((lich >> 5) & 3) == {0, 1, 2, 3} and set((lich >> 3) & 3) == {0, 1, 2, 3}
+    # frames the decoder still took on the old grid after the signal went, before it gave up: 0 .. 6
+    ridden = set()
+    for (first, count), st, (_, e) in zip(loss, starts, want):
+        lo, hi = int(st[first]), int(st[first]) + 192 * count
+        r = e[(e["type"] == 37) & (e["b"] == 0) & (e["sym_index"] >= lo) & (e["sym_index"] <= hi)]
+        if len(r) and (int(r[0]["sym_index"]) - lo) % 192 == 0:
+            ridden.add((int(r[0]["sym_index"]) - lo) // 192)
+    assert {1, 6} <= ridden, ridden            # count 1 -> one frame at count 0, then the drop; count 6 -> six frames, dropped at the seventh
+    voice = np.concatenate([e for _, e in want[24:]])
+    assert ((voice["type"] == 37) & (voice["b"] == 0)).sum() >= 6 and (voice["type"] == 34).sum() >= 12
+
+
+@pytest.mark.parametrize("chunk", [None, 1000, 193, 200, 385, 577, 769])
+def test_mixed_streams_match_oracle(ctx, mixed, chunk):
+    """Decoder bytes, events and counts of the 36 mixed channels equal the oracle decoder's, in one push and in pushes that
+    leave every number of whole frames (and, with 200, every offset) in hand."""
+    rows, _, _, _, want = mixed
+    out, ev = _decode_rows(ctx, rows, rows.shape[1] if chunk is None else chunk)
+    for b, (wo, we) in enumerate(want):
+        assert len(out[b]) == len(wo) and (out[b] == wo).all(), "channel %d: decoder bytes" % b
+        assert len(ev[b]) == len(we), "channel %d: %d events, oracle %d" % (b, len(ev[b]), len(we))
+        assert ev[b].tobytes() == we.tobytes(), "channel %d: events" % b
+
+
+def test_full_chain_narrow_rrc_sps20_mixed_frames(ctx, oracle):
+    """The chain of test_full_chain_narrow_rrc_sps20 on mixed frames (synth.nxdn_mixed_stream): every kind of Viterbi pass
+    behind the slicer, in one kernel and as two launches."""
+    accept = lambda d: oracle.nxdn_facch1(d)[0]
+    chans = []
+    for i, seed in enumerate((21, 22, 23)):
+        s, _, _ = synth.nxdn_mixed_stream(seed, 14, accept)
+        x = synth.shape(s, sps=20, taps=_taps.narrow())
+        chans.append(synth.impair(x, seed, snr_db=[None, 22, 16][i], dc=[0, 0.1, -0.2][i], delay=7 * i, gain=[1, 0.5, 1.7][i]))
+    n = min(len(c) for c in chans)
+    x = np.stack([c[:n] for c in chans])
+    ref = oracle.chain(x, rrc=2, sps=20, proto=3)
+    assert ref["out_count"].sum() > 0 and ref["event_count"].min() > 10      # (every channel locked and decoded frames)
+    for chunks in ([n], [4800, 12345]):
+        for split in (False, True):
+            res = run_engine(ctx, x, "nxdn", chunks, rrc="narrow", sps=20, split_stages=split)
+            assert_matches_oracle(res, ref, len(x), "nxdn mixed %s %s" % (chunks[:1], "split" if split else "chain"))
 
 
 def test_full_chain_narrow_rrc_sps20(ctx, oracle):
