@@ -221,19 +221,28 @@ def dmr_stream(seed, n_bursts, two_slots=True, cc=1, lead_in=37):
 YSF_SYNC = _hex_to_dibits("D471C9634D")           # decoder: ysf_phase.hpp:21
 
 
-def ysf_fich_dibits(frame_type, data_type, frame_number, frame_total=7):
-    """FICH word -> CRC16 -> 4x Golay(24,12) -> conv. code -> 5x20 interleave (decoder: fich.cpp:12-66)."""
-    word = (frame_type << 30) | (frame_number << 19) | (frame_total << 16) | (data_type << 8)
-    be = word.to_bytes(4, "big")
+def _ysf_fich_code(word):
+    """32-bit FICH word -> CRC16 -> 4x Golay(24,12) -> conv. code: the 100 dibits in codeword order (decoder: fich.cpp:20-49)."""
+    be = int(word).to_bytes(4, "big")
     bits = bytes_to_bits(be) + _bits_of(crc16_ccitt(be), 16)
     coded = []
     for i in range(4):
         coded += _bits_of(block_encode("golay_24_12", int("".join(map(str, bits[i * 12:(i + 1) * 12])), 2)), 24)
-    code = trellis_encode_bits(coded + [0, 0, 0, 0])
+    return trellis_encode_bits(coded + [0, 0, 0, 0])
+
+
+def ysf_fich_interleave(code):
+    """codeword order -> the order on the air, 5x20 (decoder: fich.cpp:12-19)."""
     tx = [0] * 100
     for i in range(100):
         tx[(i * 20) % 100 + (i * 20) // 100] = code[i]
     return tx
+
+
+def ysf_fich_dibits(frame_type, data_type, frame_number, frame_total=7):
+    """FICH word -> CRC16 -> 4x Golay(24,12) -> conv. code -> 5x20 interleave (decoder: fich.cpp:12-66)."""
+    word = (frame_type << 30) | (frame_number << 19) | (frame_total << 16) | (data_type << 8)
+    return ysf_fich_interleave(_ysf_fich_code(word))
 
 
 def _ysf_dch_code(data, nbytes):
@@ -301,8 +310,54 @@ def ysf_stream(seed, n_frames, mode="vd2", lead_in=53):
     return np.array(out, np.uint8)
 
 
+def ysf_mixed_stream(seed, n_frames, lead_in=53, loss=None, err=0.0, absent=2, force=None):
+    """Frames that walk the decoder's frame machine (ysf_phase.cpp:45-172) instead of one call shape.  Every frame draws
+
+    * its frame type 0..3 (3 is one the decoder ignores), its data type 0..3 and its frame number; the payload is built
+      for what was drawn (V/D2: DCH + five voice blocks, header / terminator: CSD1 + CSD2, otherwise random dibits);
+    * the state of its FICH: intact, replaced by random dibits (the previous FICH then governs the frame), or absent --
+      the first `absent` frames of the stream and after a loss carry random dibits there, so the decoder passes frames
+      before it has any FICH;
+    * a sync word with 0..5 wrong bits (more than three count against the sync, ysf_phase.cpp:16-18).
+
+    `loss` = (first frame, frames): that many frames from that index on are random dibits (signal lost).  `err`: share of
+    wrong dibits scattered over the result.  `force` = {frame index: {"frame_type" / "data_type" / "fich" / "sync_errors": value}}
+    replaces what that frame would have drawn.  Returns (dibits, one record per frame: start, frame_type, data_type,
+    frame_number, fich = "intact" / "random" / "absent" / "lost", sync_errors)."""
+    rng = np.random.default_rng(seed)
+    out = [int(d) for d in rng.integers(0, 4, lead_in)]
+    rec = []
+    since = 0                                               # frames since the start or the end of a loss
+    for n in range(n_frames):
+        r = {"start": len(out), "frame_type": -1, "data_type": -1, "frame_number": -1, "fich": "lost", "sync_errors": -1}
+        rec.append(r)
+        if loss is not None and loss[0] <= n < loss[0] + loss[1]:
+            out += [int(d) for d in rng.integers(0, 4, 480)]
+            since = 0
+            continue
+        ft = int(rng.choice(4, p=[0.14, 0.66, 0.1, 0.1]))
+        dt = int(rng.choice(4, p=[0.2, 0.12, 0.4, 0.28]))
+        fn = int(rng.integers(0, 8))
+        state = "absent" if since < absent else str(rng.choice(["intact", "random"], p=[0.8, 0.2]))
+        since += 1
+        k = int(rng.choice(6, p=[0.55, 0.07, 0.07, 0.11, 0.11, 0.09]))
+        f = (force or {}).get(n, {})
+        ft, dt, state, k = f.get("frame_type", ft), f.get("data_type", dt), f.get("fich", state), f.get("sync_errors", k)
+        fr = ysf_frame(rng, ft, dt, fn, corrupt_fich=state != "intact")
+        for bp in rng.choice(40, k, replace=False):
+            fr[bp // 2] ^= 2 >> (bp % 2)
+        r.update(frame_type=ft, data_type=dt, frame_number=fn, fich=state, sync_errors=k)
+        out += [int(d) for d in fr]
+    out += [int(d) for d in rng.integers(0, 4, 40)]
+    s = np.array(out, np.uint8)
+    if err > 0:
+        hit = rng.random(len(s)) < err
+        s[hit] ^= rng.integers(1, 4, int(hit.sum())).astype(np.uint8)
+    return s, rec
+
+
 # ----------------------------------------------------------------------------- NXDN48
-NXDN_SYNC = [3, 0, 3, 1, 3, 3, 1, 1, 2, 1]         # decoder: nxdn_phase.cpp:15-16
+NXDN_SYNC =[3, 0, 3, 1, 3, 3, 1, 1, 2, 1]         # decoder: nxdn_phase.cpp:15-16
 
 
 def nxdn_scramble(dibits):
