@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libdigiham_amd.so")
 DH_OK, DH_EINVAL, DH_ENOMEM, DH_EDEVICE, DH_ENODEV, DH_ECAPACITY = 0, -1, -2, -3, -4, -5
 RRC = {"none": 0, None: 0, "wide": 1, "narrow": 2, "custom": 3}
 DEMOD = {"none": 0, None: 0, "fsk": 2, "fsk2": 2, "gfsk": 4, "gfsk4": 4}
-PROTO = {"none": 0, None: 0, "dmr": 1, "ysf": 2, "nxdn": 3, "pocsag": 4, "dstar": 5}
+PROTO = {"none": 0, None: 0, "dmr": 1, "ysf": 2, "nxdn": 3, "pocsag": 4, "dstar": 5, "scan": 6}
 FLAG_FAST_FIR, FLAG_KEEP_FILTERED, FLAG_FSK_INVERT, FLAG_NO_EVENTS, FLAG_ORDERED_TIMING, FLAG_SPLIT_STAGES = 1, 2, 4, 8, 16, 32
 FLAG_EXACT_SYMBOLS, FLAG_EXACT_FIR, FLAG_OVERLAP_PUSHES, FLAG_ONE_LAUNCH = 64, 128, 256, 512
 
@@ -37,6 +37,11 @@ class ChannelizerPowerConfig(C.Structure):
                 ("hang_blocks", C.c_uint32), ("d_power", C.c_void_p), ("d_gate", C.c_void_p), ("d_counts", C.c_void_p),
                 ("stride", C.c_size_t)]
 
+
+# protocol scan (DH_PROTO_SCAN): the patterns in the order of DH_SCAN_*, dh_scan_stat, DH_EV_SCAN_HIT
+SCAN_PATTERNS = ("dmr_bs_data", "dmr_bs_voice", "dmr_ms_data", "dmr_ms_voice", "ysf", "nxdn", "dstar_header", "dstar_voice", "pocsag")
+SCAN_STAT_DTYPE = [("hits", "<u4"), ("periodic", "<u4"), ("last_sym", "<u4"), ("best_dist", "u1"), ("pad", "u1", (3,))]
+EV_SCAN_HIT = 80
 
 CZ_INPUT = {"cs16": 1, "cf32": 2}
 CZ_OUTPUT = {"iq": 1, "fm": 2}

@@ -390,6 +390,108 @@ class Engine:
         return out
 
 
+SCAN_STAT_DTYPE = np.dtype(_capi.SCAN_STAT_DTYPE)
+SCAN_PATTERNS = _capi.SCAN_PATTERNS
+# the four demodulator front ends the five protocols are received through (Engine arguments)
+SCAN_FRONTS = {"wide10": dict(rrc="wide", demod="gfsk", sps=10, invert=False),        # DMR, YSF
+               "narrow20": dict(rrc="narrow", demod="gfsk", sps=20, invert=False),    # NXDN48
+               "fsk10": dict(rrc="none", demod="fsk", sps=10, invert=False),          # D-Star
+               "fsk40i": dict(rrc="none", demod="fsk", sps=40, invert=True)}          # POCSAG 1200
+# the front end each pattern is read from, and the families classify() chooses between, in its order of preference
+SCAN_SOURCE = ("wide10",) * 5 + ("narrow20", "fsk10", "fsk10", "fsk40i")
+SCAN_FAMILIES = (("dmr", (0, 1, 2, 3)), ("ysf", (4,)), ("nxdn", (5,)), ("dstar", (6, 7)), ("pocsag", (8,)))
+
+
+class Scanner:
+    """Which protocol does each channel carry?  One protocol-scan engine (proto="scan", include/digiham_amd.h "Protocol
+    scan") per front end in `fronts`, all fed the same rows: what Channelizer.push returns, with its squelch-gated
+    `counts`, or any float32 [B][n] device array Engine.push takes.  Every engine counts, per channel, the hits of all nine
+    sync patterns and how many of them came one frame period behind an earlier hit of the same family.
+
+    stats() is a [B][9] array of SCAN_STAT_DTYPE (hits, periodic, last_sym, best_dist), each pattern read from the front
+    end that can receive it (SCAN_SOURCE); classify() names the family with the most periodic hits.
+
+    Why a single hit is not enough: a test passes on random symbols with probability sum_k C(n, k) / 2^n over the
+    distances k it accepts.  For NXDN (10 dibits = 20 bits, <= 2 errors) that is 211 / 2^20, about once in 5 000 positions
+    or once every two seconds of noise at 2 400 symbols per second; for DMR (48 bits, <= 3) it is about once in 10^10.
+    Two hits exactly one frame apart are what a transmission produces and noise does not: with a hit every 5 000
+    positions, a given period is met by chance once in 5 000 hits.  Requiring the period is what makes NXDN usable."""
+
+    def __init__(self, n_channels, max_samples, fronts=("wide10", "narrow20", "fsk10", "fsk40i"), ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        self.B, self.max_samples = n_channels, max_samples
+        self.fronts = tuple(fronts)
+        self.engines = {}
+        for f in self.fronts:
+            self.engines[f] = Engine(n_channels, max_samples, proto="scan", ctx=self.ctx, **SCAN_FRONTS[f])
+
+    def close(self):
+        for e in getattr(self, "engines", {}).values():
+            e.close()
+        self.engines = {}
+
+    __del__ = close
+
+    def reset(self):
+        for e in self.engines.values():
+            e.reset()
+
+    def reset_channel(self, ch):
+        for e in self.engines.values():
+            e.reset_channel(ch)
+
+    def push(self, x, n=None, counts=None):
+        """The same rows into every front end (Engine.push: float32 [B][stride], the first n samples, or counts[b] <= n)."""
+        mem = self.ctx.mem
+        if not mem.is_device_array(x):
+            x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(self.B, -1))
+        if counts is not None and not mem.is_device_array(counts):
+            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        for e in self.engines.values():
+            e.push(x, n=n, counts=counts)
+
+    def front_stats(self, front):
+        """[B][9] SCAN_STAT_DTYPE of one front end, all nine patterns (a channel that has not been pushed since its
+        reset: no hits, best_dist 255)."""
+        rows, counts = self.engines[front].frames()
+        out = np.zeros((self.B, len(SCAN_PATTERNS)), SCAN_STAT_DTYPE)
+        out["best_dist"] = 255
+        have = counts >= out.itemsize * len(SCAN_PATTERNS)
+        got = np.ascontiguousarray(rows[:, :out.itemsize * len(SCAN_PATTERNS)]).view(SCAN_STAT_DTYPE)
+        out[have] = got[have]
+        return out
+
+    def stats(self):
+        out = np.zeros((self.B, len(SCAN_PATTERNS)), SCAN_STAT_DTYPE)
+        out["best_dist"] = 255
+        for f in self.fronts:
+            ids = [i for i, src in enumerate(SCAN_SOURCE) if src == f]
+            if ids:
+                out[:, ids] = self.front_stats(f)[:, ids]
+        return out
+
+    def hits(self, channel):
+        """The DH_EV_SCAN_HIT events of the last push of one channel (EVENT_DTYPE: sym_index, a = pattern, b = distance),
+        each pattern from its own front end, ordered by position, then pattern.  A position counts the symbols of the
+        pattern's front end since create or reset."""
+        parts = []
+        for f in self.fronts:
+            ids = [i for i, src in enumerate(SCAN_SOURCE) if src == f]
+            rows, counts = self.engines[f].read_rows("events", [channel])
+            ev = rows[0, :counts[0]]
+            parts.append(ev[np.isin(ev["a"], ids)])
+        ev = np.concatenate(parts) if parts else np.zeros(0, EVENT_DTYPE)
+        return ev[np.lexsort((ev["a"], ev["sym_index"]))]
+
+    def classify(self, confirm=2):
+        """Per channel None or "dmr" / "ysf" / "nxdn" / "dstar" / "pocsag": the family whose patterns have the most periodic
+        hits, at least `confirm` of them; the first in that order where two are level."""
+        periodic = self.stats()["periodic"].astype(np.int64)
+        sums = np.stack([periodic[:, list(ids)].sum(axis=1) for _, ids in SCAN_FAMILIES], axis=1)
+        best = sums.argmax(axis=1)                       # (the first of equal sums)
+        return [SCAN_FAMILIES[k][0] if sums[b, k] >= confirm else None for b, k in enumerate(best)]
+
+
 def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0, interpolation=1):
     """Real low-pass prototype for Channelizer: a Kaiser-windowed sinc with its cut-off halfway between the pass- and
     stopband edges, the length and beta of Kaiser's estimates for `atten_db` of stopband attenuation, unity gain at DC.

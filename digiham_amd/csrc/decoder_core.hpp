@@ -168,12 +168,14 @@ struct DhState {
     }
     __device__ __forceinline__ void load(const uint32_t* g) { reg = threadIdx.x < DH_DEC_STATE_WORDS ? g[threadIdx.x] : 0u; }
     __device__ __forceinline__ void store(uint32_t* g) const { if (threadIdx.x < DH_DEC_STATE_WORDS) g[threadIdx.x] = reg; }
+    __device__ __forceinline__ void store_words(uint32_t* g, uint32_t first, uint32_t n) const { if (threadIdx.x - first < n) g[threadIdx.x - first] = reg; }     // words [first, first + n)
 #else
     uint32_t w[DH_DEC_STATE_WORDS];
     uint32_t get(uint32_t i) const { return w[i]; }
     void set(uint32_t i, uint32_t v) { w[i] = v; }
     void load(const uint32_t* g) { for (int i = 0; i < DH_DEC_STATE_WORDS; i++) w[i] = g[i]; }
     void store(uint32_t* g) const { for (int i = 0; i < DH_DEC_STATE_WORDS; i++) g[i] = w[i]; }
+    void store_words(uint32_t* g, uint32_t first, uint32_t n) const { for (uint32_t i = 0; i < n; i++) g[i] = w[first + i]; }
 #endif
     struct Ref {
         DhState* st; uint32_t i;
@@ -2630,5 +2632,143 @@ DH_HD void dh_dstar_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, u
     s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
     s[DS_CARRY] = rem < DH_DSTAR_CARRY_MAX ? rem : DH_DSTAR_CARRY_MAX;
     s.store(st_global);
+    DH_BARRIER();
+}
+
+// =============================================================================================
+// Protocol scan (DH_PROTO_SCAN; own specification, include/digiham_amd.h "Protocol scan"): no frame state machine.
+// EVERY symbol position is tested against the nine sync patterns the five decoders search for, with the decoders' own
+// predicates: one candidate position per lane, 64 positions per step, nine votes.  The hits of a step (rare: one per
+// frame on a signal, one per few thousand positions on noise) are then walked in order by scalar code, which keeps
+// the statistics and the period history in the state register.  Position p is examined in the push that brings symbol
+// p + DH_SCAN_SPAN - 1, whatever the pattern's length: the result does not depend on how the stream is cut.
+// =============================================================================================
+#define DH_SCAN_SPAN 32u                                 // symbols of the longest pattern (POCSAG's sync word)
+#define DH_SCAN_FAMILIES 5
+// distance limit of each pattern: dh_dmr_sync_type, dh_ysf_is_sync, dh_nxdn_is_sync_planes, dh_dstar_channel's SyncPhase, dh_pocsag_channel's
+DH_HD uint32_t dh_scan_limit(int id) { return id == DH_SCAN_NXDN || id == DH_SCAN_DSTAR_HEADER ? 2u : id == DH_SCAN_DSTAR_VOICE ? 1u : 3u; }
+DH_HD uint32_t dh_scan_family(int id) { return id <= DH_SCAN_DMR_MS_VOICE ? 0u : id == DH_SCAN_YSF ? 1u : id == DH_SCAN_NXDN ? 2u : id == DH_SCAN_POCSAG ? 4u : 3u; }
+// sync words one frame apart: a DMR burst is 144 dibits and a slot's next one 288, a YSF frame 480, an NXDN frame 192, a
+// D-Star superframe 21 x 96 bits, a POCSAG batch the sync word + 16 codewords of 32 bits
+DH_HD bool dh_scan_is_period(uint32_t family, uint32_t d) {
+    return family == 0u ? d == 144u || d == 288u : d == (family == 1u ? 480u : family == 2u ? 192u : family == 3u ? 2016u : 544u);
+}
+enum {
+    DS_SC_HCOUNT = 2,                 // remembered positions of the families: 2 bits each
+    DS_SC_HIST = 10,                  // [family][2]: the most recent hit position, the one before      (10 words)
+    DS_SC_STAT = 28                   // the nine dh_scan_stat records as they are delivered            (36 words)
+};
+static_assert((int) DS_SC_HIST > (int) DS_SLOT_FILTER && DS_SC_HIST + 2 * DH_SCAN_FAMILIES <= (int) DS_CONSUMED && (int) DS_SC_STAT > (int) DS_SLOT_FILTER_DECODER
+              && DS_SC_STAT + DH_SCAN_PATTERNS * 4 <= DH_DEC_STATE_WORDS, "scan state (the two slot filter words are set at reset)");
+static_assert(sizeof(dh_scan_stat) == 16, "dh_scan_stat");
+
+// the distances of the nine patterns at symbol `start` of the planes
+DH_HD void dh_scan_distances(const DhPlanes& p, int start, uint32_t d[DH_SCAN_PATTERNS]) {
+    const uint32_t h = dh_plane_range(p.h, start, 32), l = dh_plane_range(p.l, start, 32);
+    constexpr uint32_t SL = DH_DMR_SYNC_L, BD = DH_DMR_BS_DATA_H, BV = DH_DMR_BS_VOICE_H, MD = DH_DMR_MS_DATA_H, MV = DH_DMR_MS_VOICE_H;
+    constexpr uint32_t YH = DH_YSF_SYNC_H, YL = DH_YSF_SYNC_L, DHS = DH_DSTAR_HEADER_SYNC, DVS = DH_DSTAR_VOICE_SYNC;
+    constexpr uint32_t M24 = (1u << 24) - 1u, M20 = (1u << 20) - 1u, M10 = (1u << 10) - 1u;
+    const uint32_t h24 = h & M24, l24 = l & M24;
+    const uint32_t dl = (uint32_t) dh_popc32(l24 ^ SL), ph = (uint32_t) dh_popc32(h24);
+    d[DH_SCAN_DMR_BS_DATA] = (uint32_t) dh_popc32(h24 ^ BD) + dl;
+    d[DH_SCAN_DMR_BS_VOICE] = (uint32_t) dh_popc32(h24 ^ BV) + dl;
+    d[DH_SCAN_DMR_MS_DATA] = (uint32_t) dh_popc32(h24 ^ MD) + dl;
+    d[DH_SCAN_DMR_MS_VOICE] = (uint32_t) dh_popc32(h24 ^ MV) + dl;
+    d[DH_SCAN_YSF] = (uint32_t) (dh_popc32((h & M20) ^ YH) + dh_popc32((l & M20) ^ YL));
+    d[DH_SCAN_NXDN] = (uint32_t) (dh_popc32((h & M10) ^ DH_NXDN_SYNC_H) + dh_popc32((l & M10) ^ DH_NXDN_SYNC_L));
+    d[DH_SCAN_DSTAR_HEADER] = (uint32_t) dh_popc32(l24 ^ DHS) + ph;
+    d[DH_SCAN_DSTAR_VOICE] = (uint32_t) dh_popc32(l24 ^ DVS) + ph;
+    d[DH_SCAN_POCSAG] = (uint32_t) (dh_popc32(dh_brev32(l) ^ DH_POCSAG_SYNC) + dh_popc32(h));
+}
+
+DH_HD void dh_scan_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S) {
+    DhDecCtx c;
+    c.P = &P; c.T = nullptr;
+    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
+    DhState s; s.load(st_global);
+    c.st = &s;
+    c.out = P.out + (size_t) ch * P.out_stride;
+    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
+    c.nout = 0; c.nev = 0; c.overflow = false;
+    c.consumed = s[DS_CONSUMED];
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+    c.writer = threadIdx.x == 0;
+#else
+    c.writer = true;
+#endif
+    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
+    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride;
+    syms.nfresh = P.sym_count[ch]; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    const uint32_t total = syms.nc + syms.nfresh;
+    DH_FOR_LANES(lane) { for (uint32_t j = (uint32_t) lane; j < syms.nc; j += DH_WAVE) S.carry[j] = carry_buf[j]; }
+    DH_BARRIER();
+    for (int id = 0; id < DH_SCAN_PATTERNS; id++)                      // (a zeroed state: no hit yet)
+        if (s[DS_SC_STAT + 4 * id] == 0u) s[DS_SC_STAT + 4 * id + 3] = 255u;
+    uint32_t pos = 0;
+
+    for (;;) {
+        const uint32_t avail = total - pos;
+        if (avail < DH_SCAN_SPAN) break;
+        DhPlanes& pl = S.planes;
+        dh_view_ensure(syms, pos, 128);
+        dh_load_planes(syms, pos, total, pl, 2);
+        uint64_t m[DH_SCAN_PATTERNS];
+        for (int id = 0; id < DH_SCAN_PATTERNS; id++) m[id] = 0;
+        DH_FOR_LANES(lane) {
+            const bool valid = avail - (uint32_t) lane >= DH_SCAN_SPAN && avail > (uint32_t) lane;
+            uint32_t d[DH_SCAN_PATTERNS];
+            dh_scan_distances(pl, lane, d);
+            for (int id = 0; id < DH_SCAN_PATTERNS; id++) DH_BALLOT_ACC(m[id], valid && d[id] <= dh_scan_limit(id), lane);
+        }
+        uint64_t any = 0;
+        for (int id = 0; id < DH_SCAN_PATTERNS; id++) any |= m[id];
+        const uint32_t base = c.consumed;
+        while (any) {                                                  // the hits of this step, in order of position (scalar code)
+            const uint32_t l = (uint32_t) dh_ffs64(any);
+            any &= any - 1ull;
+            const uint32_t p = base + l;
+            uint32_t d[DH_SCAN_PATTERNS];
+            dh_scan_distances(pl, (int) l, d);
+            c.consumed = p;
+            const uint32_t hcount = s[DS_SC_HCOUNT];
+            uint32_t entered = 0;
+            for (int id = 0; id < DH_SCAN_PATTERNS; id++) {
+                if (!((m[id] >> l) & 1ull)) continue;
+                const uint32_t f = dh_scan_family(id), nh = (hcount >> (2u * f)) & 3u;
+                bool periodic = false;                                 // against the history before p, for every pattern at p
+                for (uint32_t k = 0; k < nh; k++) periodic = periodic || dh_scan_is_period(f, p - (uint32_t) s[DS_SC_HIST + 2u * f + k]);
+                const uint32_t w = (uint32_t) (DS_SC_STAT + 4 * id);
+                s[w] = (uint32_t) s[w] + 1u;
+                if (periodic) s[w + 1u] = (uint32_t) s[w + 1u] + 1u;
+                s[w + 2u] = p;
+                if (d[id] < (uint32_t) s[w + 3u]) s[w + 3u] = d[id];
+                dh_emit_w(c, DH_EV_SCAN_HIT, (uint32_t) id, d[id], 0);
+                entered |= 1u << f;
+            }
+            for (uint32_t f = 0; f < DH_SCAN_FAMILIES; f++) {          // then p enters the history of its families, once
+                if (!((entered >> f) & 1u)) continue;
+                const uint32_t nh = (s[DS_SC_HCOUNT] >> (2u * f)) & 3u;
+                s[DS_SC_HIST + 2u * f + 1u] = s[DS_SC_HIST + 2u * f];
+                s[DS_SC_HIST + 2u * f] = p;
+                if (nh < 2u) s[DS_SC_HCOUNT] = (uint32_t) s[DS_SC_HCOUNT] + (1u << (2u * f));
+            }
+        }
+        const uint32_t adv = dh_min<uint32_t>(64u, avail - (DH_SCAN_SPAN - 1u));
+        pos += adv; c.consumed = base + adv;
+    }
+
+    const uint32_t rem = total - pos;                                  // < DH_SCAN_SPAN
+    dh_view_ensure(syms, pos, rem);
+    DH_FOR_LANES(lane) {
+        for (uint32_t j = lane; j < rem; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
+        if (DH_IS_LANE0(lane)) {
+            P.out_count[ch] = (uint32_t) (DH_SCAN_PATTERNS * sizeof(dh_scan_stat));
+            if (P.ev_count) P.ev_count[ch] = c.nev;
+            if (c.overflow && P.overflow) *P.overflow = 1u;
+        }
+    }
+    s[DS_CONSUMED] = c.consumed; s[DS_CARRY] = rem;
+    s.store(st_global);
+    s.store_words(reinterpret_cast<uint32_t*>(c.out), DS_SC_STAT, DH_SCAN_PATTERNS * 4);      // the statistics row, rewritten by every push
     DH_BARRIER();
 }

@@ -221,6 +221,12 @@ __global__ __launch_bounds__(DH_WAVE) void k_pocsag(const DhDecParams P) {
     dh_pocsag_channel(P, blockIdx.x, S);
 }
 
+// protocol scan: nine sync tests at every symbol position, no frame state machine (decoder_core.hpp, dh_scan_channel)
+__global__ __launch_bounds__(DH_WAVE) void k_scan(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_scan_channel(P, blockIdx.x, S);
+}
+
 #define DH_DSTAR_LB 4
 __global__ __launch_bounds__(DH_WAVE, DH_DSTAR_LB) void k_dstar(const DhDecParams P) {
     __shared__ DhDecShared S;
@@ -858,6 +864,7 @@ struct HipBackend {
         else if (proto == DH_PROTO_YSF) hipLaunchKernelGGL(k_ysf, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
         else if (proto == DH_PROTO_NXDN) hipLaunchKernelGGL(k_nxdn, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
         else if (proto == DH_PROTO_POCSAG) hipLaunchKernelGGL(k_pocsag, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
+        else if (proto == DH_PROTO_SCAN) hipLaunchKernelGGL(k_scan, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
         else hipLaunchKernelGGL(k_dstar, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
         return launched("k_decoder");
     }

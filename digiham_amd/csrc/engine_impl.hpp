@@ -48,7 +48,7 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
         if (!(c.rrc_gain == c.rrc_gain) || c.rrc_gain == 0.0 || (c.flags & DH_FLAG_FAST_FIR)) return DH_EINVAL;      // exact arithmetic only
     }
     if (c.demod != DH_DEMOD_NONE && c.demod != DH_DEMOD_FSK2 && c.demod != DH_DEMOD_GFSK4) return DH_EINVAL;
-    if (c.proto < DH_PROTO_NONE || c.proto > DH_PROTO_DSTAR) return DH_EINVAL;
+    if (c.proto < DH_PROTO_NONE || c.proto > DH_PROTO_SCAN) return DH_EINVAL;
     if (c.demod != DH_DEMOD_NONE && (c.sps < 3 || c.sps > DH_MAX_SPS)) return DH_EINVAL;
     if (c.demod == DH_DEMOD_NONE && c.rrc == DH_RRC_NONE && c.proto == DH_PROTO_NONE) return DH_EINVAL;
     L.B = c.n_channels; L.max_samples = c.max_samples; L.sps = c.demod ? c.sps : 1;
@@ -76,6 +76,7 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
     else if (L.proto == DH_PROTO_NXDN) { L.out_cap = (max_syms / 192 + 1) * 36; L.ev_cap = (max_syms / 192 + 1) * 7 + 8; }
     else if (L.proto == DH_PROTO_POCSAG) { L.out_cap = max_syms / 2 + 256; L.ev_cap = max_syms / 32 + 8; }
     else if (L.proto == DH_PROTO_DSTAR) { L.out_cap = (max_syms / 96 + 1) * 9; L.ev_cap = max_syms / 32 + 16; }
+    else if (L.proto == DH_PROTO_SCAN) { L.out_cap = DH_SCAN_PATTERNS * sizeof(dh_scan_stat); L.ev_cap = max_syms / 16 + 16; }
     else { L.out_cap = 0; L.ev_cap = 0; }
     L.out_cap = round_up(L.out_cap, 64);
     return DH_OK;

@@ -58,7 +58,7 @@ template <class Go> int dh_plan_rrc_tiles(uint32_t nz, bool fast, Go&& go) {
     return -1;
 }
 
-// The decoder of one channel; sym_base / append are the tail split's (POCSAG is never chained and takes neither).
+// The decoder of one channel; sym_base / append are the tail split's (POCSAG and the protocol scan are never chained and take neither).
 // k_chain keeps its own four-way switch and its own part bounds (below): stated through these functions the NXDN chain
 // kernels allocate registers differently, and the device code is not this header's to change.
 DH_HD void dh_decode_channel(int proto, const DhDecParams& D, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
@@ -66,6 +66,7 @@ DH_HD void dh_decode_channel(int proto, const DhDecParams& D, uint32_t ch, DhDec
     else if (proto == DH_PROTO_DSTAR) dh_dstar_channel(D, ch, S, sym_base, append);
     else if (proto == DH_PROTO_NXDN) dh_nxdn_channel(D, ch, S, sym_base, append);
     else if (proto == DH_PROTO_POCSAG) dh_pocsag_channel(D, ch, S);
+    else if (proto == DH_PROTO_SCAN) dh_scan_channel(D, ch, S);
     else dh_ysf_channel(D, ch, S, sym_base, append);
 }
 

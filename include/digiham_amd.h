@@ -98,7 +98,8 @@ typedef struct dh_engine dh_engine;
 enum { DH_RRC_NONE = 0, DH_RRC_WIDE = 1, DH_RRC_NARROW = 2,
        DH_RRC_CUSTOM = 3 };   /* the caller's coefficient table: RrcFilter(nZeros, gain, coeffs[]), include/rrc_filter.hpp:12 */
 enum { DH_DEMOD_NONE = 0, DH_DEMOD_FSK2 = 2, DH_DEMOD_GFSK4 = 4 };
-enum { DH_PROTO_NONE = 0, DH_PROTO_DMR = 1, DH_PROTO_YSF = 2, DH_PROTO_NXDN = 3, DH_PROTO_POCSAG = 4, DH_PROTO_DSTAR = 5 };
+enum { DH_PROTO_NONE = 0, DH_PROTO_DMR = 1, DH_PROTO_YSF = 2, DH_PROTO_NXDN = 3, DH_PROTO_POCSAG = 4, DH_PROTO_DSTAR = 5,
+       DH_PROTO_SCAN = 6 };   /* no decoder: the sync words of all five protocols, counted ("Protocol scan" below) */
 
 /* flags */
 #define DH_FLAG_FAST_FIR        0x1   /* FMA FIR: float outputs within 1e-6 of the reference, dibits NOT guaranteed bit-exact */
@@ -180,8 +181,51 @@ enum {
      * (:113): the consumer now parses its simple-data lines (DPRS / NMEA, :218-245); META_RESET = MetaCollector::reset
      * (b = 0 terminator, 1 sync lost) */
     DH_EV_DSTAR_HEADER = 64, DH_EV_DSTAR_VOICE_START = 65, DH_EV_DSTAR_SYNC_VOICE = 66, DH_EV_DSTAR_MESSAGE = 67,
-    DH_EV_DSTAR_SIMPLE = 68, DH_EV_DSTAR_FRAME_SYNC = 69, DH_EV_DSTAR_META_RESET = 70
+    DH_EV_DSTAR_SIMPLE = 68, DH_EV_DSTAR_FRAME_SYNC = 69, DH_EV_DSTAR_META_RESET = 70,
+    /* protocol scan: a sync pattern found (sym_index = its first symbol, a = DH_SCAN_* pattern, b = distance, len = 0) */
+    DH_EV_SCAN_HIT = 80
 };
+
+/* ----------------------------------------------------------------------
+ * Protocol scan (DH_PROTO_SCAN): which protocol does a channel carry?  Own specification; the reference has no
+ * counterpart (there one person picks one mode for one channel).  The decoder stage of such an engine is a free-running
+ * correlator with no frame state machine: behind whatever front end the engine was created with, EVERY symbol position
+ * is tested against the nine sync patterns the five decoders search for, with the decoders' own tests:
+ *
+ *   DH_SCAN_DMR_BS_DATA .. DH_SCAN_DMR_MS_VOICE   24 dibits   distance <= 3   Dmr::SyncPhase (dmr_phase.cpp:18-33), each of the four on its own
+ *   DH_SCAN_YSF                                   20 dibits   distance <= 3   ysf_phase.cpp:16-18
+ *   DH_SCAN_NXDN                                  10 dibits   distance <= 2   nxdn_phase.cpp:21
+ *   DH_SCAN_DSTAR_HEADER                          24 bits     distance <= 2   dstar_phase.cpp:17-34
+ *   DH_SCAN_DSTAR_VOICE                           24 bits     distance <= 1   dstar_phase.cpp:17-34 (also where the header pattern hits)
+ *   DH_SCAN_POCSAG                                32 bits     distance <= 3   pocsag_phase.cpp:18-28
+ *
+ * The distance is the number of differing bits; against a pattern of bits a symbol 2 or 3 counts one more.  All nine are
+ * tested whatever the front end; there is no configuration word.
+ *
+ * Positions.  p counts the channel's symbols since create or reset, modulo 2^32.  Position p is examined, for all nine
+ * patterns, in the push that brings symbol p + 31, and never again: at most 31 symbols are carried between pushes, and
+ * the last 31 positions of a stream stay unexamined until more symbols arrive.  Nothing depends on how the stream is
+ * cut into pushes.
+ *
+ * Events.  A hit is one dh_event: type DH_EV_SCAN_HIT, sym_index = p, a = pattern, b = distance, len = 0; in ascending p,
+ * then ascending pattern.  When the event row is full the push reports DH_ECAPACITY and the events are truncated; the
+ * statistics still count every hit.
+ *
+ * Statistics.  The "frames" row of the channel (dh_engine_frames / dh_engine_read_frames: 144 bytes) holds
+ * dh_scan_stat[DH_SCAN_PATTERNS], cumulative since create or reset and rewritten by every push: hits, the hits that
+ * were periodic, the position of the last hit, the smallest distance seen (255 before the first hit).
+ *
+ * Periodic hits.  The patterns form five families with the distances, in symbols, between sync words of a running
+ * transmission: DMR (the four DMR patterns) {144, 288}; YSF {480}; NXDN {192}; D-Star (header, voice) {2016} -- 21
+ * frames of 96 bits; POCSAG {544} -- the sync word and 16 codewords.  Every family remembers the two most recent
+ * distinct positions at which one of its patterns hit.  A hit at p counts as periodic when p - q (unsigned) is one of
+ * the family's distances for a remembered q; all patterns that hit at p are judged against the positions before p, then
+ * p is remembered, once.  A single hit says little -- the NXDN test passes on random dibits about once in 5 000
+ * positions -- a hit one frame behind another says a lot.
+ * ---------------------------------------------------------------------- */
+enum { DH_SCAN_DMR_BS_DATA = 0, DH_SCAN_DMR_BS_VOICE = 1, DH_SCAN_DMR_MS_DATA = 2, DH_SCAN_DMR_MS_VOICE = 3, DH_SCAN_YSF = 4,
+       DH_SCAN_NXDN = 5, DH_SCAN_DSTAR_HEADER = 6, DH_SCAN_DSTAR_VOICE = 7, DH_SCAN_POCSAG = 8, DH_SCAN_PATTERNS = 9 };
+typedef struct { uint32_t hits, periodic, last_sym; uint8_t best_dist, pad[3]; } dh_scan_stat;
 
 int  dh_engine_create(const dh_engine_config* cfg, dh_engine** out);
 void dh_engine_destroy(dh_engine* e);
