@@ -38,6 +38,13 @@ class ChannelizerPowerConfig(C.Structure):
                 ("stride", C.c_size_t)]
 
 
+class PrerollConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("depth", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
+PREROLL_NONE = 0xFFFFFFFFFFFFFFFF          # DH_PREROLL_NONE
+
 # protocol scan (DH_PROTO_SCAN): the patterns in the order of DH_SCAN_*, dh_scan_stat, DH_EV_SCAN_HIT
 SCAN_PATTERNS = ("dmr_bs_data", "dmr_bs_voice", "dmr_ms_data", "dmr_ms_voice", "ysf", "nxdn", "dstar_header", "dstar_voice", "pocsag")
 SCAN_STAT_DTYPE = [("hits", "<u4"), ("periodic", "<u4"), ("last_sym", "<u4"), ("best_dist", "u1"), ("pad", "u1", (3,))]
@@ -102,6 +109,10 @@ def declare(L, lenient=False):
         "dh_channelizer_power_enable": [vp, C.POINTER(ChannelizerPowerConfig)],
         "dh_channelizer_set_squelch": [vp, C.c_float, C.c_float, u32],
         "dh_channelizer_power_last": [vp, C.POINTER(C.c_uint64), C.POINTER(sz)],
+        "dh_preroll_create": [C.POINTER(PrerollConfig), C.POINTER(vp)],
+        "dh_preroll_reset": [vp], "dh_preroll_append": [vp, vp, sz, sz, vp],
+        "dh_preroll_total": [vp, C.POINTER(C.c_uint64)], "dh_preroll_open_at": [vp, vp],
+        "dh_preroll_gather": [vp, vp, C.c_uint64, sz, vp, sz, vp, vp],
     }
     for name, args in sig.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
@@ -111,9 +122,10 @@ def declare(L, lenient=False):
         fn.restype = C.c_int
     L.dh_engine_destroy.argtypes = [vp]
     L.dh_engine_destroy.restype = None
-    if hasattr(L, "dh_channelizer_destroy"):
-        L.dh_channelizer_destroy.argtypes = [vp]
-        L.dh_channelizer_destroy.restype = None
+    for name in ("dh_channelizer_destroy", "dh_preroll_destroy"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [vp]
+            getattr(L, name).restype = None
     return L
 
 
@@ -129,6 +141,8 @@ EXPORTED_SYMBOLS = [
     "dh_channelizer_create", "dh_channelizer_destroy", "dh_channelizer_reset", "dh_channelizer_retune", "dh_channelizer_push",
     "dh_channelizer_push_host", "dh_channelizer_phasor", "dh_channelizer_power_enable", "dh_channelizer_set_squelch",
     "dh_channelizer_power_last",
+    "dh_preroll_create", "dh_preroll_destroy", "dh_preroll_reset", "dh_preroll_append", "dh_preroll_total", "dh_preroll_open_at",
+    "dh_preroll_gather",
 ]
 
 _LIB = None

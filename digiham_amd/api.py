@@ -400,6 +400,8 @@ SCAN_FRONTS = {"wide10": dict(rrc="wide", demod="gfsk", sps=10, invert=False),  
 # the front end each pattern is read from, and the families classify() chooses between, in its order of preference
 SCAN_SOURCE = ("wide10",) * 5 + ("narrow20", "fsk10", "fsk10", "fsk40i")
 SCAN_FAMILIES = (("dmr", (0, 1, 2, 3)), ("ysf", (4,)), ("nxdn", (5,)), ("dstar", (6, 7)), ("pocsag", (8,)))
+# the front end a protocol's decoder sits behind: the one its sync patterns are read from
+PROTO_FRONT = {"dmr": "wide10", "ysf": "wide10", "nxdn": "narrow20", "dstar": "fsk10", "pocsag": "fsk40i"}
 
 
 class Scanner:
@@ -490,6 +492,238 @@ class Scanner:
         sums = np.stack([periodic[:, list(ids)].sum(axis=1) for _, ids in SCAN_FAMILIES], axis=1)
         best = sums.argmax(axis=1)                       # (the first of equal sums)
         return [SCAN_FAMILIES[k][0] if sums[b, k] >= confirm else None for b, k in enumerate(best)]
+
+
+PREROLL_NONE = _capi.PREROLL_NONE
+
+
+def _float_rows(mem, x, B, what):
+    """(array, row stride) of float32 [B][n] rows the library can read where they are: a device array whose rows are
+    contiguous -- a column slice of a wider array included, rows need no alignment -- or a copy of anything else."""
+    torch = getattr(mem, "torch", None)
+    if torch is not None and torch.is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != B or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise ValueError("%s: need a float32 [%d][n] device array with contiguous rows, got %s %s strides %s"
+                             % (what, B, x.dtype, tuple(x.shape), tuple(x.stride())))
+        if x.device.index != mem.index:
+            raise ValueError("%s: the array lives on cuda:%s, the handle on cuda:%s" % (what, x.device.index, mem.index))
+        return x, (x.stride(0) if B > 1 else x.shape[1])
+    in_place = torch is None and isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.shape[0] == B and \
+        (x.shape[1] <= 1 or x.strides[1] == 4) and (B == 1 or (x.strides[0] > 0 and x.strides[0] % 4 == 0))
+    if not in_place:
+        x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(B, -1))
+    if callable(getattr(x, "stride", None)):
+        return x, (x.stride(0) if B > 1 else x.shape[1])
+    return x, (x.strides[0] // 4 if B > 1 else x.shape[1])
+
+
+class Preroll:
+    """Every channel's last `depth` samples in a ring on the device (dh_preroll; include/digiham_amd.h "Pre-roll"), and
+    for every channel the stream index at which its current run of open pushes began.
+
+    append(rows, n, counts) takes what Channelizer.push returns and cz.counts; gather(from_, skip, max_n) hands back,
+    per channel, the samples from max(from_[b], oldest) + skip on as (rows, counts, start): rows and counts are device
+    arrays, exactly what Engine.push(rows, n=max_n, counts=counts) takes.  The counts array is the handle's own and is
+    rewritten by the next gather.  The ring takes n_channels x depth x 4 bytes."""
+
+    def __init__(self, n_channels, depth, ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        lib, mem = self.ctx.lib, self.ctx.mem
+        self.B, self.depth = int(n_channels), int(depth)
+        cfg = _capi.PrerollConfig(C.sizeof(_capi.PrerollConfig), getattr(mem, "index", 0), self.B, self.depth, mem.stream())
+        h = C.c_void_p()
+        _check(lib.dh_preroll_create(C.byref(cfg), C.byref(h)), "dh_preroll_create", lib)
+        self._h = h
+        self._counts = mem.zeros((self.B,), np.uint32)
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx.lib.dh_preroll_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        _check(self.ctx.lib.dh_preroll_reset(self._h), "dh_preroll_reset", self.ctx.lib)
+
+    def append(self, rows, n=None, counts=None):
+        """rows: float32 [B][stride]; the first n samples of every row (default: all).  counts: [B] uint32, non-zero = the
+        channel's gate was open in this push; None = every channel is open."""
+        mem = self.ctx.mem
+        x, stride = _float_rows(mem, rows, self.B, "Preroll.append")
+        n = x.shape[1] if n is None else int(n)
+        c = None
+        if counts is not None:
+            c = counts if mem.is_device_array(counts) else mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        self._keep = (x, c)         # the launch is asynchronous: keep the inputs alive
+        _check(self.ctx.lib.dh_preroll_append(self._h, mem.ptr(x), stride, n, mem.ptr(c) if c is not None else None),
+               "dh_preroll_append", self.ctx.lib)
+
+    @property
+    def total(self):
+        t = C.c_uint64(0)
+        _check(self.ctx.lib.dh_preroll_total(self._h, C.byref(t)), "dh_preroll_total", self.ctx.lib)
+        return t.value
+
+    def open_at(self):
+        """[B] uint64: PREROLL_NONE for a channel whose gate was closed in the last push.  Synchronises."""
+        out = np.empty(self.B, np.uint64)
+        _check(self.ctx.lib.dh_preroll_open_at(self._h, out.ctypes.data_as(C.c_void_p)), "dh_preroll_open_at", self.ctx.lib)
+        return out
+
+    def gather(self, from_, skip, max_n, out=None):
+        """from_: [B] stream indices, PREROLL_NONE for channels that are not wanted.  Returns (rows [B][>= max_n] device
+        float32 -- `out` if given --, counts [B] device uint32, start [B] numpy uint64)."""
+        mem = self.ctx.mem
+        f = np.ascontiguousarray(from_, np.uint64)
+        if f.shape != (self.B,):
+            raise ValueError("Preroll.gather: from_ needs %d entries" % self.B)
+        max_n = int(max_n)
+        if out is None:
+            out = mem.zeros((self.B, max(max_n, 1)), np.float32)
+        rows, stride = _float_rows(mem, out, self.B, "Preroll.gather")
+        if rows is not out:
+            raise ValueError("Preroll.gather: out must be a float32 [%d][n] device array with contiguous rows" % self.B)
+        start = np.empty(self.B, np.uint64)
+        _check(self.ctx.lib.dh_preroll_gather(self._h, f.ctypes.data_as(C.c_void_p), int(skip), max_n, mem.ptr(rows), stride,
+                                              mem.ptr(self._counts), start.ctypes.data_as(C.c_void_p)), "dh_preroll_gather", self.ctx.lib)
+        return rows, self._counts, start
+
+
+class Monitor:
+    """A band monitor over the rows of a channelizer: one Scanner names the protocol an open channel carries, one Preroll
+    keeps every channel's recent past, and one Engine per protocol in `protos` (behind the front end of PROTO_FRONT)
+    decodes a named channel FROM WHERE ITS SQUELCH OPENED -- `lead` samples earlier, as far as the ring reaches -- not from
+    where the scanner made up its mind.  The monitor does not own the channelizer:
+
+        blocks = mon.push(*cz.push(iq), counts=cz.counts)
+
+    is the whole receiver.  `counts` is read as a flag per channel (non-zero: open, and the channel brings all n samples);
+    None means every channel is open.  One round:
+
+      1. n == 0 returns [].
+      2. The ring appends the rows; a channel is closed in this round when its open_at is PREROLL_NONE.
+      3. An unassigned channel that closed in this round has its scanner state reset; an assigned channel closed for
+         `release` rounds in a row becomes unassigned.
+      4. The scanner sees the open, unassigned channels only; names = classify(confirm).
+      5. An open, unassigned channel with a name is assigned: start = max(open_at - lead, total - depth, 0), the channel
+         is reset in its engine and in the scanner, and the ring is replayed from start into the engine in chunks of
+         max_samples.  The ring already holds this round's samples, so the channel gets no live push in this round.
+      6. Every engine gets one ragged push of the rows for the channels assigned before this round and open now.
+      7. The outputs come back as blocks ordered by channel, then by stream position: dicts with `channel`, `proto`,
+         `first_sample` (stream index of the block's first input sample), `frames` (uint8) and `events` (EVENT_DTYPE).
+         A push that produced neither frames nor events for a channel makes no block.  (Read with Engine.read_rows;
+         from a sixteenth of the channels on, with frames() / events() whole.)
+
+    `assigned[b]` is None or the protocol's name, `start[b]` the stream index where the decoder's input began.
+
+    Known limit: a transmission that ends before the scanner has confirmed it is never decoded -- a single POCSAG batch,
+    a D-Star transmission shorter than three sync periods.  (Lowering `confirm` per family is a later question.)"""
+
+    def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
+        self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
+        self.protos = tuple(protos)
+        self.engines = {}
+        self.scanner = Scanner(self.B, self.max_samples, fronts=tuple(dict.fromkeys(PROTO_FRONT[p] for p in self.protos)), ctx=self.ctx)
+        self.pre = Preroll(self.B, self.depth, ctx=self.ctx)
+        self.stage = self.ctx.mem.zeros((self.B, self.max_samples), np.float32)
+        for p in self.protos:
+            self.engines[p] = Engine(self.B, self.max_samples, proto=p, ctx=self.ctx, **SCAN_FRONTS[PROTO_FRONT[p]])
+        self._clear()
+
+    def _clear(self):
+        self.assigned = [None] * self.B
+        self.start = [None] * self.B
+        self.closed_run = np.zeros(self.B, np.int64)
+
+    def close(self):
+        for e in getattr(self, "engines", {}).values():
+            e.close()
+        self.engines = {}
+        for h in ("scanner", "pre"):
+            if getattr(self, h, None) is not None:
+                getattr(self, h).close()
+                setattr(self, h, None)
+
+    __del__ = close
+
+    def reset(self):
+        self.scanner.reset()
+        self.pre.reset()
+        for e in self.engines.values():
+            e.reset()
+        self._clear()
+
+    def _collect(self, name, channels, first_sample, blocks):
+        eng = self.engines[name]
+        if 16 * len(channels) >= self.B:                 # many rows: two whole arrays cost less than a copy per row (~17 us each on an MI355X)
+            (frames, fc), (events, ec) = eng.frames(), eng.events()
+            frames, fc, events, ec = frames[channels], fc[channels], events[channels], ec[channels]
+        else:
+            frames, fc = eng.read_rows("frames", channels)
+            events, ec = eng.read_rows("events", channels)
+        for j, b in enumerate(channels):
+            if fc[j] or ec[j]:
+                blocks.append({"channel": b, "proto": name, "first_sample": int(first_sample[j]),
+                               "frames": frames[j, :fc[j]].copy(), "events": events[j, :ec[j]].copy()})
+
+    def push(self, rows, n=None, counts=None):
+        mem = self.ctx.mem
+        x, _ = _float_rows(mem, rows, self.B, "Monitor.push")
+        n = x.shape[1] if n is None else int(n)
+        if n == 0:
+            return []
+        if n > self.max_samples:
+            raise DhError(_capi.DH_EINVAL, "Monitor.push", "n = %d > max_samples = %d" % (n, self.max_samples))
+        if counts is not None and not mem.is_device_array(counts):
+            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        self.pre.append(x, n, counts)
+        open_at, total = self.pre.open_at(), self.pre.total
+        is_open = open_at != np.uint64(PREROLL_NONE)
+        self.closed_run = np.where(is_open, 0, self.closed_run + 1)
+        for b in np.flatnonzero(~is_open):
+            if self.assigned[b] is None:
+                if self.closed_run[b] == 1:
+                    self.scanner.reset_channel(int(b))
+            elif self.closed_run[b] >= self.release:
+                self.assigned[b], self.start[b] = None, None
+        before = list(self.assigned)
+        scan = np.array([n if is_open[b] and before[b] is None else 0 for b in range(self.B)], np.uint32)
+        new = {}
+        if scan.any():                                   # (a push of all-zero counts would change nothing)
+            self.scanner.push(x, n=n, counts=scan)
+            names = self.scanner.classify(self.confirm)
+            for b in np.flatnonzero(scan):
+                if names[b] in self.engines:
+                    new.setdefault(names[b], []).append(int(b))
+        blocks = []
+        for name, chans in new.items():
+            eng = self.engines[name]
+            from_ = np.full(self.B, PREROLL_NONE, np.uint64)
+            for b in chans:
+                self.start[b] = max(int(open_at[b]) - self.lead, total - self.depth, 0)
+                self.assigned[b] = name
+                eng.reset_channel(b)
+                self.scanner.reset_channel(b)
+                from_[b] = self.start[b]
+            first = np.array([self.start[b] for b in chans], np.int64)
+            for skip in range(0, total - int(first.min()), self.max_samples):
+                stage, cnt, _ = self.pre.gather(from_, skip, self.max_samples, out=self.stage)
+                eng.push(stage, n=self.max_samples, counts=cnt)
+                self._collect(name, chans, first + skip, blocks)
+        for name, eng in self.engines.items():
+            chans = [b for b in range(self.B) if before[b] == name and is_open[b]]
+            if chans:
+                live = np.zeros(self.B, np.uint32)
+                live[chans] = n
+                eng.push(x, n=n, counts=live)
+                self._collect(name, chans, np.full(len(chans), total - n, np.int64), blocks)
+        blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
+        return blocks
 
 
 def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0, interpolation=1):

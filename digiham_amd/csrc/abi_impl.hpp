@@ -458,3 +458,120 @@ int dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n) {
 }
 
 }  // extern "C"
+
+// ---- the pre-roll ring (preroll_core.hpp): host bookkeeping over the backend's memory and two launches ---------------
+//   dh_be_preroll_append(const DhPrAppend& A, void* stream);
+//   dh_be_preroll_gather(const DhPrGather& G, void* stream);
+// (engine.hip defines the gfx950 ones; preroll_core.hpp the CPU harness's.)  `total` is the host's: every position a
+// launch needs is reduced mod depth here.
+struct dh_preroll {
+    DH_BACKEND be;
+    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
+    void* stream = nullptr;
+    uint32_t B = 0, depth = 0;
+    uint64_t total = 0;
+    uint32_t* d_ring = nullptr;                         // [B][depth]
+    uint64_t* d_open = nullptr;                         // [B]
+    uint64_t* d_from = nullptr;                         // [B]: a gather's h_from
+    std::vector<uint64_t> none;                         // [B] x DH_PREROLL_NONE: what a reset uploads
+
+    auto scope() const { return be.scope(); }
+    void release() { bufs.free_all(); }
+    uint64_t oldest() const { return total > depth ? total - depth : 0; }
+    int clear() {
+        total = 0;
+        if (be.upload(d_open, none.data(), sizeof(uint64_t) * B)) return DH_EDEVICE;        // (the ring needs no clearing: nothing before
+        return be.sync() ? DH_EDEVICE : DH_OK;                                              // sample 0 is ever read)
+    }
+    int init(const dh_preroll_config& c) {
+        B = c.n_channels; depth = c.depth;
+        none.assign(B, DH_PREROLL_NONE);
+        bool ok = bufs.alloc(d_ring, (size_t) B * depth);
+        ok &= bufs.alloc(d_open, B);
+        ok &= bufs.alloc(d_from, B);
+        return ok ? clear() : DH_ENOMEM;
+    }
+    int append(const float* rows, size_t stride, size_t n, const uint32_t* counts) {
+        if (!n) return DH_OK;
+        if (!rows || stride < n) return DH_EINVAL;
+        DhPrAppend A{};
+        A.ring = d_ring; A.open_at = d_open; A.rows = (const uint32_t*) rows; A.stride = stride; A.counts = counts;
+        A.B = B; A.depth = depth; A.base = total;
+        A.n = (uint32_t) std::min<size_t>(n, depth);
+        A.rows += n - A.n;                              // n > depth: the last depth samples of every row
+        A.w0 = (uint32_t) ((total + (n - A.n)) % depth);
+        if (dh_be_preroll_append(A, stream)) return DH_EDEVICE;
+        total += n;
+        return DH_OK;
+    }
+    int gather(const uint64_t* from, uint64_t skip, size_t max_n, float* out, size_t out_stride, uint32_t* counts, uint64_t* h_start) {
+        if (out_stride < max_n || (max_n && (!from || !out || !counts))) return DH_EINVAL;
+        if (h_start && from)
+            for (uint32_t b = 0; b < B; b++) h_start[b] = from[b] == DH_PREROLL_NONE ? DH_PREROLL_NONE : dh_pr_start(from[b], oldest());
+        if (!max_n) return counts && be.zero(counts, sizeof(uint32_t) * B) ? DH_EDEVICE : DH_OK;
+        if (be.upload(d_from, from, sizeof(uint64_t) * B)) return DH_EDEVICE;
+        DhPrGather G{};
+        G.ring = d_ring; G.from = d_from; G.out = (uint32_t*) out; G.out_stride = out_stride; G.counts = counts;
+        G.B = B; G.depth = depth; G.max_n = (uint32_t) std::min<size_t>(max_n, depth);      // (no channel holds more)
+        G.total = total; G.oldest = oldest(); G.skip = skip; G.r0 = (uint32_t) (G.oldest % depth);
+        return dh_be_preroll_gather(G, stream) ? DH_EDEVICE : DH_OK;
+    }
+};
+
+extern "C" {
+
+int dh_preroll_create(const dh_preroll_config* cfg, dh_preroll** out) {
+    if (!cfg || !out) return DH_EINVAL;
+    *out = nullptr;
+    if (cfg->struct_size < sizeof(dh_preroll_config) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->depth < 1 ||
+        cfg->depth > (1u << 24))
+        return DH_EINVAL;
+    dh_preroll* p = new (std::nothrow) dh_preroll;
+    if (!p) return DH_ENOMEM;
+    int rc = p->be.open(cfg->device, cfg->stream);
+    if (rc == DH_OK) {
+        DH_ON_DEVICE(p);
+        p->stream = cfg->stream;
+        rc = p->init(*cfg);
+        if (rc != DH_OK) p->release();
+    }
+    if (rc != DH_OK) { delete p; return rc; }
+    *out = p;
+    return DH_OK;
+}
+
+void dh_preroll_destroy(dh_preroll* p) {
+    if (!p) return;
+    {
+        DH_ON_DEVICE(p);
+        p->be.sync();
+        p->be.close();
+        p->release();
+    }
+    delete p;
+}
+
+int dh_preroll_reset(dh_preroll* p) { if (!p) return DH_EINVAL; DH_ON_DEVICE(p); return p->clear(); }
+int dh_preroll_append(dh_preroll* p, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts) {
+    if (!p) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->append(d_rows, stride, n, d_counts);
+}
+int dh_preroll_total(dh_preroll* p, uint64_t* total) {
+    if (!p || !total) return DH_EINVAL;
+    *total = p->total;
+    return DH_OK;
+}
+int dh_preroll_open_at(dh_preroll* p, uint64_t* h_open_at) {
+    if (!p || !h_open_at) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->be.download(h_open_at, p->d_open, sizeof(uint64_t) * p->B) ? DH_EDEVICE : DH_OK;
+}
+int dh_preroll_gather(dh_preroll* p, const uint64_t* h_from, uint64_t skip, size_t max_n, float* d_out, size_t out_stride,
+                      uint32_t* d_counts, uint64_t* h_start) {
+    if (!p) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->gather(h_from, skip, max_n, d_out, out_stride, d_counts, h_start);
+}
+
+}  // extern "C"

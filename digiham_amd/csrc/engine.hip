@@ -1018,6 +1018,37 @@ __global__ __launch_bounds__(DH_WAVE) void k_cz_gate(const DhCzPowerParams P) {
     if (b < P.B) dh_cz_gate_channel(P, b);
 }
 
+// ---------------------------------------------------------------------------------- pre-roll ring (preroll_core.hpp)
+// One workgroup per (1 024-sample tile, channel), blockIdx.y looping over the channels as in k_cz_fm.  Lane l of the 256
+// takes samples l, l + 256, l + 512, l + 768 of the tile: every wave instruction moves one contiguous 256-byte piece on
+// both sides, except the one piece per tile that may straddle the ring's seam.  The tile-0 workgroup of a channel is
+// the only one that touches that channel's open_at (append) or count (gather).
+__global__ __launch_bounds__(256) void k_preroll_append(const DhPrAppend A) {
+    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
+    for (uint32_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) dh_pr_append_open(A, b);
+#pragma unroll
+        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
+            const uint32_t i = i0 + 256u * k;
+            if (i < A.n) dh_pr_append_item(A, b, i);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_preroll_gather(const DhPrGather G) {
+    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
+    for (uint32_t b = blockIdx.y; b < G.B; b += gridDim.y) {
+        uint32_t pos;
+        const uint32_t count = dh_pr_count(G, b, pos);
+        if (blockIdx.x == 0 && threadIdx.x == 0) G.counts[b] = count;
+#pragma unroll
+        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
+            const uint32_t i = i0 + 256u * k;
+            if (i < count) dh_pr_gather_item(G, b, pos, i);
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------- ABI hooks
@@ -1170,6 +1201,19 @@ static int dh_be_cz_power(const DhCzPowerParams& P, void* stream) {
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(k_cz_gate, dim3((P.B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, P);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+
+static int dh_be_preroll_append(const DhPrAppend& A, void* stream) {
+    if (!A.n) return DH_OK;
+    hipLaunchKernelGGL(k_preroll_append, dim3((A.n + DH_PR_TILE - 1) / DH_PR_TILE, A.B < 65535u ? A.B : 65535u), dim3(256), 0, (hipStream_t) stream, A);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_preroll_gather(const DhPrGather& G, void* stream) {
+    if (!G.max_n) return DH_OK;
+    hipLaunchKernelGGL(k_preroll_gather, dim3((G.max_n + DH_PR_TILE - 1) / DH_PR_TILE, G.B < 65535u ? G.B : 65535u), dim3(256), 0, (hipStream_t) stream, G);
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }

@@ -6,6 +6,7 @@
 #include "dsp_core.hpp"
 #include "frontend_core.hpp"
 #include "channelizer_core.hpp"
+#include "preroll_core.hpp"
 #include "decoder_core.hpp"
 
 // ---- engine state initialisation: what the reference's constructors leave behind ------------

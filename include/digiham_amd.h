@@ -388,6 +388,59 @@ int  dh_channelizer_power_last(dh_channelizer* c, uint64_t* first_block, size_t*
 int  dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n);
 
 /* ------------------------------------------------------------------------
+ * Pre-roll: a per-channel history ring on the device.  Own specification; the reference has no counterpart (there a
+ * decoder is started by hand, before the transmission).  A band monitor learns which protocol a channel carries some
+ * time AFTER its squelch opened (Protocol scan: D-Star needs three sync words 2 016 bits apart); the ring keeps every
+ * channel's last `depth` samples so that the decoder is then fed from where the squelch opened, call set-up included.
+ *
+ * Stream.  Every channel's stream is counted from create or reset; `total` is the number of samples appended so far,
+ * the same for all channels and therefore a host scalar (dh_preroll_total: host arithmetic, no sync).
+ *
+ * Append.  dh_preroll_append adds the first n samples of every row d_rows[b][0..n) ([n_channels][stride] float32, what
+ * dh_channelizer_push wrote), gated or not.  Afterwards the ring holds samples [max(0, total - depth), total) of each
+ * channel bit for bit (NaN payloads, -0 and subnormals included).  n > depth keeps the last depth samples; n = 0 changes
+ * nothing and launches nothing; stride >= n, rows need no particular alignment.  Asynchronous on the stream.
+ *
+ * open_at.  d_counts is the channelizer's d_counts: non-zero = the channel's gate was open in this push; NULL = every
+ * channel is open.  With base = total before the append: an open channel whose open_at is DH_PREROLL_NONE gets
+ * open_at = base; a closed channel gets open_at = DH_PREROLL_NONE; otherwise open_at stays.  So open_at[b] is the stream
+ * index of the first sample of the first push of the current run of open pushes.  dh_preroll_open_at copies the
+ * n_channels values to the host and synchronises.
+ *
+ * Gather.  Asynchronous on the stream.  h_from is a host array of n_channels entries, uploaded by the call.  With
+ * oldest = total > depth ? total - depth : 0, a wanted channel b has
+ *     start_b = max(h_from[b], oldest),   first = start_b + skip,
+ *     count_b = first < total ? min(max_n, total - first) : 0,
+ *     d_out[b][i] = x_b[first + i] for i < count_b,   d_counts[b] = count_b.
+ * A channel with h_from[b] == DH_PREROLL_NONE gets d_counts[b] = 0 and its output row is not touched.  h_start (optional,
+ * host, n_channels entries) receives start_b, or DH_PREROLL_NONE for unwanted channels: host arithmetic.  A long history
+ * is replayed in chunks by stepping skip by max_n, so engines keep their ordinary max_samples; the output row index is
+ * the channel index, and (d_out, out_stride, d_counts, max_n) are exactly the arguments of dh_engine_push_ragged.
+ *
+ * Memory: the ring takes n_channels x depth x 4 bytes -- 192 channels x 2 s at 48 kS/s is 74 MB.
+ * DH_EINVAL: null handles or pointers (where n or max_n is not 0), struct_size too small, n_channels outside 1 .. 65536,
+ * depth outside 1 .. 2^24, stride < n, out_stride < max_n.
+ * ---------------------------------------------------------------------- */
+#define DH_PREROLL_NONE UINT64_MAX          /* open_at: gate closed;  from: channel not wanted */
+typedef struct dh_preroll dh_preroll;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(dh_preroll_config) */
+    int32_t  device;
+    uint32_t n_channels;
+    uint32_t depth;                /* samples kept per channel */
+    void*    stream;               /* hipStream_t; NULL = default stream */
+} dh_preroll_config;
+int  dh_preroll_create(const dh_preroll_config* cfg, dh_preroll** out);
+void dh_preroll_destroy(dh_preroll* p);
+/* back to sample 0, every open_at = DH_PREROLL_NONE */
+int  dh_preroll_reset(dh_preroll* p);
+int  dh_preroll_append(dh_preroll* p, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts);
+int  dh_preroll_total(dh_preroll* p, uint64_t* total);
+int  dh_preroll_open_at(dh_preroll* p, uint64_t* h_open_at);
+int  dh_preroll_gather(dh_preroll* p, const uint64_t* h_from, uint64_t skip, size_t max_n,
+                       float* d_out, size_t out_stride, uint32_t* d_counts, uint64_t* h_start);
+
+/* ------------------------------------------------------------------------
  * Diagnostics: the RRC output scaling `(float)((double)sum / gain)` of
  * src/rrc_filter/rrc_filter.cpp:33 exactly as the FIR kernels evaluate it
  * (reciprocal multiply + exact-division fallback near float rounding ties).
