@@ -43,6 +43,20 @@ class PrerollConfig(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class MonitorConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_samples", C.c_uint32),
+                ("depth", C.c_uint32), ("lead", C.c_uint32), ("confirm", C.c_uint32), ("release", C.c_uint32),
+                ("protos", C.c_uint32), ("stream", C.c_void_p)]
+
+
+class MonitorPushInfo(C.Structure):
+    _fields_ = [("proto", C.c_int32), ("replay", C.c_int32), ("engine", C.c_void_p), ("d_counts", C.c_void_p),
+                ("d_start", C.c_void_p), ("skip", C.c_uint64), ("live_first", C.c_uint64)]
+
+
+MONITOR_SINK = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(MonitorPushInfo))       # dh_monitor_sink
+MONITOR_FRONTS = ("wide10", "narrow20", "fsk10", "fsk40i")                    # dh_monitor_scan_engine's index
+
 PREROLL_NONE = 0xFFFFFFFFFFFFFFFF          # DH_PREROLL_NONE
 
 # protocol scan (DH_PROTO_SCAN): the patterns in the order of DH_SCAN_*, dh_scan_stat, DH_EV_SCAN_HIT
@@ -113,6 +127,11 @@ def declare(L, lenient=False):
         "dh_preroll_reset": [vp], "dh_preroll_append": [vp, vp, sz, sz, vp],
         "dh_preroll_total": [vp, C.POINTER(C.c_uint64)], "dh_preroll_open_at": [vp, vp],
         "dh_preroll_gather": [vp, vp, C.c_uint64, sz, vp, sz, vp, vp],
+        "dh_preroll_gather_device": [vp, vp, C.c_uint64, sz, vp, sz, vp],
+        "dh_engine_reset_channels": [vp, vp],
+        "dh_monitor_create": [C.POINTER(MonitorConfig), C.POINTER(vp)], "dh_monitor_reset": [vp],
+        "dh_monitor_push": [vp, vp, sz, sz, vp, MONITOR_SINK, vp], "dh_monitor_state": [vp, vp, vp],
+        "dh_monitor_total": [vp, C.POINTER(C.c_uint64)],
     }
     for name, args in sig.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
@@ -122,10 +141,14 @@ def declare(L, lenient=False):
         fn.restype = C.c_int
     L.dh_engine_destroy.argtypes = [vp]
     L.dh_engine_destroy.restype = None
-    for name in ("dh_channelizer_destroy", "dh_preroll_destroy"):
+    for name in ("dh_channelizer_destroy", "dh_preroll_destroy", "dh_monitor_destroy"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [vp]
             getattr(L, name).restype = None
+    for name in ("dh_monitor_engine", "dh_monitor_scan_engine"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [vp, C.c_int]
+            getattr(L, name).restype = vp
     return L
 
 
@@ -142,7 +165,9 @@ EXPORTED_SYMBOLS = [
     "dh_channelizer_push_host", "dh_channelizer_phasor", "dh_channelizer_power_enable", "dh_channelizer_set_squelch",
     "dh_channelizer_power_last",
     "dh_preroll_create", "dh_preroll_destroy", "dh_preroll_reset", "dh_preroll_append", "dh_preroll_total", "dh_preroll_open_at",
-    "dh_preroll_gather",
+    "dh_preroll_gather", "dh_preroll_gather_device", "dh_engine_reset_channels",
+    "dh_monitor_create", "dh_monitor_destroy", "dh_monitor_reset", "dh_monitor_push", "dh_monitor_state", "dh_monitor_total",
+    "dh_monitor_engine", "dh_monitor_scan_engine",
 ]
 
 _LIB = None

@@ -32,11 +32,11 @@ class TorchCudaMemory:
         self.index = device
 
     _NP2T = {"uint8": "uint8", "int16": "int16", "uint16": "int16", "uint32": "int32", "int32": "int32",
-             "float32": "float32"}
+             "float32": "float32", "uint64": "int64", "int64": "int64"}
 
     def from_numpy(self, a):
         a = np.ascontiguousarray(a)
-        t = self.torch.from_numpy(a.view(getattr(np, self._NP2T[a.dtype.name])) if a.dtype.name in ("uint16", "uint32") else a)
+        t = self.torch.from_numpy(a.view(getattr(np, self._NP2T[a.dtype.name])) if a.dtype.name in ("uint16", "uint32", "uint64") else a)
         return t.to(self.device)
 
     def zeros(self, shape, dtype):
@@ -223,9 +223,20 @@ class Engine:
         self._overlap = bool(overlap_pushes)
         self._inflight = []
 
+    @classmethod
+    def _borrowed(cls, ctx, handle, n_channels, max_samples):
+        """A view of an engine another handle owns (DeviceMonitor's): every call of Engine, and close() leaves it alive."""
+        self = cls.__new__(cls)
+        self.ctx, self._h, self._owned = ctx, C.c_void_p(handle), False
+        self.B, self.max_samples = n_channels, max_samples
+        self.has_demod, self.has_proto, self.keep_filtered = True, True, False
+        self._keep, self._overlap, self._inflight = None, False, []
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
-            self.ctx.lib.dh_engine_destroy(self._h)
+            if getattr(self, "_owned", True):
+                self.ctx.lib.dh_engine_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -237,6 +248,15 @@ class Engine:
 
     def reset_channel(self, ch):
         _check(self.ctx.lib.dh_engine_reset_channel(self._h, ch), "dh_engine_reset_channel", self.ctx.lib)
+
+    def reset_channels(self, flags):
+        """reset_channel for every channel with flags[b] != 0 ([B] uint8, numpy or a device array), in one launch."""
+        mem = self.ctx.mem
+        f = flags if mem.is_device_array(flags) and not isinstance(flags, np.ndarray) else mem.from_numpy(np.ascontiguousarray(flags, np.uint8))
+        if tuple(f.shape) != (self.B,) or (f.element_size() if callable(getattr(f, "element_size", None)) else f.itemsize) != 1:
+            raise ValueError("Engine.reset_channels: flags needs %d entries" % self.B)
+        self._keep_flags = f        # the launch is asynchronous: keep the flags alive
+        _check(self.ctx.lib.dh_engine_reset_channels(self._h, mem.ptr(f)), "dh_engine_reset_channels", self.ctx.lib)
 
     def set_slot_filter(self, f):
         _check(self.ctx.lib.dh_engine_set_slot_filter(self._h, f), "dh_engine_set_slot_filter", self.ctx.lib)
@@ -590,6 +610,24 @@ class Preroll:
                                               mem.ptr(self._counts), start.ctypes.data_as(C.c_void_p)), "dh_preroll_gather", self.ctx.lib)
         return rows, self._counts, start
 
+    def gather_device(self, from_dev, skip, max_n, out=None):
+        """gather with `from_dev` ([B] uint64, or int64 holding the same bits) on the device already: no upload, no start.
+        Returns (rows, counts)."""
+        mem = self.ctx.mem
+        f = from_dev if mem.is_device_array(from_dev) else mem.from_numpy(np.ascontiguousarray(from_dev, np.uint64))
+        if tuple(f.shape) != (self.B,) or (f.element_size() if callable(getattr(f, "element_size", None)) else f.itemsize) != 8:
+            raise ValueError("Preroll.gather_device: from_dev needs %d 64-bit entries" % self.B)
+        max_n = int(max_n)
+        if out is None:
+            out = mem.zeros((self.B, max(max_n, 1)), np.float32)
+        rows, stride = _float_rows(mem, out, self.B, "Preroll.gather_device")
+        if rows is not out:
+            raise ValueError("Preroll.gather_device: out must be a float32 [%d][n] device array with contiguous rows" % self.B)
+        self._keep = (f, rows)
+        _check(self.ctx.lib.dh_preroll_gather_device(self._h, mem.ptr(f), int(skip), max_n, mem.ptr(rows), stride, mem.ptr(self._counts)),
+               "dh_preroll_gather_device", self.ctx.lib)
+        return rows, self._counts
+
 
 class Monitor:
     """A band monitor over the rows of a channelizer: one Scanner names the protocol an open channel carries, one Preroll
@@ -722,6 +760,132 @@ class Monitor:
                 live[chans] = n
                 eng.push(x, n=n, counts=live)
                 self._collect(name, chans, np.full(len(chans), total - n, np.int64), blocks)
+        blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
+        return blocks
+
+
+PROTO_NAMES = {_capi.PROTO[name]: name for name in ("dmr", "ysf", "nxdn", "pocsag", "dstar")}
+
+
+class DeviceMonitor:
+    """Monitor behind the C ABI (dh_monitor; include/digiham_amd.h "Band monitor"): the same constructor arguments, the same
+    rounds, the same blocks from push() -- but the scan engines, the ring, the protocol engines and the staging array
+    belong to one library handle, and the per-round bookkeeping runs in kernels: the host reads one fixed-size summary per
+    step instead of every channel's open_at, resets channels with one masked launch per engine, and uploads nothing per
+    channel.  Blocks are built in the handle's sink, after every engine push, from one download of that push's counts and
+    starts and the engine's frames() / events() (read_rows for fewer than a sixteenth of the channels), as Monitor does.
+
+    `assigned` and `start` are read from the device when asked for (once per round at most); `engines` and
+    `scanner.engines` are views of the handle's engines and die with it."""
+
+    def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        lib, mem = self.ctx.lib, self.ctx.mem
+        self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
+        self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
+        self.protos = tuple(protos)
+        bits = 0
+        for p in self.protos:
+            bits |= 1 << _capi.PROTO[p]
+        cfg = _capi.MonitorConfig(C.sizeof(_capi.MonitorConfig), getattr(mem, "index", 0), self.B, self.max_samples, self.depth,
+                                  self.lead, self.confirm, self.release, bits, mem.stream())
+        h = C.c_void_p()
+        _check(lib.dh_monitor_create(C.byref(cfg), C.byref(h)), "dh_monitor_create", lib)
+        self._h = h
+        self.engines = {p: Engine._borrowed(self.ctx, lib.dh_monitor_engine(h, _capi.PROTO[p]), self.B, self.max_samples) for p in self.protos}
+        self.scanner = Scanner.__new__(Scanner)
+        self.scanner.ctx, self.scanner.B, self.scanner.max_samples = self.ctx, self.B, self.max_samples
+        self.scanner.engines = {}
+        for i, f in enumerate(_capi.MONITOR_FRONTS):
+            e = lib.dh_monitor_scan_engine(h, i)
+            if e:
+                self.scanner.engines[f] = Engine._borrowed(self.ctx, e, self.B, self.max_samples)
+        self.scanner.fronts = tuple(self.scanner.engines)
+        self.scanner_engines = self.scanner.engines
+        self._sink = _capi.MONITOR_SINK(self._on_push)
+        self._blocks, self._error, self._state, self._keep = None, None, None, None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for e in list(self.engines.values()) + list(self.scanner.engines.values()):
+                e.close()
+            self.ctx.lib.dh_monitor_destroy(self._h)
+            self._h = None
+            self.engines, self.scanner.engines = {}, {}
+
+    __del__ = close
+
+    def reset(self):
+        _check(self.ctx.lib.dh_monitor_reset(self._h), "dh_monitor_reset", self.ctx.lib)
+        self._state = None
+
+    @property
+    def total(self):
+        t = C.c_uint64(0)
+        _check(self.ctx.lib.dh_monitor_total(self._h, C.byref(t)), "dh_monitor_total", self.ctx.lib)
+        return t.value
+
+    def _read_state(self):
+        if self._state is None:
+            a, s = np.empty(self.B, np.uint8), np.empty(self.B, np.uint64)
+            _check(self.ctx.lib.dh_monitor_state(self._h, a.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)), "dh_monitor_state", self.ctx.lib)
+            self._state = ([PROTO_NAMES.get(int(v)) for v in a], [None if int(v) == PREROLL_NONE else int(v) for v in s])
+        return self._state
+
+    @property
+    def assigned(self):
+        return self._read_state()[0]
+
+    @property
+    def start(self):
+        return self._read_state()[1]
+
+    def _on_push(self, user, info):
+        try:
+            lib, i = self.ctx.lib, info.contents
+            name = PROTO_NAMES[i.proto]
+            eng = self.engines[name]
+            eng.sync()
+            counts, start = np.empty(self.B, np.uint32), np.empty(self.B, np.uint64)
+            _check(lib.dh_copy_to_host(counts.ctypes.data_as(C.c_void_p), C.c_void_p(i.d_counts), counts.nbytes), "dh_copy_to_host", lib)
+            channels = np.flatnonzero(counts)
+            if i.replay:
+                _check(lib.dh_copy_to_host(start.ctypes.data_as(C.c_void_p), C.c_void_p(i.d_start), start.nbytes), "dh_copy_to_host", lib)
+                first = start[channels].astype(np.int64) + int(i.skip)
+            else:
+                first = np.full(len(channels), int(i.live_first), np.int64)
+            if 16 * len(channels) >= self.B:
+                (frames, fc), (events, ec) = eng.frames(), eng.events()
+                frames, fc, events, ec = frames[channels], fc[channels], events[channels], ec[channels]
+            else:
+                frames, fc = eng.read_rows("frames", channels)
+                events, ec = eng.read_rows("events", channels)
+            for j, b in enumerate(channels):
+                if fc[j] or ec[j]:
+                    self._blocks.append({"channel": int(b), "proto": name, "first_sample": int(first[j]),
+                                         "frames": frames[j, :fc[j]].copy(), "events": events[j, :ec[j]].copy()})
+        except BaseException as e:          # (an exception cannot cross the C frames: push() raises it)
+            if self._error is None:
+                self._error = e
+
+    def push(self, rows, n=None, counts=None):
+        mem = self.ctx.mem
+        x, stride = _float_rows(mem, rows, self.B, "DeviceMonitor.push")
+        n = x.shape[1] if n is None else int(n)
+        if n == 0:
+            return []
+        if n > self.max_samples:
+            raise DhError(_capi.DH_EINVAL, "DeviceMonitor.push", "n = %d > max_samples = %d" % (n, self.max_samples))
+        if counts is not None and not mem.is_device_array(counts):
+            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        self._keep = (x, counts)
+        self._blocks, self._error, self._state = [], None, None
+        rc = self.ctx.lib.dh_monitor_push(self._h, mem.ptr(x), stride, n, mem.ptr(counts) if counts is not None else None, self._sink, None)
+        blocks, self._blocks = self._blocks, None
+        if self._error is not None:
+            raise self._error
+        _check(rc, "dh_monitor_push", self.ctx.lib)
         blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
         return blocks
 

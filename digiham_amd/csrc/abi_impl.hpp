@@ -138,6 +138,7 @@ void dh_engine_destroy(dh_engine* e) {
 int dh_engine_reset(dh_engine* e) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset(); }
 int dh_engine_set_slot_filter(dh_engine* e, uint32_t f) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.set_slot_filter(f); }
 int dh_engine_reset_channel(dh_engine* e, uint32_t ch) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset_channel(ch); }
+int dh_engine_reset_channels(dh_engine* e, const uint8_t* d_flags) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset_channels(d_flags); }
 int dh_engine_set_slot_filter_channel(dh_engine* e, uint32_t ch, uint32_t f) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.set_slot_filter_channel(ch, f); }
 int dh_engine_push(dh_engine* e, const float* d, size_t stride, size_t n) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.push(d, stride, n); }
 int dh_engine_push_host(dh_engine* e, const float* h, size_t stride, size_t n) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.push_host(h, stride, n); }
@@ -508,10 +509,15 @@ struct dh_preroll {
         if (out_stride < max_n || (max_n && (!from || !out || !counts))) return DH_EINVAL;
         if (h_start && from)
             for (uint32_t b = 0; b < B; b++) h_start[b] = from[b] == DH_PREROLL_NONE ? DH_PREROLL_NONE : dh_pr_start(from[b], oldest());
+        if (max_n && be.upload(d_from, from, sizeof(uint64_t) * B)) return DH_EDEVICE;
+        return gather_device(d_from, skip, max_n, out, out_stride, counts);
+    }
+    // ... with `from` on the device already (the band monitor's step B wrote it): no upload, no host arithmetic
+    int gather_device(const uint64_t* from, uint64_t skip, size_t max_n, float* out, size_t out_stride, uint32_t* counts) {
+        if (out_stride < max_n || (max_n && (!from || !out || !counts))) return DH_EINVAL;
         if (!max_n) return counts && be.zero(counts, sizeof(uint32_t) * B) ? DH_EDEVICE : DH_OK;
-        if (be.upload(d_from, from, sizeof(uint64_t) * B)) return DH_EDEVICE;
         DhPrGather G{};
-        G.ring = d_ring; G.from = d_from; G.out = (uint32_t*) out; G.out_stride = out_stride; G.counts = counts;
+        G.ring = d_ring; G.from = from; G.out = (uint32_t*) out; G.out_stride = out_stride; G.counts = counts;
         G.B = B; G.depth = depth; G.max_n = (uint32_t) std::min<size_t>(max_n, depth);      // (no channel holds more)
         G.total = total; G.oldest = oldest(); G.skip = skip; G.r0 = (uint32_t) (G.oldest % depth);
         return dh_be_preroll_gather(G, stream) ? DH_EDEVICE : DH_OK;
@@ -573,5 +579,195 @@ int dh_preroll_gather(dh_preroll* p, const uint64_t* h_from, uint64_t skip, size
     DH_ON_DEVICE(p);
     return p->gather(h_from, skip, max_n, d_out, out_stride, d_counts, h_start);
 }
+int dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t skip, size_t max_n, float* d_out, size_t out_stride,
+                             uint32_t* d_counts) {
+    if (!p) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->gather_device(d_from, skip, max_n, d_out, out_stride, d_counts);
+}
+
+}  // extern "C"
+
+// ---- the band monitor (monitor_core.hpp): scan engines, ring and protocol engines behind one handle ------------------
+//   dh_be_monitor_open(const DhMonOpen& A, void* stream);        step A
+//   dh_be_monitor_assign(const DhMonAssign& S, void* stream);    step B
+// (engine.hip defines the gfx950 ones; monitor_core.hpp the CPU harness's.)  All the host learns of a round is the summary
+// block, read once after each step; everything [B]-sized stays on the device.
+struct dh_monitor {
+    DH_BACKEND be;
+    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
+    void* stream = nullptr;
+    uint32_t B = 0, max_samples = 0;
+    dh_engine* scan[DH_MON_FRONTS] = {};               // null: no configured protocol sits behind that front end
+    dh_engine* eng[DH_MON_PROTOS] = {};                // by DH_PROTO_*; null: not configured
+    dh_preroll* pre = nullptr;
+    float* d_stage = nullptr;                           // [B][max_samples]: a replay chunk
+    uint32_t* d_chunk_counts = nullptr;                 // [B]: its counts
+    DhMonSummary* d_sum = nullptr;
+    DhMonSummary sum{}, sum0{};                         // what was read last; what a round starts from
+    DhMonOpen A{}; DhMonAssign S{};                     // what create fixes; a round adds n and total
+    std::vector<uint64_t> none;
+
+    auto scope() const { return be.scope(); }
+    static uint32_t front_of(int proto) { return proto == DH_PROTO_NXDN ? 1u : proto == DH_PROTO_DSTAR ? 2u : proto == DH_PROTO_POCSAG ? 3u : 0u; }
+    void release() {
+        for (dh_engine*& e : scan) { dh_engine_destroy(e); e = nullptr; }
+        for (dh_engine*& e : eng) { dh_engine_destroy(e); e = nullptr; }
+        dh_preroll_destroy(pre); pre = nullptr;
+        bufs.free_all();
+    }
+    int clear() {
+        if (be.zero(A.assigned, B) || be.zero(A.closed_run, sizeof(uint32_t) * B) || be.upload(A.start, none.data(), sizeof(uint64_t) * B))
+            return DH_EDEVICE;
+        return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    int make_engine(const dh_monitor_config& c, uint32_t front, int proto, dh_engine** out) {
+        dh_engine_config ec{};
+        ec.struct_size = sizeof(dh_engine_config); ec.device = c.device; ec.n_channels = c.n_channels; ec.max_samples = c.max_samples;
+        ec.rrc = front == 0u ? DH_RRC_WIDE : front == 1u ? DH_RRC_NARROW : DH_RRC_NONE;
+        ec.demod = front < 2u ? DH_DEMOD_GFSK4 : DH_DEMOD_FSK2;
+        ec.sps = front == 1u ? 20u : front == 3u ? 40u : 10u;
+        ec.flags = front == 3u ? DH_FLAG_FSK_INVERT : 0u;
+        ec.proto = proto; ec.slot_filter = 3; ec.stream = c.stream;
+        return dh_engine_create(&ec, out);
+    }
+    int init(const dh_monitor_config& c) {
+        B = c.n_channels; max_samples = c.max_samples;
+        none.assign(B, DH_PREROLL_NONE);
+        for (int p = 1; p < (int) DH_MON_PROTOS; p++) {
+            if (!(c.protos >> p & 1u)) continue;
+            const uint32_t f = front_of(p);
+            int rc = scan[f] ? DH_OK : make_engine(c, f, DH_PROTO_SCAN, &scan[f]);
+            if (rc == DH_OK) rc = make_engine(c, f, p, &eng[p]);
+            if (rc != DH_OK) return rc;
+        }
+        dh_preroll_config pc{};
+        pc.struct_size = sizeof(pc); pc.device = c.device; pc.n_channels = B; pc.depth = c.depth; pc.stream = c.stream;
+        int rc = dh_preroll_create(&pc, &pre);
+        if (rc != DH_OK) return rc;
+        bool ok = bufs.alloc(d_stage, (size_t) B * max_samples);
+        ok &= bufs.alloc(d_chunk_counts, B);
+        ok &= bufs.alloc(d_sum, 1);
+        ok &= bufs.alloc(A.assigned, B); ok &= bufs.alloc(A.closed_run, B); ok &= bufs.alloc(A.start, B);
+        ok &= bufs.alloc(A.scan_reset, B); ok &= bufs.alloc(A.scan_counts, B);
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++)
+            if (eng[p]) { ok &= bufs.alloc(A.live_counts[p], B); ok &= bufs.alloc(S.new_flags[p], B); ok &= bufs.alloc(S.from[p], B); }
+        if (!ok) return DH_ENOMEM;
+        A.open_at = pre->d_open; A.sum = d_sum; A.B = B; A.release = c.release;
+        for (uint32_t f = 0; f < DH_MON_FRONTS; f++)
+            if (scan[f]) { S.stats[f] = scan[f]->impl.frames; S.stat_count[f] = scan[f]->impl.frame_count; S.stat_stride[f] = scan[f]->impl.L.out_cap; }
+        S.scan_counts = A.scan_counts; S.open_at = pre->d_open; S.assigned = A.assigned; S.start = A.start; S.scan_reset = A.scan_reset;
+        S.sum = d_sum; S.B = B; S.lead = c.lead; S.depth = c.depth; S.confirm = c.confirm;
+        for (uint32_t p = 0; p < DH_MON_PROTOS; p++) sum0.min_start[p] = DH_PREROLL_NONE;
+        return clear();
+    }
+    int reset() {
+        int rc = dh_preroll_reset(pre);
+        for (dh_engine* e : scan) if (e && rc == DH_OK) rc = dh_engine_reset(e);
+        for (dh_engine* e : eng) if (e && rc == DH_OK) rc = dh_engine_reset(e);
+        return rc == DH_OK ? clear() : rc;
+    }
+    int reset_scanners() {
+        for (dh_engine* e : scan) if (e) { const int rc = e->impl.reset_channels(A.scan_reset); if (rc != DH_OK) return rc; }
+        return DH_OK;
+    }
+    int read_summary() { return be.download(&sum, d_sum, sizeof(sum)) ? DH_EDEVICE : DH_OK; }      // (synchronises)
+    int push(const float* rows, size_t stride, size_t n, const uint32_t* counts, dh_monitor_sink sink, void* user) {
+        if (!n) return DH_OK;
+        if (!rows || n > max_samples || stride < n) return DH_EINVAL;
+        int rc = pre->append(rows, stride, n, counts);                                      // 1
+        if (rc != DH_OK) return rc;
+        const uint64_t total = pre->total;
+        if (be.upload(d_sum, &sum0, sizeof(sum0))) return DH_EDEVICE;
+        A.n = (uint32_t) n;
+        if (dh_be_monitor_open(A, stream)) return DH_EDEVICE;                               // 2
+        if ((rc = read_summary()) != DH_OK) return rc;
+        if (sum.n_reset && (rc = reset_scanners()) != DH_OK) return rc;                     // 3
+        if (sum.n_scan) {
+            for (dh_engine* e : scan)                                                       // 4
+                if (e && (rc = e->impl.push(rows, stride, n, A.scan_counts)) != DH_OK) return rc;
+            S.total = total;
+            if (dh_be_monitor_assign(S, stream)) return DH_EDEVICE;                         // 5
+            if ((rc = read_summary()) != DH_OK) return rc;
+        }
+        dh_monitor_push_info info{};
+        info.live_first = total - n;
+        bool any_new = false;
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++) any_new |= sum.n_new[p] != 0u;
+        if (any_new && (rc = reset_scanners()) != DH_OK) return rc;                         // 6 (scan_reset: the channels step B named)
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++) {
+            if (!eng[p] || !sum.n_new[p]) continue;
+            if ((rc = eng[p]->impl.reset_channels(S.new_flags[p])) != DH_OK) return rc;
+            const uint64_t span = total - sum.min_start[p];
+            for (uint64_t skip = 0; skip < span; skip += max_samples) {
+                if ((rc = pre->gather_device(S.from[p], skip, max_samples, d_stage, max_samples, d_chunk_counts)) != DH_OK) return rc;
+                if ((rc = eng[p]->impl.push(d_stage, max_samples, max_samples, d_chunk_counts)) != DH_OK) return rc;
+                info.proto = (int32_t) p; info.replay = 1; info.engine = eng[p]; info.d_counts = d_chunk_counts; info.d_start = S.from[p]; info.skip = skip;
+                if (sink) sink(user, &info);
+            }
+        }
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++) {                                      // 7
+            if (!eng[p] || !sum.n_live[p]) continue;
+            if ((rc = eng[p]->impl.push(rows, stride, n, A.live_counts[p])) != DH_OK) return rc;
+            info.proto = (int32_t) p; info.replay = 0; info.engine = eng[p]; info.d_counts = A.live_counts[p]; info.d_start = A.start; info.skip = 0;
+            if (sink) sink(user, &info);
+        }
+        return DH_OK;
+    }
+};
+
+extern "C" {
+
+int dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out) {
+    if (!cfg || !out) return DH_EINVAL;
+    *out = nullptr;
+    if (cfg->struct_size < sizeof(dh_monitor_config) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
+        cfg->depth < 1 || cfg->depth > (1u << 24) || cfg->protos == 0 || (cfg->protos & ~0x3Eu))
+        return DH_EINVAL;
+    dh_monitor* m = new (std::nothrow) dh_monitor;
+    if (!m) return DH_ENOMEM;
+    int rc = m->be.open(cfg->device, cfg->stream);
+    if (rc == DH_OK) {
+        DH_ON_DEVICE(m);
+        m->stream = cfg->stream;
+        rc = m->init(*cfg);
+        if (rc != DH_OK) m->release();
+    }
+    if (rc != DH_OK) { delete m; return rc; }
+    *out = m;
+    return DH_OK;
+}
+
+void dh_monitor_destroy(dh_monitor* m) {
+    if (!m) return;
+    {
+        DH_ON_DEVICE(m);
+        m->be.sync();
+        m->be.close();
+        m->release();
+    }
+    delete m;
+}
+
+int dh_monitor_reset(dh_monitor* m) { if (!m) return DH_EINVAL; DH_ON_DEVICE(m); return m->reset(); }
+int dh_monitor_push(dh_monitor* m, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts, dh_monitor_sink sink, void* user) {
+    if (!m) return DH_EINVAL;
+    DH_ON_DEVICE(m);
+    return m->push(d_rows, stride, n, d_counts, sink, user);
+}
+int dh_monitor_state(dh_monitor* m, uint8_t* h_assigned, uint64_t* h_start) {
+    if (!m) return DH_EINVAL;
+    DH_ON_DEVICE(m);
+    if (h_assigned && m->be.download(h_assigned, m->A.assigned, m->B)) return DH_EDEVICE;
+    if (h_start && m->be.download(h_start, m->A.start, sizeof(uint64_t) * m->B)) return DH_EDEVICE;
+    return DH_OK;
+}
+int dh_monitor_total(dh_monitor* m, uint64_t* total) {
+    if (!m || !total) return DH_EINVAL;
+    *total = m->pre->total;
+    return DH_OK;
+}
+dh_engine* dh_monitor_engine(dh_monitor* m, int proto) { return m && proto > 0 && proto < (int) DH_MON_PROTOS ? m->eng[proto] : nullptr; }
+dh_engine* dh_monitor_scan_engine(dh_monitor* m, int front) { return m && front >= 0 && front < (int) DH_MON_FRONTS ? m->scan[front] : nullptr; }
 
 }  // extern "C"

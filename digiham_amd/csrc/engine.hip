@@ -1049,6 +1049,51 @@ __global__ __launch_bounds__(256) void k_preroll_gather(const DhPrGather G) {
     }
 }
 
+// ---------------------------------------------------------------------------------- band monitor (monitor_core.hpp)
+// Steps A and B of a round: one lane per channel, 256-thread workgroups, the loop bound the same for every lane of a
+// workgroup so that the votes below see whole wavefronts.  Ordinary vector stores for the state and the per-channel
+// outputs; the summary block takes one vector atomic per wavefront and non-zero count (A), per newly named channel (B).
+__global__ __launch_bounds__(256) void k_monitor_open(const DhMonOpen A) {
+    const bool first = (threadIdx.x & (DH_WAVE - 1)) == 0;
+    for (uint32_t base = blockIdx.x * 256u; base < A.B; base += gridDim.x * 256u) {
+        const uint32_t b = base + threadIdx.x;
+        const uint32_t r = b < A.B ? dh_mon_open_channel(A, b) : 0u;
+        const uint32_t n_scan = (uint32_t) __popcll(__builtin_amdgcn_ballot_w64((r & 1u) != 0u));
+        const uint32_t n_reset = (uint32_t) __popcll(__builtin_amdgcn_ballot_w64((r & 2u) != 0u));
+        if (first && n_scan) atomicAdd(&A.sum->n_scan, n_scan);
+        if (first && n_reset) atomicAdd(&A.sum->n_reset, n_reset);
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++) {
+            const uint32_t n_live = (uint32_t) __popcll(__builtin_amdgcn_ballot_w64((r >> 8) == p));
+            if (first && n_live) atomicAdd(&A.sum->n_live[p], n_live);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_monitor_assign(const DhMonAssign S) {
+    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < S.B; b += gridDim.x * 256u) {
+        uint64_t start;
+        const uint32_t p = dh_mon_assign_channel(S, b, start);
+        if (p) {
+            atomicAdd(&S.sum->n_new[p], 1u);
+            atomicMin((unsigned long long*) &S.sum->min_start[p], (unsigned long long) start);
+        }
+    }
+}
+
+// Masked reset of an engine: workgroup i takes channels i, i + gridDim.x, ...; a channel whose flag is 0 costs one byte
+// read.  The 256 lanes zero row b of every declared buffer; the fence and the barrier put those zeros in memory before
+// one lane writes the few non-zero words of a fresh channel over them (the flag is the same for the whole workgroup, so
+// is the way through the barrier).
+__global__ __launch_bounds__(256) void k_reset_channels(const DhResetChannels R) {
+    for (uint32_t b = blockIdx.x; b < R.B; b += gridDim.x) {
+        if (!R.flags[b]) continue;
+        dh_rst_zero_rows(R, b, threadIdx.x, 256u);
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) dh_rst_init(R, b);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------- ABI hooks
@@ -1216,6 +1261,22 @@ static int dh_be_preroll_gather(const DhPrGather& G, void* stream) {
     hipLaunchKernelGGL(k_preroll_gather, dim3((G.max_n + DH_PR_TILE - 1) / DH_PR_TILE, G.B < 65535u ? G.B : 65535u), dim3(256), 0, (hipStream_t) stream, G);
     HIP_TRY(hipGetLastError());
     return DH_OK;
+}
+
+static int dh_be_monitor_open(const DhMonOpen& A, void* stream) {
+    hipLaunchKernelGGL(k_monitor_open, dim3(grid_for(A.B, 256)), dim3(256), 0, (hipStream_t) stream, A);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_monitor_assign(const DhMonAssign& S, void* stream) {
+    hipLaunchKernelGGL(k_monitor_assign, dim3(grid_for(S.B, 256)), dim3(256), 0, (hipStream_t) stream, S);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+// (on the engine's stream, behind whatever the engine has in flight on streams of its own: HipBackend::ms)
+static int dh_be_reset_channels(HipBackend& be, const DhResetChannels& R) {
+    hipLaunchKernelGGL(k_reset_channels, dim3(R.B < 2048u ? R.B : 2048u), dim3(256), 0, be.ms(), R);
+    return be.launched("k_reset_channels");
 }
 
 #define DH_BACKEND HipBackend

@@ -22,6 +22,7 @@
 #include "../../include/digiham_amd.h"
 #include "dsp_core.hpp"
 #include "decoder_core.hpp"
+#include "kernels_core.hpp"
 #include "fec_tables.hpp"
 #include "rrc_taps.h"
 
@@ -115,6 +116,8 @@ inline void fill_taps(int rrc, P& p) {
 //   int launch_decoder(const DhDecParams&, int proto);
 //   int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
 //   int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B);
+// and, beside it, the free function dh_be_reset_channels(BE&, const DhResetChannels&) (monitor_core.hpp: the CPU harness's;
+// engine.hip: the gfx950 one).
 
 // The device buffers of one handle (an engine, a channelizer).  Every buffer is allocated through alloc() and stated
 // nowhere else: free_all() frees what was allocated, zero_all() and zero_row() clear what was declared as state.
@@ -289,6 +292,22 @@ struct Engine {
         rc |= be.launch_init_state(dsp_state ? dsp_state + (size_t) ch * L.state_words : nullptr, L.state_words, L.fused ? L.nz : 0u,
                                    dec_state ? dec_state + (size_t) ch * DH_DEC_STATE_WORDS : nullptr, slot_filter, 1);
         return rc ? DH_EDEVICE : DH_OK;
+    }
+
+    // ... of every channel with d_flags[b] != 0 ([B] bytes on the device), in one launch: the rows zero_row() clears, then
+    // what launch_init_state writes.  The buffer table travels in the kernel's arguments.
+    int reset_channels(const uint8_t* d_flags) {
+        if (!d_flags) return DH_EINVAL;
+        DhResetChannels R{};
+        R.flags = d_flags;
+        for (const auto& b : bufs.list) {
+            if (b.zeroed != ZERO_PER_CHANNEL) continue;
+            if (R.n_bufs == DH_RST_MAX_BUFS) return DH_EINVAL;
+            R.buf[R.n_bufs].p = b.p; R.buf[R.n_bufs].row_bytes = (uint32_t) (b.bytes / L.B); R.n_bufs++;
+        }
+        R.dsp_state = dsp_state; R.state_words = L.state_words; R.tail0 = L.fused ? L.nz : 0u;
+        R.dec_state = dec_state; R.slot_filter = slot_filter; R.B = L.B;
+        return dh_be_reset_channels(be, R) ? DH_EDEVICE : DH_OK;
     }
 
     // d_counts (device, [B], or null): ragged push -- channel b brings d_counts[b] <= n samples of its row

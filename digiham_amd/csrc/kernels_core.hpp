@@ -223,3 +223,5 @@ DH_HD void dh_dvfilter_channel(const int16_t* in, int16_t* out, float* st, size_
     }
     for (int i = 0; i < 11; i++) { st[i] = xv[i]; st[11 + i] = yv[i]; }
 }
+
+#include "monitor_core.hpp"       // (needs dh_init_state_channel)

@@ -244,6 +244,10 @@ int  dh_engine_push_host(dh_engine* e, const float* h_samples, size_t stride, si
  * (the other channels keep streaming).  What a module instance attached to a shared engine needs. */
 int  dh_engine_reset_channel(dh_engine* e, uint32_t channel);
 int  dh_engine_set_slot_filter_channel(dh_engine* e, uint32_t channel, uint32_t filter);
+/* dh_engine_reset_channel for every channel b with d_flags[b] != 0 (n_channels bytes on the device), in ONE launch however
+ * many are flagged: a flagged channel ends in exactly the state dh_engine_reset_channel leaves it in, the others are not
+ * touched.  Asynchronous on the engine stream; the flags are read when the launch runs. */
+int  dh_engine_reset_channels(dh_engine* e, const uint8_t* d_flags);
 /* Ragged pushes: channel b brings d_counts[b] (<= max_n) new samples of its row; the others stay where they are.  One launch
  * for N module instances whose ring buffers hold different amounts (include/digiham/shared_engine.hpp); a real-time receiver
  * whose channels arrive in blocks of unequal length.  Engines with a foreign tap table (DH_RRC_CUSTOM) take whole pushes only. */
@@ -439,6 +443,92 @@ int  dh_preroll_total(dh_preroll* p, uint64_t* total);
 int  dh_preroll_open_at(dh_preroll* p, uint64_t* h_open_at);
 int  dh_preroll_gather(dh_preroll* p, const uint64_t* h_from, uint64_t skip, size_t max_n,
                        float* d_out, size_t out_stride, uint32_t* d_counts, uint64_t* h_start);
+/* dh_preroll_gather with `from` on the device already (n_channels entries, read when the launch runs): no upload, and no
+ * h_start -- start_b is max(d_from[b], oldest) as above.  Same kernel, same counts. */
+int  dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t skip, size_t max_n,
+                              float* d_out, size_t out_stride, uint32_t* d_counts);
+
+/* ------------------------------------------------------------------------
+ * Band monitor: scanner, ring and decoders behind one handle.  Own specification; the reference has no counterpart.
+ * A dh_monitor owns, all on the configuration's stream: one protocol-scan engine per front end that its protocols need
+ * (wide10: DMR, YSF; narrow20: NXDN; fsk10: D-Star; fsk40i: POCSAG -- the engine arguments of api.SCAN_FRONTS), one
+ * pre-roll ring of `depth`, one decoding engine per protocol in `protos` behind that protocol's front end, and one
+ * [n_channels][max_samples] staging array.  It does not own the channelizer: d_rows, stride, n and d_counts of
+ * dh_monitor_push are what dh_channelizer_push and its power stage wrote.  d_counts is read as a flag per channel
+ * (non-zero: the gate is open and the channel brings all n samples); NULL: every channel is open.
+ *
+ * State, per channel, on the device: assigned (uint8: 0 or a DH_PROTO_*), closed_run (uint32, saturating: rounds in a
+ * row with the gate closed), start (uint64: the stream index at which the decoder's input began; DH_PREROLL_NONE while
+ * unassigned).  dh_monitor_state copies assigned and start to the host (either pointer may be NULL) and synchronises.
+ *
+ * One round, dh_monitor_push with 0 < n <= max_samples (n = 0: DH_OK, nothing happens):
+ *   1. The ring appends the rows (Pre-roll); open = (open_at[b] != DH_PREROLL_NONE).
+ *   2. Step A, one kernel, per channel: closed_run = open ? 0 : closed_run + 1.  A closed channel that is unassigned with
+ *      closed_run == 1 gets scan_reset[b] = 1 (every other channel 0); a closed channel that is assigned with
+ *      closed_run >= release becomes unassigned, start = DH_PREROLL_NONE.  Then scan_counts[b] = (open && assigned == 0)
+ *      ? n : 0, and for every configured protocol p live_counts[p][b] = (open && assigned == p) ? n : 0.
+ *   3. Where any scan_reset is set, the scan engines get dh_engine_reset_channels(scan_reset).
+ *   4. Where any scan_counts is non-zero, every scan engine gets a ragged push of the rows with scan_counts.
+ *   5. Step B (only then), one kernel, per channel with scan_counts != 0: the `periodic` counts of the nine patterns are
+ *      summed per family -- DMR (patterns 0-3), YSF (4), NXDN (5), D-Star (6, 7), POCSAG (8) -- each pattern read from the
+ *      statistics row of the scan engine of its own front end (a row of fewer than 144 bytes, or a front end that is not
+ *      configured, reads as zeros).  The family with the largest sum wins, the first in that order where sums are equal.
+ *      If its sum is >= confirm and its protocol p is configured, the channel is assigned: assigned = p, start =
+ *      max(open_at - lead, total - depth, 0) with both differences saturating at 0 (total: after this round's append),
+ *      new_flags[p][b] = 1, from[p][b] = start, scan_reset[b] = 1.  Every other new_flags entry is 0, every other from
+ *      entry DH_PREROLL_NONE, every other scan_reset 0.  If the winner's protocol is not configured the channel stays
+ *      unassigned; the next-best family is not considered.
+ *   6. Where a channel was assigned, the scan engines get dh_engine_reset_channels(scan_reset); then per protocol p with
+ *      new channels: dh_engine_reset_channels(new_flags[p]) of its engine, and for skip = 0, max_samples, ... while
+ *      skip < total - (the smallest start among p's new channels): dh_preroll_gather_device(from[p], skip, max_samples)
+ *      into the staging array and a ragged push of it.  The ring already holds this round's samples: a channel named in
+ *      this round gets no live push in it.
+ *   7. Per protocol p with any live_counts[p] non-zero: one ragged push of the caller's rows with live_counts[p].
+ *
+ * The sink.  After EVERY engine push of steps 6 and 7, before the next push overwrites that engine's outputs, `sink`
+ * (may be NULL) is called on the calling thread with: proto; replay = 1 (step 6) or 0 (step 7); the engine, whose
+ * outputs the callee reads with the engine's own calls (dh_engine_frames, dh_engine_read_events, ...); d_counts
+ * [n_channels], device: channel b took part in this push when d_counts[b] != 0; d_start [n_channels], device; skip;
+ * live_first = total - n.  The first input sample of channel b's block has stream index d_start[b] + skip in a replay
+ * and live_first in a live push.  d_counts and d_start are the monitor's own arrays: valid during the call only.
+ *
+ * What the host reads.  Steps A and B each add up one fixed-size summary block on the device -- how many channels are
+ * scanned, how many have scan_reset, how many are live per protocol; how many are new per protocol and the smallest
+ * start among them -- and dh_monitor_push reads that block at most twice per round, after step A and after step B: one
+ * small copy each, which synchronises.  It reads nothing whose size grows with n_channels, uploads nothing per channel,
+ * and issues a fixed number of launches per engine however many channels are reset.
+ *
+ * DH_EINVAL: null handle or configuration, struct_size too small, n_channels outside 1 .. 65536, max_samples = 0, depth
+ * outside 1 .. 2^24, protos == 0 or with bits other than DH_PROTO_DMR .. DH_PROTO_DSTAR, n > max_samples, stride < n, null
+ * rows with n != 0.  dh_monitor_engine / dh_monitor_scan_engine return the owned handles (NULL: not configured, or out of
+ * range) for reading outputs and statistics; they stay the monitor's and go with dh_monitor_destroy.
+ * ---------------------------------------------------------------------- */
+typedef struct dh_monitor dh_monitor;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(dh_monitor_config) */
+    int32_t  device;
+    uint32_t n_channels, max_samples, depth, lead, confirm, release;
+    uint32_t protos;               /* bit DH_PROTO_x set: that protocol is decoded */
+    void*    stream;               /* hipStream_t; NULL = default stream */
+} dh_monitor_config;
+typedef struct {
+    int32_t proto, replay;
+    dh_engine* engine;
+    const uint32_t* d_counts;      /* [B] samples each channel brought in this push */
+    const uint64_t* d_start;       /* [B] */
+    uint64_t skip, live_first;
+} dh_monitor_push_info;
+typedef void (*dh_monitor_sink)(void* user, const dh_monitor_push_info* info);
+int  dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out);
+void dh_monitor_destroy(dh_monitor* m);
+/* ring, every engine and the state back to where create left them */
+int  dh_monitor_reset(dh_monitor* m);
+int  dh_monitor_push(dh_monitor* m, const float* d_rows, size_t stride, size_t n,
+                     const uint32_t* d_counts, dh_monitor_sink sink, void* user);
+int  dh_monitor_state(dh_monitor* m, uint8_t* h_assigned, uint64_t* h_start);       /* synchronises */
+int  dh_monitor_total(dh_monitor* m, uint64_t* total);
+dh_engine* dh_monitor_engine(dh_monitor* m, int proto);
+dh_engine* dh_monitor_scan_engine(dh_monitor* m, int front /* 0..3: wide10, narrow20, fsk10, fsk40i */);
 
 /* ------------------------------------------------------------------------
  * Diagnostics: the RRC output scaling `(float)((double)sum / gain)` of
