@@ -332,6 +332,12 @@ class Engine:
                "dh_engine_timing_stats", self.ctx.lib)
         return blocks, ordered
 
+    def dmr_pass_b_stats(self):
+        """(lanes, scalar) per channel: chunks of the DMR decoder whose slot / superframe bookkeeping (pass B) ran one burst per
+        lane, and chunks that took the burst-serial pass (irregular traffic, the chunk behind a sync search, or
+        DH_DMR_SCALAR_PASS_B=1 when the engine was created), since the channel's last reset."""
+        return self.debug_header(100 + 30), self.debug_header(100 + 31)
+
     def debug_header(self, word):
         out = np.zeros(self.B, np.uint32)
         _check(self.ctx.lib.dh_engine_debug_header(self._h, word, out.ctypes.data_as(C.c_void_p)), "dh_engine_debug_header", self.ctx.lib)

@@ -65,6 +65,8 @@ enum {
     DS_SLOT_SYNC0 = 6, DS_SLOT_SYNC1 = 7, DS_ACTIVE_SLOT = 8, DS_SLOT_FILTER = 9, DS_SUPERFRAME0 = 10,
     DS_SUPERFRAME1 = 11, DS_EMB_OFF0 = 12, DS_EMB_OFF1 = 13, DS_EMB_DATA0 = 14 /*4 words*/, DS_EMB_DATA1 = 18,
     DS_CONSUMED = 22, DS_CARRY = 23, DS_SLOT_FILTER_DECODER = 24, DS_HAS_FICH = 25, DS_FICH = 26, DS_EXPECT_SUB = 27,
+    // DMR statistics (Engine.dmr_pass_b_stats): chunks whose pass B ran lane-parallel / burst by burst, since the last reset
+    DS_PASS_B_LANES = 30, DS_PASS_B_SCALAR = 31,
     // NXDN (Nxdn::FramedPhase, nxdn_phase.hpp:31-40): LICH + 1 (0 = none yet), collected SACCH fragments (bit i),
     // their bytes 1..4 as big-endian words
     DS_NX_LICH = 2, DS_NX_HAVE = 3, DS_NX_SACCH0 = 4,
@@ -87,6 +89,7 @@ struct DhDecParams {
     uint32_t* overflow;
     const DhFecTables* T;
     uint32_t n_channels;
+    uint32_t dmr_scalar_pass_b;                // 1: pass B of the DMR decoder always burst by burst (DH_DMR_SCALAR_PASS_B in the environment when the engine is created: A/B runs, tests)
 };
 
 #define DH_PLANE_WORDS 8            // 512 symbols: a YSF frame is 480, a DMR burst + search window 154
@@ -381,9 +384,10 @@ DH_HD const DhFecTables& dh_lds_tables(const DhDecShared& S) { return *reinterpr
 //   planes  the chunk's dibits -> two bit planes in LDS (16 dibits per lane and load, packed in registers)
 //   pass A  one burst per LANE: its 144 dibits as 2 x 5 words from the planes, every block code of the burst decoded lane-locally
 //           (bit-sliced Hamming(13,9) over the BPTC columns), results condensed into a summary word
-//   pass B  the reference's state machine, burst after burst, on the summaries: scalar code only (v_readlane in, v_writelane
-//           out), leaves one word of event / output flags per burst; a burst that sends the decoder back to its SyncPhase
-//           ends the chunk
+//   pass B  the reference's state machine on the summaries, leaves one word of event / output flags per burst.  A regular chunk
+//           (dh_dmr_pass_b_lanes: the slot alternates, every burst carries a sync or a good EMB inside a voice superframe) is
+//           taken one burst per lane, closed forms over wave-wide votes; any other chunk burst after burst, scalar code only
+//           (v_readlane in, v_writelane out): a burst that sends the decoder back to its SyncPhase ends the chunk
 //   pass C  one burst per lane again: embedded LCs, event records (offsets by a vote-based prefix sum), voice payloads
 //           (staged in LDS, stored coalesced)
 // The SyncPhase search (dmr_phase.cpp:35-47) is unchanged.
@@ -756,6 +760,172 @@ DH_HD uint32_t dh_dmr_pass_b(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_LAN
     return to_sync ? k - 1u : k;
 }
 
+// index of the highest set bit, x != 0
+DH_HD int dh_top64(uint64_t x) {
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+    return 63 - __clzll((long long) x);
+#else
+    return 63 - __builtin_clzll(x);
+#endif
+}
+// a field of lane j, j a per-lane value (ds_bpermute; every lane of the wave takes part)
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#define DH_LS_GATHER(name, field, j) ((uint32_t) __shfl((int) (name).field, (int) (j), DH_WAVE))
+#else
+#define DH_LS_GATHER(name, field, j) ((uint32_t) (name)[j].field)
+#endif
+
+// pass B, lane-parallel: the same bookkeeping for a REGULAR chunk, one burst per lane as in passes A and C.  A chunk is regular when,
+// from the state on entry, slot != -1; every burst has a TACT that names the expected slot (the slot alternates, no switch, no
+// DH_DF_RESET_OTHER); every burst carries a sync, or sits in a voice superframe of its slot with sf < 5 and has a good EMB (no burst is
+// `lost`, so none returns to the SyncPhase); and the voice payloads fit `room`.  Then nothing a burst needs from its predecessors has to
+// be walked to:
+//   slot              lane parity (lane k: entry slot ^ 1 ^ k & 1); "the bursts of my slot in front of me" = a parity mask below the lane
+//   stab, sync_count, ss   only ever count up: saturating sums over the chunk
+//   st, sf            from the last sync burst of the slot (top bit of sync votes & same-slot-below), else the entry word
+//   eo                collecting bursts (LCSS != 0) since the slot's last reset point -- a sync burst or a STOP (0 behind it), a START
+//                     (0 in front of it) -- else counted on from the entry word; capped at 4, a burst writes index eo while eo <= 3
+//   embedded words    index i of a slot = the fragment of the last burst that wrote index i (votes per index), else the carried word
+//   active            claims (voice burst of a slot the filter lets through) and releases (data sync) as two votes; the value changes
+//                     only at the first claim while free and at the holder's first release, so it is walked from change to change
+//                     on the masks, not burst by burst
+// The lanes compute all this as if the chunk were regular, then the conditions themselves are voted on; if a lane fails, or the voice
+// payloads do not fit, NOTHING has been written and the caller runs dh_dmr_pass_b on the whole chunk.  On success it leaves what the
+// scalar pass leaves: every burst's flag word, S.dmr.emb_words of the bursts that close an embedded LC, the carried embedded words, M and
+// room (nflag = consumed = n, to_sync = false, overflow untouched).
+DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_LANE_STRUCT_REF(DhDmrLane, L), uint32_t n, uint32_t& room) {
+    if (M.slot < 0 || n == 0u) return false;
+    const uint64_t valid = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    constexpr uint64_t EVEN = 0x5555555555555555ull;
+    const uint32_t e = (uint32_t) (M.slot ^ 1) & 1u;                   // the slot of lane 0; the even lanes carry it, the odd ones the other
+    const int st_ev = e ? M.st1 : M.st0, sf_ev = e ? M.sf1 : M.sf0, eo_ev = e ? M.eo1 : M.eo0;
+    const int st_od = e ? M.st0 : M.st1, sf_od = e ? M.sf0 : M.sf1, eo_od = e ? M.eo0 : M.eo1;
+    const uint32_t filter = (uint32_t) M.filter;
+    // votes on the summaries: TACT as expected, voice / data sync, and among the bursts without a sync the EMB's START / STOP / CONTINUATION
+    uint64_t tact = 0, vs = 0, dsy = 0, lstart = 0, lstop = 0, lcont = 0;
+    DH_FOR_LANES(lane) {
+        const uint32_t sm = DH_LS(L, lane).summary;
+        const bool in = (uint32_t) lane < n;
+        const uint32_t sy = (sm >> DH_DS_SYNC_SHIFT) & 3u;
+        const uint32_t lcss = (sy == 0u && (sm & DH_DS_EMB_OK)) ? (sm >> DH_DS_LCSS_SHIFT) & 3u : 0u;
+        DH_BALLOT_ACC(tact, in && (sm & 3u) == (DH_DS_HAS_TACT | (e ^ ((uint32_t) lane & 1u)) << DH_DS_TACT_SLOT_SHIFT), lane);
+        DH_BALLOT_ACC(vs, in && sy == DH_SYNCTYPE_VOICE, lane); DH_BALLOT_ACC(dsy, in && sy == DH_SYNCTYPE_DATA, lane);
+        DH_BALLOT_ACC(lstart, in && lcss == 1u, lane); DH_BALLOT_ACC(lstop, in && lcss == 2u, lane); DH_BALLOT_ACC(lcont, in && lcss == 3u, lane);
+    }
+    // every lane's burst as if the chunk were regular
+    uint64_t regular = 0, claim = 0, release = 0, lcm = 0, wr[4] = { 0, 0, 0, 0 };
+    DH_LANE_VALUE(uint32_t, pk);                                       // flag word | (st | sf << 2 | eo << 5 behind the burst) << 16
+    DH_FOR_LANES(lane) {
+        const uint32_t sm = DH_LS(L, lane).summary;
+        const bool in = (uint32_t) lane < n, odd = (lane & 1) != 0;
+        const uint64_t below = (EVEN << (lane & 1)) & ((1ull << lane) - 1ull);      // the bursts of my slot in front of me
+        const uint32_t sy = (sm >> DH_DS_SYNC_SHIFT) & 3u;
+        const uint32_t slot = e ^ ((uint32_t) lane & 1u);
+        // the slot's sync type and superframe count in front of this burst
+        const uint64_t rs = (vs | dsy) & below;
+        int st_prev, sf_prev;
+        if (rs) { const int j = dh_top64(rs); st_prev = ((vs >> j) & 1ull) ? DH_SYNCTYPE_VOICE : DH_SYNCTYPE_DATA; sf_prev = ((lane - j) >> 1) - 1; }
+        else { st_prev = odd ? st_od : st_ev; sf_prev = (odd ? sf_od : sf_ev) + (lane >> 1); }
+        // collecting bursts since the slot's last reset point
+        const uint64_t re = (vs | dsy | lstart | lstop) & below;
+        uint32_t c;
+        if (re) { const int j = dh_top64(re); c = (uint32_t) ((lstart >> j) & 1ull) + (uint32_t) dh_popc64(lcont & below & ~((2ull << j) - 1ull)); }
+        else c = (uint32_t) (odd ? eo_od : eo_ev) + (uint32_t) dh_popc64(lcont & below);
+        const uint32_t eo_prev = dh_min<uint32_t>(c, 4u);
+        uint32_t fl = slot ? (uint32_t) DH_DF_SLOT : 0u, st, sf, eo, widx = 4u;
+        bool ok = ((tact >> lane) & 1ull) != 0, lc = false;
+        if (sy > 0u) {
+            fl |= DH_DF_SYNC | ((st_prev == DH_SYNCTYPE_VOICE && sy != DH_SYNCTYPE_VOICE) ? (uint32_t) DH_DF_SOFT : 0u);
+            st = sy; sf = 0u; eo = 0u;
+        } else {
+            ok = ok && st_prev == DH_SYNCTYPE_VOICE && sf_prev < 5 && (sm & DH_DS_EMB_OK);
+            const uint32_t lcss = (sm >> DH_DS_LCSS_SHIFT) & 3u;
+            st = DH_SYNCTYPE_VOICE; sf = (uint32_t) (sf_prev + 1) & 7u;
+            fl |= DH_DF_EMB;
+            if (lcss == 0u) eo = eo_prev;
+            else {
+                widx = lcss == 1u ? 0u : eo_prev;                       // (4: the collector is full, nothing is written)
+                eo = lcss == 2u ? 0u : dh_min<uint32_t>(widx + 1u, 4u);
+                lc = lcss == 2u && eo_prev >= 2u;                       // eo >= 3 behind the STOP's own fragment
+            }
+            if (lc) fl |= DH_DF_EMB_LC;
+        }
+        if (st != DH_SYNCTYPE_VOICE) fl |= (sm >> (DH_DS_DFLAGS_SHIFT - 6)) & (DH_DF_SLOTTYPE | DH_DF_BPTC | DH_DF_BPTC_TAIL);
+        DH_BALLOT_ACC(regular, in && ok, lane);
+        DH_BALLOT_ACC(claim, in && st == DH_SYNCTYPE_VOICE && ((slot + 1u) & filter) != 0u, lane);
+        DH_BALLOT_ACC(release, in && st != DH_SYNCTYPE_VOICE, lane);
+        DH_BALLOT_ACC(lcm, in && lc, lane);
+        DH_BALLOT_ACC(wr[0], in && widx == 0u, lane); DH_BALLOT_ACC(wr[1], in && widx == 1u, lane);
+        DH_BALLOT_ACC(wr[2], in && widx == 2u, lane); DH_BALLOT_ACC(wr[3], in && widx == 3u, lane);
+        DH_LV(pk, lane) = fl | (st | sf << 2 | eo << 5) << 16;
+    }
+    if (regular != valid) return false;
+    // the active slot, from change to change: free until the first claim, held until the holder's slot releases
+    // (the lanes of slot p: EVEN << (e ^ p))
+    int active = M.active;
+    uint64_t voice = 0, rest = ~0ull;                                  // rest: the lanes still to come
+    for (;;) {
+        if (active < 0) {
+            const uint64_t m = claim & rest;
+            if (!m) break;
+            const int j = dh_ffs64(m);
+            active = (int) (e ^ ((uint32_t) j & 1u));
+            rest = ~0ull << j;                                         // (the claiming burst is the first the slot holds)
+        } else {
+            const uint64_t mine = (EVEN << (e ^ (uint32_t) active)) & rest, r = release & mine;
+            const uint64_t held = r ? mine & ((1ull << dh_ffs64(r)) - 1ull) : mine;
+            voice |= claim & held;
+            if (!r) break;
+            active = -1;
+            rest = (~0ull << dh_ffs64(r)) << 1;
+        }
+    }
+    const uint32_t nvoice = (uint32_t) dh_popc64(voice);
+    if (27u * nvoice > room) return false;
+    // the words of the embedded LCs that close in this chunk (pass C decodes them), then every burst's flag word
+    if (lcm) {
+        uint32_t carried[2][4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { carried[0][i] = s[DS_EMB_DATA0 + i]; carried[1][i] = s[DS_EMB_DATA1 + i]; }
+        DH_FOR_LANES(lane) {
+            const uint64_t upto = (EVEN << (lane & 1)) & ((2ull << lane) - 1ull);       // the bursts of my slot up to and with me
+            const uint32_t slot = e ^ ((uint32_t) lane & 1u);
+            uint32_t w[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint64_t m = wr[i] & upto;
+                const uint32_t g = DH_LS_GATHER(L, frag, m ? dh_top64(m) : lane);
+                w[i] = m ? g : (slot ? carried[1][i] : carried[0][i]);
+            }
+            if ((lcm >> lane) & 1ull) { S.dmr.emb_words[lane][0] = w[0]; S.dmr.emb_words[lane][1] = w[1]; S.dmr.emb_words[lane][2] = w[2]; S.dmr.emb_words[lane][3] = w[3]; }
+        }
+    }
+    DH_FOR_LANES(lane) {
+        if ((uint32_t) lane < n) DH_LS(L, lane).flags = (DH_LV(pk, lane) & 0xFFFFu) | (((voice >> lane) & 1ull) ? (uint32_t) DH_DF_VOICE : 0u);
+    }
+    // the machine behind the chunk
+#pragma unroll
+    for (uint32_t p = 0; p < 2u; p++) {
+        const uint64_t mine = (EVEN << (e ^ p)) & valid;
+        if (!mine) continue;
+        const uint32_t x = DH_LV_READ(pk, dh_uniform((uint32_t) dh_top64(mine))) >> 16;
+        const int st = (int) (x & 3u), sf = (int) ((x >> 2) & 7u), eo = (int) ((x >> 5) & 7u), cnt = dh_popc64(mine);
+        if (p) { M.st1 = st; M.sf1 = sf; M.eo1 = eo; M.ss1 = dh_min(M.ss1 + cnt, 5); }
+        else { M.st0 = st; M.sf0 = sf; M.eo0 = eo; M.ss0 = dh_min(M.ss0 + cnt, 5); }
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; i++) {
+            const uint64_t m = wr[i] & mine;
+            if (m) s[(p ? DS_EMB_DATA1 : DS_EMB_DATA0) + i] = DH_LS_READ(L, frag, dh_uniform((uint32_t) dh_top64(m)));
+        }
+    }
+    M.slot = (int) (e ^ ((n - 1u) & 1u));
+    M.stab = dh_min(M.stab + (int) n, 100);
+    M.sync_count = dh_min(M.sync_count + (int) n, 5);
+    M.active = active;
+    room -= 27u * nvoice;
+    return true;
+}
+
 // exclusive prefix sum over the lanes of a small per-lane count (< 16), by votes
 #if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
 #define DH_LANES_BELOW(mask, lane) ((uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) ((mask) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) (mask), 0u)))
@@ -832,7 +1002,8 @@ DH_HD void dh_dmr_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uin
         for (;;) {
             uint32_t room = dh_uniform(P.out_cap - c.nout);
             bool ovf = false;
-            ncons = dh_dmr_pass_b(M, s, S, L, n, room, nflag, to_sync, ovf);
+            if (!P.dmr_scalar_pass_b && dh_dmr_pass_b_lanes(M, s, S, L, n, room)) { ncons = nflag = n; to_sync = false; s[DS_PASS_B_LANES]++; }
+            else { ncons = dh_dmr_pass_b(M, s, S, L, n, room, nflag, to_sync, ovf); s[DS_PASS_B_SCALAR]++; }
             DH_DMARK("passC");
             DH_BARRIER();                                              // the embedded-signalling words are in LDS
             // pass C, part 1: which events does every burst emit, and where do they go

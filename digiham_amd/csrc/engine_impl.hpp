@@ -15,6 +15,7 @@
 //   rrc_hist      [B][nz] f32          only with DH_FLAG_KEEP_FILTERED
 #pragma once
 
+#include <stdlib.h>
 #include <string.h>
 #include <new>
 #include <vector>
@@ -263,6 +264,8 @@ struct Engine {
         dec.out = frames; dec.out_stride = L.out_cap; dec.out_cap = L.out_cap; dec.out_count = frame_count;
         dec.events = events; dec.ev_stride = L.ev_cap; dec.ev_cap = L.ev_cap; dec.ev_count = ev_count;
         dec.overflow = overflow; dec.T = tables; dec.n_channels = L.B;
+        const char* scalar_b = getenv("DH_DMR_SCALAR_PASS_B");         // "1": the DMR decoder's pass B burst by burst for every chunk (A/B runs, tests)
+        dec.dmr_scalar_pass_b = scalar_b && atoi(scalar_b) > 0 ? 1u : 0u;
     }
 
     void destroy() { bufs.free_all(); }
