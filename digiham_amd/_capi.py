@@ -54,6 +54,20 @@ class MonitorPushInfo(C.Structure):
                 ("d_start", C.c_void_p), ("skip", C.c_uint64), ("live_first", C.c_uint64)]
 
 
+class OutpackConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("max_entries", C.c_uint32), ("max_events", C.c_uint32),
+                ("max_frame_bytes", C.c_uint64), ("stream", C.c_void_p)]
+
+
+class OutpackHeader(C.Structure):
+    _fields_ = [("n_entries", C.c_uint32), ("n_events", C.c_uint32), ("frame_bytes", C.c_uint64), ("dropped", C.c_uint32),
+                ("appends", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# dh_outpack_entry
+OUTPACK_ENTRY_DTYPE = [("channel", "<u4"), ("user", "<u4"), ("tag", "<u8"), ("n_frame_bytes", "<u4"), ("n_events", "<u4"),
+                       ("frame_offset16", "<u4"), ("event_index", "<u4")]
+
 MONITOR_SINK = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(MonitorPushInfo))       # dh_monitor_sink
 MONITOR_FRONTS = ("wide10", "narrow20", "fsk10", "fsk40i")                    # dh_monitor_scan_engine's index
 
@@ -132,6 +146,11 @@ def declare(L, lenient=False):
         "dh_monitor_create": [C.POINTER(MonitorConfig), C.POINTER(vp)], "dh_monitor_reset": [vp],
         "dh_monitor_push": [vp, vp, sz, sz, vp, MONITOR_SINK, vp], "dh_monitor_state": [vp, vp, vp],
         "dh_monitor_total": [vp, C.POINTER(C.c_uint64)],
+        "dh_outpack_create": [C.POINTER(OutpackConfig), C.POINTER(vp)], "dh_outpack_clear": [vp],
+        "dh_outpack_append": [vp, vp, vp, vp, C.c_uint64, u32],
+        "dh_outpack_read": [vp, C.POINTER(OutpackHeader), vp, vp, vp],
+        "dh_outpack_device": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+        "dh_monitor_push_packed": [vp, vp, sz, sz, vp, vp],
     }
     for name, args in sig.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
@@ -141,7 +160,7 @@ def declare(L, lenient=False):
         fn.restype = C.c_int
     L.dh_engine_destroy.argtypes = [vp]
     L.dh_engine_destroy.restype = None
-    for name in ("dh_channelizer_destroy", "dh_preroll_destroy", "dh_monitor_destroy"):
+    for name in ("dh_channelizer_destroy", "dh_preroll_destroy", "dh_monitor_destroy", "dh_outpack_destroy"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [vp]
             getattr(L, name).restype = None
@@ -168,6 +187,8 @@ EXPORTED_SYMBOLS = [
     "dh_preroll_gather", "dh_preroll_gather_device", "dh_engine_reset_channels",
     "dh_monitor_create", "dh_monitor_destroy", "dh_monitor_reset", "dh_monitor_push", "dh_monitor_state", "dh_monitor_total",
     "dh_monitor_engine", "dh_monitor_scan_engine",
+    "dh_outpack_create", "dh_outpack_destroy", "dh_outpack_clear", "dh_outpack_append", "dh_outpack_read", "dh_outpack_device",
+    "dh_monitor_push_packed",
 ]
 
 _LIB = None

@@ -772,6 +772,72 @@ class Monitor:
 
 PROTO_NAMES = {_capi.PROTO[name]: name for name in ("dmr", "ysf", "nxdn", "pocsag", "dstar")}
 
+OUTPACK_ENTRY_DTYPE = np.dtype(_capi.OUTPACK_ENTRY_DTYPE)
+
+
+class OutPack:
+    """What the pushes of a round produced, compacted on the device (dh_outpack; include/digiham_amd.h "Packed read-out").
+
+    append(engine, ...) is asynchronous on the engine's stream and may follow any number of pushes of any engines that
+    share the pack's stream; read() synchronises once and copies what was kept: (header, entries, events, frames) with
+    header a dict of the dh_outpack_header fields, entries an OUTPACK_ENTRY_DTYPE array, events an EVENT_DTYPE array and
+    frames uint8.  Entry i owns frames[16 * frame_offset16:][:n_frame_bytes] and events[event_index:][:n_events].  A pack
+    that had to drop something says so in header["dropped"] (and `rc` is DH_ECAPACITY); what was kept is delivered."""
+
+    def __init__(self, max_entries, max_events, max_frame_bytes, ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        lib, mem = self.ctx.lib, self.ctx.mem
+        self.max_entries, self.max_events, self.max_frame_bytes = int(max_entries), int(max_events), int(max_frame_bytes)
+        cfg = _capi.OutpackConfig(C.sizeof(_capi.OutpackConfig), getattr(mem, "index", 0), self.max_entries, self.max_events,
+                                  self.max_frame_bytes, mem.stream())
+        h = C.c_void_p()
+        _check(lib.dh_outpack_create(C.byref(cfg), C.byref(h)), "dh_outpack_create", lib)
+        self._h = h
+        # dh_outpack_read takes arrays of the create capacities; only what a read fills is ever touched
+        self._entries = np.empty(self.max_entries, OUTPACK_ENTRY_DTYPE)
+        self._events = np.empty(self.max_events, EVENT_DTYPE)
+        self._frames = np.empty(self.max_frame_bytes, np.uint8)
+        self._keep, self.rc = [], 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx.lib.dh_outpack_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def clear(self):
+        _check(self.ctx.lib.dh_outpack_clear(self._h), "dh_outpack_clear", self.ctx.lib)
+
+    def append(self, engine, mask=None, tag=None, tag_add=0, user=0):
+        """mask: [B] uint32 (non-zero: the channel takes part) or None; tag: [B] uint64 or None; numpy or device arrays."""
+        mem = self.ctx.mem
+        dev = lambda a, dt: None if a is None else a if mem.is_device_array(a) and not isinstance(a, np.ndarray) else mem.from_numpy(np.ascontiguousarray(a, dt))
+        m, t = dev(mask, np.uint32), dev(tag, np.uint64)
+        self._keep.append((m, t))       # the launches are asynchronous: keep the arrays alive until the next read
+        _check(self.ctx.lib.dh_outpack_append(self._h, getattr(engine, "_h", engine), mem.ptr(m) if m is not None else None,
+                                              mem.ptr(t) if t is not None else None, int(tag_add) & 0xFFFFFFFFFFFFFFFF, int(user)),
+               "dh_outpack_append", self.ctx.lib)
+
+    def read(self):
+        lib, hdr = self.ctx.lib, _capi.OutpackHeader()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.rc = lib.dh_outpack_read(self._h, C.byref(hdr), ptr(self._entries), ptr(self._events), ptr(self._frames))
+        self._keep = []
+        if self.rc != _capi.DH_ECAPACITY:
+            _check(self.rc, "dh_outpack_read", lib)
+        header = {k: int(getattr(hdr, k)) for k in ("n_entries", "n_events", "frame_bytes", "dropped", "appends")}
+        return (header, self._entries[:hdr.n_entries].copy(), self._events[:hdr.n_events].copy(), self._frames[:hdr.frame_bytes].copy())
+
+    def blocks(self):
+        """read(), as a list of {"channel", "user", "tag", "frames", "events"} in the pack's order."""
+        _, entries, events, frames = self.read()
+        out = []
+        for en in entries.tolist():
+            b, user, tag, fc, ec, off, ei = en
+            out.append({"channel": b, "user": user, "tag": tag, "frames": frames[16 * off:16 * off + fc], "events": events[ei:ei + ec]})
+        return out
+
 
 class DeviceMonitor:
     """Monitor behind the C ABI (dh_monitor; include/digiham_amd.h "Band monitor"): the same constructor arguments, the same
@@ -782,10 +848,13 @@ class DeviceMonitor:
     starts and the engine's frames() / events() (read_rows for fewer than a sixteenth of the channels), as Monitor does.
 
     `assigned` and `start` are read from the device when asked for (once per round at most); `engines` and
-    `scanner.engines` are views of the handle's engines and die with it."""
+    `scanner.engines` are views of the handle's engines and die with it.
+
+    packed=True: the monitor owns an OutPack sized so that a round can never drop, and push() is clear,
+    dh_monitor_push_packed, one read: no sink, no read-back per engine push, copies sized by what was decoded."""
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False):
         self.ctx = ctx if ctx is not None else Context(device=device)
         lib, mem = self.ctx.lib, self.ctx.mem
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
@@ -811,8 +880,24 @@ class DeviceMonitor:
         self.scanner_engines = self.scanner.engines
         self._sink = _capi.MONITOR_SINK(self._on_push)
         self._blocks, self._error, self._state, self._keep = None, None, None, None
+        self.pack = None
+        if packed:
+            # per protocol: the engine's row capacities x B x the chunks of the longest replay (a channel is replayed or
+            # live in a round, never both)
+            chunks = max(1, -(-self.depth // self.max_samples))
+            n_ev = n_fb = 0
+            for e in self.engines.values():
+                p, stride, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
+                _check(lib.dh_engine_frames(e._h, C.byref(p), C.byref(stride), C.byref(cnt)), "dh_engine_frames", lib)
+                n_fb += stride.value * self.B * chunks
+                _check(lib.dh_engine_events(e._h, C.byref(p), C.byref(stride), C.byref(cnt)), "dh_engine_events", lib)
+                n_ev += stride.value * self.B * chunks
+            self.pack = OutPack(min(len(self.engines) * self.B * chunks, 0xFFFFFFFF), min(n_ev, 0xFFFFFFFF), min(n_fb, (1 << 36) - 16), ctx=self.ctx)
 
     def close(self):
+        if getattr(self, "pack", None) is not None:
+            self.pack.close()
+            self.pack = None
         if getattr(self, "_h", None):
             for e in list(self.engines.values()) + list(self.scanner.engines.values()):
                 e.close()
@@ -886,6 +971,18 @@ class DeviceMonitor:
         if counts is not None and not mem.is_device_array(counts):
             counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
         self._keep = (x, counts)
+        if self.pack is not None:
+            self._state = None
+            self.pack.clear()
+            _check(self.ctx.lib.dh_monitor_push_packed(self._h, mem.ptr(x), stride, n, mem.ptr(counts) if counts is not None else None, self.pack._h),
+                   "dh_monitor_push_packed", self.ctx.lib)
+            header, entries, events, frames = self.pack.read()
+            if header["dropped"]:
+                raise DhError(_capi.DH_ECAPACITY, "DeviceMonitor.push", "the pack dropped %d blocks" % header["dropped"])
+            blocks = [{"channel": b, "proto": PROTO_NAMES[user & 255], "first_sample": tag, "frames": frames[16 * off:16 * off + fc], "events": events[ei:ei + ec]}
+                      for b, user, tag, fc, ec, off, ei in entries.tolist()]
+            blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
+            return blocks
         self._blocks, self._error, self._state = [], None, None
         rc = self.ctx.lib.dh_monitor_push(self._h, mem.ptr(x), stride, n, mem.ptr(counts) if counts is not None else None, self._sink, None)
         blocks, self._blocks = self._blocks, None

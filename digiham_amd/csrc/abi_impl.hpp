@@ -28,11 +28,13 @@
 #include <numeric>
 
 #include "engine_impl.hpp"
+#include "outpack_core.hpp"
 
 static_assert(sizeof(dh_event) == 32, "dh_event layout");
 
 struct dh_engine {
     dh::Engine<DH_BACKEND> impl;
+    int device = 0; void* stream = nullptr;             // the configuration's: what a handle that works on this engine's outputs must share
     auto scope() const { return impl.be.scope(); }      // (as dh_channelizer::scope: DH_ON_DEVICE takes either handle)
 };
 // every entry that touches the device runs on its handle's device (an engine's, a channelizer's) whatever the calling
@@ -120,6 +122,7 @@ int dh_engine_create(const dh_engine_config* cfg, dh_engine** out) {
     int rc = e->impl.be.open(cfg->device, cfg->stream);
     if (rc == DH_OK) { DH_ON_DEVICE(e); rc = e->impl.init(*cfg); if (rc != DH_OK) e->impl.destroy(); }
     if (rc != DH_OK) { delete e; return rc; }
+    e->device = cfg->device; e->stream = cfg->stream;
     *out = e;
     return DH_OK;
 }
@@ -588,6 +591,111 @@ int dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t ski
 
 }  // extern "C"
 
+// ---- the packed read-out (outpack_core.hpp): host bookkeeping over the backend's memory and two launches ---------------
+//   dh_be_outpack_scan(BE& engine_backend, const DhOutpack& P);      candidates, fit rule, entries, header
+//   dh_be_outpack_copy(BE& engine_backend, const DhOutpack& P);      one workgroup per entry of this append
+// (engine.hip defines the gfx950 ones; outpack_core.hpp the CPU harness's.)  Both go out on the ENGINE's stream, behind the
+// push whose rows they read; the host knows none of the totals.
+static_assert(sizeof(dh_outpack_header) == 32 && sizeof(dh_outpack_entry) == 32, "dh_outpack layout");
+struct dh_outpack {
+    DH_BACKEND be;
+    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
+    int device = 0; void* stream = nullptr;
+    DhOutpack P{};                                      // what create fixes; an append adds the engine's rows and its arguments
+
+    auto scope() const { return be.scope(); }
+    void release() { bufs.free_all(); }
+    int clear() { return be.zero(P.hdr, sizeof(dh_outpack_header)) ? DH_EDEVICE : DH_OK; }
+    int init(const dh_outpack_config& c) {
+        P.max_entries = c.max_entries; P.max_events = c.max_events; P.max_frame_bytes = c.max_frame_bytes;
+        bool ok = bufs.alloc(P.hdr, 1);
+        ok &= bufs.alloc(P.scratch, 2);
+        ok &= bufs.alloc(P.entries, c.max_entries);
+        ok &= bufs.alloc(P.events, c.max_events);
+        ok &= bufs.alloc(P.frames, (size_t) c.max_frame_bytes);
+        if (!ok) return DH_ENOMEM;
+        const int rc = clear();
+        if (rc != DH_OK) return rc;
+        return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    bool shares_stream(int dev, void* s) const { return dev == device && s == stream; }
+    int append(dh_engine* e, const uint32_t* mask, const uint64_t* tag, uint64_t tag_add, uint32_t user) {
+        auto& E = e->impl;
+        if (!E.frames || !shares_stream(e->device, e->stream)) return DH_EINVAL;       // (no frames: proto == DH_PROTO_NONE)
+        DhOutpack A = P;
+        A.src_frames = E.frames; A.src_fc = E.frame_count; A.out_cap = E.L.out_cap;
+        A.src_events = E.events; A.src_ec = E.ev_count; A.ev_cap = E.L.ev_cap;
+        A.mask = mask; A.tag = tag; A.tag_add = tag_add; A.user = user; A.B = E.L.B;
+        if (dh_be_outpack_scan(E.be, A) || dh_be_outpack_copy(E.be, A)) return DH_EDEVICE;
+        return DH_OK;
+    }
+    int read(dh_outpack_header* hdr, dh_outpack_entry* entries, dh_event* events, uint8_t* frames) {
+        dh_outpack_header h;
+        if (be.download(&h, P.hdr, sizeof(h))) return DH_EDEVICE;                       // (synchronises)
+        if (hdr) *hdr = h;
+        if (entries && h.n_entries && be.download(entries, P.entries, sizeof(dh_outpack_entry) * h.n_entries)) return DH_EDEVICE;
+        if (events && h.n_events && be.download(events, P.events, sizeof(dh_event) * h.n_events)) return DH_EDEVICE;
+        if (frames && h.frame_bytes && be.download(frames, P.frames, (size_t) h.frame_bytes)) return DH_EDEVICE;
+        return h.dropped ? DH_ECAPACITY : DH_OK;
+    }
+};
+
+extern "C" {
+
+int dh_outpack_create(const dh_outpack_config* cfg, dh_outpack** out) {
+    if (!cfg || !out) return DH_EINVAL;
+    *out = nullptr;
+    if (cfg->struct_size < sizeof(dh_outpack_config) || cfg->max_entries == 0 || (cfg->max_frame_bytes & 15u) ||
+        cfg->max_frame_bytes > ((uint64_t) 1 << 36) - 16u)
+        return DH_EINVAL;
+    dh_outpack* p = new (std::nothrow) dh_outpack;
+    if (!p) return DH_ENOMEM;
+    int rc = p->be.open(cfg->device, cfg->stream);
+    if (rc == DH_OK) {
+        DH_ON_DEVICE(p);
+        p->device = cfg->device; p->stream = cfg->stream;
+        rc = p->init(*cfg);
+        if (rc != DH_OK) p->release();
+    }
+    if (rc != DH_OK) { delete p; return rc; }
+    *out = p;
+    return DH_OK;
+}
+
+void dh_outpack_destroy(dh_outpack* p) {
+    if (!p) return;
+    {
+        DH_ON_DEVICE(p);
+        p->be.sync();
+        p->be.close();
+        p->release();
+    }
+    delete p;
+}
+
+int dh_outpack_clear(dh_outpack* p) { if (!p) return DH_EINVAL; DH_ON_DEVICE(p); return p->clear(); }
+int dh_outpack_append(dh_outpack* p, dh_engine* e, const uint32_t* d_mask, const uint64_t* d_tag, uint64_t tag_add, uint32_t user) {
+    if (!p || !e) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->append(e, d_mask, d_tag, tag_add, user);
+}
+int dh_outpack_read(dh_outpack* p, dh_outpack_header* h_hdr, dh_outpack_entry* h_entries, dh_event* h_events, uint8_t* h_frames) {
+    if (!p) return DH_EINVAL;
+    DH_ON_DEVICE(p);
+    return p->read(h_hdr, h_entries, h_events, h_frames);
+}
+int dh_outpack_device(dh_outpack* p, const dh_outpack_header** d_hdr, const dh_outpack_entry** d_entries, const dh_event** d_events,
+                      const uint8_t** d_frames) {
+    if (!p) return DH_EINVAL;
+    if (d_hdr) *d_hdr = p->P.hdr;
+    if (d_entries) *d_entries = p->P.entries;
+    if (d_events) *d_events = p->P.events;
+    if (d_frames) *d_frames = p->P.frames;
+    return DH_OK;
+}
+
+}  // extern "C"
+
 // ---- the band monitor (monitor_core.hpp): scan engines, ring and protocol engines behind one handle ------------------
 //   dh_be_monitor_open(const DhMonOpen& A, void* stream);        step A
 //   dh_be_monitor_assign(const DhMonAssign& S, void* stream);    step B
@@ -596,7 +704,7 @@ int dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t ski
 struct dh_monitor {
     DH_BACKEND be;
     dh::DeviceBuffers<DH_BACKEND> bufs{ be };
-    void* stream = nullptr;
+    int device = 0; void* stream = nullptr;
     uint32_t B = 0, max_samples = 0;
     dh_engine* scan[DH_MON_FRONTS] = {};               // null: no configured protocol sits behind that front end
     dh_engine* eng[DH_MON_PROTOS] = {};                // by DH_PROTO_*; null: not configured
@@ -672,7 +780,8 @@ struct dh_monitor {
         return DH_OK;
     }
     int read_summary() { return be.download(&sum, d_sum, sizeof(sum)) ? DH_EDEVICE : DH_OK; }      // (synchronises)
-    int push(const float* rows, size_t stride, size_t n, const uint32_t* counts, dh_monitor_sink sink, void* user) {
+    // pack (may be null): the sink of dh_monitor_push_packed -- every engine push of steps 6 and 7 is appended to it
+    int push(const float* rows, size_t stride, size_t n, const uint32_t* counts, dh_monitor_sink sink, void* user, dh_outpack* pack = nullptr) {
         if (!n) return DH_OK;
         if (!rows || n > max_samples || stride < n) return DH_EINVAL;
         int rc = pre->append(rows, stride, n, counts);                                      // 1
@@ -704,6 +813,7 @@ struct dh_monitor {
                 if ((rc = eng[p]->impl.push(d_stage, max_samples, max_samples, d_chunk_counts)) != DH_OK) return rc;
                 info.proto = (int32_t) p; info.replay = 1; info.engine = eng[p]; info.d_counts = d_chunk_counts; info.d_start = S.from[p]; info.skip = skip;
                 if (sink) sink(user, &info);
+                if (pack && (rc = pack->append(eng[p], d_chunk_counts, S.from[p], skip, p | 1u << 8)) != DH_OK) return rc;
             }
         }
         for (uint32_t p = 1; p < DH_MON_PROTOS; p++) {                                      // 7
@@ -711,6 +821,7 @@ struct dh_monitor {
             if ((rc = eng[p]->impl.push(rows, stride, n, A.live_counts[p])) != DH_OK) return rc;
             info.proto = (int32_t) p; info.replay = 0; info.engine = eng[p]; info.d_counts = A.live_counts[p]; info.d_start = A.start; info.skip = 0;
             if (sink) sink(user, &info);
+            if (pack && (rc = pack->append(eng[p], A.live_counts[p], nullptr, info.live_first, p)) != DH_OK) return rc;
         }
         return DH_OK;
     }
@@ -729,7 +840,7 @@ int dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out) {
     int rc = m->be.open(cfg->device, cfg->stream);
     if (rc == DH_OK) {
         DH_ON_DEVICE(m);
-        m->stream = cfg->stream;
+        m->device = cfg->device; m->stream = cfg->stream;
         rc = m->init(*cfg);
         if (rc != DH_OK) m->release();
     }
@@ -754,6 +865,11 @@ int dh_monitor_push(dh_monitor* m, const float* d_rows, size_t stride, size_t n,
     if (!m) return DH_EINVAL;
     DH_ON_DEVICE(m);
     return m->push(d_rows, stride, n, d_counts, sink, user);
+}
+int dh_monitor_push_packed(dh_monitor* m, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts, dh_outpack* pack) {
+    if (!m || !pack || !pack->shares_stream(m->device, m->stream)) return DH_EINVAL;
+    DH_ON_DEVICE(m);
+    return m->push(d_rows, stride, n, d_counts, nullptr, nullptr, pack);
 }
 int dh_monitor_state(dh_monitor* m, uint8_t* h_assigned, uint64_t* h_start) {
     if (!m) return DH_EINVAL;

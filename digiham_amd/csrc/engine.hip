@@ -18,6 +18,7 @@
 
 #include "../../include/digiham_amd.h"
 #include "kernels_core.hpp"
+#include "outpack_core.hpp"
 #include "launch_plan.hpp"
 #include "fec_tables.hpp"
 #include "rrc_taps.h"
@@ -1080,6 +1081,23 @@ __global__ __launch_bounds__(256) void k_monitor_assign(const DhMonAssign S) {
     }
 }
 
+// ---------------------------------------------------------------------------------- packed read-out (outpack_core.hpp)
+// k_outpack_scan: ONE workgroup of 256 lanes walks the engine's B channels 256 at a time -- B is at most a few tens of
+// thousands of 8-byte reads -- so that the order rule is exact without any hand-over between workgroups: candidate vote
+// and popcount below the lane, two shuffle scans per wavefront, the wavefronts' totals through 48 bytes of LDS, a running
+// carry across passes.  Ordinary vector stores only.
+// k_outpack_copy: a fixed grid, workgroup i takes entries i, i + gridDim.x, ... of THIS append while i < n_new; n_new and
+// the first entry's index are the two scratch words the scan left, the same for every lane.
+__global__ __launch_bounds__(DH_OP_LANES) void k_outpack_scan(const DhOutpack P) {
+    __shared__ DhOpShared S;
+    dh_outpack_scan(P, S);
+}
+
+__global__ __launch_bounds__(256) void k_outpack_copy(const DhOutpack P) {
+    const uint32_t first = P.scratch[0], n_new = P.scratch[1];
+    for (uint32_t i = blockIdx.x; i < n_new; i += gridDim.x) dh_outpack_copy_entry(P, first + i, threadIdx.x, 256u);
+}
+
 // Masked reset of an engine: workgroup i takes channels i, i + gridDim.x, ...; a channel whose flag is 0 costs one byte
 // read.  The 256 lanes zero row b of every declared buffer; the fence and the barrier put those zeros in memory before
 // one lane writes the few non-zero words of a fresh channel over them (the flag is the same for the whole workgroup, so
@@ -1277,6 +1295,16 @@ static int dh_be_monitor_assign(const DhMonAssign& S, void* stream) {
 static int dh_be_reset_channels(HipBackend& be, const DhResetChannels& R) {
     hipLaunchKernelGGL(k_reset_channels, dim3(R.B < 2048u ? R.B : 2048u), dim3(256), 0, be.ms(), R);
     return be.launched("k_reset_channels");
+}
+
+// (both on the engine's stream, behind whatever the engine has in flight on streams of its own: HipBackend::ms)
+static int dh_be_outpack_scan(HipBackend& be, const DhOutpack& P) {
+    hipLaunchKernelGGL(k_outpack_scan, dim3(1), dim3(DH_OP_LANES), 0, be.ms(), P);
+    return be.launched("k_outpack_scan");
+}
+static int dh_be_outpack_copy(HipBackend& be, const DhOutpack& P) {
+    hipLaunchKernelGGL(k_outpack_copy, dim3(P.B < 1024u ? P.B : 1024u), dim3(256), 0, be.ms(), P);
+    return be.launched("k_outpack_copy");
 }
 
 #define DH_BACKEND HipBackend

@@ -531,6 +531,77 @@ dh_engine* dh_monitor_engine(dh_monitor* m, int proto);
 dh_engine* dh_monitor_scan_engine(dh_monitor* m, int front /* 0..3: wide10, narrow20, fsk10, fsk40i */);
 
 /* ------------------------------------------------------------------------
+ * Packed read-out: what the pushes of a round produced, in one device block.  Own specification; the reference has no
+ * counterpart.  An engine's outputs are dense [B][out_cap] and [B][ev_cap] arrays that the next push overwrites; a
+ * dh_outpack compacts, on the device, the rows that hold something, and appends across the pushes and engines of a round.
+ * A whole round then costs one synchronisation and copies sized by what was decoded, not by B.
+ *
+ * Areas.  Three device areas of fixed capacity plus the header: entries[max_entries], events[max_events],
+ * frames[max_frame_bytes]; max_frame_bytes is a multiple of 16 and at most 2^36 - 16.
+ *
+ * Candidates of an append.  The channels b of the engine, in ascending order, for which both hold:
+ * d_mask == NULL || d_mask[b] != 0, and fc[b] != 0 || ec[b] != 0.  fc is the push's frame-byte count and ec its event
+ * count (0 for an engine created with DH_FLAG_NO_EVENTS), both clamped to the row capacities.
+ *
+ * Append.  With the running totals before a candidate (E, V, F) = (n_entries, n_events, frame_bytes) and
+ * pad16(n) = n rounded up to a multiple of 16, a candidate is kept iff all four hold: dropped == 0, E + 1 <= max_entries,
+ * V + ec <= max_events, F + pad16(fc) <= max_frame_bytes.  A kept candidate writes
+ *     entry E = { b, user, (d_tag ? d_tag[b] : 0) + tag_add mod 2^64, fc, ec, F / 16, V },
+ *     frames[F, F + fc) = the row's bytes, frames[F + fc, F + pad16(fc)) = 0,
+ *     events[V, V + ec) = the row's records bit for bit,
+ * and the totals advance by (1, ec, pad16(fc)).  The first candidate that does not fit is dropped, and so is every later
+ * candidate, in this append and in later ones until dh_outpack_clear; `dropped` counts them.  The kept set is therefore
+ * always a prefix in append order, then channel order.  `appends` += 1 per call.  No byte beyond the totals is written.
+ *
+ * Streams.  The append is enqueued on the engine's stream, behind the push whose outputs it reads (an engine with
+ * DH_FLAG_OVERLAP_PUSHES is joined first, as for any other kind of work): it is asynchronous, and the totals it starts
+ * from are read on the device, so appends chain in stream order without the host knowing any total.  d_mask and d_tag
+ * ([n_channels] each, device) are read when the launch runs.  DH_EINVAL if the engine's device or stream differ from the
+ * pack's.  dh_outpack_clear is asynchronous on the same stream: header = 0, the areas are not touched.
+ *
+ * Read.  dh_outpack_read synchronises once and copies the header; then it copies exactly n_entries entries, n_events
+ * events and frame_bytes bytes into the host arrays, which hold the create capacities (a NULL array is skipped).  It
+ * returns DH_ECAPACITY when dropped != 0; the kept data is still delivered.  dh_outpack_device hands out the device
+ * addresses of the header and the three areas (any pointer may be NULL) for consumers that stay on the device.
+ *
+ * DH_EINVAL: null handles or configuration, struct_size too small, max_entries == 0, max_frame_bytes not a multiple of
+ * 16 or above 2^36 - 16, an engine with proto == DH_PROTO_NONE.
+ *
+ * Monitor.  dh_monitor_push_packed is dh_monitor_push whose internal sink, after every engine push of steps 6 and 7,
+ * calls dh_outpack_append(pack, engine, d_counts, replay ? d_start : NULL, replay ? skip : live_first,
+ * proto | replay << 8): an entry's tag is the stream index of its block's first input sample.  It does not clear the
+ * pack and does not read it; a round through it issues no output read-back at all.  DH_EINVAL, before anything happens,
+ * if the pack is NULL or not on the monitor's device and stream.
+ * ---------------------------------------------------------------------- */
+typedef struct dh_outpack dh_outpack;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(dh_outpack_config) */
+    int32_t  device;
+    uint32_t max_entries, max_events;
+    uint64_t max_frame_bytes;
+    void*    stream;               /* hipStream_t; NULL = default stream */
+} dh_outpack_config;
+typedef struct {                   /* 32 bytes; the rest reserved, 0 */
+    uint32_t n_entries, n_events;
+    uint64_t frame_bytes;
+    uint32_t dropped, appends;
+    uint32_t reserved[2];
+} dh_outpack_header;
+typedef struct {                   /* 32 bytes */
+    uint32_t channel, user;
+    uint64_t tag;
+    uint32_t n_frame_bytes, n_events, frame_offset16, event_index;
+} dh_outpack_entry;
+int  dh_outpack_create(const dh_outpack_config* cfg, dh_outpack** out);
+void dh_outpack_destroy(dh_outpack* p);
+int  dh_outpack_clear(dh_outpack* p);
+int  dh_outpack_append(dh_outpack* p, dh_engine* e, const uint32_t* d_mask, const uint64_t* d_tag, uint64_t tag_add, uint32_t user);
+int  dh_outpack_read(dh_outpack* p, dh_outpack_header* h_hdr, dh_outpack_entry* h_entries, dh_event* h_events, uint8_t* h_frames);
+int  dh_outpack_device(dh_outpack* p, const dh_outpack_header** d_hdr, const dh_outpack_entry** d_entries,
+                       const dh_event** d_events, const uint8_t** d_frames);
+int  dh_monitor_push_packed(dh_monitor* m, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts, dh_outpack* pack);
+
+/* ------------------------------------------------------------------------
  * Diagnostics: the RRC output scaling `(float)((double)sum / gain)` of
  * src/rrc_filter/rrc_filter.cpp:33 exactly as the FIR kernels evaluate it
  * (reciprocal multiply + exact-division fallback near float rounding ties).
