@@ -140,3 +140,121 @@ def npz_digest(path):
             h.update(("%s %s %s" % (name, a.dtype.str, a.shape)).encode())
             h.update(a.tobytes())
     return h.hexdigest()
+
+
+# ------------------------------------------------------------------ BPTC(196,96) on designed error patterns
+BPTC_PATTERN_SEED = 20261019
+BPTC_CLASSES = ("a_clean", "b_single", "c_pair", "d_column_triple", "d_row_triple", "e_rectangle", "f_parity_pair", "f_parity_triple",
+                "g_r3_alone", "g_r3_single", "g_r3_two_columns", "h_random")
+_BPTC_PATTERNS = None
+
+
+def bptc_cell(k, c):
+    """received bit of matrix cell (row k of 13, column c of 15): bptc_196_96.c:12-14, :24.  Received bit 0 is R(3)."""
+    return ((15 * k + c + 1) * 181) % 196
+
+
+def bptc_flip(base25, bits):
+    """copies of a 25-byte block with the received bits bits[n][w] wrong (bit r = bit 7 - r % 8 of byte r // 8)"""
+    bits = np.asarray(bits, np.int64).reshape(len(bits), -1)
+    out = np.broadcast_to(np.asarray(base25, np.uint8), (len(bits), 25)).copy()
+    rows = np.arange(len(bits))
+    for j in range(bits.shape[1]):                     # the bits of one pattern are distinct: one XOR per row and step
+        out[rows, bits[:, j] // 8] ^= (0x80 >> (bits[:, j] % 8)).astype(np.uint8)
+    return out
+
+
+def bptc_patterns(O):
+    """-> (payload [N][25], sent_info [N][12], class_id [N] into BPTC_CLASSES): codewords of O.bptc_encode with the error patterns a
+    product-code decoder can get wrong -- every single bit, every pair, every triple inside a column and inside a row, every 2 x 2
+    rectangle, pairs and triples inside the four parity rows, R(3) alone and with others, random weights 3..12.  Deterministic: the
+    expected values of tests/golden/bptc_patterns_ref.npz (make_golden_bptc_patterns.py) belong to exactly this list."""
+    global _BPTC_PATTERNS
+    if _BPTC_PATTERNS is not None:
+        return _BPTC_PATTERNS
+    from itertools import combinations
+    rng = np.random.default_rng(BPTC_PATTERN_SEED)
+    rand = rng.integers(0, 256, (8, 12)).astype(np.uint8)
+    zero, ones = np.zeros(12, np.uint8), np.full(12, 255, np.uint8)
+    cell = np.array([[bptc_cell(k, c) for c in range(15)] for k in range(13)])
+    assert sorted(cell.ravel().tolist()) == list(range(1, 196))
+    parts = []
+
+    def add(cls, info, bits):
+        bits = np.asarray(bits, np.int64)
+        n = len(bits)
+        parts.append((bptc_flip(O.bptc_encode(info), bits.reshape(n, -1)), np.broadcast_to(info, (n, 12)), np.full(n, BPTC_CLASSES.index(cls), np.uint8)))
+
+    for info in [zero, ones] + list(rand):
+        add("a_clean", info, np.zeros((1, 0)))
+    for info in (zero, ones, rand[0], rand[1]):
+        add("b_single", info, np.arange(196).reshape(196, 1))
+    add("c_pair", rand[0], list(combinations(range(196), 2)))
+    add("d_column_triple", rand[1], [cell[list(ks), c] for c in range(15) for ks in combinations(range(13), 3)])
+    add("d_row_triple", rand[2], [cell[k, list(cs)] for k in range(13) for cs in combinations(range(15), 3)])
+    add("e_rectangle", rand[3], [[cell[k0, c0], cell[k0, c1], cell[k1, c0], cell[k1, c1]]
+                                 for k0, k1 in combinations(range(13), 2) for c0, c1 in combinations(range(15), 2)])
+    parity = cell[9:13].ravel()
+    add("f_parity_pair", rand[4], list(combinations(parity.tolist(), 2)))
+    add("f_parity_triple", rand[4], [rng.choice(parity, 3, replace=False) for _ in range(1000)])
+    add("g_r3_alone", rand[5], [[0]])
+    add("g_r3_single", rand[5], [[0, r] for r in range(1, 196)])
+    add("g_r3_two_columns", rand[5], [[0, cell[rng.integers(0, 13), c0], cell[rng.integers(0, 13), c1]]
+                                      for c0, c1 in combinations(range(15), 2) for _ in range(8)])
+    for w in range(3, 13):
+        for b in range(8):
+            n = 300 // 8 + (b < 300 % 8)
+            add("h_random", rand[b], [rng.choice(196, w, replace=False) for _ in range(n)])
+    _BPTC_PATTERNS = tuple(np.ascontiguousarray(np.concatenate([p[i] for p in parts])) for i in range(3))
+    return _BPTC_PATTERNS
+
+
+def bptc_pattern_fixture(path):
+    """tests/golden/bptc_patterns_ref.npz -> (ok [N] uint8, out [N][12] with zeros where not ok, the file's arrays)"""
+    z = np.load(path)
+    n = int(z["n"])
+    ok = np.unpackbits(z["ok_bits"])[:n]
+    out = np.zeros((n, 12), np.uint8)
+    out[ok == 1] = z["out_ok"]
+    return ok, out, z
+
+
+def run_dmr_decoder(ctx, syms, cuts, scalar, monkeypatch):
+    """Dibit streams syms[B][n] through a decoder-only DMR engine in pushes of cuts[0], cuts[1], ... symbols; pass B of the decoder
+    lane-parallel where a chunk allows it or, with `scalar`, burst after burst throughout (DH_DMR_SCALAR_PASS_B, read when the engine is
+    created) -> per channel (frame bytes, event bytes), and per push the counters' increments [(lanes[B], scalar[B])]"""
+    B, n = syms.shape
+    if scalar:
+        monkeypatch.setenv("DH_DMR_SCALAR_PASS_B", "1")
+    else:
+        monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
+    eng = api.Engine(B, max(cuts), rrc="none", demod="none", proto="dmr", ctx=ctx)
+    monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
+    frames, events, counts = [[] for _ in range(B)], [[] for _ in range(B)], []
+    seen = (np.zeros(B, np.int64), np.zeros(B, np.int64))
+    lo = 0
+    for c in cuts:
+        if lo >= n:
+            break
+        part = np.ascontiguousarray(syms[:, lo:lo + c])
+        lo += c
+        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
+        eng.sync()                                               # raises when the push ran into the event or frame capacity
+        f, fc = eng.frames(); e, ec = eng.events()
+        for b in range(B):
+            frames[b].append(f[b, :fc[b]].copy()); events[b].append(e[b, :ec[b]].copy())
+        now = tuple(a.astype(np.int64) for a in eng.dmr_pass_b_stats())
+        counts.append((now[0] - seen[0], now[1] - seen[1]))
+        seen = now
+    eng.close()
+    return [(np.concatenate(frames[b]).tobytes(), np.concatenate(events[b]).tobytes()) for b in range(B)], counts
+
+
+def run_dmr_symbols(ctx, streams, chunk, scalar, monkeypatch):
+    """run_dmr_decoder in pushes of `chunk` symbols (None: one push) -> per channel (frame bytes as an array, events as records), and the
+    (lane-parallel, burst-serial) chunk counts per channel over the whole run"""
+    n = streams.shape[1]
+    chunk = n if chunk is None else chunk
+    got, counts = run_dmr_decoder(ctx, streams, [chunk] * -(-n // chunk), scalar, monkeypatch)
+    return ([(np.frombuffer(f, np.uint8), np.frombuffer(e, api.EVENT_DTYPE)) for f, e in got],
+            (sum(l for l, _ in counts), sum(s for _, s in counts)))

@@ -16,7 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from common import assert_matches_oracle, run_engine
+from common import assert_matches_oracle, run_dmr_decoder as run_decoder, run_engine
 from digiham_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,34 +64,6 @@ def push_plan(kind, n):
             cuts.append(int(rng.choice([145, 1000, 144 * 64 - 7, 144 * 64 + 1, 144 * 70, 144 * 130 + 77, 9])))
         return cuts
     return [144 * kind] * (n // (144 * kind) + 1)
-
-
-def run_decoder(ctx, syms, cuts, scalar, monkeypatch):
-    """-> per channel (frame bytes, event bytes), and per push the counters' increments [(lanes[B], scalar[B])]"""
-    B, n = syms.shape
-    if scalar:
-        monkeypatch.setenv("DH_DMR_SCALAR_PASS_B", "1")
-    else:
-        monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-    eng = api.Engine(B, max(cuts), rrc="none", demod="none", proto="dmr", ctx=ctx)
-    monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-    frames, events, counts = [[] for _ in range(B)], [[] for _ in range(B)], []
-    seen = (np.zeros(B, np.int64), np.zeros(B, np.int64))
-    lo = 0
-    for c in cuts:
-        if lo >= n:
-            break
-        part = np.ascontiguousarray(syms[:, lo:lo + c])
-        lo += c
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        f, fc = eng.frames(); e, ec = eng.events()
-        for b in range(B):
-            frames[b].append(f[b, :fc[b]].copy()); events[b].append(e[b, :ec[b]].copy())
-        now = tuple(a.astype(np.int64) for a in eng.dmr_pass_b_stats())
-        counts.append((now[0] - seen[0], now[1] - seen[1]))
-        seen = now
-    eng.close()
-    return [(np.concatenate(frames[b]).tobytes(), np.concatenate(events[b]).tobytes()) for b in range(B)], counts
 
 
 @pytest.mark.parametrize("two_slots", [False, True])
