@@ -89,107 +89,80 @@ class DhError(RuntimeError):
         self.code = code
 
 
+def _signatures():
+    """name -> (restype, argtypes) of every symbol of include/digiham_amd.h: the one list declare() and EXPORTED_SYMBOLS read."""
+    vp, sz, u32, u64, P = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER
+    def i(*args):
+        return C.c_int, list(args)
+    block, view = i(vp, vp, sz, vp), i(vp, P(vp), P(sz), P(vp))
+    return {
+        "dh_version": (C.c_char_p, []), "dh_last_error": (C.c_char_p, []), "dh_device_count": i(),
+        "dh_device_alloc": i(C.c_int, sz, P(vp)), "dh_device_free": i(vp),
+        "dh_copy_to_host": i(vp, vp, sz), "dh_copy_to_device": i(vp, vp, sz),
+        "dh_hamming_7_4": block, "dh_hamming_13_9": block, "dh_hamming_15_11": block, "dh_hamming_16_11": block,
+        "dh_quadratic_residue": block, "dh_golay_20_8": block, "dh_golay_24_12": block, "dh_bch_31_21": block,
+        "dh_bptc_196_96": i(vp, vp, vp, sz, vp),
+        "dh_trellis": i(vp, sz, C.c_int, vp, sz, vp, sz, vp),
+        "dh_crc16": i(vp, sz, C.c_int, vp, sz, vp),
+        "dh_whitening": i(vp, vp, sz, C.c_int, sz, vp),
+        "dh_dvfilter_s16": i(vp, vp, vp, sz, sz, sz, vp),
+        "dh_frontend_s16": i(vp, sz, vp, sz, vp, sz, sz, C.c_int, C.c_int, vp),
+        "dh_debug_div_gain": i(vp, vp, sz, C.c_int, vp),
+        "dh_debug_div_const": i(vp, vp, sz, C.c_uint, vp),
+        "dh_debug_mfma_f16": i(vp, vp, vp, vp, sz, vp),
+        "dh_debug_f16_split": i(vp, vp, vp, sz, C.c_float, vp),
+        "dh_debug_copy": i(vp, vp, sz, vp),
+        "dh_engine_create": i(P(EngineConfig), P(vp)), "dh_engine_destroy": (None, [vp]),
+        "dh_engine_reset": i(vp), "dh_engine_set_slot_filter": i(vp, u32),
+        "dh_engine_reset_channel": i(vp, u32), "dh_engine_reset_channels": i(vp, vp), "dh_engine_set_slot_filter_channel": i(vp, u32, u32),
+        "dh_engine_push": i(vp, vp, sz, sz), "dh_engine_push_host": i(vp, vp, sz, sz),
+        "dh_engine_push_ragged": i(vp, vp, sz, vp, sz), "dh_engine_push_host_ragged": i(vp, vp, sz, vp, sz),
+        "dh_engine_push_symbols": i(vp, vp, sz, vp),
+        "dh_engine_filtered": i(vp, P(vp), P(sz)), "dh_engine_symbols": view, "dh_engine_frames": view, "dh_engine_events": view,
+        "dh_engine_read_symbols": i(vp, u32, vp, P(sz)), "dh_engine_read_frames": i(vp, u32, vp, P(sz)),
+        "dh_engine_read_events": i(vp, u32, vp, P(sz)), "dh_engine_read_filtered": i(vp, u32, vp, P(sz)),
+        "dh_engine_sync": i(vp),
+        "dh_engine_timing_enable": i(vp, u32),
+        "dh_engine_timing_read": i(vp, vp, vp, vp, P(u32)),
+        "dh_engine_timing_read_split": i(vp, vp, vp, P(u32)),
+        "dh_engine_timing_stats": i(vp, vp, vp),
+        "dh_engine_debug_header": i(vp, u32, vp),
+        "dh_channelizer_create": i(P(ChannelizerConfig), P(vp)), "dh_channelizer_destroy": (None, [vp]),
+        "dh_channelizer_reset": i(vp), "dh_channelizer_retune": i(vp, u32, u32),
+        "dh_channelizer_push": i(vp, vp, sz, vp, sz, P(sz)), "dh_channelizer_push_host": i(vp, vp, sz, vp, sz, P(sz)),
+        "dh_channelizer_phasor": i(vp, vp, sz),
+        "dh_channelizer_power_enable": i(vp, P(ChannelizerPowerConfig)),
+        "dh_channelizer_set_squelch": i(vp, C.c_float, C.c_float, u32),
+        "dh_channelizer_power_last": i(vp, P(u64), P(sz)),
+        "dh_preroll_create": i(P(PrerollConfig), P(vp)), "dh_preroll_destroy": (None, [vp]),
+        "dh_preroll_reset": i(vp), "dh_preroll_append": i(vp, vp, sz, sz, vp),
+        "dh_preroll_total": i(vp, P(u64)), "dh_preroll_open_at": i(vp, vp),
+        "dh_preroll_gather": i(vp, vp, u64, sz, vp, sz, vp, vp),
+        "dh_preroll_gather_device": i(vp, vp, u64, sz, vp, sz, vp),
+        "dh_monitor_create": i(P(MonitorConfig), P(vp)), "dh_monitor_destroy": (None, [vp]), "dh_monitor_reset": i(vp),
+        "dh_monitor_push": i(vp, vp, sz, sz, vp, MONITOR_SINK, vp), "dh_monitor_push_packed": i(vp, vp, sz, sz, vp, vp),
+        "dh_monitor_state": i(vp, vp, vp), "dh_monitor_total": i(vp, P(u64)),
+        "dh_monitor_engine": (vp, [vp, C.c_int]), "dh_monitor_scan_engine": (vp, [vp, C.c_int]),
+        "dh_outpack_create": i(P(OutpackConfig), P(vp)), "dh_outpack_destroy": (None, [vp]), "dh_outpack_clear": i(vp),
+        "dh_outpack_append": i(vp, vp, vp, vp, u64, u32),
+        "dh_outpack_read": i(vp, P(OutpackHeader), vp, vp, vp),
+        "dh_outpack_device": i(vp, P(vp), P(vp), P(vp), P(vp)),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
+
 def declare(L, lenient=False):
     """Attach argtypes / restypes for every symbol of include/digiham_amd.h."""
-    vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
-    L.dh_version.restype = C.c_char_p
-    L.dh_last_error.restype = C.c_char_p
-    L.dh_device_count.restype = C.c_int
-    sig = {
-        "dh_device_alloc": [C.c_int, sz, C.POINTER(vp)], "dh_device_free": [vp],
-        "dh_copy_to_host": [vp, vp, sz], "dh_copy_to_device": [vp, vp, sz],
-        "dh_hamming_7_4": [vp, vp, sz, vp], "dh_hamming_13_9": [vp, vp, sz, vp], "dh_hamming_15_11": [vp, vp, sz, vp],
-        "dh_hamming_16_11": [vp, vp, sz, vp], "dh_quadratic_residue": [vp, vp, sz, vp],
-        "dh_golay_20_8": [vp, vp, sz, vp], "dh_golay_24_12": [vp, vp, sz, vp], "dh_bch_31_21": [vp, vp, sz, vp],
-        "dh_bptc_196_96": [vp, vp, vp, sz, vp],
-        "dh_trellis": [vp, sz, C.c_int, vp, sz, vp, sz, vp],
-        "dh_crc16": [vp, sz, C.c_int, vp, sz, vp],
-        "dh_whitening": [vp, vp, sz, C.c_int, sz, vp],
-        "dh_dvfilter_s16": [vp, vp, vp, sz, sz, sz, vp],
-        "dh_frontend_s16": [vp, sz, vp, sz, vp, sz, sz, C.c_int, C.c_int, vp],
-        "dh_debug_div_gain": [vp, vp, sz, C.c_int, vp],
-        "dh_debug_div_const": [vp, vp, sz, C.c_uint, vp],
-        "dh_debug_mfma_f16": [vp, vp, vp, vp, sz, vp],
-        "dh_debug_f16_split": [vp, vp, vp, sz, C.c_float, vp],
-        "dh_debug_copy": [vp, vp, sz, vp],
-        "dh_engine_create": [C.POINTER(EngineConfig), C.POINTER(vp)],
-        "dh_engine_reset": [vp], "dh_engine_set_slot_filter": [vp, u32],
-        "dh_engine_reset_channel": [vp, u32], "dh_engine_set_slot_filter_channel": [vp, u32, u32],
-        "dh_engine_push": [vp, vp, sz, sz], "dh_engine_push_host": [vp, vp, sz, sz],
-        "dh_engine_push_ragged": [vp, vp, sz, vp, sz], "dh_engine_push_host_ragged": [vp, vp, sz, vp, sz],
-        "dh_engine_push_symbols": [vp, vp, sz, vp],
-        "dh_engine_filtered": [vp, C.POINTER(vp), C.POINTER(sz)],
-        "dh_engine_symbols": [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)],
-        "dh_engine_frames": [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)],
-        "dh_engine_events": [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)],
-        "dh_engine_read_symbols": [vp, u32, vp, C.POINTER(sz)], "dh_engine_read_frames": [vp, u32, vp, C.POINTER(sz)],
-        "dh_engine_read_events": [vp, u32, vp, C.POINTER(sz)], "dh_engine_read_filtered": [vp, u32, vp, C.POINTER(sz)],
-        "dh_engine_sync": [vp],
-        "dh_engine_timing_enable": [vp, u32],
-        "dh_engine_timing_read": [vp, vp, vp, vp, C.POINTER(u32)],
-        "dh_engine_timing_read_split": [vp, vp, vp, C.POINTER(u32)],
-        "dh_engine_timing_stats": [vp, vp, vp],
-        "dh_engine_debug_header": [vp, u32, vp],
-        "dh_channelizer_create": [C.POINTER(ChannelizerConfig), C.POINTER(vp)],
-        "dh_channelizer_reset": [vp], "dh_channelizer_retune": [vp, u32, u32],
-        "dh_channelizer_push": [vp, vp, sz, vp, sz, C.POINTER(sz)], "dh_channelizer_push_host": [vp, vp, sz, vp, sz, C.POINTER(sz)],
-        "dh_channelizer_phasor": [vp, vp, sz],
-        "dh_channelizer_power_enable": [vp, C.POINTER(ChannelizerPowerConfig)],
-        "dh_channelizer_set_squelch": [vp, C.c_float, C.c_float, u32],
-        "dh_channelizer_power_last": [vp, C.POINTER(C.c_uint64), C.POINTER(sz)],
-        "dh_preroll_create": [C.POINTER(PrerollConfig), C.POINTER(vp)],
-        "dh_preroll_reset": [vp], "dh_preroll_append": [vp, vp, sz, sz, vp],
-        "dh_preroll_total": [vp, C.POINTER(C.c_uint64)], "dh_preroll_open_at": [vp, vp],
-        "dh_preroll_gather": [vp, vp, C.c_uint64, sz, vp, sz, vp, vp],
-        "dh_preroll_gather_device": [vp, vp, C.c_uint64, sz, vp, sz, vp],
-        "dh_engine_reset_channels": [vp, vp],
-        "dh_monitor_create": [C.POINTER(MonitorConfig), C.POINTER(vp)], "dh_monitor_reset": [vp],
-        "dh_monitor_push": [vp, vp, sz, sz, vp, MONITOR_SINK, vp], "dh_monitor_state": [vp, vp, vp],
-        "dh_monitor_total": [vp, C.POINTER(C.c_uint64)],
-        "dh_outpack_create": [C.POINTER(OutpackConfig), C.POINTER(vp)], "dh_outpack_clear": [vp],
-        "dh_outpack_append": [vp, vp, vp, vp, C.c_uint64, u32],
-        "dh_outpack_read": [vp, C.POINTER(OutpackHeader), vp, vp, vp],
-        "dh_outpack_device": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
-        "dh_monitor_push_packed": [vp, vp, sz, sz, vp, vp],
-    }
-    for name, args in sig.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         if lenient and not hasattr(L, name):        # A/B build variants of older sources (tools/) may lack new entry points
             continue
         fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    L.dh_engine_destroy.argtypes = [vp]
-    L.dh_engine_destroy.restype = None
-    for name in ("dh_channelizer_destroy", "dh_preroll_destroy", "dh_monitor_destroy", "dh_outpack_destroy"):
-        if hasattr(L, name):
-            getattr(L, name).argtypes = [vp]
-            getattr(L, name).restype = None
-    for name in ("dh_monitor_engine", "dh_monitor_scan_engine"):
-        if hasattr(L, name):
-            getattr(L, name).argtypes = [vp, C.c_int]
-            getattr(L, name).restype = vp
+        fn.argtypes, fn.restype = argtypes, restype
     return L
 
-
-EXPORTED_SYMBOLS = [
-    "dh_version", "dh_last_error", "dh_device_count", "dh_device_alloc", "dh_device_free", "dh_copy_to_host",
-    "dh_copy_to_device", "dh_hamming_7_4", "dh_hamming_13_9", "dh_hamming_15_11", "dh_hamming_16_11",
-    "dh_quadratic_residue", "dh_golay_20_8", "dh_golay_24_12", "dh_bch_31_21", "dh_bptc_196_96", "dh_trellis", "dh_crc16",
-    "dh_whitening", "dh_dvfilter_s16", "dh_frontend_s16", "dh_debug_div_gain", "dh_debug_div_const", "dh_debug_mfma_f16", "dh_debug_f16_split", "dh_debug_copy", "dh_engine_create", "dh_engine_destroy", "dh_engine_reset",
-    "dh_engine_set_slot_filter", "dh_engine_reset_channel", "dh_engine_set_slot_filter_channel", "dh_engine_push", "dh_engine_push_host", "dh_engine_push_ragged", "dh_engine_push_host_ragged", "dh_engine_push_symbols",
-    "dh_engine_filtered", "dh_engine_symbols", "dh_engine_frames", "dh_engine_events", "dh_engine_read_symbols",
-    "dh_engine_read_frames", "dh_engine_read_events", "dh_engine_read_filtered", "dh_engine_sync",
-    "dh_engine_timing_enable", "dh_engine_timing_read", "dh_engine_timing_read_split", "dh_engine_timing_stats", "dh_engine_debug_header",
-    "dh_channelizer_create", "dh_channelizer_destroy", "dh_channelizer_reset", "dh_channelizer_retune", "dh_channelizer_push",
-    "dh_channelizer_push_host", "dh_channelizer_phasor", "dh_channelizer_power_enable", "dh_channelizer_set_squelch",
-    "dh_channelizer_power_last",
-    "dh_preroll_create", "dh_preroll_destroy", "dh_preroll_reset", "dh_preroll_append", "dh_preroll_total", "dh_preroll_open_at",
-    "dh_preroll_gather", "dh_preroll_gather_device", "dh_engine_reset_channels",
-    "dh_monitor_create", "dh_monitor_destroy", "dh_monitor_reset", "dh_monitor_push", "dh_monitor_state", "dh_monitor_total",
-    "dh_monitor_engine", "dh_monitor_scan_engine",
-    "dh_outpack_create", "dh_outpack_destroy", "dh_outpack_clear", "dh_outpack_append", "dh_outpack_read", "dh_outpack_device",
-    "dh_monitor_push_packed",
-]
 
 _LIB = None
 

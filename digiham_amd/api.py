@@ -69,6 +69,49 @@ def _check(rc, what, lib):
         raise DhError(rc, what, lib.dh_last_error().decode(errors="replace"))
 
 
+def _host(a):
+    """The pointer the library reads or fills a host (numpy) array through, for the duration of one call."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _float_rows(mem, x, B, what):
+    """(array, row stride) of float32 [B][n] rows the library can read where they are: a device array whose rows are
+    contiguous -- a column slice of a wider array included, rows need no alignment -- or a copy of anything else."""
+    torch = getattr(mem, "torch", None)
+    if torch is not None and torch.is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != B or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise ValueError("%s: need a float32 [%d][n] device array with contiguous rows, got %s %s strides %s"
+                             % (what, B, x.dtype, tuple(x.shape), tuple(x.stride())))
+        if x.device.index != mem.index:
+            raise ValueError("%s: the array lives on cuda:%s, the handle on cuda:%s" % (what, x.device.index, mem.index))
+        return x, (x.stride(0) if B > 1 else x.shape[1])
+    in_place = torch is None and isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.shape[0] == B and \
+        (x.shape[1] <= 1 or x.strides[1] == 4) and (B == 1 or (x.strides[0] > 0 and x.strides[0] % 4 == 0))
+    if not in_place:
+        x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(B, -1))
+    if callable(getattr(x, "stride", None)):
+        return x, (x.stride(0) if B > 1 else x.shape[1])
+    return x, (x.strides[0] // 4 if B > 1 else x.shape[1])
+
+
+def _vector(mem, a, dtype, n, what):
+    """The [n] vector of a call (counts, flags, mask, tag, from): None, a device array as it is, or an upload of anything
+    else as `dtype`.  ValueError unless it has n entries (n None: any number) of dtype's size -- an int64 device array may
+    hold uint64 bits."""
+    if a is None:
+        return None
+    if not mem.is_device_array(a):
+        a = mem.from_numpy(np.ascontiguousarray(a, dtype))
+    size = np.dtype(dtype).itemsize
+    if (n is not None and tuple(a.shape) != (n,)) or (a.element_size() if callable(getattr(a, "element_size", None)) else a.itemsize) != size:
+        raise ValueError("%s needs %s %d-bit entries" % (what, "its" if n is None else n, 8 * size))
+    return a
+
+
+def _ptr(mem, a):
+    return None if a is None else mem.ptr(a)
+
+
 class Context:
     """A loaded library + a device-memory provider."""
 
@@ -76,13 +119,16 @@ class Context:
         self.lib = lib if lib is not None else _capi.load()
         self.mem = mem if mem is not None else TorchCudaMemory(device)
 
+    def _call(self, name, *args):
+        _check(getattr(self.lib, name)(*args), name, self.lib)
+
     # ------------------------------------------------------------------ batch FEC
     def block_decode(self, code, words):
         """words: numpy array -> (corrected words, ok flags) as numpy."""
         dt = _CODES[code]
         w = self.mem.from_numpy(np.ascontiguousarray(words, dt).ravel())
         ok = self.mem.zeros((w.shape[0],), np.uint8)
-        _check(getattr(self.lib, "dh_" + code)(self.mem.ptr(w), self.mem.ptr(ok), w.shape[0], self.mem.stream()), "dh_" + code, self.lib)
+        self._call("dh_" + code, self.mem.ptr(w), self.mem.ptr(ok), w.shape[0], self.mem.stream())
         return self.mem.to_numpy(w, dt), self.mem.to_numpy(ok)
 
     def bptc_196_96(self, payloads):
@@ -90,7 +136,7 @@ class Context:
         n = p.shape[0]
         out = self.mem.zeros((n, 12), np.uint8)
         ok = self.mem.zeros((n,), np.uint8)
-        _check(self.lib.dh_bptc_196_96(self.mem.ptr(p), self.mem.ptr(out), self.mem.ptr(ok), n, self.mem.stream()), "dh_bptc_196_96", self.lib)
+        self._call("dh_bptc_196_96", self.mem.ptr(p), self.mem.ptr(out), self.mem.ptr(ok), n, self.mem.stream())
         return self.mem.to_numpy(out), self.mem.to_numpy(ok)
 
     def trellis(self, packed, n_dibits):
@@ -100,8 +146,7 @@ class Context:
         d = self.mem.from_numpy(p)
         out = self.mem.zeros((n, ob), np.uint8)
         metric = self.mem.zeros((n,), np.uint8)
-        _check(self.lib.dh_trellis(self.mem.ptr(d), stride, n_dibits, self.mem.ptr(out), ob, self.mem.ptr(metric), n, self.mem.stream()),
-               "dh_trellis", self.lib)
+        self._call("dh_trellis", self.mem.ptr(d), stride, n_dibits, self.mem.ptr(out), ob, self.mem.ptr(metric), n, self.mem.stream())
         return self.mem.to_numpy(out), self.mem.to_numpy(metric)
 
     def crc16(self, data, count):
@@ -109,7 +154,7 @@ class Context:
         n, stride = a.shape
         d = self.mem.from_numpy(a)
         out = self.mem.zeros((n,), np.uint16)
-        _check(self.lib.dh_crc16(self.mem.ptr(d), stride, count, self.mem.ptr(out), n, self.mem.stream()), "dh_crc16", self.lib)
+        self._call("dh_crc16", self.mem.ptr(d), stride, count, self.mem.ptr(out), n, self.mem.stream())
         return self.mem.to_numpy(out, np.uint16)
 
     def whitening(self, data, n_bits):
@@ -117,14 +162,13 @@ class Context:
         n, stride = a.shape
         d = self.mem.from_numpy(a)
         out = self.mem.zeros((n, stride), np.uint8)
-        _check(self.lib.dh_whitening(self.mem.ptr(d), self.mem.ptr(out), stride, n_bits, n, self.mem.stream()), "dh_whitening", self.lib)
+        self._call("dh_whitening", self.mem.ptr(d), self.mem.ptr(out), stride, n_bits, n, self.mem.stream())
         return self.mem.to_numpy(out)
 
     def debug_div_gain(self, x, narrow=False):
         d = self.mem.from_numpy(np.ascontiguousarray(x, np.float32).ravel())
         out = self.mem.zeros((d.shape[0],), np.float32)
-        _check(self.lib.dh_debug_div_gain(self.mem.ptr(d), self.mem.ptr(out), d.shape[0], int(narrow), self.mem.stream()),
-               "dh_debug_div_gain", self.lib)
+        self._call("dh_debug_div_gain", self.mem.ptr(d), self.mem.ptr(out), d.shape[0], int(narrow), self.mem.stream())
         return self.mem.to_numpy(out)
 
     def frontend(self, x, mode, dcblock=True, state=None):
@@ -136,8 +180,8 @@ class Context:
         out = self.mem.zeros((B, n), np.float32)
         if state is None:
             state = self.mem.zeros((B, 4), np.float32)
-        _check(self.lib.dh_frontend_s16(self.mem.ptr(a), w, self.mem.ptr(out), n, self.mem.ptr(state), B, n,
-                                        1 if mode == "audio" else 2, int(bool(dcblock)), self.mem.stream()), "dh_frontend_s16", self.lib)
+        self._call("dh_frontend_s16", self.mem.ptr(a), w, self.mem.ptr(out), n, self.mem.ptr(state), B, n,
+                                        1 if mode == "audio" else 2, int(bool(dcblock)), self.mem.stream())
         return out, state
 
     def debug_div_const(self, x, divisor):
@@ -145,8 +189,7 @@ class Context:
         dev = self.mem.is_device_array(x)
         d = x if dev else self.mem.from_numpy(np.ascontiguousarray(x, np.float32).ravel())
         out = self.mem.zeros((d.shape[0],), np.float32)
-        _check(self.lib.dh_debug_div_const(self.mem.ptr(d), self.mem.ptr(out), d.shape[0], int(divisor), self.mem.stream()),
-               "dh_debug_div_const", self.lib)
+        self._call("dh_debug_div_const", self.mem.ptr(d), self.mem.ptr(out), d.shape[0], int(divisor), self.mem.stream())
         return out if dev else self.mem.to_numpy(out)
 
     def debug_mfma_f16(self, a, b, c):
@@ -158,8 +201,7 @@ class Context:
         da, db = self.mem.from_numpy(a.reshape(T, 512)), self.mem.from_numpy(b.reshape(T, 512))
         dc = self.mem.from_numpy(np.ascontiguousarray(c, np.float32).reshape(T, 256))
         out = self.mem.zeros((T, 256), np.float32)
-        _check(self.lib.dh_debug_mfma_f16(self.mem.ptr(da), self.mem.ptr(db), self.mem.ptr(dc), self.mem.ptr(out), T, self.mem.stream()),
-               "dh_debug_mfma_f16", self.lib)
+        self._call("dh_debug_mfma_f16", self.mem.ptr(da), self.mem.ptr(db), self.mem.ptr(dc), self.mem.ptr(out), T, self.mem.stream())
         return self.mem.to_numpy(out).reshape(T, 16, 16)
 
     def debug_f16_split(self, x, scale=1.0):
@@ -167,8 +209,7 @@ class Context:
         d = self.mem.from_numpy(np.ascontiguousarray(x, np.float32).ravel())
         n = d.shape[0]
         h1, h2 = self.mem.zeros((n,), np.uint16), self.mem.zeros((n,), np.uint16)
-        _check(self.lib.dh_debug_f16_split(self.mem.ptr(d), self.mem.ptr(h1), self.mem.ptr(h2), n, float(scale), self.mem.stream()),
-               "dh_debug_f16_split", self.lib)
+        self._call("dh_debug_f16_split", self.mem.ptr(d), self.mem.ptr(h1), self.mem.ptr(h2), n, float(scale), self.mem.stream())
         return self.mem.to_numpy(h1).view(np.float16), self.mem.to_numpy(h2).view(np.float16)
 
     def dvfilter(self, x, state=None):
@@ -181,38 +222,66 @@ class Context:
         out = self.mem.zeros((B, n), np.int16)
         if state is None:
             state = self.mem.zeros((B, 22), np.float32)
-        _check(self.lib.dh_dvfilter_s16(self.mem.ptr(d), self.mem.ptr(out), self.mem.ptr(state), B, n, n, self.mem.stream()),
-               "dh_dvfilter_s16", self.lib)
+        self._call("dh_dvfilter_s16", self.mem.ptr(d), self.mem.ptr(out), self.mem.ptr(state), B, n, n, self.mem.stream())
         return self.mem.to_numpy(out), state
 
 
-class Engine:
+class _Handle:
+    """What the classes below share.  One that owns a library handle names its kind (`_kind` = "dh_x": dh_x_create and
+    dh_x_destroy), opens it from its config struct with _open() and talks to it through _call(), which passes `_h`
+    first; close() destroys an owned handle once and a call on a closed one is the library's DH_EINVAL.  One that is made
+    of other handles (Scanner, Monitor) takes its context from _resolve(), closes its parts in close() and asks _live()
+    before it works.  A half-built object -- the constructor raised -- closes like any other."""
+    _kind, _h, _owned, _closed = None, None, True, False
+
+    def _resolve(self, ctx, device):
+        self.ctx = ctx if ctx is not None else Context(device=device)
+        return self.ctx.mem
+
+    def _open(self, ctx, device, cfg_type, **fields):
+        """dh_x_create from cfg_type(struct_size, device, stream: the context's; the rest, or other values of these: fields)."""
+        mem = self._resolve(ctx, device)
+        cfg = cfg_type(**dict(dict(struct_size=C.sizeof(cfg_type), device=getattr(mem, "index", 0), stream=mem.stream()), **fields))
+        h = C.c_void_p()
+        self.ctx._call(self._kind + "_create", C.byref(cfg), C.byref(h))
+        self._h = h
+
+    def _call(self, name, *args):
+        self.ctx._call(name, self._h, *args)
+
+    def _live(self, what):
+        if self._closed:
+            raise DhError(_capi.DH_EINVAL, what, "closed")
+
+    def close(self):
+        if self._h and self._owned:
+            getattr(self.ctx.lib, self._kind + "_destroy")(self._h)
+        self._h, self._closed = None, True
+
+    def __del__(self):
+        self.close()
+
+
+class Engine(_Handle):
     """B independent `rrc_filter | gfsk_demodulator | dmr_decoder` pipes with state resident in HBM."""
+    _kind = "dh_engine"
 
     def __init__(self, n_channels, max_samples, rrc="wide", demod="gfsk", sps=10, proto="dmr", fast_fir=False,
                  keep_filtered=False, invert=False, events=True, slot_filter=3, ctx=None, device=0, ordered_timing=False, split_stages=False,
                  taps=None, gain=None, exact_symbols=False, exact_fir=False, overlap_pushes=False, one_launch=False):
         """rrc = "custom" takes the caller's coefficient table: `taps` (nZeros + 1 floats, any shape) and `gain`, as
         Digiham::RrcFilter::RrcFilter(nZeros, gain, coeffs[]) does (include/rrc_filter.hpp:12)."""
-        self.ctx = ctx if ctx is not None else Context(device=device)
-        lib, mem = self.ctx.lib, self.ctx.mem
         flags = (_capi.FLAG_FAST_FIR if fast_fir else 0) | (_capi.FLAG_KEEP_FILTERED if keep_filtered else 0) | \
                 (_capi.FLAG_FSK_INVERT if invert else 0) | (0 if events else _capi.FLAG_NO_EVENTS) | \
                 (_capi.FLAG_ORDERED_TIMING if ordered_timing else 0) | (_capi.FLAG_SPLIT_STAGES if split_stages else 0) | \
                 (_capi.FLAG_EXACT_SYMBOLS if exact_symbols else 0) | (_capi.FLAG_EXACT_FIR if exact_fir else 0) | \
                 (_capi.FLAG_OVERLAP_PUSHES if overlap_pushes else 0) | (_capi.FLAG_ONE_LAUNCH if one_launch else 0)
-        cfg = _capi.EngineConfig(C.sizeof(_capi.EngineConfig), getattr(mem, "index", 0), n_channels, max_samples,
-                                 _capi.RRC[rrc], _capi.DEMOD[demod], sps, _capi.PROTO[proto], flags, slot_filter,
-                                 mem.stream())
-        if rrc != "custom":
-            cfg.struct_size = _capi.EngineConfig.rrc_taps.offset       # the layout before the custom-filter fields: every library version takes it
+        custom = dict(struct_size=_capi.EngineConfig.rrc_taps.offset)     # the layout before the custom-filter fields: every library version takes it
         if rrc == "custom":
-            t = np.ascontiguousarray(taps, np.float32).ravel()
-            cfg.rrc_taps = t.ctypes.data_as(C.POINTER(C.c_float))         # copied by dh_engine_create
-            cfg.rrc_nzeros, cfg.rrc_gain = len(t) - 1, float(gain)
-        h = C.c_void_p()
-        _check(lib.dh_engine_create(C.byref(cfg), C.byref(h)), "dh_engine_create", lib)
-        self._h = h
+            t = np.ascontiguousarray(taps, np.float32).ravel()                # copied by dh_engine_create
+            custom = dict(rrc_taps=t.ctypes.data_as(C.POINTER(C.c_float)), rrc_nzeros=len(t) - 1, rrc_gain=float(gain))
+        self._open(ctx, device, _capi.EngineConfig, n_channels=n_channels, max_samples=max_samples, rrc=_capi.RRC[rrc],
+                   demod=_capi.DEMOD[demod], sps=sps, proto=_capi.PROTO[proto], flags=flags, slot_filter=slot_filter, **custom)
         self.B, self.max_samples = n_channels, max_samples
         self.has_demod, self.has_proto = _capi.DEMOD[demod] != 0, _capi.PROTO[proto] != 0
         self.keep_filtered = (keep_filtered or rrc == "custom") and _capi.RRC[rrc] != 0
@@ -233,77 +302,55 @@ class Engine:
         self._keep, self._overlap, self._inflight = None, False, []
         return self
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self, "_owned", True):
-                self.ctx.lib.dh_engine_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def reset(self):
-        _check(self.ctx.lib.dh_engine_reset(self._h), "dh_engine_reset", self.ctx.lib)
+        self._call("dh_engine_reset")
         if self._inflight:
             self.sync()                          # the reset joined the streams; inputs are released once it has run
 
     def reset_channel(self, ch):
-        _check(self.ctx.lib.dh_engine_reset_channel(self._h, ch), "dh_engine_reset_channel", self.ctx.lib)
+        self._call("dh_engine_reset_channel", ch)
 
     def reset_channels(self, flags):
         """reset_channel for every channel with flags[b] != 0 ([B] uint8, numpy or a device array), in one launch."""
         mem = self.ctx.mem
-        f = flags if mem.is_device_array(flags) and not isinstance(flags, np.ndarray) else mem.from_numpy(np.ascontiguousarray(flags, np.uint8))
-        if tuple(f.shape) != (self.B,) or (f.element_size() if callable(getattr(f, "element_size", None)) else f.itemsize) != 1:
-            raise ValueError("Engine.reset_channels: flags needs %d entries" % self.B)
+        f = _vector(mem, flags, np.uint8, self.B, "Engine.reset_channels: flags")
         self._keep_flags = f        # the launch is asynchronous: keep the flags alive
-        _check(self.ctx.lib.dh_engine_reset_channels(self._h, mem.ptr(f)), "dh_engine_reset_channels", self.ctx.lib)
+        self._call("dh_engine_reset_channels", mem.ptr(f))
 
     def set_slot_filter(self, f):
-        _check(self.ctx.lib.dh_engine_set_slot_filter(self._h, f), "dh_engine_set_slot_filter", self.ctx.lib)
+        self._call("dh_engine_set_slot_filter", f)
 
     def push(self, x, n=None, counts=None):
         """x: device array float32 [B][stride] (torch CUDA tensor); processes the first n samples of every row -- or, with
         `counts` ([B] uint32), the first counts[b] <= n samples of row b (dh_engine_push_ragged)."""
         mem = self.ctx.mem
-        if not mem.is_device_array(x):
-            x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(self.B, -1))
-        elif getattr(mem, "torch", None) is not None and mem.torch.is_tensor(x):
-            # the library reads raw float32 rows: anything else would be silent garbage or an out-of-bounds read
-            if x.dtype != mem.torch.float32 or x.dim() != 2 or x.shape[0] != self.B or (x.shape[1] > 1 and x.stride(1) != 1):
-                raise ValueError("Engine.push: need a float32 [%d][n] device array with contiguous rows, got %s %s strides %s"
-                                 % (self.B, x.dtype, tuple(x.shape), tuple(x.stride())))
-            if x.device.index != mem.index:
-                raise ValueError("Engine.push: the array lives on cuda:%s, the engine on cuda:%s" % (x.device.index, mem.index))
-        stride = x.stride(0) if callable(getattr(x, "stride", None)) else x.strides[0] // x.itemsize
-        if x.shape[0] == 1:
-            stride = x.shape[1]                 # a single row: its "row stride" is arbitrary (numpy reports 0 for a new axis)
+        x, stride = _float_rows(mem, x, self.B, "Engine.push")
         n = x.shape[1] if n is None else n
         self._keep = x          # the launch is asynchronous: keep the input alive
         if self._overlap:
             self._inflight.append(x)
         if counts is not None:  # ragged push: channel b brings counts[b] <= n samples
-            c = counts if mem.is_device_array(counts) else mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+            c = _vector(mem, counts, np.uint32, self.B, "Engine.push: counts")
             self._keep = (x, c)
             if self._overlap:
                 self._inflight.append(c)
-            _check(self.ctx.lib.dh_engine_push_ragged(self._h, mem.ptr(x), stride, mem.ptr(c), n), "dh_engine_push_ragged", self.ctx.lib)
+            self._call("dh_engine_push_ragged", mem.ptr(x), stride, mem.ptr(c), n)
             return
-        _check(self.ctx.lib.dh_engine_push(self._h, mem.ptr(x), stride, n), "dh_engine_push", self.ctx.lib)
+        self._call("dh_engine_push", mem.ptr(x), stride, n)
 
     def push_host(self, x):
         a = np.ascontiguousarray(x, np.float32).reshape(self.B, -1)
-        _check(self.ctx.lib.dh_engine_push_host(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[1]),
-               "dh_engine_push_host", self.ctx.lib)
+        self._call("dh_engine_push_host", _host(a), a.shape[1], a.shape[1])
 
     def push_symbols(self, syms, counts):
         mem = self.ctx.mem
         s = syms if mem.is_device_array(syms) else mem.from_numpy(np.ascontiguousarray(syms, np.uint8).reshape(self.B, -1))
-        c = counts if mem.is_device_array(counts) else mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        c = _vector(mem, counts, np.uint32, self.B, "Engine.push_symbols: counts")
         self._keep = (s, c)
-        _check(self.ctx.lib.dh_engine_push_symbols(self._h, mem.ptr(s), s.shape[1], mem.ptr(c)), "dh_engine_push_symbols", self.ctx.lib)
+        self._call("dh_engine_push_symbols", mem.ptr(s), s.shape[1], mem.ptr(c))
 
     def timing_enable(self, max_pushes):
-        _check(self.ctx.lib.dh_engine_timing_enable(self._h, max_pushes), "dh_engine_timing_enable", self.ctx.lib)
+        self._call("dh_engine_timing_enable", max_pushes)
         self._timing_cap = max_pushes
 
     def timing_read(self):
@@ -311,8 +358,8 @@ class Engine:
         cap = getattr(self, "_timing_cap", 0)
         a, b, c = (np.zeros(max(cap, 1), np.float32) for _ in range(3))
         n = C.c_uint32(cap)
-        _check(self.ctx.lib.dh_engine_timing_read(self._h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
-                                                  c.ctypes.data_as(C.c_void_p), C.byref(n)), "dh_engine_timing_read", self.ctx.lib)
+        self._call("dh_engine_timing_read", _host(a), _host(b),
+                                                  _host(c), C.byref(n))
         return a[:n.value], b[:n.value], c[:n.value]
 
     def timing_read_split(self):
@@ -321,15 +368,13 @@ class Engine:
         cap = getattr(self, "_timing_cap", 0)
         a, c = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.uint32)
         n = C.c_uint32(cap)
-        _check(self.ctx.lib.dh_engine_timing_read_split(self._h, a.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.byref(n)),
-               "dh_engine_timing_read_split", self.ctx.lib)
+        self._call("dh_engine_timing_read_split", _host(a), _host(c), C.byref(n))
         return a[:n.value], c[:n.value]
 
     def timing_stats(self):
         """(blocks, ordered) per channel: 100-symbol timing blocks evaluated, and those decided by the in-order chain."""
         blocks, ordered = np.zeros(self.B, np.uint32), np.zeros(self.B, np.uint32)
-        _check(self.ctx.lib.dh_engine_timing_stats(self._h, blocks.ctypes.data_as(C.c_void_p), ordered.ctypes.data_as(C.c_void_p)),
-               "dh_engine_timing_stats", self.ctx.lib)
+        self._call("dh_engine_timing_stats", _host(blocks), _host(ordered))
         return blocks, ordered
 
     def dmr_pass_b_stats(self):
@@ -340,79 +385,72 @@ class Engine:
 
     def debug_header(self, word):
         out = np.zeros(self.B, np.uint32)
-        _check(self.ctx.lib.dh_engine_debug_header(self._h, word, out.ctypes.data_as(C.c_void_p)), "dh_engine_debug_header", self.ctx.lib)
+        self._call("dh_engine_debug_header", word, _host(out))
         return out
 
     def sync(self):
         try:
-            _check(self.ctx.lib.dh_engine_sync(self._h), "dh_engine_sync", self.ctx.lib)
+            self._call("dh_engine_sync")
         finally:
             del self._inflight[:-1]              # everything queued has run (the latest stays in _keep as before)
 
-    def _fetch(self, getter, elem_dtype, with_counts=True):
-        lib = self.ctx.lib
+    _ROWS = {"symbols": np.dtype(np.uint8), "frames": np.dtype(np.uint8), "events": EVENT_DTYPE, "filtered": np.dtype(np.float32)}
+
+    def _view(self, what):
+        """(device pointer, row stride in elements, device pointer of the counts -- null for "filtered") of one output."""
         p, stride, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
-        if with_counts:
-            _check(getter(self._h, C.byref(p), C.byref(stride), C.byref(cnt)), getter.__name__, lib)
-        else:
-            _check(getter(self._h, C.byref(p), C.byref(stride)), getter.__name__, lib)
+        self._call("dh_engine_" + what, C.byref(p), C.byref(stride), *([] if what == "filtered" else [C.byref(cnt)]))
+        return p, stride.value, cnt
+
+    def _read_counts(self, cnt):
+        counts = np.empty(self.B, np.uint32)
+        self.ctx._call("dh_copy_to_host", _host(counts), cnt, counts.nbytes)
+        return counts
+
+    def _fetch(self, what):
+        p, stride, cnt = self._view(what)
         self.sync()
-        rows = np.empty((self.B, stride.value), elem_dtype)
-        _check(lib.dh_copy_to_host(rows.ctypes.data_as(C.c_void_p), p, rows.nbytes), "dh_copy_to_host", lib)
-        counts = None
-        if with_counts:
-            counts = np.empty(self.B, np.uint32)
-            _check(lib.dh_copy_to_host(counts.ctypes.data_as(C.c_void_p), cnt, counts.nbytes), "dh_copy_to_host", lib)
-        return rows, counts
+        rows = np.empty((self.B, stride), self._ROWS[what])
+        self.ctx._call("dh_copy_to_host", _host(rows), p, rows.nbytes)
+        return rows, (self._read_counts(cnt) if cnt else None)
 
     def symbols(self):
         """(dibits [B][stride] uint8, counts [B]) of the last push."""
-        return self._fetch(self.ctx.lib.dh_engine_symbols, np.uint8)
+        return self._fetch("symbols")
 
     def frames(self):
-        return self._fetch(self.ctx.lib.dh_engine_frames, np.uint8)
+        return self._fetch("frames")
 
     def events(self):
-        return self._fetch(self.ctx.lib.dh_engine_events, EVENT_DTYPE)
+        return self._fetch("events")
 
     def filtered(self):
-        rows, _ = self._fetch(self.ctx.lib.dh_engine_filtered, np.float32, with_counts=False)
-        return rows
+        return self._fetch("filtered")[0]
 
     def read_rows(self, what, channels):
         """The current push's rows of the given channels only: what = "symbols" | "frames" | "events" -> (rows [len(channels)][stride],
         counts [len(channels)]); "filtered" -> (rows, None).  For looking at a few channels of a large engine (bench.py checks the
         engine it has just timed) without copying every row to the host."""
-        lib = self.ctx.lib
-        getter, dt = {"symbols": (lib.dh_engine_symbols, np.dtype(np.uint8)), "frames": (lib.dh_engine_frames, np.dtype(np.uint8)),
-                      "events": (lib.dh_engine_events, EVENT_DTYPE), "filtered": (lib.dh_engine_filtered, np.dtype(np.float32))}[what]
-        p, stride, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
-        if what == "filtered":
-            _check(getter(self._h, C.byref(p), C.byref(stride)), getter.__name__, lib)
-        else:
-            _check(getter(self._h, C.byref(p), C.byref(stride), C.byref(cnt)), getter.__name__, lib)
+        p, stride, cnt = self._view(what)
         self.sync()
         channels = [int(c) for c in channels]
-        rows = np.empty((len(channels), stride.value), dt)
-        row_bytes = stride.value * dt.itemsize
+        rows = np.empty((len(channels), stride), self._ROWS[what])
+        row_bytes = stride * rows.itemsize
         for j, b in enumerate(channels):
             if not 0 <= b < self.B:
                 raise ValueError("Engine.read_rows: channel %d of %d" % (b, self.B))
-            _check(lib.dh_copy_to_host(rows[j].ctypes.data_as(C.c_void_p), C.c_void_p(p.value + b * row_bytes), row_bytes), "dh_copy_to_host", lib)
-        if what == "filtered":
-            return rows, None
-        counts = np.empty(self.B, np.uint32)
-        _check(lib.dh_copy_to_host(counts.ctypes.data_as(C.c_void_p), cnt, counts.nbytes), "dh_copy_to_host", lib)
-        return rows, counts[channels]
+            self.ctx._call("dh_copy_to_host", _host(rows[j]), C.c_void_p(p.value + b * row_bytes), row_bytes)
+        return rows, (self._read_counts(cnt)[channels] if cnt else None)
 
     def device_views(self):
         """Raw device pointers of the output buffers (for zero-copy consumers)."""
-        lib = self.ctx.lib
         out = {}
-        for name, getter in (("symbols", lib.dh_engine_symbols), ("frames", lib.dh_engine_frames), ("events", lib.dh_engine_events)):
-            p, stride, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
-            if getter(self._h, C.byref(p), C.byref(stride), C.byref(cnt)) == 0:
-                out[name] = (p.value, stride.value, cnt.value)
+        for name in ("symbols", "frames", "events"):
+            try:
+                p, stride, cnt = self._view(name)
+                out[name] = (p.value, stride, cnt.value)
+            except DhError:             # the engine has no such output
+                pass
         return out
 
 
@@ -430,7 +468,7 @@ SCAN_FAMILIES = (("dmr", (0, 1, 2, 3)), ("ysf", (4,)), ("nxdn", (5,)), ("dstar",
 PROTO_FRONT = {"dmr": "wide10", "ysf": "wide10", "nxdn": "narrow20", "dstar": "fsk10", "pocsag": "fsk40i"}
 
 
-class Scanner:
+class Scanner(_Handle):
     """Which protocol does each channel carry?  One protocol-scan engine (proto="scan", include/digiham_amd.h "Protocol
     scan") per front end in `fronts`, all fed the same rows: what Channelizer.push returns, with its squelch-gated
     `counts`, or any float32 [B][n] device array Engine.push takes.  Every engine counts, per channel, the hits of all nine
@@ -446,7 +484,7 @@ class Scanner:
     positions, a given period is met by chance once in 5 000 hits.  Requiring the period is what makes NXDN usable."""
 
     def __init__(self, n_channels, max_samples, fronts=("wide10", "narrow20", "fsk10", "fsk40i"), ctx=None, device=0):
-        self.ctx = ctx if ctx is not None else Context(device=device)
+        self._resolve(ctx, device)
         self.B, self.max_samples = n_channels, max_samples
         self.fronts = tuple(fronts)
         self.engines = {}
@@ -457,24 +495,23 @@ class Scanner:
         for e in getattr(self, "engines", {}).values():
             e.close()
         self.engines = {}
-
-    __del__ = close
+        super().close()
 
     def reset(self):
+        self._live("Scanner.reset")
         for e in self.engines.values():
             e.reset()
 
     def reset_channel(self, ch):
+        self._live("Scanner.reset_channel")
         for e in self.engines.values():
             e.reset_channel(ch)
 
     def push(self, x, n=None, counts=None):
         """The same rows into every front end (Engine.push: float32 [B][stride], the first n samples, or counts[b] <= n)."""
-        mem = self.ctx.mem
-        if not mem.is_device_array(x):
-            x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(self.B, -1))
-        if counts is not None and not mem.is_device_array(counts):
-            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        self._live("Scanner.push")
+        x, _ = _float_rows(self.ctx.mem, x, self.B, "Scanner.push")
+        counts = _vector(self.ctx.mem, counts, np.uint32, self.B, "Scanner.push: counts")
         for e in self.engines.values():
             e.push(x, n=n, counts=counts)
 
@@ -523,27 +560,7 @@ class Scanner:
 PREROLL_NONE = _capi.PREROLL_NONE
 
 
-def _float_rows(mem, x, B, what):
-    """(array, row stride) of float32 [B][n] rows the library can read where they are: a device array whose rows are
-    contiguous -- a column slice of a wider array included, rows need no alignment -- or a copy of anything else."""
-    torch = getattr(mem, "torch", None)
-    if torch is not None and torch.is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != B or (x.shape[1] > 1 and x.stride(1) != 1):
-            raise ValueError("%s: need a float32 [%d][n] device array with contiguous rows, got %s %s strides %s"
-                             % (what, B, x.dtype, tuple(x.shape), tuple(x.stride())))
-        if x.device.index != mem.index:
-            raise ValueError("%s: the array lives on cuda:%s, the handle on cuda:%s" % (what, x.device.index, mem.index))
-        return x, (x.stride(0) if B > 1 else x.shape[1])
-    in_place = torch is None and isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.shape[0] == B and \
-        (x.shape[1] <= 1 or x.strides[1] == 4) and (B == 1 or (x.strides[0] > 0 and x.strides[0] % 4 == 0))
-    if not in_place:
-        x = mem.from_numpy(np.ascontiguousarray(x, np.float32).reshape(B, -1))
-    if callable(getattr(x, "stride", None)):
-        return x, (x.stride(0) if B > 1 else x.shape[1])
-    return x, (x.strides[0] // 4 if B > 1 else x.shape[1])
-
-
-class Preroll:
+class Preroll(_Handle):
     """Every channel's last `depth` samples in a ring on the device (dh_preroll; include/digiham_amd.h "Pre-roll"), and
     for every channel the stream index at which its current run of open pushes began.
 
@@ -551,27 +568,16 @@ class Preroll:
     per channel, the samples from max(from_[b], oldest) + skip on as (rows, counts, start): rows and counts are device
     arrays, exactly what Engine.push(rows, n=max_n, counts=counts) takes.  The counts array is the handle's own and is
     rewritten by the next gather.  The ring takes n_channels x depth x 4 bytes."""
+    _kind = "dh_preroll"
 
     def __init__(self, n_channels, depth, ctx=None, device=0):
-        self.ctx = ctx if ctx is not None else Context(device=device)
-        lib, mem = self.ctx.lib, self.ctx.mem
         self.B, self.depth = int(n_channels), int(depth)
-        cfg = _capi.PrerollConfig(C.sizeof(_capi.PrerollConfig), getattr(mem, "index", 0), self.B, self.depth, mem.stream())
-        h = C.c_void_p()
-        _check(lib.dh_preroll_create(C.byref(cfg), C.byref(h)), "dh_preroll_create", lib)
-        self._h = h
-        self._counts = mem.zeros((self.B,), np.uint32)
+        self._open(ctx, device, _capi.PrerollConfig, n_channels=self.B, depth=self.depth)
+        self._counts = self.ctx.mem.zeros((self.B,), np.uint32)
         self._keep = None
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx.lib.dh_preroll_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def reset(self):
-        _check(self.ctx.lib.dh_preroll_reset(self._h), "dh_preroll_reset", self.ctx.lib)
+        self._call("dh_preroll_reset")
 
     def append(self, rows, n=None, counts=None):
         """rows: float32 [B][stride]; the first n samples of every row (default: all).  counts: [B] uint32, non-zero = the
@@ -579,23 +585,20 @@ class Preroll:
         mem = self.ctx.mem
         x, stride = _float_rows(mem, rows, self.B, "Preroll.append")
         n = x.shape[1] if n is None else int(n)
-        c = None
-        if counts is not None:
-            c = counts if mem.is_device_array(counts) else mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        c = _vector(mem, counts, np.uint32, self.B, "Preroll.append: counts")
         self._keep = (x, c)         # the launch is asynchronous: keep the inputs alive
-        _check(self.ctx.lib.dh_preroll_append(self._h, mem.ptr(x), stride, n, mem.ptr(c) if c is not None else None),
-               "dh_preroll_append", self.ctx.lib)
+        self._call("dh_preroll_append", mem.ptr(x), stride, n, _ptr(mem, c))
 
     @property
     def total(self):
         t = C.c_uint64(0)
-        _check(self.ctx.lib.dh_preroll_total(self._h, C.byref(t)), "dh_preroll_total", self.ctx.lib)
+        self._call("dh_preroll_total", C.byref(t))
         return t.value
 
     def open_at(self):
         """[B] uint64: PREROLL_NONE for a channel whose gate was closed in the last push.  Synchronises."""
         out = np.empty(self.B, np.uint64)
-        _check(self.ctx.lib.dh_preroll_open_at(self._h, out.ctypes.data_as(C.c_void_p)), "dh_preroll_open_at", self.ctx.lib)
+        self._call("dh_preroll_open_at", _host(out))
         return out
 
     def gather(self, from_, skip, max_n, out=None):
@@ -612,17 +615,15 @@ class Preroll:
         if rows is not out:
             raise ValueError("Preroll.gather: out must be a float32 [%d][n] device array with contiguous rows" % self.B)
         start = np.empty(self.B, np.uint64)
-        _check(self.ctx.lib.dh_preroll_gather(self._h, f.ctypes.data_as(C.c_void_p), int(skip), max_n, mem.ptr(rows), stride,
-                                              mem.ptr(self._counts), start.ctypes.data_as(C.c_void_p)), "dh_preroll_gather", self.ctx.lib)
+        self._call("dh_preroll_gather", _host(f), int(skip), max_n, mem.ptr(rows), stride,
+                                              mem.ptr(self._counts), _host(start))
         return rows, self._counts, start
 
     def gather_device(self, from_dev, skip, max_n, out=None):
         """gather with `from_dev` ([B] uint64, or int64 holding the same bits) on the device already: no upload, no start.
         Returns (rows, counts)."""
         mem = self.ctx.mem
-        f = from_dev if mem.is_device_array(from_dev) else mem.from_numpy(np.ascontiguousarray(from_dev, np.uint64))
-        if tuple(f.shape) != (self.B,) or (f.element_size() if callable(getattr(f, "element_size", None)) else f.itemsize) != 8:
-            raise ValueError("Preroll.gather_device: from_dev needs %d 64-bit entries" % self.B)
+        f = _vector(mem, from_dev, np.uint64, self.B, "Preroll.gather_device: from_dev")
         max_n = int(max_n)
         if out is None:
             out = mem.zeros((self.B, max(max_n, 1)), np.float32)
@@ -630,12 +631,38 @@ class Preroll:
         if rows is not out:
             raise ValueError("Preroll.gather_device: out must be a float32 [%d][n] device array with contiguous rows" % self.B)
         self._keep = (f, rows)
-        _check(self.ctx.lib.dh_preroll_gather_device(self._h, mem.ptr(f), int(skip), max_n, mem.ptr(rows), stride, mem.ptr(self._counts)),
-               "dh_preroll_gather_device", self.ctx.lib)
+        self._call("dh_preroll_gather_device", mem.ptr(f), int(skip), max_n, mem.ptr(rows), stride, mem.ptr(self._counts))
         return rows, self._counts
 
 
-class Monitor:
+def _row_blocks(eng, name, channels, first_sample, blocks):
+    """The monitors' blocks of one engine push, read from the engine's rows: one per channel of `channels` (first_sample
+    [len(channels)]) that has frames or events."""
+    if 16 * len(channels) >= eng.B:                      # many rows: two whole arrays cost less than a copy per row (~17 us each on an MI355X)
+        (frames, fc), (events, ec) = eng.frames(), eng.events()
+        frames, fc, events, ec = frames[channels], fc[channels], events[channels], ec[channels]
+    else:
+        frames, fc = eng.read_rows("frames", channels)
+        events, ec = eng.read_rows("events", channels)
+    for j, b in enumerate(channels):
+        if fc[j] or ec[j]:
+            blocks.append({"channel": int(b), "proto": name, "first_sample": int(first_sample[j]),
+                           "frames": frames[j, :fc[j]].copy(), "events": events[j, :ec[j]].copy()})
+
+
+def _packed_blocks(entries, events, frames, user_key, tag_key, names=None):
+    """One dict per entry of a pack that was read: "channel", the entry's user word under user_key (names: the name of its
+    low byte instead), its tag under tag_key, and its "frames" and "events"."""
+    return [{"channel": b, user_key: user if names is None else names[user & 255], tag_key: tag,
+             "frames": frames[16 * off:16 * off + fc], "events": events[ei:ei + ec]} for b, user, tag, fc, ec, off, ei in entries.tolist()]
+
+
+def _by_position(blocks):
+    blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
+    return blocks
+
+
+class Monitor(_Handle):
     """A band monitor over the rows of a channelizer: one Scanner names the protocol an open channel carries, one Preroll
     keeps every channel's recent past, and one Engine per protocol in `protos` (behind the front end of PROTO_FRONT)
     decodes a named channel FROM WHERE ITS SQUELCH OPENED -- `lead` samples earlier, as far as the ring reaches -- not from
@@ -667,7 +694,7 @@ class Monitor:
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
                  protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0):
-        self.ctx = ctx if ctx is not None else Context(device=device)
+        self._resolve(ctx, device)
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
         self.protos = tuple(protos)
@@ -692,30 +719,18 @@ class Monitor:
             if getattr(self, h, None) is not None:
                 getattr(self, h).close()
                 setattr(self, h, None)
-
-    __del__ = close
+        super().close()
 
     def reset(self):
+        self._live("Monitor.reset")
         self.scanner.reset()
         self.pre.reset()
         for e in self.engines.values():
             e.reset()
         self._clear()
 
-    def _collect(self, name, channels, first_sample, blocks):
-        eng = self.engines[name]
-        if 16 * len(channels) >= self.B:                 # many rows: two whole arrays cost less than a copy per row (~17 us each on an MI355X)
-            (frames, fc), (events, ec) = eng.frames(), eng.events()
-            frames, fc, events, ec = frames[channels], fc[channels], events[channels], ec[channels]
-        else:
-            frames, fc = eng.read_rows("frames", channels)
-            events, ec = eng.read_rows("events", channels)
-        for j, b in enumerate(channels):
-            if fc[j] or ec[j]:
-                blocks.append({"channel": b, "proto": name, "first_sample": int(first_sample[j]),
-                               "frames": frames[j, :fc[j]].copy(), "events": events[j, :ec[j]].copy()})
-
     def push(self, rows, n=None, counts=None):
+        self._live("Monitor.push")
         mem = self.ctx.mem
         x, _ = _float_rows(mem, rows, self.B, "Monitor.push")
         n = x.shape[1] if n is None else int(n)
@@ -723,8 +738,7 @@ class Monitor:
             return []
         if n > self.max_samples:
             raise DhError(_capi.DH_EINVAL, "Monitor.push", "n = %d > max_samples = %d" % (n, self.max_samples))
-        if counts is not None and not mem.is_device_array(counts):
-            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        counts = _vector(mem, counts, np.uint32, self.B, "Monitor.push: counts")
         self.pre.append(x, n, counts)
         open_at, total = self.pre.open_at(), self.pre.total
         is_open = open_at != np.uint64(PREROLL_NONE)
@@ -758,16 +772,15 @@ class Monitor:
             for skip in range(0, total - int(first.min()), self.max_samples):
                 stage, cnt, _ = self.pre.gather(from_, skip, self.max_samples, out=self.stage)
                 eng.push(stage, n=self.max_samples, counts=cnt)
-                self._collect(name, chans, first + skip, blocks)
+                _row_blocks(eng, name, chans, first + skip, blocks)
         for name, eng in self.engines.items():
             chans = [b for b in range(self.B) if before[b] == name and is_open[b]]
             if chans:
                 live = np.zeros(self.B, np.uint32)
                 live[chans] = n
                 eng.push(x, n=n, counts=live)
-                self._collect(name, chans, np.full(len(chans), total - n, np.int64), blocks)
-        blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
-        return blocks
+                _row_blocks(eng, name, chans, np.full(len(chans), total - n, np.int64), blocks)
+        return _by_position(blocks)
 
 
 PROTO_NAMES = {_capi.PROTO[name]: name for name in ("dmr", "ysf", "nxdn", "pocsag", "dstar")}
@@ -775,7 +788,7 @@ PROTO_NAMES = {_capi.PROTO[name]: name for name in ("dmr", "ysf", "nxdn", "pocsa
 OUTPACK_ENTRY_DTYPE = np.dtype(_capi.OUTPACK_ENTRY_DTYPE)
 
 
-class OutPack:
+class OutPack(_Handle):
     """What the pushes of a round produced, compacted on the device (dh_outpack; include/digiham_amd.h "Packed read-out").
 
     append(engine, ...) is asynchronous on the engine's stream and may follow any number of pushes of any engines that
@@ -783,46 +796,32 @@ class OutPack:
     header a dict of the dh_outpack_header fields, entries an OUTPACK_ENTRY_DTYPE array, events an EVENT_DTYPE array and
     frames uint8.  Entry i owns frames[16 * frame_offset16:][:n_frame_bytes] and events[event_index:][:n_events].  A pack
     that had to drop something says so in header["dropped"] (and `rc` is DH_ECAPACITY); what was kept is delivered."""
+    _kind = "dh_outpack"
 
     def __init__(self, max_entries, max_events, max_frame_bytes, ctx=None, device=0):
-        self.ctx = ctx if ctx is not None else Context(device=device)
-        lib, mem = self.ctx.lib, self.ctx.mem
         self.max_entries, self.max_events, self.max_frame_bytes = int(max_entries), int(max_events), int(max_frame_bytes)
-        cfg = _capi.OutpackConfig(C.sizeof(_capi.OutpackConfig), getattr(mem, "index", 0), self.max_entries, self.max_events,
-                                  self.max_frame_bytes, mem.stream())
-        h = C.c_void_p()
-        _check(lib.dh_outpack_create(C.byref(cfg), C.byref(h)), "dh_outpack_create", lib)
-        self._h = h
+        self._open(ctx, device, _capi.OutpackConfig, max_entries=self.max_entries, max_events=self.max_events,
+                   max_frame_bytes=self.max_frame_bytes)
         # dh_outpack_read takes arrays of the create capacities; only what a read fills is ever touched
         self._entries = np.empty(self.max_entries, OUTPACK_ENTRY_DTYPE)
         self._events = np.empty(self.max_events, EVENT_DTYPE)
         self._frames = np.empty(self.max_frame_bytes, np.uint8)
         self._keep, self.rc = [], 0
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx.lib.dh_outpack_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def clear(self):
-        _check(self.ctx.lib.dh_outpack_clear(self._h), "dh_outpack_clear", self.ctx.lib)
+        self._call("dh_outpack_clear")
 
     def append(self, engine, mask=None, tag=None, tag_add=0, user=0):
         """mask: [B] uint32 (non-zero: the channel takes part) or None; tag: [B] uint64 or None; numpy or device arrays."""
         mem = self.ctx.mem
-        dev = lambda a, dt: None if a is None else a if mem.is_device_array(a) and not isinstance(a, np.ndarray) else mem.from_numpy(np.ascontiguousarray(a, dt))
-        m, t = dev(mask, np.uint32), dev(tag, np.uint64)
+        B = getattr(engine, "B", None)          # (None: a bare dh_engine handle, whose channel count only the caller knows)
+        m, t = _vector(mem, mask, np.uint32, B, "OutPack.append: mask"), _vector(mem, tag, np.uint64, B, "OutPack.append: tag")
         self._keep.append((m, t))       # the launches are asynchronous: keep the arrays alive until the next read
-        _check(self.ctx.lib.dh_outpack_append(self._h, getattr(engine, "_h", engine), mem.ptr(m) if m is not None else None,
-                                              mem.ptr(t) if t is not None else None, int(tag_add) & 0xFFFFFFFFFFFFFFFF, int(user)),
-               "dh_outpack_append", self.ctx.lib)
+        self._call("dh_outpack_append", getattr(engine, "_h", engine), _ptr(mem, m), _ptr(mem, t), int(tag_add) & 0xFFFFFFFFFFFFFFFF, int(user))
 
     def read(self):
         lib, hdr = self.ctx.lib, _capi.OutpackHeader()
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        self.rc = lib.dh_outpack_read(self._h, C.byref(hdr), ptr(self._entries), ptr(self._events), ptr(self._frames))
+        self.rc = lib.dh_outpack_read(self._h, C.byref(hdr), _host(self._entries), _host(self._events), _host(self._frames))
         self._keep = []
         if self.rc != _capi.DH_ECAPACITY:
             _check(self.rc, "dh_outpack_read", lib)
@@ -831,15 +830,10 @@ class OutPack:
 
     def blocks(self):
         """read(), as a list of {"channel", "user", "tag", "frames", "events"} in the pack's order."""
-        _, entries, events, frames = self.read()
-        out = []
-        for en in entries.tolist():
-            b, user, tag, fc, ec, off, ei = en
-            out.append({"channel": b, "user": user, "tag": tag, "frames": frames[16 * off:16 * off + fc], "events": events[ei:ei + ec]})
-        return out
+        return _packed_blocks(*self.read()[1:], "user", "tag")
 
 
-class DeviceMonitor:
+class DeviceMonitor(_Handle):
     """Monitor behind the C ABI (dh_monitor; include/digiham_amd.h "Band monitor"): the same constructor arguments, the same
     rounds, the same blocks from push() -- but the scan engines, the ring, the protocol engines and the staging array
     belong to one library handle, and the per-round bookkeeping runs in kernels: the host reads one fixed-size summary per
@@ -852,22 +846,19 @@ class DeviceMonitor:
 
     packed=True: the monitor owns an OutPack sized so that a round can never drop, and push() is clear,
     dh_monitor_push_packed, one read: no sink, no read-back per engine push, copies sized by what was decoded."""
+    _kind = "dh_monitor"
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
                  protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False):
-        self.ctx = ctx if ctx is not None else Context(device=device)
-        lib, mem = self.ctx.lib, self.ctx.mem
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
         self.protos = tuple(protos)
         bits = 0
         for p in self.protos:
             bits |= 1 << _capi.PROTO[p]
-        cfg = _capi.MonitorConfig(C.sizeof(_capi.MonitorConfig), getattr(mem, "index", 0), self.B, self.max_samples, self.depth,
-                                  self.lead, self.confirm, self.release, bits, mem.stream())
-        h = C.c_void_p()
-        _check(lib.dh_monitor_create(C.byref(cfg), C.byref(h)), "dh_monitor_create", lib)
-        self._h = h
+        self._open(ctx, device, _capi.MonitorConfig, n_channels=self.B, max_samples=self.max_samples, depth=self.depth, lead=self.lead,
+                   confirm=self.confirm, release=self.release, protos=bits)
+        lib, h = self.ctx.lib, self._h
         self.engines = {p: Engine._borrowed(self.ctx, lib.dh_monitor_engine(h, _capi.PROTO[p]), self.B, self.max_samples) for p in self.protos}
         self.scanner = Scanner.__new__(Scanner)
         self.scanner.ctx, self.scanner.B, self.scanner.max_samples = self.ctx, self.B, self.max_samples
@@ -887,40 +878,34 @@ class DeviceMonitor:
             chunks = max(1, -(-self.depth // self.max_samples))
             n_ev = n_fb = 0
             for e in self.engines.values():
-                p, stride, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
-                _check(lib.dh_engine_frames(e._h, C.byref(p), C.byref(stride), C.byref(cnt)), "dh_engine_frames", lib)
-                n_fb += stride.value * self.B * chunks
-                _check(lib.dh_engine_events(e._h, C.byref(p), C.byref(stride), C.byref(cnt)), "dh_engine_events", lib)
-                n_ev += stride.value * self.B * chunks
+                n_fb += e._view("frames")[1] * self.B * chunks
+                n_ev += e._view("events")[1] * self.B * chunks
             self.pack = OutPack(min(len(self.engines) * self.B * chunks, 0xFFFFFFFF), min(n_ev, 0xFFFFFFFF), min(n_fb, (1 << 36) - 16), ctx=self.ctx)
 
     def close(self):
         if getattr(self, "pack", None) is not None:
             self.pack.close()
             self.pack = None
-        if getattr(self, "_h", None):
+        if self._h:
             for e in list(self.engines.values()) + list(self.scanner.engines.values()):
                 e.close()
-            self.ctx.lib.dh_monitor_destroy(self._h)
-            self._h = None
             self.engines, self.scanner.engines = {}, {}
-
-    __del__ = close
+        super().close()
 
     def reset(self):
-        _check(self.ctx.lib.dh_monitor_reset(self._h), "dh_monitor_reset", self.ctx.lib)
+        self._call("dh_monitor_reset")
         self._state = None
 
     @property
     def total(self):
         t = C.c_uint64(0)
-        _check(self.ctx.lib.dh_monitor_total(self._h, C.byref(t)), "dh_monitor_total", self.ctx.lib)
+        self._call("dh_monitor_total", C.byref(t))
         return t.value
 
     def _read_state(self):
         if self._state is None:
             a, s = np.empty(self.B, np.uint8), np.empty(self.B, np.uint64)
-            _check(self.ctx.lib.dh_monitor_state(self._h, a.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)), "dh_monitor_state", self.ctx.lib)
+            self._call("dh_monitor_state", _host(a), _host(s))
             self._state = ([PROTO_NAMES.get(int(v)) for v in a], [None if int(v) == PREROLL_NONE else int(v) for v in s])
         return self._state
 
@@ -934,28 +919,18 @@ class DeviceMonitor:
 
     def _on_push(self, user, info):
         try:
-            lib, i = self.ctx.lib, info.contents
+            i = info.contents
             name = PROTO_NAMES[i.proto]
             eng = self.engines[name]
             eng.sync()
-            counts, start = np.empty(self.B, np.uint32), np.empty(self.B, np.uint64)
-            _check(lib.dh_copy_to_host(counts.ctypes.data_as(C.c_void_p), C.c_void_p(i.d_counts), counts.nbytes), "dh_copy_to_host", lib)
-            channels = np.flatnonzero(counts)
+            channels = np.flatnonzero(eng._read_counts(C.c_void_p(i.d_counts)))
             if i.replay:
-                _check(lib.dh_copy_to_host(start.ctypes.data_as(C.c_void_p), C.c_void_p(i.d_start), start.nbytes), "dh_copy_to_host", lib)
+                start = np.empty(self.B, np.uint64)
+                self.ctx._call("dh_copy_to_host", _host(start), C.c_void_p(i.d_start), start.nbytes)
                 first = start[channels].astype(np.int64) + int(i.skip)
             else:
                 first = np.full(len(channels), int(i.live_first), np.int64)
-            if 16 * len(channels) >= self.B:
-                (frames, fc), (events, ec) = eng.frames(), eng.events()
-                frames, fc, events, ec = frames[channels], fc[channels], events[channels], ec[channels]
-            else:
-                frames, fc = eng.read_rows("frames", channels)
-                events, ec = eng.read_rows("events", channels)
-            for j, b in enumerate(channels):
-                if fc[j] or ec[j]:
-                    self._blocks.append({"channel": int(b), "proto": name, "first_sample": int(first[j]),
-                                         "frames": frames[j, :fc[j]].copy(), "events": events[j, :ec[j]].copy()})
+            _row_blocks(eng, name, channels, first, self._blocks)
         except BaseException as e:          # (an exception cannot cross the C frames: push() raises it)
             if self._error is None:
                 self._error = e
@@ -968,29 +943,23 @@ class DeviceMonitor:
             return []
         if n > self.max_samples:
             raise DhError(_capi.DH_EINVAL, "DeviceMonitor.push", "n = %d > max_samples = %d" % (n, self.max_samples))
-        if counts is not None and not mem.is_device_array(counts):
-            counts = mem.from_numpy(np.ascontiguousarray(counts, np.uint32))
+        counts = _vector(mem, counts, np.uint32, self.B, "DeviceMonitor.push: counts")
         self._keep = (x, counts)
         if self.pack is not None:
             self._state = None
             self.pack.clear()
-            _check(self.ctx.lib.dh_monitor_push_packed(self._h, mem.ptr(x), stride, n, mem.ptr(counts) if counts is not None else None, self.pack._h),
-                   "dh_monitor_push_packed", self.ctx.lib)
+            self._call("dh_monitor_push_packed", mem.ptr(x), stride, n, _ptr(mem, counts), self.pack._h)
             header, entries, events, frames = self.pack.read()
             if header["dropped"]:
                 raise DhError(_capi.DH_ECAPACITY, "DeviceMonitor.push", "the pack dropped %d blocks" % header["dropped"])
-            blocks = [{"channel": b, "proto": PROTO_NAMES[user & 255], "first_sample": tag, "frames": frames[16 * off:16 * off + fc], "events": events[ei:ei + ec]}
-                      for b, user, tag, fc, ec, off, ei in entries.tolist()]
-            blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
-            return blocks
+            return _by_position(_packed_blocks(entries, events, frames, "proto", "first_sample", PROTO_NAMES))
         self._blocks, self._error, self._state = [], None, None
-        rc = self.ctx.lib.dh_monitor_push(self._h, mem.ptr(x), stride, n, mem.ptr(counts) if counts is not None else None, self._sink, None)
+        rc = self.ctx.lib.dh_monitor_push(self._h, mem.ptr(x), stride, n, _ptr(mem, counts), self._sink, None)
         blocks, self._blocks = self._blocks, None
         if self._error is not None:
             raise self._error
         _check(rc, "dh_monitor_push", self.ctx.lib)
-        blocks.sort(key=lambda blk: (blk["channel"], blk["first_sample"]))
-        return blocks
+        return _by_position(blocks)
 
 
 def channel_taps(input_rate, decimation, passband_hz, stopband_hz, atten_db=60.0, interpolation=1):
@@ -1040,7 +1009,7 @@ def resample_ratio(input_rate, output_rate=48000.0):
     return L, M
 
 
-class Channelizer:
+class Channelizer(_Handle):
     """One wideband complex stream -> one row per channel at input_rate * interpolation / decimation (dh_channelizer; the
     arithmetic is specified in digiham_amd/csrc/channelizer_core.hpp).  interpolation is 1 unless the capture rate is no
     multiple of the output rate; resample_ratio gives the pair, and `taps` is then channel_taps(..., interpolation=L).
@@ -1050,23 +1019,20 @@ class Channelizer:
     valid in [:, :n_out] until the next push.
     enable_power(...) adds per-channel block power and a squelch gate: after every push `counts` (device uint32 [B]) is what
     Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed."""
+    _kind = "dh_channelizer"
 
     def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
                  ctx=None, device=0, interpolation=1):
-        self.ctx = ctx if ctx is not None else Context(device=device)
-        lib, mem = self.ctx.lib, self.ctx.mem
         self.rate, self.D, self.B = float(input_rate), int(decimation), len(freqs_hz)
         self.L = max(int(interpolation), 1)
         self.input, self.output = input, output
         t = np.ascontiguousarray(taps, np.float32).ravel()
         inc = np.array([nco_increment(f, input_rate) for f in freqs_hz], np.uint32)
-        cfg = _capi.ChannelizerConfig(C.sizeof(_capi.ChannelizerConfig), getattr(mem, "index", 0), self.B, self.D,
-                                      t.ctypes.data_as(C.POINTER(C.c_float)), len(t), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      _capi.CZ_INPUT[input], _capi.CZ_OUTPUT[output], int(bool(dcblock) and output == "fm"),
-                                      int(max_input), mem.stream(), int(interpolation))
-        h = C.c_void_p()
-        _check(lib.dh_channelizer_create(C.byref(cfg), C.byref(h)), "dh_channelizer_create", lib)
-        self._h = h
+        self._open(ctx, device, _capi.ChannelizerConfig, n_channels=self.B, decimation=self.D, taps=t.ctypes.data_as(C.POINTER(C.c_float)),
+                   n_taps=len(t), increments=inc.ctypes.data_as(C.POINTER(C.c_uint32)), input_format=_capi.CZ_INPUT[input],
+                   output_mode=_capi.CZ_OUTPUT[output], dcblock=int(bool(dcblock) and output == "fm"), max_input=int(max_input),
+                   interpolation=int(interpolation))
+        mem = self.ctx.mem
         self.max_input = int(max_input)
         self.out_stride = self.max_input * self.L // self.D + 1
         self.rows = mem.zeros((self.B, self.out_stride) if output == "fm" else (self.B, self.out_stride, 2), np.float32)
@@ -1089,31 +1055,23 @@ class Channelizer:
         counts = mem.zeros((self.B,), np.uint32)
         cfg = _capi.ChannelizerPowerConfig(C.sizeof(_capi.ChannelizerPowerConfig), block, self._level(open_db), self._level(close_db),
                                            int(hang_blocks), mem.ptr(power), mem.ptr(gate), mem.ptr(counts), stride)
-        _check(self.ctx.lib.dh_channelizer_power_enable(self._h, C.byref(cfg)), "dh_channelizer_power_enable", self.ctx.lib)
+        self._call("dh_channelizer_power_enable", C.byref(cfg))
         self.block, self.power, self.gate, self.counts = block, power, gate, counts
 
     def set_squelch(self, open_db, close_db, hang_blocks):
-        _check(self.ctx.lib.dh_channelizer_set_squelch(self._h, self._level(open_db), self._level(close_db), int(hang_blocks)),
-               "dh_channelizer_set_squelch", self.ctx.lib)
+        self._call("dh_channelizer_set_squelch", self._level(open_db), self._level(close_db), int(hang_blocks))
 
     def power_blocks(self):
         """(power[:, :n], gate[:, :n], first_block) of the last push, device arrays: column i is block first_block + i."""
         first, n = C.c_uint64(0), C.c_size_t(0)
-        _check(self.ctx.lib.dh_channelizer_power_last(self._h, C.byref(first), C.byref(n)), "dh_channelizer_power_last", self.ctx.lib)
+        self._call("dh_channelizer_power_last", C.byref(first), C.byref(n))
         return self.power[:, :n.value], self.gate[:, :n.value], first.value
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx.lib.dh_channelizer_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def reset(self):
-        _check(self.ctx.lib.dh_channelizer_reset(self._h), "dh_channelizer_reset", self.ctx.lib)
+        self._call("dh_channelizer_reset")
 
     def retune(self, ch, hz):
-        _check(self.ctx.lib.dh_channelizer_retune(self._h, int(ch), nco_increment(hz, self.rate)), "dh_channelizer_retune", self.ctx.lib)
+        self._call("dh_channelizer_retune", int(ch), nco_increment(hz, self.rate))
 
     def push(self, x):
         """x: numpy (host) or a device array: int16 [n][2] / [2 n] for "cs16", float32 [n][2] / [2 n] or complex64 [n] for
@@ -1129,16 +1087,14 @@ class Channelizer:
                 raise ValueError("Channelizer.push: need a contiguous %s device array, got %s" % (want, x.dtype))
             a, n, dev = x, x.numel() // 2, True
         cnt = C.c_size_t(0)
-        fn = self.ctx.lib.dh_channelizer_push if dev else self.ctx.lib.dh_channelizer_push_host
-        ptr = mem.ptr(a) if dev else a.ctypes.data_as(C.c_void_p)
         self._keep = a              # asynchronous: the input stays alive until the next push
-        _check(fn(self._h, ptr, n, mem.ptr(self.rows), self.out_stride, C.byref(cnt)), "dh_channelizer_push", self.ctx.lib)
+        self._call("dh_channelizer_push" if dev else "dh_channelizer_push_host", mem.ptr(a) if dev else _host(a), n, mem.ptr(self.rows),
+                   self.out_stride, C.byref(cnt))
         return self.rows, cnt.value
 
     def phasor(self, phi):
         """P(phi) of the specification for uint32 phase words (host arithmetic) -> complex128 array."""
         p = np.ascontiguousarray(phi, np.uint32).ravel()
         out = np.zeros((p.size, 2), np.float32)
-        _check(self.ctx.lib.dh_channelizer_phasor(p.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), p.size),
-               "dh_channelizer_phasor", self.ctx.lib)
+        self.ctx._call("dh_channelizer_phasor", _host(p), _host(out), p.size)
         return out[:, 0].astype(np.float64) + 1j * out[:, 1].astype(np.float64)

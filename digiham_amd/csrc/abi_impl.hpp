@@ -21,7 +21,16 @@
 //   int  dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, float* d, size_t tiles, void* stream);
 //   int  dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* stream);
 //   int  dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream);
-//   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_fm: the channelizer's launches, listed where they are used (below)
+// and the launches of the four later handles, each listed at the head of its section below:
+//   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_gemm_rat / dh_be_cz_fm / dh_be_cz_power      the channelizer
+//   dh_be_preroll_append / dh_be_preroll_gather                                            the pre-roll ring
+//   dh_be_outpack_scan / dh_be_outpack_copy                                                the packed read-out
+//   dh_be_monitor_open / dh_be_monitor_assign, dh_be_reset_channels                        the band monitor, the masked reset
+// (engine.hip defines the gfx950 ones; the *_core.hpp files the CPU harness's.)
+//
+// A handle kind is a struct over dh_place (device, stream) with a backend `be`, scope() and release(), an init() that
+// allocates through its DeviceBuffers, and a dh_*_create that validates its configuration and calls dh_create; dh_destroy,
+// DH_ENTER and shares_stream() are the same for all of them.
 #pragma once
 
 #include <cstddef>
@@ -32,14 +41,88 @@
 
 static_assert(sizeof(dh_event) == 32, "dh_event layout");
 
-struct dh_engine {
-    dh::Engine<DH_BACKEND> impl;
-    int device = 0; void* stream = nullptr;             // the configuration's: what a handle that works on this engine's outputs must share
-    auto scope() const { return impl.be.scope(); }      // (as dh_channelizer::scope: DH_ON_DEVICE takes either handle)
+// where a handle lives: what two handles that work on each other's buffers must have in common
+struct dh_place {
+    int device = 0; void* stream = nullptr;
+    bool shares_stream(const dh_place& o) const { return device == o.device && stream == o.stream; }
 };
-// every entry that touches the device runs on its handle's device (an engine's, a channelizer's) whatever the calling
-// thread's current device is (HipBackend::Scope)
+// one [B][stride] output of an engine: what a getter hands out and what a row read needs
+struct DhRows { const void* base; size_t stride; const uint32_t* counts; size_t elem; uint32_t most; };      // stride in elements
+enum { DH_ROWS_SYMBOLS, DH_ROWS_FRAMES, DH_ROWS_EVENTS, DH_ROWS_FILTERED };
+struct dh_engine : dh_place {
+    dh::Engine<DH_BACKEND> impl;
+    DH_BACKEND& be = impl.be;                           // the face every handle shows dh_create, dh_destroy and DH_ON_DEVICE
+    auto scope() const { return be.scope(); }
+    void release() { impl.destroy(); }
+    DhRows rows(int which) const {
+        const auto& L = impl.L;
+        switch (which) {
+        case DH_ROWS_SYMBOLS: return { impl.syms, L.sym_stride, impl.sym_count, 1, ~0u };
+        case DH_ROWS_FRAMES: return { impl.frames, L.out_cap, impl.frame_count, 1, ~0u };
+        case DH_ROWS_EVENTS: return { impl.events, L.ev_cap, impl.ev_count, sizeof(dh_event), ~0u };
+        default: return { impl.filtered, L.max_samples, impl.last_counts, sizeof(float), impl.last_n };     // (the last push's samples)
+        }
+    }
+};
+// the four handles that own their backend and their buffers (a handle whose release() has more to let go of hides this one)
+struct dh_state : dh_place {
+    DH_BACKEND be;
+    dh::DeviceBuffers<DH_BACKEND> bufs{ be };           // release(), and what the handle's clear() / retune() act on
+    auto scope() const { return be.scope(); }
+    void release() { bufs.free_all(); }
+};
+// every entry that touches the device runs on its handle's device whatever the calling thread's current device is
+// (HipBackend::Scope)
 #define DH_ON_DEVICE(h) auto dh_on_device_ = (h)->scope(); (void) dh_on_device_
+// the opening of such an entry: a null handle (or a failed argument check, which may read the handle) is answered before
+// anything touches the device
+#define DH_ENTER_IF(h, ok) if (!(h) || !(ok)) return DH_EINVAL; DH_ON_DEVICE(h)
+#define DH_ENTER(h) DH_ENTER_IF(h, true)
+
+// dh_*_create behind its own validation: the handle, its backend, its place, then init(handle) on the handle's device; a
+// failed init lets go of whatever it had allocated
+template <class H, class Cfg, class Init>
+static int dh_create(const Cfg& c, H** out, Init init) {
+    *out = nullptr;
+    H* h = new (std::nothrow) H;
+    if (!h) return DH_ENOMEM;
+    int rc = h->be.open(c.device, c.stream);
+    if (rc == DH_OK) {
+        DH_ON_DEVICE(h);
+        h->device = c.device; h->stream = c.stream;
+        rc = init(*h);
+        if (rc != DH_OK) h->release();
+    }
+    if (rc != DH_OK) { delete h; return rc; }
+    *out = h;
+    return DH_OK;
+}
+template <class H>
+static void dh_destroy(H* h) {
+    if (!h) return;
+    {
+        DH_ON_DEVICE(h);
+        h->be.sync();
+        h->be.close();
+        h->release();
+    }
+    delete h;
+}
+
+// the engine's four outputs behind dh_engine_symbols / frames / events / filtered and dh_engine_read_*
+static int dh_rows_view(const dh_engine* e, int which, const void** d, size_t* stride, const uint32_t** cnt) {
+    const void* base = e ? e->rows(which).base : nullptr;
+    if (!base) return DH_EINVAL;
+    if (d) *d = base;
+    if (stride) *stride = e->rows(which).stride;
+    if (cnt) *cnt = e->rows(which).counts;
+    return DH_OK;
+}
+static int dh_rows_read(dh_engine* e, int which, uint32_t ch, void* h, size_t* n) {
+    DH_ENTER_IF(e, e->rows(which).base);
+    const DhRows r = e->rows(which);
+    return e->impl.read_row(r.base, r.elem * r.stride, ch, r.counts, r.elem, h, n, r.most);
+}
 
 enum { DH_CODE_H74 = 0, DH_CODE_H139, DH_CODE_H1511, DH_CODE_H1611, DH_CODE_QR, DH_CODE_G208, DH_CODE_G2412, DH_CODE_BCH3121 };
 
@@ -116,118 +199,54 @@ int dh_debug_copy(const void* src, void* dst, size_t n_bytes, void* s) {
 
 int dh_engine_create(const dh_engine_config* cfg, dh_engine** out) {
     if (!cfg || !out) return DH_EINVAL;
-    *out = nullptr;
-    dh_engine* e = new (std::nothrow) dh_engine;
-    if (!e) return DH_ENOMEM;
-    int rc = e->impl.be.open(cfg->device, cfg->stream);
-    if (rc == DH_OK) { DH_ON_DEVICE(e); rc = e->impl.init(*cfg); if (rc != DH_OK) e->impl.destroy(); }
-    if (rc != DH_OK) { delete e; return rc; }
-    e->device = cfg->device; e->stream = cfg->stream;
-    *out = e;
-    return DH_OK;
+    return dh_create(*cfg, out, [&](dh_engine& e) { return e.impl.init(*cfg); });      // (init validates: make_layout)
 }
+void dh_engine_destroy(dh_engine* e) { dh_destroy(e); }
 
-void dh_engine_destroy(dh_engine* e) {
-    if (!e) return;
-    {
-        DH_ON_DEVICE(e);
-        e->impl.be.sync();
-        e->impl.be.close();
-        e->impl.destroy();
-    }
-    delete e;
-}
-
-int dh_engine_reset(dh_engine* e) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset(); }
-int dh_engine_set_slot_filter(dh_engine* e, uint32_t f) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.set_slot_filter(f); }
-int dh_engine_reset_channel(dh_engine* e, uint32_t ch) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset_channel(ch); }
-int dh_engine_reset_channels(dh_engine* e, const uint8_t* d_flags) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.reset_channels(d_flags); }
-int dh_engine_set_slot_filter_channel(dh_engine* e, uint32_t ch, uint32_t f) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.set_slot_filter_channel(ch, f); }
-int dh_engine_push(dh_engine* e, const float* d, size_t stride, size_t n) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.push(d, stride, n); }
-int dh_engine_push_host(dh_engine* e, const float* h, size_t stride, size_t n) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.push_host(h, stride, n); }
+int dh_engine_reset(dh_engine* e) { DH_ENTER(e); return e->impl.reset(); }
+int dh_engine_set_slot_filter(dh_engine* e, uint32_t f) { DH_ENTER(e); return e->impl.set_slot_filter(f); }
+int dh_engine_reset_channel(dh_engine* e, uint32_t ch) { DH_ENTER(e); return e->impl.reset_channel(ch); }
+int dh_engine_reset_channels(dh_engine* e, const uint8_t* d_flags) { DH_ENTER(e); return e->impl.reset_channels(d_flags); }
+int dh_engine_set_slot_filter_channel(dh_engine* e, uint32_t ch, uint32_t f) { DH_ENTER(e); return e->impl.set_slot_filter_channel(ch, f); }
+int dh_engine_push(dh_engine* e, const float* d, size_t stride, size_t n) { DH_ENTER(e); return e->impl.push(d, stride, n); }
+int dh_engine_push_host(dh_engine* e, const float* h, size_t stride, size_t n) { DH_ENTER(e); return e->impl.push_host(h, stride, n); }
 int dh_engine_push_ragged(dh_engine* e, const float* d, size_t stride, const uint32_t* d_counts, size_t max_n) {
-    if (!e || !d_counts) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER_IF(e, d_counts);
     return e->impl.push(d, stride, max_n, d_counts);
 }
 int dh_engine_push_host_ragged(dh_engine* e, const float* h, size_t stride, const uint32_t* h_counts, size_t max_n) {
-    if (!e || !h_counts) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER_IF(e, h_counts);
     return e->impl.push_host(h, stride, max_n, h_counts);
 }
-int dh_engine_push_symbols(dh_engine* e, const uint8_t* d, size_t stride, const uint32_t* cnt) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.push_symbols(d, stride, cnt); }
+int dh_engine_push_symbols(dh_engine* e, const uint8_t* d, size_t stride, const uint32_t* cnt) { DH_ENTER(e); return e->impl.push_symbols(d, stride, cnt); }
 
-int dh_engine_filtered(dh_engine* e, const float** d, size_t* stride) {
-    if (!e || !e->impl.filtered) return DH_EINVAL;
-    if (d) *d = e->impl.filtered;
-    if (stride) *stride = e->impl.L.max_samples;
-    return DH_OK;
-}
-int dh_engine_symbols(dh_engine* e, const uint8_t** d, size_t* stride, const uint32_t** cnt) {
-    if (!e || !e->impl.syms) return DH_EINVAL;
-    if (d) *d = e->impl.syms;
-    if (stride) *stride = e->impl.L.sym_stride;
-    if (cnt) *cnt = e->impl.sym_count;
-    return DH_OK;
-}
-int dh_engine_frames(dh_engine* e, const uint8_t** d, size_t* stride, const uint32_t** cnt) {
-    if (!e || !e->impl.frames) return DH_EINVAL;
-    if (d) *d = e->impl.frames;
-    if (stride) *stride = e->impl.L.out_cap;
-    if (cnt) *cnt = e->impl.frame_count;
-    return DH_OK;
-}
-int dh_engine_events(dh_engine* e, const dh_event** d, size_t* stride, const uint32_t** cnt) {
-    if (!e || !e->impl.events) return DH_EINVAL;
-    if (d) *d = e->impl.events;
-    if (stride) *stride = e->impl.L.ev_cap;
-    if (cnt) *cnt = e->impl.ev_count;
-    return DH_OK;
-}
+int dh_engine_filtered(dh_engine* e, const float** d, size_t* stride) { return dh_rows_view(e, DH_ROWS_FILTERED, (const void**) d, stride, nullptr); }
+int dh_engine_symbols(dh_engine* e, const uint8_t** d, size_t* stride, const uint32_t** cnt) { return dh_rows_view(e, DH_ROWS_SYMBOLS, (const void**) d, stride, cnt); }
+int dh_engine_frames(dh_engine* e, const uint8_t** d, size_t* stride, const uint32_t** cnt) { return dh_rows_view(e, DH_ROWS_FRAMES, (const void**) d, stride, cnt); }
+int dh_engine_events(dh_engine* e, const dh_event** d, size_t* stride, const uint32_t** cnt) { return dh_rows_view(e, DH_ROWS_EVENTS, (const void**) d, stride, cnt); }
 int dh_engine_debug_header(dh_engine* e, uint32_t word, uint32_t* h_out) {
-    if (!e) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER(e);
     return e->impl.debug_header(word, h_out);
 }
 int dh_engine_timing_stats(dh_engine* e, uint32_t* h_blocks, uint32_t* h_ordered) {
-    if (!e) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER(e);
     return e->impl.timing_stats(h_blocks, h_ordered);
 }
-int dh_engine_read_symbols(dh_engine* e, uint32_t ch, uint8_t* h, size_t* n) {
-    if (!e || !e->impl.syms) return DH_EINVAL;
-    DH_ON_DEVICE(e);
-    return e->impl.read_row(e->impl.syms, e->impl.L.sym_stride, ch, e->impl.sym_count, 1, h, n);
-}
-int dh_engine_read_frames(dh_engine* e, uint32_t ch, uint8_t* h, size_t* n) {
-    if (!e || !e->impl.frames) return DH_EINVAL;
-    DH_ON_DEVICE(e);
-    return e->impl.read_row(e->impl.frames, e->impl.L.out_cap, ch, e->impl.frame_count, 1, h, n);
-}
-int dh_engine_read_events(dh_engine* e, uint32_t ch, dh_event* h, size_t* n) {
-    if (!e || !e->impl.events) return DH_EINVAL;
-    DH_ON_DEVICE(e);
-    return e->impl.read_row(e->impl.events, sizeof(dh_event) * e->impl.L.ev_cap, ch, e->impl.ev_count, sizeof(dh_event), h, n);
-}
-int dh_engine_read_filtered(dh_engine* e, uint32_t ch, float* h, size_t* n) {
-    if (!e) return DH_EINVAL;
-    DH_ON_DEVICE(e);
-    return e->impl.read_filtered(ch, h, n);
-}
-int dh_engine_timing_enable(dh_engine* e, uint32_t max_pushes) { if (!e) return DH_EINVAL; DH_ON_DEVICE(e); return e->impl.be.timing_enable(max_pushes); }
+int dh_engine_read_symbols(dh_engine* e, uint32_t ch, uint8_t* h, size_t* n) { return dh_rows_read(e, DH_ROWS_SYMBOLS, ch, h, n); }
+int dh_engine_read_frames(dh_engine* e, uint32_t ch, uint8_t* h, size_t* n) { return dh_rows_read(e, DH_ROWS_FRAMES, ch, h, n); }
+int dh_engine_read_events(dh_engine* e, uint32_t ch, dh_event* h, size_t* n) { return dh_rows_read(e, DH_ROWS_EVENTS, ch, h, n); }
+int dh_engine_read_filtered(dh_engine* e, uint32_t ch, float* h, size_t* n) { return dh_rows_read(e, DH_ROWS_FILTERED, ch, h, n); }
+int dh_engine_timing_enable(dh_engine* e, uint32_t max_pushes) { DH_ENTER(e); return e->impl.be.timing_enable(max_pushes); }
 int dh_engine_timing_read_split(dh_engine* e, float* first_ms, uint32_t* first_channels, uint32_t* n) {
-    if (!e || !n) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER_IF(e, n);
     return e->impl.be.timing_read_split(first_ms, first_channels, n);
 }
 int dh_engine_timing_read(dh_engine* e, float* rrc_ms, float* slicer_ms, float* decoder_ms, uint32_t* n) {
-    if (!e || !n) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER_IF(e, n);
     return e->impl.be.timing_read(rrc_ms, slicer_ms, decoder_ms, n);
 }
 int dh_engine_sync(dh_engine* e) {
-    if (!e) return DH_EINVAL;
-    DH_ON_DEVICE(e);
+    DH_ENTER(e);
     if (e->impl.be.sync()) return DH_EDEVICE;
     return e->impl.check_overflow();
 }
@@ -242,10 +261,7 @@ int dh_engine_sync(dh_engine* e) {
 //   dh_be_cz_power(const DhCzPowerParams& P, void* stream);      (only with power enabled: block power, then the gate and the counts)
 // (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
 // window is the last H = T' - 1 samples of the previous one followed by the new samples.
-struct dh_channelizer {
-    DH_BACKEND be;
-    dh::DeviceBuffers<DH_BACKEND> bufs{ be };           // release(), clear() and retune() act on what init() and power_enable() declare
-    void* stream = nullptr;
+struct dh_channelizer : dh_state {                      // (clear() and retune() act on what init() and power_enable() declare)
     uint32_t B = 0, D = 0, L = 1, tpad = 0, ncols = 0, max_input = 0;      // rate = input L / D
     int cf32 = 0, fm = 0, dcblock = 0;
     std::vector<float> taps;                            // [L][T']: the phases h_p of h, each zero-padded to T'
@@ -267,8 +283,6 @@ struct dh_channelizer {
     uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
     uint64_t pw_first = 0; size_t pw_n = 0;             // blocks completed by the last push
 
-    auto scope() const { return be.scope(); }
-    void release() { bufs.free_all(); }
     size_t in_bytes() const { return cf32 ? 8u : 4u; }
     uint64_t outputs(uint64_t n) const { return (uint64_t) L * n / D; }         // outputs that exist after n input samples
     size_t bank() const { return (size_t) 2 * tpad * ncols; }
@@ -403,46 +417,22 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
         return DH_EINVAL;
     for (uint32_t k = 0; k < c.n_taps; k++)
         if (!(c.taps[k] - c.taps[k] == 0.0f)) return DH_EINVAL;        // finite taps only
-    dh_channelizer* z = new (std::nothrow) dh_channelizer;
-    if (!z) return DH_ENOMEM;
-    int rc = z->be.open(c.device, c.stream);
-    if (rc == DH_OK) {
-        DH_ON_DEVICE(z);
-        z->stream = c.stream;
-        rc = z->init(c, L);
-        if (rc != DH_OK) z->release();
-    }
-    if (rc != DH_OK) { delete z; return rc; }
-    *out = z;
-    return DH_OK;
+    return dh_create(c, out, [&](dh_channelizer& z) { return z.init(c, L); });
 }
+void dh_channelizer_destroy(dh_channelizer* z) { dh_destroy(z); }
 
-void dh_channelizer_destroy(dh_channelizer* c) {
-    if (!c) return;
-    {
-        DH_ON_DEVICE(c);
-        c->be.sync();
-        c->be.close();
-        c->release();
-    }
-    delete c;
-}
-
-int dh_channelizer_reset(dh_channelizer* c) { if (!c) return DH_EINVAL; DH_ON_DEVICE(c); return c->clear(); }
-int dh_channelizer_retune(dh_channelizer* c, uint32_t ch, uint32_t u) { if (!c || ch >= c->B) return DH_EINVAL; DH_ON_DEVICE(c); return c->retune(ch, u); }
+int dh_channelizer_reset(dh_channelizer* c) { DH_ENTER(c); return c->clear(); }
+int dh_channelizer_retune(dh_channelizer* c, uint32_t ch, uint32_t u) { DH_ENTER_IF(c, ch < c->B); return c->retune(ch, u); }
 int dh_channelizer_push(dh_channelizer* c, const void* d_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
-    if (!c) return DH_EINVAL;
-    DH_ON_DEVICE(c);
+    DH_ENTER(c);
     return c->push(d_in, n_in, d_out, out_stride, n_out, false);
 }
 int dh_channelizer_push_host(dh_channelizer* c, const void* h_in, size_t n_in, float* d_out, size_t out_stride, size_t* n_out) {
-    if (!c) return DH_EINVAL;
-    DH_ON_DEVICE(c);
+    DH_ENTER(c);
     return c->push(h_in, n_in, d_out, out_stride, n_out, true);
 }
 int dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg) {
-    if (!c || !cfg) return DH_EINVAL;
-    DH_ON_DEVICE(c);
+    DH_ENTER_IF(c, cfg);
     return c->power_enable(*cfg);
 }
 int dh_channelizer_set_squelch(dh_channelizer* c, float open_level, float close_level, uint32_t hang_blocks) {
@@ -468,10 +458,7 @@ int dh_channelizer_phasor(const uint32_t* h_phi, float* h_out, size_t n) {
 //   dh_be_preroll_gather(const DhPrGather& G, void* stream);
 // (engine.hip defines the gfx950 ones; preroll_core.hpp the CPU harness's.)  `total` is the host's: every position a
 // launch needs is reduced mod depth here.
-struct dh_preroll {
-    DH_BACKEND be;
-    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
-    void* stream = nullptr;
+struct dh_preroll : dh_state {
     uint32_t B = 0, depth = 0;
     uint64_t total = 0;
     uint32_t* d_ring = nullptr;                         // [B][depth]
@@ -479,8 +466,6 @@ struct dh_preroll {
     uint64_t* d_from = nullptr;                         // [B]: a gather's h_from
     std::vector<uint64_t> none;                         // [B] x DH_PREROLL_NONE: what a reset uploads
 
-    auto scope() const { return be.scope(); }
-    void release() { bufs.free_all(); }
     uint64_t oldest() const { return total > depth ? total - depth : 0; }
     int clear() {
         total = 0;
@@ -535,35 +520,13 @@ int dh_preroll_create(const dh_preroll_config* cfg, dh_preroll** out) {
     if (cfg->struct_size < sizeof(dh_preroll_config) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->depth < 1 ||
         cfg->depth > (1u << 24))
         return DH_EINVAL;
-    dh_preroll* p = new (std::nothrow) dh_preroll;
-    if (!p) return DH_ENOMEM;
-    int rc = p->be.open(cfg->device, cfg->stream);
-    if (rc == DH_OK) {
-        DH_ON_DEVICE(p);
-        p->stream = cfg->stream;
-        rc = p->init(*cfg);
-        if (rc != DH_OK) p->release();
-    }
-    if (rc != DH_OK) { delete p; return rc; }
-    *out = p;
-    return DH_OK;
+    return dh_create(*cfg, out, [&](dh_preroll& p) { return p.init(*cfg); });
 }
+void dh_preroll_destroy(dh_preroll* p) { dh_destroy(p); }
 
-void dh_preroll_destroy(dh_preroll* p) {
-    if (!p) return;
-    {
-        DH_ON_DEVICE(p);
-        p->be.sync();
-        p->be.close();
-        p->release();
-    }
-    delete p;
-}
-
-int dh_preroll_reset(dh_preroll* p) { if (!p) return DH_EINVAL; DH_ON_DEVICE(p); return p->clear(); }
+int dh_preroll_reset(dh_preroll* p) { DH_ENTER(p); return p->clear(); }
 int dh_preroll_append(dh_preroll* p, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts) {
-    if (!p) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER(p);
     return p->append(d_rows, stride, n, d_counts);
 }
 int dh_preroll_total(dh_preroll* p, uint64_t* total) {
@@ -572,20 +535,17 @@ int dh_preroll_total(dh_preroll* p, uint64_t* total) {
     return DH_OK;
 }
 int dh_preroll_open_at(dh_preroll* p, uint64_t* h_open_at) {
-    if (!p || !h_open_at) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER_IF(p, h_open_at);
     return p->be.download(h_open_at, p->d_open, sizeof(uint64_t) * p->B) ? DH_EDEVICE : DH_OK;
 }
 int dh_preroll_gather(dh_preroll* p, const uint64_t* h_from, uint64_t skip, size_t max_n, float* d_out, size_t out_stride,
                       uint32_t* d_counts, uint64_t* h_start) {
-    if (!p) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER(p);
     return p->gather(h_from, skip, max_n, d_out, out_stride, d_counts, h_start);
 }
 int dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t skip, size_t max_n, float* d_out, size_t out_stride,
                              uint32_t* d_counts) {
-    if (!p) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER(p);
     return p->gather_device(d_from, skip, max_n, d_out, out_stride, d_counts);
 }
 
@@ -597,14 +557,9 @@ int dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t ski
 // (engine.hip defines the gfx950 ones; outpack_core.hpp the CPU harness's.)  Both go out on the ENGINE's stream, behind the
 // push whose rows they read; the host knows none of the totals.
 static_assert(sizeof(dh_outpack_header) == 32 && sizeof(dh_outpack_entry) == 32, "dh_outpack layout");
-struct dh_outpack {
-    DH_BACKEND be;
-    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
-    int device = 0; void* stream = nullptr;
+struct dh_outpack : dh_state {
     DhOutpack P{};                                      // what create fixes; an append adds the engine's rows and its arguments
 
-    auto scope() const { return be.scope(); }
-    void release() { bufs.free_all(); }
     int clear() { return be.zero(P.hdr, sizeof(dh_outpack_header)) ? DH_EDEVICE : DH_OK; }
     int init(const dh_outpack_config& c) {
         P.max_entries = c.max_entries; P.max_events = c.max_events; P.max_frame_bytes = c.max_frame_bytes;
@@ -618,10 +573,9 @@ struct dh_outpack {
         if (rc != DH_OK) return rc;
         return be.sync() ? DH_EDEVICE : DH_OK;
     }
-    bool shares_stream(int dev, void* s) const { return dev == device && s == stream; }
     int append(dh_engine* e, const uint32_t* mask, const uint64_t* tag, uint64_t tag_add, uint32_t user) {
         auto& E = e->impl;
-        if (!E.frames || !shares_stream(e->device, e->stream)) return DH_EINVAL;       // (no frames: proto == DH_PROTO_NONE)
+        if (!E.frames || !shares_stream(*e)) return DH_EINVAL;       // (no frames: proto == DH_PROTO_NONE)
         DhOutpack A = P;
         A.src_frames = E.frames; A.src_fc = E.frame_count; A.out_cap = E.L.out_cap;
         A.src_events = E.events; A.src_ec = E.ev_count; A.ev_cap = E.L.ev_cap;
@@ -648,40 +602,17 @@ int dh_outpack_create(const dh_outpack_config* cfg, dh_outpack** out) {
     if (cfg->struct_size < sizeof(dh_outpack_config) || cfg->max_entries == 0 || (cfg->max_frame_bytes & 15u) ||
         cfg->max_frame_bytes > ((uint64_t) 1 << 36) - 16u)
         return DH_EINVAL;
-    dh_outpack* p = new (std::nothrow) dh_outpack;
-    if (!p) return DH_ENOMEM;
-    int rc = p->be.open(cfg->device, cfg->stream);
-    if (rc == DH_OK) {
-        DH_ON_DEVICE(p);
-        p->device = cfg->device; p->stream = cfg->stream;
-        rc = p->init(*cfg);
-        if (rc != DH_OK) p->release();
-    }
-    if (rc != DH_OK) { delete p; return rc; }
-    *out = p;
-    return DH_OK;
+    return dh_create(*cfg, out, [&](dh_outpack& p) { return p.init(*cfg); });
 }
+void dh_outpack_destroy(dh_outpack* p) { dh_destroy(p); }
 
-void dh_outpack_destroy(dh_outpack* p) {
-    if (!p) return;
-    {
-        DH_ON_DEVICE(p);
-        p->be.sync();
-        p->be.close();
-        p->release();
-    }
-    delete p;
-}
-
-int dh_outpack_clear(dh_outpack* p) { if (!p) return DH_EINVAL; DH_ON_DEVICE(p); return p->clear(); }
+int dh_outpack_clear(dh_outpack* p) { DH_ENTER(p); return p->clear(); }
 int dh_outpack_append(dh_outpack* p, dh_engine* e, const uint32_t* d_mask, const uint64_t* d_tag, uint64_t tag_add, uint32_t user) {
-    if (!p || !e) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER_IF(p, e);
     return p->append(e, d_mask, d_tag, tag_add, user);
 }
 int dh_outpack_read(dh_outpack* p, dh_outpack_header* h_hdr, dh_outpack_entry* h_entries, dh_event* h_events, uint8_t* h_frames) {
-    if (!p) return DH_EINVAL;
-    DH_ON_DEVICE(p);
+    DH_ENTER(p);
     return p->read(h_hdr, h_entries, h_events, h_frames);
 }
 int dh_outpack_device(dh_outpack* p, const dh_outpack_header** d_hdr, const dh_outpack_entry** d_entries, const dh_event** d_events,
@@ -701,10 +632,7 @@ int dh_outpack_device(dh_outpack* p, const dh_outpack_header** d_hdr, const dh_o
 //   dh_be_monitor_assign(const DhMonAssign& S, void* stream);    step B
 // (engine.hip defines the gfx950 ones; monitor_core.hpp the CPU harness's.)  All the host learns of a round is the summary
 // block, read once after each step; everything [B]-sized stays on the device.
-struct dh_monitor {
-    DH_BACKEND be;
-    dh::DeviceBuffers<DH_BACKEND> bufs{ be };
-    int device = 0; void* stream = nullptr;
+struct dh_monitor : dh_state {
     uint32_t B = 0, max_samples = 0;
     dh_engine* scan[DH_MON_FRONTS] = {};               // null: no configured protocol sits behind that front end
     dh_engine* eng[DH_MON_PROTOS] = {};                // by DH_PROTO_*; null: not configured
@@ -716,9 +644,8 @@ struct dh_monitor {
     DhMonOpen A{}; DhMonAssign S{};                     // what create fixes; a round adds n and total
     std::vector<uint64_t> none;
 
-    auto scope() const { return be.scope(); }
     static uint32_t front_of(int proto) { return proto == DH_PROTO_NXDN ? 1u : proto == DH_PROTO_DSTAR ? 2u : proto == DH_PROTO_POCSAG ? 3u : 0u; }
-    void release() {
+    void release() {                                    // (hides dh_state's: the engines and the ring first)
         for (dh_engine*& e : scan) { dh_engine_destroy(e); e = nullptr; }
         for (dh_engine*& e : eng) { dh_engine_destroy(e); e = nullptr; }
         dh_preroll_destroy(pre); pre = nullptr;
@@ -835,45 +762,21 @@ int dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out) {
     if (cfg->struct_size < sizeof(dh_monitor_config) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
         cfg->depth < 1 || cfg->depth > (1u << 24) || cfg->protos == 0 || (cfg->protos & ~0x3Eu))
         return DH_EINVAL;
-    dh_monitor* m = new (std::nothrow) dh_monitor;
-    if (!m) return DH_ENOMEM;
-    int rc = m->be.open(cfg->device, cfg->stream);
-    if (rc == DH_OK) {
-        DH_ON_DEVICE(m);
-        m->device = cfg->device; m->stream = cfg->stream;
-        rc = m->init(*cfg);
-        if (rc != DH_OK) m->release();
-    }
-    if (rc != DH_OK) { delete m; return rc; }
-    *out = m;
-    return DH_OK;
+    return dh_create(*cfg, out, [&](dh_monitor& m) { return m.init(*cfg); });
 }
+void dh_monitor_destroy(dh_monitor* m) { dh_destroy(m); }
 
-void dh_monitor_destroy(dh_monitor* m) {
-    if (!m) return;
-    {
-        DH_ON_DEVICE(m);
-        m->be.sync();
-        m->be.close();
-        m->release();
-    }
-    delete m;
-}
-
-int dh_monitor_reset(dh_monitor* m) { if (!m) return DH_EINVAL; DH_ON_DEVICE(m); return m->reset(); }
+int dh_monitor_reset(dh_monitor* m) { DH_ENTER(m); return m->reset(); }
 int dh_monitor_push(dh_monitor* m, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts, dh_monitor_sink sink, void* user) {
-    if (!m) return DH_EINVAL;
-    DH_ON_DEVICE(m);
+    DH_ENTER(m);
     return m->push(d_rows, stride, n, d_counts, sink, user);
 }
 int dh_monitor_push_packed(dh_monitor* m, const float* d_rows, size_t stride, size_t n, const uint32_t* d_counts, dh_outpack* pack) {
-    if (!m || !pack || !pack->shares_stream(m->device, m->stream)) return DH_EINVAL;
-    DH_ON_DEVICE(m);
+    DH_ENTER_IF(m, pack && pack->shares_stream(*m));
     return m->push(d_rows, stride, n, d_counts, nullptr, nullptr, pack);
 }
 int dh_monitor_state(dh_monitor* m, uint8_t* h_assigned, uint64_t* h_start) {
-    if (!m) return DH_EINVAL;
-    DH_ON_DEVICE(m);
+    DH_ENTER(m);
     if (h_assigned && m->be.download(h_assigned, m->A.assigned, m->B)) return DH_EDEVICE;
     if (h_start && m->be.download(h_start, m->A.start, sizeof(uint64_t) * m->B)) return DH_EDEVICE;
     return DH_OK;

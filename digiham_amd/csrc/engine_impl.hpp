@@ -318,7 +318,7 @@ struct Engine {
         if ((!d_in && n) || n > L.max_samples || stride < n) return DH_EINVAL;
         if (d_counts && L.rrc == DH_RRC_CUSTOM) return DH_EINVAL;          // (the generic FIR takes whole pushes only)
         if (!L.rrc && !L.demod) return DH_EINVAL;
-        // what read_filtered needs to know later is kept in a buffer of the engine's own: the caller's counts only
+        // what dh_engine_read_filtered needs to know later is kept in a buffer of the engine's own: the caller's counts only
         // have to live as long as the sample rows (until the push has run)
         last_counts = nullptr;
         if (d_counts && filtered) {
@@ -417,7 +417,8 @@ struct Engine {
         return be.download2d(h_out, sizeof(uint32_t), dsp_state + word, sizeof(uint32_t) * L.state_words, sizeof(uint32_t), L.B) ? DH_EDEVICE : DH_OK;
     }
 
-    // row `channel` of an output: counts[channel] elements of it (counts null: all the same), `most` at most
+    // row `channel` of an output: counts[channel] elements of it (counts null: all the same), `most` at most -- the filtered
+    // samples of the last push are last_n of them, or the channel's own count where the push was ragged (dh_engine::rows)
     int read_row(const void* base, size_t row_bytes, uint32_t channel, const uint32_t* counts, size_t elem, void* h_out, size_t* n, uint32_t most = ~0u) {
         if (channel >= L.B || !n || !base) return DH_EINVAL;
         uint32_t cnt = most;
@@ -428,10 +429,6 @@ struct Engine {
         if (cnt > cap) return DH_ECAPACITY;
         if (cnt && h_out && be.download(h_out, (const char*) base + row_bytes * channel, cnt * elem)) return DH_EDEVICE;
         return DH_OK;
-    }
-    // the filtered samples of the last push: last_n of them, or this channel's own count where the push was ragged
-    int read_filtered(uint32_t channel, float* h_out, size_t* n) {
-        return read_row(filtered, sizeof(float) * L.max_samples, channel, last_counts, sizeof(float), h_out, n, last_n);
     }
 };
 

@@ -26,12 +26,15 @@ const DhFecTables& host_tables() {
     return *T;
 }
 
+// test only (tests/host_cpp/handle_lifecycle.cpp): k > 0 makes the k-th backend allocation from now fail, once
+int g_alloc_fail_in = 0;
+
 struct HostBackend {
     struct Scope {};
     Scope scope() const { return Scope(); }
     void close() {}
     int open(int, void*) { return 0; }
-    void* alloc(size_t bytes) { return calloc(1, bytes ? bytes : 1); }
+    void* alloc(size_t bytes) { return g_alloc_fail_in && !--g_alloc_fail_in ? nullptr : calloc(1, bytes ? bytes : 1); }
     void free(void* p) { ::free(p); }
     int zero(void* p, size_t bytes) { memset(p, 0, bytes); return 0; }
     int upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
