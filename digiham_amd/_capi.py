@@ -16,6 +16,8 @@ DEMOD = {"none": 0, None: 0, "fsk": 2, "fsk2": 2, "gfsk": 4, "gfsk4": 4}
 PROTO = {"none": 0, None: 0, "dmr": 1, "ysf": 2, "nxdn": 3, "pocsag": 4, "dstar": 5, "scan": 6}
 FLAG_FAST_FIR, FLAG_KEEP_FILTERED, FLAG_FSK_INVERT, FLAG_NO_EVENTS, FLAG_ORDERED_TIMING, FLAG_SPLIT_STAGES = 1, 2, 4, 8, 16, 32
 FLAG_EXACT_SYMBOLS, FLAG_EXACT_FIR, FLAG_OVERLAP_PUSHES, FLAG_ONE_LAUNCH = 64, 128, 256, 512
+FLAG_DMR_BOTH_SLOTS = 0x400
+DMR_SLOT_RECORD_BYTES = 28                 # DH_DMR_SLOT_RECORD_BYTES: 27 payload bytes and the slot
 
 
 class EngineConfig(C.Structure):
@@ -46,7 +48,10 @@ class PrerollConfig(C.Structure):
 class MonitorConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_samples", C.c_uint32),
                 ("depth", C.c_uint32), ("lead", C.c_uint32), ("confirm", C.c_uint32), ("release", C.c_uint32),
-                ("protos", C.c_uint32), ("stream", C.c_void_p)]
+                ("protos", C.c_uint32), ("stream", C.c_void_p), ("dmr_both_slots", C.c_uint32)]
+
+
+MONITOR_CONFIG_V1_SIZE = MonitorConfig.dmr_both_slots.offset       # DH_MONITOR_CONFIG_V1_SIZE
 
 
 class MonitorPushInfo(C.Structure):

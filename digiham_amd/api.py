@@ -56,6 +56,21 @@ class TorchCudaMemory:
         return self.torch.is_tensor(x) and x.is_cuda
 
 
+def dmr_split_slots(frame_bytes):
+    """The frames of a DMR engine with dmr_both_slots=True -- 28-byte records, 27 payload bytes and the slot -- as (slot0, slot1):
+    two uint8 arrays of 27-byte payloads, each in the order of its bursts.  ValueError on a length that is no multiple of 28 or
+    on a tag above 1."""
+    a = np.ascontiguousarray(frame_bytes, np.uint8).ravel()
+    rec = _capi.DMR_SLOT_RECORD_BYTES
+    if a.size % rec:
+        raise ValueError("dmr_split_slots: %d bytes are no whole number of %d-byte records" % (a.size, rec))
+    a = a.reshape(-1, rec)
+    tag = a[:, rec - 1]
+    if (tag > 1).any():
+        raise ValueError("dmr_split_slots: a record tagged %d" % int(tag[tag > 1][0]))
+    return a[tag == 0, :rec - 1].ravel().copy(), a[tag == 1, :rec - 1].ravel().copy()
+
+
 def parse_lc(payload):
     """Fields of a 9-byte DMR link control word (DH_EV_DMR_LC payload): what Digiham::Dmr::Lc's getters return
     (src/dmr_decoder/lc.cpp:26-43)."""
@@ -268,14 +283,17 @@ class Engine(_Handle):
 
     def __init__(self, n_channels, max_samples, rrc="wide", demod="gfsk", sps=10, proto="dmr", fast_fir=False,
                  keep_filtered=False, invert=False, events=True, slot_filter=3, ctx=None, device=0, ordered_timing=False, split_stages=False,
-                 taps=None, gain=None, exact_symbols=False, exact_fir=False, overlap_pushes=False, one_launch=False):
+                 taps=None, gain=None, exact_symbols=False, exact_fir=False, overlap_pushes=False, one_launch=False, dmr_both_slots=False):
         """rrc = "custom" takes the caller's coefficient table: `taps` (nZeros + 1 floats, any shape) and `gain`, as
-        Digiham::RrcFilter::RrcFilter(nZeros, gain, coeffs[]) does (include/rrc_filter.hpp:12)."""
+        Digiham::RrcFilter::RrcFilter(nZeros, gain, coeffs[]) does (include/rrc_filter.hpp:12).
+        dmr_both_slots (proto "dmr" only): the voice of both timeslots leaves as 28-byte slot-tagged records
+        (DH_FLAG_DMR_BOTH_SLOTS; dmr_split_slots takes them apart)."""
         flags = (_capi.FLAG_FAST_FIR if fast_fir else 0) | (_capi.FLAG_KEEP_FILTERED if keep_filtered else 0) | \
                 (_capi.FLAG_FSK_INVERT if invert else 0) | (0 if events else _capi.FLAG_NO_EVENTS) | \
                 (_capi.FLAG_ORDERED_TIMING if ordered_timing else 0) | (_capi.FLAG_SPLIT_STAGES if split_stages else 0) | \
                 (_capi.FLAG_EXACT_SYMBOLS if exact_symbols else 0) | (_capi.FLAG_EXACT_FIR if exact_fir else 0) | \
-                (_capi.FLAG_OVERLAP_PUSHES if overlap_pushes else 0) | (_capi.FLAG_ONE_LAUNCH if one_launch else 0)
+                (_capi.FLAG_OVERLAP_PUSHES if overlap_pushes else 0) | (_capi.FLAG_ONE_LAUNCH if one_launch else 0) | \
+                (_capi.FLAG_DMR_BOTH_SLOTS if dmr_both_slots else 0)
         custom = dict(struct_size=_capi.EngineConfig.rrc_taps.offset)     # the layout before the custom-filter fields: every library version takes it
         if rrc == "custom":
             t = np.ascontiguousarray(taps, np.float32).ravel()                # copied by dh_engine_create
@@ -319,6 +337,9 @@ class Engine(_Handle):
 
     def set_slot_filter(self, f):
         self._call("dh_engine_set_slot_filter", f)
+
+    def set_slot_filter_channel(self, ch, f):
+        self._call("dh_engine_set_slot_filter_channel", ch, f)
 
     def push(self, x, n=None, counts=None):
         """x: device array float32 [B][stride] (torch CUDA tensor); processes the first n samples of every row -- or, with
@@ -689,11 +710,14 @@ class Monitor(_Handle):
 
     `assigned[b]` is None or the protocol's name, `start[b]` the stream index where the decoder's input began.
 
+    dmr_both_slots=True: the DMR engine is created with it, and the `frames` of a "dmr" block are 28-byte slot-tagged
+    records (dmr_split_slots) -- both calls of a two-slot channel instead of the one that holds the decoder's output.
+
     Known limit: a transmission that ends before the scanner has confirmed it is never decoded -- a single POCSAG batch,
     a D-Star transmission shorter than three sync periods.  (Lowering `confirm` per family is a later question.)"""
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, dmr_both_slots=False):
         self._resolve(ctx, device)
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
@@ -703,7 +727,8 @@ class Monitor(_Handle):
         self.pre = Preroll(self.B, self.depth, ctx=self.ctx)
         self.stage = self.ctx.mem.zeros((self.B, self.max_samples), np.float32)
         for p in self.protos:
-            self.engines[p] = Engine(self.B, self.max_samples, proto=p, ctx=self.ctx, **SCAN_FRONTS[PROTO_FRONT[p]])
+            self.engines[p] = Engine(self.B, self.max_samples, proto=p, ctx=self.ctx, dmr_both_slots=bool(dmr_both_slots) and p == "dmr",
+                                     **SCAN_FRONTS[PROTO_FRONT[p]])
         self._clear()
 
     def _clear(self):
@@ -844,12 +869,14 @@ class DeviceMonitor(_Handle):
     `assigned` and `start` are read from the device when asked for (once per round at most); `engines` and
     `scanner.engines` are views of the handle's engines and die with it.
 
+    dmr_both_slots=True: as for Monitor (dh_monitor_config.dmr_both_slots); "dmr" blocks carry 28-byte slot-tagged records.
+
     packed=True: the monitor owns an OutPack sized so that a round can never drop, and push() is clear,
     dh_monitor_push_packed, one read: no sink, no read-back per engine push, copies sized by what was decoded."""
     _kind = "dh_monitor"
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False, dmr_both_slots=False):
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
         self.protos = tuple(protos)
@@ -857,7 +884,7 @@ class DeviceMonitor(_Handle):
         for p in self.protos:
             bits |= 1 << _capi.PROTO[p]
         self._open(ctx, device, _capi.MonitorConfig, n_channels=self.B, max_samples=self.max_samples, depth=self.depth, lead=self.lead,
-                   confirm=self.confirm, release=self.release, protos=bits)
+                   confirm=self.confirm, release=self.release, protos=bits, dmr_both_slots=int(bool(dmr_both_slots)))
         lib, h = self.ctx.lib, self._h
         self.engines = {p: Engine._borrowed(self.ctx, lib.dh_monitor_engine(h, _capi.PROTO[p]), self.B, self.max_samples) for p in self.protos}
         self.scanner = Scanner.__new__(Scanner)

@@ -662,7 +662,7 @@ struct dh_monitor : dh_state {
         ec.rrc = front == 0u ? DH_RRC_WIDE : front == 1u ? DH_RRC_NARROW : DH_RRC_NONE;
         ec.demod = front < 2u ? DH_DEMOD_GFSK4 : DH_DEMOD_FSK2;
         ec.sps = front == 1u ? 20u : front == 3u ? 40u : 10u;
-        ec.flags = front == 3u ? DH_FLAG_FSK_INVERT : 0u;
+        ec.flags = (front == 3u ? DH_FLAG_FSK_INVERT : 0u) | (proto == DH_PROTO_DMR && c.dmr_both_slots ? DH_FLAG_DMR_BOTH_SLOTS : 0u);
         ec.proto = proto; ec.slot_filter = 3; ec.stream = c.stream;
         return dh_engine_create(&ec, out);
     }
@@ -759,10 +759,14 @@ extern "C" {
 int dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out) {
     if (!cfg || !out) return DH_EINVAL;
     *out = nullptr;
-    if (cfg->struct_size < sizeof(dh_monitor_config) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
+    if ((cfg->struct_size != DH_MONITOR_CONFIG_V1_SIZE && cfg->struct_size < sizeof(dh_monitor_config)) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
         cfg->depth < 1 || cfg->depth > (1u << 24) || cfg->protos == 0 || (cfg->protos & ~0x3Eu))
         return DH_EINVAL;
-    return dh_create(*cfg, out, [&](dh_monitor& m) { return m.init(*cfg); });
+    // dmr_both_slots was appended to the struct: a caller built against the older header passes the older size and means 0
+    // (only the bytes the caller's struct has are read)
+    dh_monitor_config c{};
+    memcpy(&c, cfg, cfg->struct_size == DH_MONITOR_CONFIG_V1_SIZE ? DH_MONITOR_CONFIG_V1_SIZE : sizeof c);
+    return dh_create(c, out, [&](dh_monitor& m) { return m.init(c); });
 }
 void dh_monitor_destroy(dh_monitor* m) { dh_destroy(m); }
 

@@ -59,6 +59,9 @@ static __device__ __forceinline__ uint32_t dh_writelane(uint32_t reg, uint32_t l
 #define DH_DSTAR_CARRY_MAX 704        // D-Star: the header phase waits for more than 660 bits (dstar_phase.hpp:52)
 DH_HD uint32_t dh_carry_max(int proto) { return proto == DH_PROTO_DSTAR ? DH_DSTAR_CARRY_MAX : DH_SYM_CARRY_MAX; }
 #define DH_DEC_STATE_WORDS 64
+// DH_FLAG_DMR_BOTH_SLOTS: the mode travels with the slot filter, as bit 2 of the state words DS_SLOT_FILTER and DS_SLOT_FILTER_DECODER
+// (the engine writes it with every filter; (slot + 1) & filter never meets it).  Voice records are then 28 bytes, the slot in the last.
+#define DH_DMR_BOTH_SLOTS_BIT 4
 
 enum {
     DS_PHASE = 0, DS_SYNC_COUNT = 1, DS_SLOT = 2, DS_SLOT_STABILITY = 3, DS_SYNC_TYPE0 = 4, DS_SYNC_TYPE1 = 5,
@@ -643,6 +646,8 @@ struct DhDmrMachine {
 // pass B: FramePhase::process (dmr_phase.cpp:65-254) for bursts 0 .. n - 1 of the chunk on their summaries.  Returns the number of
 // bursts consumed; `nflag` = bursts that got a flag word (one more when the last one sent the decoder back to its SyncPhase
 // without being consumed, :163-170, :201-204); `to_sync` says so.  `room` = bytes left in the output row.
+// With DH_DMR_BOTH_SLOTS_BIT in M.filter the gate of :207 is the filter alone, a voice burst takes 28 bytes of `room`, and `active` is
+// neither read nor claimed (it enters and leaves as -1).
 // The machine crosses the burst loop in THREE scalar registers -- g = slot + 1 | (stability + 128) << 2 | sync count << 10 | active
 // slot + 1 << 13; x0 / x1 = sync type + 1 | slot sync count << 2 | superframe << 5 | embedded offset << 8 -- and is unpacked into
 // locals per burst.  (Measured, profiles/r05_a_ab_logs.txt: with its thirteen members as thirteen loop-carried registers every join
@@ -657,6 +662,8 @@ DH_HD uint32_t dh_dmr_pass_b(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_LAN
     uint32_t x0 = (uint32_t) (M.st0 + 1) | (uint32_t) M.ss0 << 2 | (uint32_t) M.sf0 << 5 | (uint32_t) M.eo0 << 8;
     uint32_t x1 = (uint32_t) (M.st1 + 1) | (uint32_t) M.ss1 << 2 | (uint32_t) M.sf1 << 5 | (uint32_t) M.eo1 << 8;
     const int filter = M.filter;
+    const bool both = (filter & DH_DMR_BOTH_SLOTS_BIT) != 0;          // every voice burst the filter lets through leaves, `active` takes no part
+    const uint32_t rec = both ? 28u : 27u;
     uint32_t k = 0;
     bool stop = false;
     for (; k < n && !stop; k++) {
@@ -735,9 +742,9 @@ DH_HD uint32_t dh_dmr_pass_b(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_LAN
             }
             if (DH_LIKELY(!stop)) {
                 if (st == DH_SYNCTYPE_VOICE) {
-                    if (((slot + 1) & filter) && (active == -1 || active == slot)) {
-                        active = slot;
-                        if (DH_UNLIKELY(room < 27u)) overflow = true; else { fl |= DH_DF_VOICE; room -= 27u; }
+                    if (((slot + 1) & filter) && (both || active == -1 || active == slot)) {
+                        if (!both) active = slot;
+                        if (DH_UNLIKELY(room < rec)) overflow = true; else { fl |= DH_DF_VOICE; room -= rec; }
                     }
                 } else {
                     if (active == slot) active = -1;
@@ -788,7 +795,7 @@ DH_HD int dh_top64(uint64_t x) {
 //   embedded words    index i of a slot = the fragment of the last burst that wrote index i (votes per index), else the carried word
 //   active            claims (voice burst of a slot the filter lets through) and releases (data sync) as two votes; the value changes
 //                     only at the first claim while free and at the holder's first release, so it is walked from change to change
-//                     on the masks, not burst by burst
+//                     on the masks, not burst by burst (DH_DMR_BOTH_SLOTS_BIT in M.filter: no walk, every claim is a voice burst of 28 bytes)
 // The lanes compute all this as if the chunk were regular, then the conditions themselves are voted on; if a lane fails, or the voice
 // payloads do not fit, NOTHING has been written and the caller runs dh_dmr_pass_b on the whole chunk.  On success it leaves what the
 // scalar pass leaves: every burst's flag word, S.dmr.emb_words of the bursts that close an embedded LC, the carried embedded words, M and
@@ -861,10 +868,12 @@ DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_L
     }
     if (regular != valid) return false;
     // the active slot, from change to change: free until the first claim, held until the holder's slot releases
-    // (the lanes of slot p: EVEN << (e ^ p))
+    // (the lanes of slot p: EVEN << (e ^ p)).  Both-slots mode: no active slot, the voice bursts are the claims themselves.
+    const bool both = (filter & DH_DMR_BOTH_SLOTS_BIT) != 0u;
+    const uint32_t rec = both ? 28u : 27u;
     int active = M.active;
-    uint64_t voice = 0, rest = ~0ull;                                  // rest: the lanes still to come
-    for (;;) {
+    uint64_t voice = both ? claim : 0ull, rest = ~0ull;                // rest: the lanes still to come
+    while (!both) {
         if (active < 0) {
             const uint64_t m = claim & rest;
             if (!m) break;
@@ -881,7 +890,7 @@ DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_L
         }
     }
     const uint32_t nvoice = (uint32_t) dh_popc64(voice);
-    if (27u * nvoice > room) return false;
+    if (rec * nvoice > room) return false;
     // the words of the embedded LCs that close in this chunk (pass C decodes them), then every burst's flag word
     if (lcm) {
         uint32_t carried[2][4];
@@ -922,7 +931,7 @@ DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_L
     M.stab = dh_min(M.stab + (int) n, 100);
     M.sync_count = dh_min(M.sync_count + (int) n, 5);
     M.active = active;
-    room -= 27u * nvoice;
+    room -= rec * nvoice;
     return true;
 }
 
@@ -1113,21 +1122,35 @@ DH_HD void dh_dmr_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uin
                     for (int j = 0; j < 7; j++) {
                         const uint32_t h16 = (hh[j >> 1] >> (16 * (j & 1))) & 0xFFFFu, l16 = (ll[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
                         const uint32_t be = j < 6 ? dh_pack_msb(h16, l16, 16) : dh_pack_msb(h16, l16, 12) << 8;      // first dibit on top
-                        S.dmr.voice[rank][j] = (be >> 24) | ((be >> 8) & 0xFF00u) | ((be << 8) & 0xFF0000u) | (be << 24);
+                        // (byte 27 of the staged record, zero in the seventh word: the burst's slot, which only the both-slots copy-out takes along)
+                        const uint32_t tag = j == 6 ? (DH_LV(ev_set, lane) & DH_DF_SLOT) << (24 - 11) : 0u;
+                        S.dmr.voice[rank][j] = (be >> 24) | ((be >> 8) & 0xFF00u) | ((be << 8) & 0xFF0000u) | (be << 24) | tag;
                     }
                 }
             }
             DH_BARRIER();
-            const uint32_t nbytes = 27u * (uint32_t) dh_popc64(voice_mask);
-            uint8_t* const o = c.out + c.nout;
-            const uint8_t* const stage = reinterpret_cast<const uint8_t*>(S.dmr.voice);
-            DH_FOR_LANES(lane) {
-                for (uint32_t j = (uint32_t) lane; j < nbytes; j += DH_WAVE) {
-                    const uint32_t r = j / 27u;
-                    o[j] = stage[r * 28u + (j - r * 27u)];
+            const uint32_t nvoice = (uint32_t) dh_popc64(voice_mask);
+            if (M.filter & DH_DMR_BOTH_SLOTS_BIT) {
+                // whole 28-byte records as words: the row starts at a multiple of 64 and holds records of 28 bytes only
+                uint32_t* const o = reinterpret_cast<uint32_t*>(c.out + c.nout);
+                const uint32_t* const stage = &S.dmr.voice[0][0];
+                const uint32_t nwords = 7u * nvoice;
+                DH_FOR_LANES(lane) {
+                    for (uint32_t j = (uint32_t) lane; j < nwords; j += DH_WAVE) o[j] = stage[j];
                 }
+                c.nout += 28u * nvoice;
+            } else {
+                const uint32_t nbytes = 27u * nvoice;
+                uint8_t* const o = c.out + c.nout;
+                const uint8_t* const stage = reinterpret_cast<const uint8_t*>(S.dmr.voice);
+                DH_FOR_LANES(lane) {
+                    for (uint32_t j = (uint32_t) lane; j < nbytes; j += DH_WAVE) {
+                        const uint32_t r = j / 27u;
+                        o[j] = stage[r * 28u + (j - r * 27u)];
+                    }
+                }
+                c.nout += nbytes;
             }
-            c.nout += nbytes;
             DH_BARRIER();
         }
         DH_DMARK("chunk end");

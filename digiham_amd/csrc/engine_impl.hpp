@@ -51,6 +51,7 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
     }
     if (c.demod != DH_DEMOD_NONE && c.demod != DH_DEMOD_FSK2 && c.demod != DH_DEMOD_GFSK4) return DH_EINVAL;
     if (c.proto < DH_PROTO_NONE || c.proto > DH_PROTO_SCAN) return DH_EINVAL;
+    if ((c.flags & DH_FLAG_DMR_BOTH_SLOTS) && c.proto != DH_PROTO_DMR) return DH_EINVAL;
     if (c.demod != DH_DEMOD_NONE && (c.sps < 3 || c.sps > DH_MAX_SPS)) return DH_EINVAL;
     if (c.demod == DH_DEMOD_NONE && c.rrc == DH_RRC_NONE && c.proto == DH_PROTO_NONE) return DH_EINVAL;
     L.B = c.n_channels; L.max_samples = c.max_samples; L.sps = c.demod ? c.sps : 1;
@@ -73,7 +74,8 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
     L.sym_stride = round_up(L.sym_cap, 64);
     L.state_words = round_up(dh_state_words(L.sps), 16);
     const uint32_t max_syms = dh_carry_max(L.proto) + L.sym_cap;
-    if (L.proto == DH_PROTO_DMR) { L.out_cap = (max_syms / 144 + 1) * 27; L.ev_cap = (max_syms / 144 + 1) * 4 + 8; }
+    // (DH_FLAG_DMR_BOTH_SLOTS: a 28-byte record for every burst position, so the row cannot overflow)
+    if (L.proto == DH_PROTO_DMR) { L.out_cap = (max_syms / 144 + 1) * ((L.flags & DH_FLAG_DMR_BOTH_SLOTS) ? DH_DMR_SLOT_RECORD_BYTES : 27); L.ev_cap = (max_syms / 144 + 1) * 4 + 8; }
     else if (L.proto == DH_PROTO_YSF) { L.out_cap = (max_syms / 480 + 1) * 95; L.ev_cap = (max_syms / 480 + 1) * 5 + 8; }
     else if (L.proto == DH_PROTO_NXDN) { L.out_cap = (max_syms / 192 + 1) * 36; L.ev_cap = (max_syms / 192 + 1) * 7 + 8; }
     else if (L.proto == DH_PROTO_POCSAG) { L.out_cap = max_syms / 2 + 256; L.ev_cap = max_syms / 32 + 8; }
@@ -157,7 +159,7 @@ struct Engine {
     BE be;
     DeviceBuffers<BE> bufs{ be };
     Layout L;
-    uint32_t slot_filter;
+    uint32_t slot_filter;                // what the state words DS_SLOT_FILTER / DS_SLOT_FILTER_DECODER are written with: filter_word()
     // device buffers
     uint32_t* dsp_state = nullptr;
     uint8_t* syms = nullptr;
@@ -184,7 +186,7 @@ struct Engine {
         int rc = make_layout(c, L);
         if (rc) return rc;
         be.overlap_pushes = (L.flags & DH_FLAG_OVERLAP_PUSHES) != 0;
-        slot_filter = c.slot_filter;
+        slot_filter = filter_word(c.slot_filter);
         const size_t B = L.B;
         bool ok = bufs.alloc(overflow, 16, ZERO_ON_RESET);
         ok &= bufs.alloc(sym_count, B, ZERO_PER_CHANNEL);
@@ -278,15 +280,22 @@ struct Engine {
         return rc ? DH_EDEVICE : DH_OK;
     }
 
+    // the caller's slot filter (bits 0 and 1) with the engine's mode: DH_DMR_BOTH_SLOTS_BIT travels in the filter's state words
+    // (the other protocols' engines pass the configuration's value on as it is: their decoders own these state words)
+    uint32_t filter_word(uint32_t f) const {
+        if (L.proto != DH_PROTO_DMR) return f;
+        return (f & 3u) | ((L.flags & DH_FLAG_DMR_BOTH_SLOTS) ? (uint32_t) DH_DMR_BOTH_SLOTS_BIT : 0u);
+    }
+
     int set_slot_filter(uint32_t f) {
         if (L.proto != DH_PROTO_DMR) return DH_EINVAL;
-        slot_filter = f;
-        return be.launch_set_slot_filter(dec_state, f, L.B) ? DH_EDEVICE : DH_OK;
+        slot_filter = filter_word(f);
+        return be.launch_set_slot_filter(dec_state, slot_filter, L.B) ? DH_EDEVICE : DH_OK;
     }
     // one channel only (a module instance attached to a shared engine: include/digiham/shared_engine.hpp)
     int set_slot_filter_channel(uint32_t ch, uint32_t f) {
         if (L.proto != DH_PROTO_DMR || ch >= L.B) return DH_EINVAL;
-        return be.launch_set_slot_filter(dec_state + (size_t) ch * DH_DEC_STATE_WORDS, f, 1) ? DH_EDEVICE : DH_OK;
+        return be.launch_set_slot_filter(dec_state + (size_t) ch * DH_DEC_STATE_WORDS, filter_word(f), 1) ? DH_EDEVICE : DH_OK;
     }
     // back to the freshly-constructed state of ONE channel (the others keep streaming)
     int reset_channel(uint32_t ch) {

@@ -126,6 +126,34 @@ enum { DH_PROTO_NONE = 0, DH_PROTO_DMR = 1, DH_PROTO_YSF = 2, DH_PROTO_NXDN = 3,
                                          untouched until dh_engine_sync() (or any read) returns, and the raw device
                                          views of the outputs (dh_engine_symbols / _frames / _events) are only valid after dh_engine_sync().
                                          Results are identical. */
+#define DH_FLAG_DMR_BOTH_SLOTS  0x400 /* proto == DH_PROTO_DMR only (DH_EINVAL otherwise, before anything is allocated): the voice of BOTH timeslots of a
+                                         channel leaves the decoder, as slot-tagged records ("DMR: both timeslots" below).  Off: the reference's one output
+                                         pipe, one active slot at a time, records of 27 untagged bytes. */
+
+/* ----------------------------------------------------------------------
+ * DMR: both timeslots (DH_FLAG_DMR_BOTH_SLOTS).  Own specification, held to the reference through its slot filter.
+ *
+ * The reference's FramePhase has one output pipe and therefore one activeSlot (dmr_phase.cpp:207-231): while a call holds
+ * it, the voice bursts of the other slot are dropped.  In this mode, fixed when the engine is created:
+ *
+ * Gate.  A voice burst -- one whose slot has syncTypes[slot] == VOICE after the burst's own bookkeeping (:207) -- is emitted
+ * iff (slot + 1) & slot_filter.  activeSlot takes no part and is never claimed: it stays -1.
+ *
+ * Records.  The frames row of a channel is a sequence of DH_DMR_SLOT_RECORD_BYTES = 28 byte records in burst order: the 27
+ * payload bytes of :213-226, then one tag byte, the slot (0 or 1; its upper seven bits are 0).
+ *
+ * Contract.  For every channel, every slot filter f in 0..3 and any way the stream is cut into pushes, the payloads of the
+ * records tagged s, in order, are byte for byte the frames of the decoder without the flag on the same input at slot
+ * filter f & (s + 1); the events are the decoder's at any filter (they never depended on it); the symbols are untouched.
+ * Concatenated over a stream, the frames bytes do not depend on how the stream is cut into pushes.
+ *
+ * Capacity.  The frames row holds (max_syms / 144 + 1) * 28 bytes, rounded up to 64: a voice burst in every burst position
+ * of a push fits, so the row cannot overflow in this mode.
+ *
+ * dh_engine_set_slot_filter and _channel keep their meaning (bits 0 and 1 of the filter; higher bits are ignored) and do
+ * not switch the mode; dh_engine_reset, _reset_channel and _reset_channels keep it.
+ * ---------------------------------------------------------------------- */
+#define DH_DMR_SLOT_RECORD_BYTES 28
 
 typedef struct {
     uint32_t struct_size;     /* = sizeof(dh_engine_config) */
@@ -510,7 +538,11 @@ typedef struct {
     uint32_t n_channels, max_samples, depth, lead, confirm, release;
     uint32_t protos;               /* bit DH_PROTO_x set: that protocol is decoded */
     void*    stream;               /* hipStream_t; NULL = default stream */
+    uint32_t dmr_both_slots;       /* non-zero: the DMR engine is created with DH_FLAG_DMR_BOTH_SLOTS, its blocks carry 28-byte slot-tagged
+                                      records; 0 (and a struct_size that ends before this field): the reference's one active slot */
 } dh_monitor_config;
+/* sizeof(dh_monitor_config) before dmr_both_slots was added: still accepted as struct_size (that size exactly, or the whole struct) */
+#define DH_MONITOR_CONFIG_V1_SIZE offsetof(dh_monitor_config, dmr_both_slots)
 typedef struct {
     int32_t proto, replay;
     dh_engine* engine;
