@@ -48,10 +48,12 @@ class PrerollConfig(C.Structure):
 class MonitorConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_samples", C.c_uint32),
                 ("depth", C.c_uint32), ("lead", C.c_uint32), ("confirm", C.c_uint32), ("release", C.c_uint32),
-                ("protos", C.c_uint32), ("stream", C.c_void_p), ("dmr_both_slots", C.c_uint32)]
+                ("protos", C.c_uint32), ("stream", C.c_void_p), ("dmr_both_slots", C.c_uint32), ("reserved", C.c_uint32),
+                ("close_hits", C.c_uint32 * 5), ("close_dist", C.c_uint32 * 5)]
 
 
 MONITOR_CONFIG_V1_SIZE = MonitorConfig.dmr_both_slots.offset       # DH_MONITOR_CONFIG_V1_SIZE
+MONITOR_CONFIG_V2_SIZE = MonitorConfig.close_hits.offset           # DH_MONITOR_CONFIG_V2_SIZE
 
 
 class MonitorPushInfo(C.Structure):

@@ -683,6 +683,22 @@ def _by_position(blocks):
     return blocks
 
 
+# naming on close (Monitor, DeviceMonitor: on_close="default"): per family (hits, dist) -- the hits a closing channel
+# needs and the largest best distance accepted; hits = 0: the family is never named on close
+CLOSE_DEFAULT = {"dmr": (1, 1), "ysf": (1, 1), "nxdn": (0, 0), "dstar": (2, 1), "pocsag": (1, 1)}
+
+
+def _close_rule(on_close):
+    """on_close as (close_hits[5], close_dist[5]) in the order of SCAN_FAMILIES; None: all zeros, the mode is off"""
+    rule = {} if on_close is None else CLOSE_DEFAULT if isinstance(on_close, str) and on_close == "default" else on_close
+    if not isinstance(rule, dict) or set(rule) - {name for name, _ in SCAN_FAMILIES}:
+        raise ValueError("on_close: None, \"default\" or {family: (hits, dist)} over %s" % ", ".join(name for name, _ in SCAN_FAMILIES))
+    pairs = [tuple(int(v) for v in rule.get(name, (0, 0))) for name, _ in SCAN_FAMILIES]
+    if any(len(p) != 2 or not 0 <= p[0] <= 0xFFFFFFFF or not 0 <= p[1] <= 0xFFFFFFFF for p in pairs):
+        raise ValueError("on_close: (hits, dist) are two unsigned 32-bit numbers per family")
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
 class Monitor(_Handle):
     """A band monitor over the rows of a channelizer: one Scanner names the protocol an open channel carries, one Preroll
     keeps every channel's recent past, and one Engine per protocol in `protos` (behind the front end of PROTO_FRONT)
@@ -696,8 +712,9 @@ class Monitor(_Handle):
 
       1. n == 0 returns [].
       2. The ring appends the rows; a channel is closed in this round when its open_at is PREROLL_NONE.
-      3. An unassigned channel that closed in this round has its scanner state reset; an assigned channel closed for
-         `release` rounds in a row becomes unassigned.
+      3. An unassigned channel that closed in this round has its scanner state reset -- with `on_close`, after its
+         evidence was judged once more (below); an assigned channel closed for `release` rounds in a row becomes
+         unassigned.
       4. The scanner sees the open, unassigned channels only; names = classify(confirm).
       5. An open, unassigned channel with a name is assigned: start = max(open_at - lead, total - depth, 0), the channel
          is reset in its engine and in the scanner, and the ring is replayed from start into the engine in chunks of
@@ -713,14 +730,25 @@ class Monitor(_Handle):
     dmr_both_slots=True: the DMR engine is created with it, and the `frames` of a "dmr" block are 28-byte slot-tagged
     records (dmr_split_slots) -- both calls of a two-slot channel instead of the one that holds the decoder's output.
 
-    Known limit: a transmission that ends before the scanner has confirmed it is never decoded -- a single POCSAG batch,
-    a D-Star transmission shorter than three sync periods.  (Lowering `confirm` per family is a later question.)"""
+    on_close=None | "default" (CLOSE_DEFAULT) | {family: (hits, dist)}: naming on close.  In the round in which an
+    unassigned channel closes, before its scanner state is reset, H = the sum of `hits` and D = the smallest `best_dist`
+    over each family's patterns are read from scanner.stats().  A family with hits != 0, H >= hits and D <= dist is
+    eligible; the eligible family with the largest H wins, the first in the order of SCAN_FAMILIES where two are level.
+    If its protocol is in `protos` the channel is assigned as in step 5, with open_at that of its last open round; the
+    replay runs to the end of this round, whose samples flush the decoder's look-ahead.  Otherwise it stays unassigned
+    (the next-best family is not considered).  A channel named on close is closed: it gets no live push, is released by
+    the ordinary rule after `release` closed rounds, and continues live in the same engine if its gate opens before.
+
+    Without on_close, a transmission that ends before the scanner has confirmed it is never decoded -- a single POCSAG
+    batch, a D-Star transmission shorter than three sync periods.  With it, what is lost is a transmission whose
+    evidence stays below its family's thresholds; under CLOSE_DEFAULT, NXDN is never named on close."""
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, dmr_both_slots=False):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, dmr_both_slots=False, on_close=None):
         self._resolve(ctx, device)
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
+        self.close_hits, self.close_dist = _close_rule(on_close)
         self.protos = tuple(protos)
         self.engines = {}
         self.scanner = Scanner(self.B, self.max_samples, fronts=tuple(dict.fromkeys(PROTO_FRONT[p] for p in self.protos)), ctx=self.ctx)
@@ -735,6 +763,16 @@ class Monitor(_Handle):
         self.assigned = [None] * self.B
         self.start = [None] * self.B
         self.closed_run = np.zeros(self.B, np.int64)
+        self.opened = np.full(self.B, PREROLL_NONE, np.uint64)
+
+    def _name_on_close(self, st):
+        """the family a closing channel with the statistics st [9] is named as, or None"""
+        best, most = None, 0
+        for k, (name, ids) in enumerate(SCAN_FAMILIES):
+            H, D = int(st["hits"][list(ids)].astype(np.int64).sum()), int(st["best_dist"][list(ids)].min())
+            if self.close_hits[k] != 0 and H >= self.close_hits[k] and D <= self.close_dist[k] and (best is None or H > most):
+                best, most = name, H
+        return best
 
     def close(self):
         for e in getattr(self, "engines", {}).values():
@@ -768,27 +806,39 @@ class Monitor(_Handle):
         open_at, total = self.pre.open_at(), self.pre.total
         is_open = open_at != np.uint64(PREROLL_NONE)
         self.closed_run = np.where(is_open, 0, self.closed_run + 1)
+        self.opened[is_open] = open_at[is_open]
+        closing = []
         for b in np.flatnonzero(~is_open):
             if self.assigned[b] is None:
                 if self.closed_run[b] == 1:
-                    self.scanner.reset_channel(int(b))
+                    closing.append(int(b))
             elif self.closed_run[b] >= self.release:
                 self.assigned[b], self.start[b] = None, None
         before = list(self.assigned)
+        new, since = {}, {}
+        if closing and any(self.close_hits):             # naming on close: the evidence, before the reset forgets it
+            stats = self.scanner.stats()
+            for b in closing:
+                name = self._name_on_close(stats[b])
+                if name in self.engines:
+                    new.setdefault(name, []).append(b)
+                    since[b] = int(self.opened[b])
+        for b in closing:
+            self.scanner.reset_channel(b)
         scan = np.array([n if is_open[b] and before[b] is None else 0 for b in range(self.B)], np.uint32)
-        new = {}
         if scan.any():                                   # (a push of all-zero counts would change nothing)
             self.scanner.push(x, n=n, counts=scan)
             names = self.scanner.classify(self.confirm)
             for b in np.flatnonzero(scan):
                 if names[b] in self.engines:
                     new.setdefault(names[b], []).append(int(b))
+                    since[int(b)] = int(open_at[b])
         blocks = []
         for name, chans in new.items():
             eng = self.engines[name]
             from_ = np.full(self.B, PREROLL_NONE, np.uint64)
             for b in chans:
-                self.start[b] = max(int(open_at[b]) - self.lead, total - self.depth, 0)
+                self.start[b] = max(since[b] - self.lead, total - self.depth, 0)
                 self.assigned[b] = name
                 eng.reset_channel(b)
                 self.scanner.reset_channel(b)
@@ -871,20 +921,24 @@ class DeviceMonitor(_Handle):
 
     dmr_both_slots=True: as for Monitor (dh_monitor_config.dmr_both_slots); "dmr" blocks carry 28-byte slot-tagged records.
 
+    on_close: as for Monitor (dh_monitor_config.close_hits, close_dist; step C of a round, one more kernel).
+
     packed=True: the monitor owns an OutPack sized so that a round can never drop, and push() is clear,
     dh_monitor_push_packed, one read: no sink, no read-back per engine push, copies sized by what was decoded."""
     _kind = "dh_monitor"
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False, dmr_both_slots=False):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, packed=False, dmr_both_slots=False, on_close=None):
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
         self.protos = tuple(protos)
+        self.close_hits, self.close_dist = _close_rule(on_close)
         bits = 0
         for p in self.protos:
             bits |= 1 << _capi.PROTO[p]
         self._open(ctx, device, _capi.MonitorConfig, n_channels=self.B, max_samples=self.max_samples, depth=self.depth, lead=self.lead,
-                   confirm=self.confirm, release=self.release, protos=bits, dmr_both_slots=int(bool(dmr_both_slots)))
+                   confirm=self.confirm, release=self.release, protos=bits, dmr_both_slots=int(bool(dmr_both_slots)),
+                   close_hits=(C.c_uint32 * 5)(*self.close_hits), close_dist=(C.c_uint32 * 5)(*self.close_dist))
         lib, h = self.ctx.lib, self._h
         self.engines = {p: Engine._borrowed(self.ctx, lib.dh_monitor_engine(h, _capi.PROTO[p]), self.B, self.max_samples) for p in self.protos}
         self.scanner = Scanner.__new__(Scanner)

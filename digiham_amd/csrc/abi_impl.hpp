@@ -630,6 +630,7 @@ int dh_outpack_device(dh_outpack* p, const dh_outpack_header** d_hdr, const dh_o
 // ---- the band monitor (monitor_core.hpp): scan engines, ring and protocol engines behind one handle ------------------
 //   dh_be_monitor_open(const DhMonOpen& A, void* stream);        step A
 //   dh_be_monitor_assign(const DhMonAssign& S, void* stream);    step B
+//   dh_be_monitor_close(const DhMonClose& C, void* stream);      step C (naming on close)
 // (engine.hip defines the gfx950 ones; monitor_core.hpp the CPU harness's.)  All the host learns of a round is the summary
 // block, read once after each step; everything [B]-sized stays on the device.
 struct dh_monitor : dh_state {
@@ -641,7 +642,8 @@ struct dh_monitor : dh_state {
     uint32_t* d_chunk_counts = nullptr;                 // [B]: its counts
     DhMonSummary* d_sum = nullptr;
     DhMonSummary sum{}, sum0{};                         // what was read last; what a round starts from
-    DhMonOpen A{}; DhMonAssign S{};                     // what create fixes; a round adds n and total
+    DhMonOpen A{}; DhMonAssign S{}; DhMonClose Cl{};    // what create fixes; a round adds n and total
+    bool close_on = false;                              // naming on close: any close_hits != 0
     std::vector<uint64_t> none;
 
     static uint32_t front_of(int proto) { return proto == DH_PROTO_NXDN ? 1u : proto == DH_PROTO_DSTAR ? 2u : proto == DH_PROTO_POCSAG ? 3u : 0u; }
@@ -652,7 +654,8 @@ struct dh_monitor : dh_state {
         bufs.free_all();
     }
     int clear() {
-        if (be.zero(A.assigned, B) || be.zero(A.closed_run, sizeof(uint32_t) * B) || be.upload(A.start, none.data(), sizeof(uint64_t) * B))
+        if (be.zero(A.assigned, B) || be.zero(A.closed_run, sizeof(uint32_t) * B) || be.upload(A.start, none.data(), sizeof(uint64_t) * B) ||
+            be.upload(A.opened, none.data(), sizeof(uint64_t) * B))
             return DH_EDEVICE;
         return be.sync() ? DH_EDEVICE : DH_OK;
     }
@@ -668,6 +671,10 @@ struct dh_monitor : dh_state {
     }
     int init(const dh_monitor_config& c) {
         B = c.n_channels; max_samples = c.max_samples;
+        for (uint32_t f = 0; f < DH_MON_FAMILIES; f++) {
+            Cl.close_hits[f] = c.close_hits[f]; Cl.close_dist[f] = c.close_dist[f];
+            close_on |= c.close_hits[f] != 0u;
+        }
         none.assign(B, DH_PREROLL_NONE);
         for (int p = 1; p < (int) DH_MON_PROTOS; p++) {
             if (!(c.protos >> p & 1u)) continue;
@@ -683,7 +690,7 @@ struct dh_monitor : dh_state {
         bool ok = bufs.alloc(d_stage, (size_t) B * max_samples);
         ok &= bufs.alloc(d_chunk_counts, B);
         ok &= bufs.alloc(d_sum, 1);
-        ok &= bufs.alloc(A.assigned, B); ok &= bufs.alloc(A.closed_run, B); ok &= bufs.alloc(A.start, B);
+        ok &= bufs.alloc(A.assigned, B); ok &= bufs.alloc(A.closed_run, B); ok &= bufs.alloc(A.start, B); ok &= bufs.alloc(A.opened, B);
         ok &= bufs.alloc(A.scan_reset, B); ok &= bufs.alloc(A.scan_counts, B);
         for (uint32_t p = 1; p < DH_MON_PROTOS; p++)
             if (eng[p]) { ok &= bufs.alloc(A.live_counts[p], B); ok &= bufs.alloc(S.new_flags[p], B); ok &= bufs.alloc(S.from[p], B); }
@@ -693,6 +700,10 @@ struct dh_monitor : dh_state {
             if (scan[f]) { S.stats[f] = scan[f]->impl.frames; S.stat_count[f] = scan[f]->impl.frame_count; S.stat_stride[f] = scan[f]->impl.L.out_cap; }
         S.scan_counts = A.scan_counts; S.open_at = pre->d_open; S.assigned = A.assigned; S.start = A.start; S.scan_reset = A.scan_reset;
         S.sum = d_sum; S.B = B; S.lead = c.lead; S.depth = c.depth; S.confirm = c.confirm;
+        static_cast<DhMonStats&>(Cl) = S;
+        Cl.scan_reset = A.scan_reset; Cl.opened = A.opened; Cl.assigned = A.assigned; Cl.start = A.start;
+        for (uint32_t p = 1; p < DH_MON_PROTOS; p++) { Cl.new_flags[p] = S.new_flags[p]; Cl.from[p] = S.from[p]; }
+        Cl.sum = d_sum; Cl.B = B; Cl.lead = c.lead; Cl.depth = c.depth;
         for (uint32_t p = 0; p < DH_MON_PROTOS; p++) sum0.min_start[p] = DH_PREROLL_NONE;
         return clear();
     }
@@ -718,6 +729,11 @@ struct dh_monitor : dh_state {
         A.n = (uint32_t) n;
         if (dh_be_monitor_open(A, stream)) return DH_EDEVICE;                               // 2
         if ((rc = read_summary()) != DH_OK) return rc;
+        const bool closing = close_on && sum.n_reset;                                       // C, in front of the reset that
+        if (closing) {                                                                      // forgets what it judges
+            Cl.total = total;
+            if (dh_be_monitor_close(Cl, stream)) return DH_EDEVICE;
+        }
         if (sum.n_reset && (rc = reset_scanners()) != DH_OK) return rc;                     // 3
         if (sum.n_scan) {
             for (dh_engine* e : scan)                                                       // 4
@@ -725,12 +741,12 @@ struct dh_monitor : dh_state {
             S.total = total;
             if (dh_be_monitor_assign(S, stream)) return DH_EDEVICE;                         // 5
             if ((rc = read_summary()) != DH_OK) return rc;
-        }
+        } else if (closing && (rc = read_summary()) != DH_OK) return rc;
         dh_monitor_push_info info{};
         info.live_first = total - n;
         bool any_new = false;
         for (uint32_t p = 1; p < DH_MON_PROTOS; p++) any_new |= sum.n_new[p] != 0u;
-        if (any_new && (rc = reset_scanners()) != DH_OK) return rc;                         // 6 (scan_reset: the channels step B named)
+        if (any_new && sum.n_scan && (rc = reset_scanners()) != DH_OK) return rc;           // 6 (scan_reset: the channels step B named)
         for (uint32_t p = 1; p < DH_MON_PROTOS; p++) {
             if (!eng[p] || !sum.n_new[p]) continue;
             if ((rc = eng[p]->impl.reset_channels(S.new_flags[p])) != DH_OK) return rc;
@@ -759,13 +775,14 @@ extern "C" {
 int dh_monitor_create(const dh_monitor_config* cfg, dh_monitor** out) {
     if (!cfg || !out) return DH_EINVAL;
     *out = nullptr;
-    if ((cfg->struct_size != DH_MONITOR_CONFIG_V1_SIZE && cfg->struct_size < sizeof(dh_monitor_config)) || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
+    const bool size_ok = cfg->struct_size == DH_MONITOR_CONFIG_V1_SIZE || cfg->struct_size == DH_MONITOR_CONFIG_V2_SIZE || cfg->struct_size >= sizeof(dh_monitor_config);
+    if (!size_ok || cfg->n_channels < 1 || cfg->n_channels > 65536 || cfg->max_samples < 1 ||
         cfg->depth < 1 || cfg->depth > (1u << 24) || cfg->protos == 0 || (cfg->protos & ~0x3Eu))
         return DH_EINVAL;
-    // dmr_both_slots was appended to the struct: a caller built against the older header passes the older size and means 0
-    // (only the bytes the caller's struct has are read)
+    // dmr_both_slots, then close_hits and close_dist were appended to the struct: a caller built against an older header
+    // passes that header's size and means 0 (only the bytes the caller's struct has are read)
     dh_monitor_config c{};
-    memcpy(&c, cfg, cfg->struct_size == DH_MONITOR_CONFIG_V1_SIZE ? DH_MONITOR_CONFIG_V1_SIZE : sizeof c);
+    memcpy(&c, cfg, cfg->struct_size < sizeof c ? cfg->struct_size : sizeof c);
     return dh_create(c, out, [&](dh_monitor& m) { return m.init(c); });
 }
 void dh_monitor_destroy(dh_monitor* m) { dh_destroy(m); }

@@ -1051,9 +1051,9 @@ __global__ __launch_bounds__(256) void k_preroll_gather(const DhPrGather G) {
 }
 
 // ---------------------------------------------------------------------------------- band monitor (monitor_core.hpp)
-// Steps A and B of a round: one lane per channel, 256-thread workgroups, the loop bound the same for every lane of a
+// Steps A, B and C of a round: one lane per channel, 256-thread workgroups, the loop bound the same for every lane of a
 // workgroup so that the votes below see whole wavefronts.  Ordinary vector stores for the state and the per-channel
-// outputs; the summary block takes one vector atomic per wavefront and non-zero count (A), per newly named channel (B).
+// outputs; the summary block takes one vector atomic per wavefront and non-zero count (A), per newly named channel (B, C).
 __global__ __launch_bounds__(256) void k_monitor_open(const DhMonOpen A) {
     const bool first = (threadIdx.x & (DH_WAVE - 1)) == 0;
     for (uint32_t base = blockIdx.x * 256u; base < A.B; base += gridDim.x * 256u) {
@@ -1077,6 +1077,17 @@ __global__ __launch_bounds__(256) void k_monitor_assign(const DhMonAssign S) {
         if (p) {
             atomicAdd(&S.sum->n_new[p], 1u);
             atomicMin((unsigned long long*) &S.sum->min_start[p], (unsigned long long) start);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_monitor_close(const DhMonClose C) {
+    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < C.B; b += gridDim.x * 256u) {
+        uint64_t start;
+        const uint32_t p = dh_mon_close_channel(C, b, start);
+        if (p) {
+            atomicAdd(&C.sum->n_new[p], 1u);
+            atomicMin((unsigned long long*) &C.sum->min_start[p], (unsigned long long) start);
         }
     }
 }
@@ -1288,6 +1299,11 @@ static int dh_be_monitor_open(const DhMonOpen& A, void* stream) {
 }
 static int dh_be_monitor_assign(const DhMonAssign& S, void* stream) {
     hipLaunchKernelGGL(k_monitor_assign, dim3(grid_for(S.B, 256)), dim3(256), 0, (hipStream_t) stream, S);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_monitor_close(const DhMonClose& C, void* stream) {
+    hipLaunchKernelGGL(k_monitor_close, dim3(grid_for(C.B, 256)), dim3(256), 0, (hipStream_t) stream, C);
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }

@@ -487,14 +487,26 @@ int  dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t sk
  *
  * State, per channel, on the device: assigned (uint8: 0 or a DH_PROTO_*), closed_run (uint32, saturating: rounds in a
  * row with the gate closed), start (uint64: the stream index at which the decoder's input began; DH_PREROLL_NONE while
- * unassigned).  dh_monitor_state copies assigned and start to the host (either pointer may be NULL) and synchronises.
+ * unassigned), opened (uint64: open_at of the channel's last open round; DH_PREROLL_NONE after create and reset).
+ * dh_monitor_state copies assigned and start to the host (either pointer may be NULL) and synchronises.
  *
  * One round, dh_monitor_push with 0 < n <= max_samples (n = 0: DH_OK, nothing happens):
  *   1. The ring appends the rows (Pre-roll); open = (open_at[b] != DH_PREROLL_NONE).
  *   2. Step A, one kernel, per channel: closed_run = open ? 0 : closed_run + 1.  A closed channel that is unassigned with
  *      closed_run == 1 gets scan_reset[b] = 1 (every other channel 0); a closed channel that is assigned with
  *      closed_run >= release becomes unassigned, start = DH_PREROLL_NONE.  Then scan_counts[b] = (open && assigned == 0)
- *      ? n : 0, and for every configured protocol p live_counts[p][b] = (open && assigned == p) ? n : 0.
+ *      ? n : 0, and for every configured protocol p live_counts[p][b] = (open && assigned == p) ? n : 0.  An open channel
+ *      gets opened[b] = open_at[b].
+ *   C. Naming on close -- only with some close_hits[f] != 0, and only where step A set any scan_reset: one kernel, per
+ *      CLOSING channel (scan_reset[b] = 1: closed, unassigned, closed_run == 1), before step 3 forgets what it judges.
+ *      Per family f in the order DMR, YSF, NXDN, D-Star, POCSAG: H_f = the sum of `hits` and D_f = the smallest
+ *      best_dist over the family's patterns, read as step 5 reads `periodic` (a short row or a front end that is not
+ *      configured: zeros and 255).  f is eligible iff close_hits[f] != 0 && H_f >= close_hits[f] && D_f <= close_dist[f];
+ *      the eligible family with the largest H_f wins, the first in that order where two are level.  If its protocol p
+ *      is configured the channel is assigned: assigned = p, start = max(opened - lead, total - depth, 0) as in step 5,
+ *      new_flags[p][b] = 1, from[p][b] = start; every other new_flags entry is 0, every other from entry
+ *      DH_PREROLL_NONE.  Otherwise the channel stays unassigned (the next-best family is not considered).  closed_run
+ *      and scan_reset stay as step A left them.
  *   3. Where any scan_reset is set, the scan engines get dh_engine_reset_channels(scan_reset).
  *   4. Where any scan_counts is non-zero, every scan engine gets a ragged push of the rows with scan_counts.
  *   5. Step B (only then), one kernel, per channel with scan_counts != 0: the `periodic` counts of the nine patterns are
@@ -504,13 +516,17 @@ int  dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t sk
  *      If its sum is >= confirm and its protocol p is configured, the channel is assigned: assigned = p, start =
  *      max(open_at - lead, total - depth, 0) with both differences saturating at 0 (total: after this round's append),
  *      new_flags[p][b] = 1, from[p][b] = start, scan_reset[b] = 1.  Every other new_flags entry is 0, every other from
- *      entry DH_PREROLL_NONE, every other scan_reset 0.  If the winner's protocol is not configured the channel stays
- *      unassigned; the next-best family is not considered.
- *   6. Where a channel was assigned, the scan engines get dh_engine_reset_channels(scan_reset); then per protocol p with
- *      new channels: dh_engine_reset_channels(new_flags[p]) of its engine, and for skip = 0, max_samples, ... while
+ *      entry DH_PREROLL_NONE, every other scan_reset 0 -- except that the new_flags and from entries of a channel step C
+ *      named in this round are left alone.  If the winner's protocol is not configured the channel stays unassigned; the
+ *      next-best family is not considered.
+ *   6. Where step 5 assigned a channel, the scan engines get dh_engine_reset_channels(scan_reset); then -- also in a round
+ *      in which nothing was scanned -- per protocol p with channels new from step C or step 5:
+ *      dh_engine_reset_channels(new_flags[p]) of its engine, and for skip = 0, max_samples, ... while
  *      skip < total - (the smallest start among p's new channels): dh_preroll_gather_device(from[p], skip, max_samples)
  *      into the staging array and a ragged push of it.  The ring already holds this round's samples: a channel named in
- *      this round gets no live push in it.
+ *      this round gets no live push in it.  For a channel named on close those are the closing round's own samples,
+ *      which flush the decoder's look-ahead; being closed it gets no live push, is released by step A's ordinary rule
+ *      when closed_run >= release, and continues live in the same engine if its gate opens before that.
  *   7. Per protocol p with any live_counts[p] non-zero: one ragged push of the caller's rows with live_counts[p].
  *
  * The sink.  After EVERY engine push of steps 6 and 7, before the next push overwrites that engine's outputs, `sink`
@@ -522,11 +538,17 @@ int  dh_preroll_gather_device(dh_preroll* p, const uint64_t* d_from, uint64_t sk
  *
  * What the host reads.  Steps A and B each add up one fixed-size summary block on the device -- how many channels are
  * scanned, how many have scan_reset, how many are live per protocol; how many are new per protocol and the smallest
- * start among them -- and dh_monitor_push reads that block at most twice per round, after step A and after step B: one
- * small copy each, which synchronises.  It reads nothing whose size grows with n_channels, uploads nothing per channel,
+ * start among them (steps B and C add to the same fields) -- and dh_monitor_push reads that block at most twice per round,
+ * after step A and after step B, or after step C in a round where step C ran and step B did not: one small copy each,
+ * which synchronises.  Without naming on close no round launches or reads anything more than before.  It reads nothing whose size grows with n_channels, uploads nothing per channel,
  * and issues a fixed number of launches per engine however many channels are reset.
  *
- * DH_EINVAL: null handle or configuration, struct_size too small, n_channels outside 1 .. 65536, max_samples = 0, depth
+ * What is never decoded.  Without naming on close: a transmission that ends before the scanner has confirmed it (three
+ * sync words one frame period apart, seen while the gate is open) -- a single POCSAG batch, a D-Star transmission shorter
+ * than three sync periods.  With it: a transmission whose evidence stays below its family's thresholds; a family with
+ * close_hits = 0 is never named on close.
+ *
+ * DH_EINVAL: null handle or configuration, struct_size none of the accepted sizes, n_channels outside 1 .. 65536, max_samples = 0, depth
  * outside 1 .. 2^24, protos == 0 or with bits other than DH_PROTO_DMR .. DH_PROTO_DSTAR, n > max_samples, stride < n, null
  * rows with n != 0.  dh_monitor_engine / dh_monitor_scan_engine return the owned handles (NULL: not configured, or out of
  * range) for reading outputs and statistics; they stay the monitor's and go with dh_monitor_destroy.
@@ -540,9 +562,14 @@ typedef struct {
     void*    stream;               /* hipStream_t; NULL = default stream */
     uint32_t dmr_both_slots;       /* non-zero: the DMR engine is created with DH_FLAG_DMR_BOTH_SLOTS, its blocks carry 28-byte slot-tagged
                                       records; 0 (and a struct_size that ends before this field): the reference's one active slot */
+    uint32_t reserved;             /* the struct's tail padding before naming on close was added; not read */
+    uint32_t close_hits[5];        /* naming on close, by family: DMR, YSF, NXDN, D-Star, POCSAG.  0: never named on close; all 0 */
+    uint32_t close_dist[5];        /* (and a struct_size that ends before these fields): the mode is off.  The largest best distance accepted */
 } dh_monitor_config;
-/* sizeof(dh_monitor_config) before dmr_both_slots was added: still accepted as struct_size (that size exactly, or the whole struct) */
+/* sizeof(dh_monitor_config) before dmr_both_slots was added, and before close_hits and close_dist were: both still accepted
+ * as struct_size (one of these sizes exactly, or the whole struct); the fields a shorter struct lacks are zeros */
 #define DH_MONITOR_CONFIG_V1_SIZE offsetof(dh_monitor_config, dmr_both_slots)
+#define DH_MONITOR_CONFIG_V2_SIZE offsetof(dh_monitor_config, close_hits)
 typedef struct {
     int32_t proto, replay;
     dh_engine* engine;
