@@ -364,17 +364,75 @@ DH_HD void dh_load_planes(const DhSymView& syms, uint32_t pos, uint32_t total, D
     }
 }
 
-// kernel prologue: carried symbols and the small FEC tables into LDS
-DH_HD void dh_stage_decoder_lds(const DhDecParams& P, DhDecShared& S, const uint8_t* carry_buf, uint32_t nc) {
+// kernel prologue: carried symbols and, with `tables`, the small FEC tables into LDS
+DH_HD void dh_stage_decoder_lds(const DhDecParams& P, DhDecShared& S, uint8_t* lds_carry, const uint8_t* carry_buf, uint32_t nc, bool tables) {
     const uint32_t* tsrc = reinterpret_cast<const uint32_t*>(P.T);
     DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < nc; j += DH_WAVE) S.carry[j] = carry_buf[j];
-        for (uint32_t j = lane; j < sizeof(S.fec_small) / 4; j += DH_WAVE) S.fec_small[j] = tsrc[j];
+        for (uint32_t j = lane; j < nc; j += DH_WAVE) lds_carry[j] = carry_buf[j];
+        if (tables) for (uint32_t j = lane; j < sizeof(S.fec_small) / 4; j += DH_WAVE) S.fec_small[j] = tsrc[j];
     }
     DH_BARRIER();
 }
 // the LDS copy viewed as a DhFecTables: valid for the codes and the small LUTs only (not lut_g208 / lut_g2412)
 DH_HD const DhFecTables& dh_lds_tables(const DhDecShared& S) { return *reinterpret_cast<const DhFecTables*>(S.fec_small); }
+
+// ---------------------------------------------------------------------------------------------
+// The bookends of a channel's push.  A decoder body is: its three locals (DhDecCtx c; DhState s; DhSymView syms; -- the caller's, so
+// that they stay in registers), dh_channel_open, its phase loop, its own members back into s, dh_channel_close.
+// After dh_channel_open:
+//   s      holds the channel's state words, c.st points at it
+//   syms   is the push's virtual symbol stream from position 0 to syms.nc + syms.nfresh: the symbols the previous push left unread
+//          (copied to `lds_carry`, an LDS block of the caller's choice), then the fresh ones behind sym_base (dh_view_ensure / dh_view_at)
+//   c      writes the channel's output and event rows.  c.nout / c.nev start at 0, or with `append` -- a later part of a split push,
+//          k_chain; POCSAG and the scan are never split and pass 0, false -- at the rows' counts; c.consumed continues DS_CONSUMED,
+//          c.overflow is false, c.writer names the one lane that performs the wave-uniform global stores
+//   c.T    with `tables`: the small FEC tables, staged in LDS (`lds_carry` is then S.carry); without: nullptr, S.fec_small is free
+//   and a barrier has been passed: every lane sees the LDS copies.
+// Before dh_channel_close the decoder leaves: pos, the first symbol it has not consumed -- [pos, end) is carried into the next push, at
+// most carry_max (dh_carry_max of the protocol) symbols of it, more is an overflow --; phase, for DS_PHASE; c.consumed advanced by what
+// pos advanced; c.nout, c.nev, c.overflow as the emit functions left them.  dh_channel_close stores the carry row, the counts, the
+// overflow flag and the state row and ends with a barrier: the LDS block is free for whatever the kernel does next.
+DH_HD void dh_channel_open(DhDecCtx& c, DhState& s, DhSymView& syms, const DhDecParams& P, uint32_t ch, DhDecShared& S,
+                           uint8_t* lds_carry, bool tables, uint32_t sym_base, bool append) {
+    c.P = &P; c.T = tables ? &dh_lds_tables(S) : nullptr;
+    s.load(P.state + (size_t) ch * P.state_stride); c.st = &s;
+    c.out = P.out + (size_t) ch * P.out_stride;
+    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
+    c.nout = dh_uniform(append ? P.out_count[ch] : 0u); c.nev = dh_uniform(append && P.ev_count ? P.ev_count[ch] : 0u); c.overflow = false;
+    c.consumed = s[DS_CONSUMED];
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+    c.writer = threadIdx.x == 0;
+#else
+    c.writer = true;
+#endif
+    syms.carry = lds_carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
+    syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    dh_stage_decoder_lds(P, S, lds_carry, P.carry + (size_t) ch * P.carry_stride, syms.nc, tables);
+}
+
+// the carry-out half of dh_channel_close: the unread symbols to the front of the global carry row (the sources are LDS, carried part or
+// window: no overlap to worry about), the row counts and the overflow flag.  Returns the new carry length.
+DH_HD uint32_t dh_channel_carry_out(const DhDecCtx& c, DhSymView& syms, const DhDecParams& P, uint32_t ch, uint32_t pos, uint32_t carry_max) {
+    const uint32_t rem = syms.nc + syms.nfresh - pos, keep = rem < carry_max ? rem : carry_max;
+    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
+    dh_view_ensure(syms, pos, keep);
+    DH_FOR_LANES(lane) {
+        for (uint32_t j = lane; j < keep; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
+        if (DH_IS_LANE0(lane)) {
+            P.out_count[ch] = c.nout;
+            if (P.ev_count) P.ev_count[ch] = c.nev;
+            if ((c.overflow || rem > carry_max) && P.overflow) *P.overflow = 1u;
+        }
+    }
+    return keep;
+}
+
+DH_HD void dh_channel_close(DhDecCtx& c, DhState& s, DhSymView& syms, const DhDecParams& P, uint32_t ch, uint32_t pos, uint32_t phase, uint32_t carry_max) {
+    const uint32_t keep = dh_channel_carry_out(c, syms, P, ch, pos, carry_max);
+    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed; s[DS_CARRY] = keep;
+    s.store(P.state + (size_t) ch * P.state_stride);
+    DH_BARRIER();
+}
 
 // =============================================================================================
 // Frame-parallel DMR decoder (round 5).
@@ -943,25 +1001,9 @@ DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_L
 #endif
 
 DH_HD void dh_dmr_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
-    DhDecCtx c;
-    c.P = &P; c.T = &dh_lds_tables(S);
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = dh_uniform(append ? P.out_count[ch] : 0u); c.nev = dh_uniform(append && P.ev_count ? P.ev_count[ch] : 0u); c.overflow = false;      // (append: the second part of a split push, k_chain)
-    c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
-    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
-    syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, S.carry, true, sym_base, append);
     const uint32_t total = syms.nc + syms.nfresh;
-    dh_stage_decoder_lds(P, S, carry_buf, syms.nc);
     const DhFecTables& T = dh_lds_tables(S);
     uint32_t pos = 0;
     uint32_t phase = s[DS_PHASE];
@@ -1159,23 +1201,8 @@ DH_HD void dh_dmr_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uin
         if (c.overflow) break;
     }
 
-    // carry the unread symbols to the front of the buffer
-    const uint32_t rem = total - pos;
-    dh_view_ensure(syms, pos, rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX);
-    DH_FOR_LANES(lane) {
-        // sources are LDS (carried part / window), destination is the global carry row: no overlap to worry about
-        for (uint32_t j = lane; j < rem && j < DH_SYM_CARRY_MAX; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = c.nout;
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if ((c.overflow || rem > DH_SYM_CARRY_MAX) && P.overflow) *P.overflow = 1u;
-        }
-    }
     if (phase == 1) M.store(s);
-    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
-    s[DS_CARRY] = rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX;
-    s.store(st_global);
-    DH_BARRIER();
+    dh_channel_close(c, s, syms, P, ch, pos, phase, dh_carry_max(DH_PROTO_DMR));
 }
 
 
@@ -1694,25 +1721,9 @@ DH_HD void dh_ysf_decode_ahead(const DhDecParams& P, const DhFecTables& T, const
 // One YSF channel, one push.
 DH_HD void dh_ysf_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
     const DhFecTables& T = dh_lds_tables(S);
-    DhDecCtx c;
-    c.P = &P; c.T = &T;
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = append ? P.out_count[ch] : 0u; c.nev = append && P.ev_count ? P.ev_count[ch] : 0u; c.overflow = false;      // (append: the second part of a split push, k_chain)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.consumed = s[DS_CONSUMED];
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
-    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
-    syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, S.carry, true, sym_base, append);
     const uint32_t total = syms.nc + syms.nfresh;
-    dh_stage_decoder_lds(P, S, carry_buf, syms.nc);
     uint32_t pos = 0, phase = s[DS_PHASE];
     // frames whose two codewords are already decoded (dh_ysf_decode_ahead): the one at ahead_pos is S.ysf.res[ahead_i], ahead_n in all
     uint32_t ahead_pos = 0xFFFFFFFFu, ahead_i = 0, ahead_n = 0;
@@ -1880,22 +1891,8 @@ DH_HD void dh_ysf_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uin
         if (c.overflow) break;
     }
 
-    const uint32_t rem = total - pos;
-    dh_view_ensure(syms, pos, rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX);
-    DH_FOR_LANES(lane) {
-        // sources are LDS (carried part / window), destination is the global carry row: no overlap to worry about
-        for (uint32_t j = lane; j < rem && j < DH_SYM_CARRY_MAX; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = c.nout;
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if ((c.overflow || rem > DH_SYM_CARRY_MAX) && P.overflow) *P.overflow = 1u;
-        }
-    }
     s[DS_SYNC_COUNT] = (uint32_t) sync_count; s[DS_FICH] = running_fich; s[DS_HAS_FICH] = has_fich; s[DS_EXPECT_SUB] = expect_sub;
-    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
-    s[DS_CARRY] = rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX;
-    s.store(st_global);
-    DH_BARRIER();
+    dh_channel_close(c, s, syms, P, ch, pos, phase, dh_carry_max(DH_PROTO_YSF));
 }
 
 // =============================================================================================
@@ -1951,25 +1948,9 @@ DH_HD bool dh_nxdn_crc_ok(const uint8_t* in, int nbits, int width, uint32_t init
 
 // One NXDN channel, one push.
 DH_HD void dh_nxdn_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
-    DhDecCtx c;
-    c.P = &P; c.T = &dh_lds_tables(S);
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = append ? P.out_count[ch] : 0u; c.nev = append && P.ev_count ? P.ev_count[ch] : 0u; c.overflow = false;      // (append: the second part of a split push, k_chain)
-    c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
-    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
-    syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, S.carry, true, sym_base, append);
     const uint32_t total = syms.nc + syms.nfresh;
-    dh_stage_decoder_lds(P, S, carry_buf, syms.nc);
     uint32_t pos = 0, phase = s[DS_PHASE];
     uint32_t ahead_pos = 0xFFFFFFFFu, ahead_n = 0;                 // SACCH codewords decoded ahead: frames at ahead_pos + 192 j, j < ahead_n (S.colword)
 
@@ -2190,20 +2171,7 @@ DH_HD void dh_nxdn_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, ui
         if (c.overflow) break;
     }
 
-    const uint32_t rem = total - pos;
-    dh_view_ensure(syms, pos, rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX);
-    DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < rem && j < DH_SYM_CARRY_MAX; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = c.nout;
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if ((c.overflow || rem > DH_SYM_CARRY_MAX) && P.overflow) *P.overflow = 1u;
-        }
-    }
-    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
-    s[DS_CARRY] = rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX;
-    s.store(st_global);
-    DH_BARRIER();
+    dh_channel_close(c, s, syms, P, ch, pos, phase, dh_carry_max(DH_PROTO_NXDN));
 }
 
 // =============================================================================================
@@ -2283,25 +2251,9 @@ DH_HD void dh_pocsag_append(DhState& s, uint32_t data) {
 }
 
 DH_HD void dh_pocsag_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S) {
-    DhDecCtx c;
-    c.P = &P; c.T = &dh_lds_tables(S);
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = 0; c.nev = 0; c.overflow = false;
-    c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
-    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride;
-    syms.nfresh = P.sym_count[ch]; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, S.carry, true, 0, false);
     const uint32_t total = syms.nc + syms.nfresh;
-    dh_stage_decoder_lds(P, S, carry_buf, syms.nc);
     uint32_t pos = 0, phase = s[DS_PHASE];
 
     for (;;) {
@@ -2377,20 +2329,7 @@ DH_HD void dh_pocsag_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S) 
         if (c.overflow) break;
     }
 
-    const uint32_t rem = total - pos;
-    dh_view_ensure(syms, pos, rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX);
-    DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < rem && j < DH_SYM_CARRY_MAX; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = c.nout;
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if ((c.overflow || rem > DH_SYM_CARRY_MAX) && P.overflow) *P.overflow = 1u;
-        }
-    }
-    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
-    s[DS_CARRY] = rem < DH_SYM_CARRY_MAX ? rem : DH_SYM_CARRY_MAX;
-    s.store(st_global);
-    DH_BARRIER();
+    dh_channel_close(c, s, syms, P, ch, pos, phase, dh_carry_max(DH_PROTO_POCSAG));
 }
 
 // =============================================================================================
@@ -2628,29 +2567,12 @@ DH_HD bool dh_dstar_is_terminator(uint32_t d0, uint32_t d1) {
 #define DH_DSTAR_BATCH 5          // data frames handled per round on the fast path (5 x 96 + 24 bits <= 512)
 
 DH_HD void dh_dstar_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
-    DhDecCtx c;
-    c.P = &P; c.T = &dh_lds_tables(S);
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = append ? P.out_count[ch] : 0u; c.nev = append && P.ev_count ? P.ev_count[ch] : 0u; c.overflow = false;      // (append: the second part of a split push, k_chain)
-    c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
     uint8_t* const lds_carry = reinterpret_cast<uint8_t*>(S.vit_dec);          // 1536 bytes, no K=5 Viterbi in this protocol
     static_assert(sizeof(S.vit_dec) >= DH_DSTAR_CARRY_MAX, "D-Star carry");
-    DhDstarScratch& X = *reinterpret_cast<DhDstarScratch*>(S.carry);
-    DhSymView syms; syms.carry = lds_carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
-    syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDstarScratch& X = *reinterpret_cast<DhDstarScratch*>(S.carry);           // (and no FEC tables: S.carry and what follows it is the header's scratch)
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, lds_carry, false, sym_base, append);
     const uint32_t total = syms.nc + syms.nfresh;
-    DH_FOR_LANES(lane) { for (uint32_t j = (uint32_t) lane; j < syms.nc; j += DH_WAVE) lds_carry[j] = carry_buf[j]; }
-    DH_BARRIER();
     uint32_t pos = 0, phase = s[DS_PHASE];
     DhBits128 bits;
 
@@ -2813,20 +2735,7 @@ DH_HD void dh_dstar_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, u
         if (c.overflow) break;
     }
 
-    const uint32_t rem = total - pos;
-    dh_view_ensure(syms, pos, rem < DH_DSTAR_CARRY_MAX ? rem : DH_DSTAR_CARRY_MAX);
-    DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < rem && j < DH_DSTAR_CARRY_MAX; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = c.nout;
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if ((c.overflow || rem > DH_DSTAR_CARRY_MAX) && P.overflow) *P.overflow = 1u;
-        }
-    }
-    s[DS_PHASE] = phase; s[DS_CONSUMED] = c.consumed;
-    s[DS_CARRY] = rem < DH_DSTAR_CARRY_MAX ? rem : DH_DSTAR_CARRY_MAX;
-    s.store(st_global);
-    DH_BARRIER();
+    dh_channel_close(c, s, syms, P, ch, pos, phase, dh_carry_max(DH_PROTO_DSTAR));
 }
 
 // =============================================================================================
@@ -2876,26 +2785,9 @@ DH_HD void dh_scan_distances(const DhPlanes& p, int start, uint32_t d[DH_SCAN_PA
 }
 
 DH_HD void dh_scan_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S) {
-    DhDecCtx c;
-    c.P = &P; c.T = nullptr;
-    uint32_t* const st_global = P.state + (size_t) ch * P.state_stride;
-    DhState s; s.load(st_global);
-    c.st = &s;
-    c.out = P.out + (size_t) ch * P.out_stride;
-    c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
-    c.nout = 0; c.nev = 0; c.overflow = false;
-    c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
-    uint8_t* const carry_buf = P.carry + (size_t) ch * P.carry_stride;
-    DhSymView syms; syms.carry = S.carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride;
-    syms.nfresh = P.sym_count[ch]; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
+    DhDecCtx c; DhState s; DhSymView syms;
+    dh_channel_open(c, s, syms, P, ch, S, S.carry, false, 0, false);
     const uint32_t total = syms.nc + syms.nfresh;
-    DH_FOR_LANES(lane) { for (uint32_t j = (uint32_t) lane; j < syms.nc; j += DH_WAVE) S.carry[j] = carry_buf[j]; }
-    DH_BARRIER();
     for (int id = 0; id < DH_SCAN_PATTERNS; id++)                      // (a zeroed state: no hit yet)
         if (s[DS_SC_STAT + 4 * id] == 0u) s[DS_SC_STAT + 4 * id + 3] = 255u;
     uint32_t pos = 0;
@@ -2951,18 +2843,10 @@ DH_HD void dh_scan_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S) {
         pos += adv; c.consumed = base + adv;
     }
 
-    const uint32_t rem = total - pos;                                  // < DH_SCAN_SPAN
-    dh_view_ensure(syms, pos, rem);
-    DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < rem; j += DH_WAVE) carry_buf[j] = (uint8_t) dh_view_at(syms, pos + j);
-        if (DH_IS_LANE0(lane)) {
-            P.out_count[ch] = (uint32_t) (DH_SCAN_PATTERNS * sizeof(dh_scan_stat));
-            if (P.ev_count) P.ev_count[ch] = c.nev;
-            if (c.overflow && P.overflow) *P.overflow = 1u;
-        }
-    }
-    s[DS_CONSUMED] = c.consumed; s[DS_CARRY] = rem;
-    s.store(st_global);
-    s.store_words(reinterpret_cast<uint32_t*>(c.out), DS_SC_STAT, DH_SCAN_PATTERNS * 4);      // the statistics row, rewritten by every push
+    // no phase (DS_PHASE stays as the reset left it); the output is the statistics row, rewritten by every push
+    c.nout = (uint32_t) (DH_SCAN_PATTERNS * sizeof(dh_scan_stat));
+    s[DS_CONSUMED] = c.consumed; s[DS_CARRY] = dh_channel_carry_out(c, syms, P, ch, pos, DH_SCAN_SPAN);      // (fewer than DH_SCAN_SPAN are left)
+    s.store(P.state + (size_t) ch * P.state_stride);
+    s.store_words(reinterpret_cast<uint32_t*>(c.out), DS_SC_STAT, DH_SCAN_PATTERNS * 4);
     DH_BARRIER();
 }

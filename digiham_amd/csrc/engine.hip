@@ -153,10 +153,7 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_c
 #ifdef DH_SKIP_DECODER                      // diagnostic builds (tools/phase_budget.sh): the slicer half alone (the hand-over of the tail split still takes place)
     if (!P.n_channels)
 #endif
-    if (PROTO == DH_PROTO_DMR) dh_dmr_channel(D, ch, S, sym_base, part != 0);
-    else if (PROTO == DH_PROTO_DSTAR) dh_dstar_channel(D, ch, S, sym_base, part != 0);
-    else if (PROTO == DH_PROTO_NXDN) dh_nxdn_channel(D, ch, S, sym_base, part != 0);
-    else dh_ysf_channel(D, ch, S, sym_base, part != 0);
+    dh_decode_channel(PROTO, D, ch, S, sym_base, part != 0);
     // (which part this is, and its flag word, worked out again: nothing of the hand-over stays live through the two halves)
     uint32_t part_end = 0, bid_end = blockIdx.x;
     DH_OPAQUE_SGPR(bid_end);

@@ -59,8 +59,8 @@ template <class Go> int dh_plan_rrc_tiles(uint32_t nz, bool fast, Go&& go) {
 }
 
 // The decoder of one channel; sym_base / append are the tail split's (POCSAG and the protocol scan are never chained and take neither).
-// k_chain keeps its own four-way switch and its own part bounds (below): stated through these functions the NXDN chain
-// kernels allocate registers differently, and the device code is not this header's to change.
+// k_chain calls it with its PROTO template constant, so the switch folds.  It keeps its own part bounds (below): stated through
+// these functions the NXDN chain kernels allocate registers differently, and the device code is not this header's to change.
 DH_HD void dh_decode_channel(int proto, const DhDecParams& D, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
     if (proto == DH_PROTO_DMR) dh_dmr_channel(D, ch, S, sym_base, append);
     else if (proto == DH_PROTO_DSTAR) dh_dstar_channel(D, ch, S, sym_base, append);

@@ -498,3 +498,58 @@ def test_reset_channel_resets_that_channel_only(ctx, kw):
         assert got["reset"][b] == got["continued"][b], b
     for kind in got["fresh"][2]:          # ... and the reset had something to undo in every kind of output
         assert got["fresh"][2][kind] != got["continued"][2][kind], kind
+
+
+DS_CARRY = 23                                   # decoder_core.hpp: word of the decoder state that holds the carry length
+
+
+def _carry_seam_stream(proto):
+    """(row, p0, L): a sync acquisition plus a few frames, the position p0 just behind a sync word from which on the decoder waits,
+    and the protocol's longest wait L (symbols it may leave unread: decoder_core.hpp, the `avail >` tests of the frame phases)."""
+    if proto == "dmr":                          # lead-in 37, bursts of 144 with the sync word at 66..89; p0 behind the second burst's
+        return synth.dmr_stream(61, 6, lead_in=37), 37 + 144 + 90, 144
+    if proto == "ysf":                          # lead-in 53, frames of 480 that open with the 20-dibit sync word
+        return synth.ysf_stream(63, 5, lead_in=53), 53 + 480 + 20, 480
+    if proto == "nxdn":                         # lead-in 29, frames of 192 that open with the 10-dibit sync word
+        return synth.nxdn_stream(65, 5, lead_in=29), 29 + 192 + 10, 192
+    if proto == "pocsag":                       # lead-in 37, 576 preamble bits, the 32-bit sync word, codewords of 32
+        return synth.pocsag_stream(67, 1, lead_in=37)[0], 37 + 576 + 32, 32
+    # D-Star: 41 noise bits, 64 bits of bit sync, the 15-bit frame sync -- then the header phase waits for MORE than 660 bits without
+    # consuming any: a cut b >= 1 bits into the header leaves a carry of b, past DH_SYM_CARRY_MAX (512) and up to the D-Star limit
+    rng = np.random.default_rng(69)
+    bits, _, _ = synth.dstar_transmission(rng, n_superframes=1)
+    return np.concatenate([rng.integers(0, 2, 41).astype(np.uint8), bits, rng.integers(0, 2, 60).astype(np.uint8)]), 41 + 64 + 15, 660
+
+
+@pytest.mark.parametrize("proto", ["dmr", "ysf", "nxdn", "pocsag", "dstar"])
+def test_carry_seam_at_every_carry_length(ctx, oracle, proto):
+    """A decoder leaves the symbols it could not use yet in the channel's carry row and finds them in front of the next push
+    (dh_channel_close / dh_channel_open).  L + 1 channels carry the same stream; channel b's first push ends b symbols behind a sync
+    word, its second push brings the rest.  Between them the channels leave every carry length a waiting decoder can leave, 1 .. L
+    (it waits for MORE than it needs, so it never leaves nothing; a carry of 0 is what every channel's first push opens with), and
+    every channel's frames and events are the oracle's for the whole stream."""
+    row, p0, L = _carry_seam_stream(proto)
+    n, B = len(row), L + 1
+    assert p0 + L < n
+    want_f, want_e = oracle.Decoder(proto).process(row)
+    assert len(want_f) > 0 and len(want_e) > 0
+    cuts = p0 + np.arange(B)
+    eng = api.Engine(B, n, rrc="none", demod="none", proto=proto, ctx=ctx)
+    first = np.ascontiguousarray(np.broadcast_to(row[:p0 + L], (B, p0 + L)))
+    rest = np.zeros((B, n - p0), np.uint8)
+    for b in range(B):
+        rest[b, :n - cuts[b]] = row[cuts[b]:]
+    got_f, got_e = [[] for _ in range(B)], [[] for _ in range(B)]
+    carried = None
+    for part, cnt in ((first, cuts), (rest, n - cuts)):
+        eng.push_symbols(part, cnt.astype(np.uint32))
+        f, fc = eng.frames(); e, ec = eng.events()
+        for b in range(B):
+            got_f[b].append(f[b, :fc[b]].copy()); got_e[b].append(e[b, :ec[b]].copy())
+        if carried is None:
+            carried = eng.debug_header(100 + DS_CARRY)
+    eng.close()
+    assert set(range(1, L + 1)) <= set(carried.tolist()) and carried.max() == L
+    for b in range(B):
+        assert np.concatenate(got_f[b]).tobytes() == want_f.tobytes(), b
+        assert np.concatenate(got_e[b]).tobytes() == want_e.tobytes(), b

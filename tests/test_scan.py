@@ -258,6 +258,38 @@ def test_cut_invariance(ctx):
         assert st[b].tobytes() == st1[b].tobytes() == want[b][1].tobytes(), b
 
 
+def test_carry_seam_at_every_carry_length(ctx):
+    """The scan keeps the symbols whose position could not be examined yet in the channel's carry row (dh_channel_carry_out /
+    dh_channel_open): fewer than SPAN of them.  SPAN + 1 channels carry the same row, which opens with a sync word; channel b's first
+    push ends b symbols into it, its second push brings the rest.  Between them the channels leave every carry length the scan can
+    leave, 0 .. SPAN - 1, and every channel's events and statistics are the model's for the whole row."""
+    rows, _ = _cut_rows()
+    row = rows[0].copy()
+    plant(row, 0, PATTERNS[8])
+    want_ev, want_st = model(row)
+    B = SPAN + 1
+    cuts = np.arange(B)
+    eng = api.Engine(B, T, rrc="none", demod="none", proto="scan", ctx=ctx)
+    rest = np.zeros((B, T), np.uint8)
+    for b in range(B):
+        rest[b, :T - b] = row[b:]
+    evs = [[] for _ in range(B)]
+    eng.push_symbols(np.ascontiguousarray(np.broadcast_to(row[:SPAN], (B, SPAN))), cuts.astype(np.uint32))
+    e, ec = eng.events()
+    carried = eng.debug_header(100 + 23)                  # DS_CARRY (decoder_core.hpp)
+    for b in range(B):
+        evs[b].append(e[b, :ec[b]].copy())
+    eng.push_symbols(rest, (T - cuts).astype(np.uint32))
+    e, ec = eng.events()
+    st = read_stats(eng)
+    eng.close()
+    assert carried.tolist() == [min(b, SPAN - 1) for b in range(B)]
+    for b in range(B):
+        evs[b].append(e[b, :ec[b]].copy())
+        assert cat(evs[b]).tobytes() == want_ev.tobytes(), b
+        assert st[b].tobytes() == want_st.tobytes(), b
+
+
 def test_empty_push_and_no_events(ctx):
     rows, _ = _cut_rows()
     want = [model(r) for r in rows]
