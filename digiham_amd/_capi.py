@@ -31,7 +31,7 @@ class ChannelizerConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
                 ("taps", C.POINTER(C.c_float)), ("n_taps", C.c_uint32), ("increments", C.POINTER(C.c_uint32)),
                 ("input_format", C.c_int32), ("output_mode", C.c_int32), ("dcblock", C.c_int32), ("max_input", C.c_uint32),
-                ("stream", C.c_void_p), ("interpolation", C.c_uint32)]
+                ("stream", C.c_void_p), ("interpolation", C.c_uint32), ("raster", C.c_uint32), ("bins", C.POINTER(C.c_int32))]
 
 
 class ChannelizerPowerConfig(C.Structure):
@@ -84,6 +84,14 @@ PREROLL_NONE = 0xFFFFFFFFFFFFFFFF          # DH_PREROLL_NONE
 SCAN_PATTERNS = ("dmr_bs_data", "dmr_bs_voice", "dmr_ms_data", "dmr_ms_voice", "ysf", "nxdn", "dstar_header", "dstar_voice", "pocsag")
 SCAN_STAT_DTYPE = [("hits", "<u4"), ("periodic", "<u4"), ("last_sym", "<u4"), ("best_dist", "u1"), ("pad", "u1", (3,))]
 EV_SCAN_HIT = 80
+
+
+class _ChannelizerConfigV2(C.Structure):    # dh_channelizer_config when it ended with interpolation
+    _fields_ = ChannelizerConfig._fields_[:-2]
+
+
+# what a caller built against that header passes as struct_size: its tail padding (where raster now sits) included
+CHANNELIZER_CONFIG_V2_SIZE = C.sizeof(_ChannelizerConfigV2)
 
 CZ_INPUT = {"cs16": 1, "cf32": 2}
 CZ_OUTPUT = {"iq": 1, "fm": 2}

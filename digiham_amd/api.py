@@ -1075,6 +1075,7 @@ def nco_increment(offset_hz, input_rate):
 
 
 CZ_MAX_INTERPOLATION, CZ_MAX_DECIMATION = 64, 1024
+CZ_MAX_RASTER = 16384
 
 
 def resample_ratio(input_rate, output_rate=48000.0):
@@ -1090,6 +1091,31 @@ def resample_ratio(input_rate, output_rate=48000.0):
     return L, M
 
 
+def raster_steps(input_rate, raster_hz):
+    """K = input_rate / raster_hz of a uniform raster: an integer within 1e-9 relative, in 2 .. 16384, else ValueError."""
+    k = float(input_rate) / float(raster_hz)
+    K = int(round(k))
+    if K < 1 or abs(k - K) > 1e-9 * K:
+        raise ValueError("raster: input_rate / raster_hz = %.12g is no integer" % k)
+    if not 2 <= K <= CZ_MAX_RASTER:
+        raise ValueError("raster: input_rate / raster_hz = %d steps, outside 2 .. %d" % (K, CZ_MAX_RASTER))
+    return K
+
+
+def raster_bins(freqs_hz, input_rate, raster_hz):
+    """int32 bins of channels on a uniform raster: freqs_hz[b] = bins[b] * raster_hz, each within 1e-9 relative (of the
+    raster step for bin 0), else ValueError naming the channel.  What Channelizer(raster_hz=...) passes as `bins`."""
+    raster_steps(input_rate, raster_hz)
+    bins = np.zeros(len(freqs_hz), np.int32)
+    for b, f in enumerate(freqs_hz):
+        q = float(f) / float(raster_hz)
+        n = int(round(q))
+        if abs(q - n) > 1e-9 * max(abs(n), 1) or abs(n) >= 1 << 31:
+            raise ValueError("raster: channel %d at %.12g Hz is no multiple of the %.12g Hz raster" % (b, float(f), float(raster_hz)))
+        bins[b] = n
+    return bins
+
+
 class Channelizer(_Handle):
     """One wideband complex stream -> one row per channel at input_rate * interpolation / decimation (dh_channelizer; the
     arithmetic is specified in digiham_amd/csrc/channelizer_core.hpp).  interpolation is 1 unless the capture rate is no
@@ -1098,21 +1124,31 @@ class Channelizer(_Handle):
     complex64); output "fm" (discriminator audio for Engine.push, optionally DC-blocked) or "iq" (complex rows).
     push(x) returns (rows, n_out): rows is the channelizer's own device array [B][max_input * L // D + 1] (x 2 for "iq"),
     valid in [:, :n_out] until the next push.
+    raster_hz: every channel sits on a multiple of raster_hz and input_rate / raster_hz is an integer K (12.5 kHz steps of a
+    2.4 MS/s capture: K = 192).  All channels then share one polyphase fold of `taps` and differ in a K-point DFT -- the
+    same bank for about n_taps / K times less matrix work; needs interpolation = 1.  Without it (the general case) each
+    channel may sit anywhere.
     enable_power(...) adds per-channel block power and a squelch gate: after every push `counts` (device uint32 [B]) is what
     Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed."""
     _kind = "dh_channelizer"
 
     def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
-                 ctx=None, device=0, interpolation=1):
+                 ctx=None, device=0, interpolation=1, raster_hz=None):
         self.rate, self.D, self.B = float(input_rate), int(decimation), len(freqs_hz)
         self.L = max(int(interpolation), 1)
         self.input, self.output = input, output
+        self.raster_hz = None if raster_hz is None else float(raster_hz)
         t = np.ascontiguousarray(taps, np.float32).ravel()
-        inc = np.array([nco_increment(f, input_rate) for f in freqs_hz], np.uint32)
+        if raster_hz is None:
+            inc = np.array([nco_increment(f, input_rate) for f in freqs_hz], np.uint32)
+            where = dict(increments=inc.ctypes.data_as(C.POINTER(C.c_uint32)))
+        else:                         # increments stays NULL: the library does not read it on a raster
+            bins = raster_bins(freqs_hz, input_rate, raster_hz)
+            where = dict(raster=raster_steps(input_rate, raster_hz), bins=bins.ctypes.data_as(C.POINTER(C.c_int32)))
         self._open(ctx, device, _capi.ChannelizerConfig, n_channels=self.B, decimation=self.D, taps=t.ctypes.data_as(C.POINTER(C.c_float)),
-                   n_taps=len(t), increments=inc.ctypes.data_as(C.POINTER(C.c_uint32)), input_format=_capi.CZ_INPUT[input],
+                   n_taps=len(t), input_format=_capi.CZ_INPUT[input],
                    output_mode=_capi.CZ_OUTPUT[output], dcblock=int(bool(dcblock) and output == "fm"), max_input=int(max_input),
-                   interpolation=int(interpolation))
+                   interpolation=int(interpolation), **where)
         mem = self.ctx.mem
         self.max_input = int(max_input)
         self.out_stride = self.max_input * self.L // self.D + 1
@@ -1152,7 +1188,14 @@ class Channelizer(_Handle):
         self._call("dh_channelizer_reset")
 
     def retune(self, ch, hz):
-        self._call("dh_channelizer_retune", int(ch), nco_increment(hz, self.rate))
+        if self.raster_hz is not None:
+            try:
+                v = int(raster_bins([hz], self.rate, self.raster_hz)[0]) & 0xFFFFFFFF
+            except ValueError:
+                raise ValueError("raster: channel %d at %.12g Hz is no multiple of the %.12g Hz raster" % (ch, float(hz), self.raster_hz)) from None
+        else:
+            v = nco_increment(hz, self.rate)
+        self._call("dh_channelizer_retune", int(ch), v)
 
     def push(self, x):
         """x: numpy (host) or a device array: int16 [n][2] / [2 n] for "cs16", float32 [n][2] / [2 n] or complex64 [n] for

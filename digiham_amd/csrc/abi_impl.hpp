@@ -23,6 +23,7 @@
 //   int  dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream);
 // and the launches of the four later handles, each listed at the head of its section below:
 //   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_gemm_rat / dh_be_cz_fm / dh_be_cz_power      the channelizer
+//   dh_be_cz_fold / dh_be_cz_gemm_raster                                                   ... in raster mode
 //   dh_be_preroll_append / dh_be_preroll_gather                                            the pre-roll ring
 //   dh_be_outpack_scan / dh_be_outpack_copy                                                the packed read-out
 //   dh_be_monitor_open / dh_be_monitor_assign, dh_be_reset_channels                        the band monitor, the masked reset
@@ -257,12 +258,15 @@ int dh_engine_sync(dh_engine* e) {
 //   dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream);
 //   dh_be_cz_gemm(const DhCzParams& P, void* stream);
 //   dh_be_cz_gemm_rat(const DhCzRatParams& R, void* stream);      (interpolation L > 1: one converter bank per phase)
+//   dh_be_cz_fold(const DhCzFoldParams& F, void* stream);         (raster: the polyphase fold of one slab of output instants)
+//   dh_be_cz_gemm_raster(const DhCzRasterParams& R, void* stream);         (... and its DFT + rotation)
 //   dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream);
 //   dh_be_cz_power(const DhCzPowerParams& P, void* stream);      (only with power enabled: block power, then the gate and the counts)
 // (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
-// window is the last H = T' - 1 samples of the previous one followed by the new samples.
+// window is the last H = T' - 1 samples (raster: P K - 1) of the previous one followed by the new samples.
 struct dh_channelizer : dh_state {                      // (clear() and retune() act on what init() and power_enable() declare)
     uint32_t B = 0, D = 0, L = 1, tpad = 0, ncols = 0, max_input = 0;      // rate = input L / D
+    uint32_t hist = 0;                                  // H: T' - 1, or P K - 1 on a raster
     int cf32 = 0, fm = 0, dcblock = 0;
     std::vector<float> taps;                            // [L][T']: the phases h_p of h, each zero-padded to T'
     std::vector<uint32_t> inc;
@@ -278,6 +282,17 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
     uint64_t n0 = 0;                                    // samples pushed since create / reset
     DhCzRatParams rat{};                                // rat.g: what init() fixes; a push adds its window, its output rows and its
                                                         // position (L = 1), or its slots (L > 1)
+    // uniform raster (K != 0; tpad = K', taps = h padded to P K, bmat = one bank built from G): the fold buffer and what the
+    // rotation reads; K = 0: nothing of it is allocated or launched
+    uint32_t K = 0;
+    std::vector<uint32_t> cbin;                         // [B] c_b
+    float* d_taps = nullptr;                            // [P K]
+    float* d_fold = nullptr;                            // [slab_rows][K'][2]
+    uint32_t* d_cbin = nullptr;                         // [B]
+    uint32_t* d_phi = nullptr;                          // [K] Phi(q)
+    uint32_t slab_rows = 0;
+    DhCzFoldParams fold{};
+    DhCzRasterParams ras{};
     // block power and gate (dh_channelizer_power_enable); pw.L = 0: off, nothing allocated and nothing launched
     DhCzPowerParams pw{};                               // what power_enable() and set_squelch() fix; a push adds its outputs and its position
     uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
@@ -290,8 +305,77 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
         return bufs.zero_all() ? DH_EDEVICE : DH_OK;
     }
-    int init(const dh_channelizer_config& c, uint32_t interp) {
+    // raster mode: the B operand is one bank [2 K'][ncols] of G, the windows hold H = P K - 1, one fold slab
+    int init_raster(const dh_channelizer_config& c) {
+        B = c.n_channels; D = c.decimation; L = 1; K = c.raster; tpad = dh_cz_tpad(K); ncols = dh_cz_ncols(B); max_input = c.max_input;
+        cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
+        const uint32_t P = (c.n_taps + K - 1u) / K;
+        hist = P * K - 1u; slab_rows = dh_cz_fold_slab_rows(tpad);
+        taps.assign((size_t) P * K, 0.0f);
+        std::copy(c.taps, c.taps + c.n_taps, taps.begin());
+        cbin.resize(B);
+        for (uint32_t b = 0; b < B; b++) cbin[b] = dh_cz_raster_bin(c.bins[b], K);
+        const size_t bm = bank(), win = 2 * ((size_t) hist + max_input);
+        bool ok = bufs.alloc(d_tables, 4 * 4096);
+        ok &= bufs.alloc(d_cbin, B);
+        ok &= bufs.alloc(d_phi, K);
+        ok &= bufs.alloc(d_taps, taps.size());
+        ok &= bufs.alloc(d_bmat, bm);
+        ok &= bufs.alloc(d_win[0], win, dh::ZERO_ON_RESET);
+        ok &= bufs.alloc(d_win[1], win, dh::ZERO_ON_RESET);
+        ok &= bufs.alloc(d_fold, (size_t) 2 * slab_rows * tpad);
+        ok &= bufs.alloc(d_state, (size_t) DH_CZ_STATE_WORDS * B, dh::ZERO_PER_CHANNEL);
+        if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) outputs(max_input) + 1) * B);
+        ok &= bufs.alloc(d_stage, in_bytes() * max_input);
+        if (!ok) return DH_ENOMEM;
+        DhCzParams& g = ras.g;
+        g.win = d_fold; g.bmat = d_bmat; g.coarse = d_tables; g.fine = d_tables + 8192; g.zbuf = d_zbuf;
+        g.D = D; g.tpad = tpad; g.B = B; g.ncols = ncols; g.fm = fm;
+        ras.cbin = d_cbin; ras.phi = d_phi; ras.K = K;
+        fold.h = d_taps; fold.fold = d_fold; fold.K = K; fold.kpad = tpad; fold.P = P; fold.D = D;
+        std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
+        for (uint32_t b = 0; b < B; b++) {
+            dh_cz_raster_columns(K, tpad, cbin[b], re.data(), im.data());
+            const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
+            for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bmat[r * ncols + cr] = re[r]; bmat[r * ncols + ci] = im[r]; }
+        }
+        std::vector<uint32_t> phi(K);
+        for (uint32_t q = 0; q < K; q++) phi[q] = dh_cz_raster_phi(q, K);
+        if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_cbin, cbin.data(), sizeof(uint32_t) * B) ||
+            be.upload(d_phi, phi.data(), sizeof(uint32_t) * K) || be.upload(d_taps, taps.data(), sizeof(float) * taps.size()) ||
+            be.upload(d_bmat, bmat.data(), sizeof(float) * bm)) return DH_EDEVICE;
+        const int rc = clear();
+        if (rc != DH_OK) return rc;
+        return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    // raster: v is the new bin, a two's-complement int32
+    int retune_raster(uint32_t ch, uint32_t v) {
+        std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
+        cbin[ch] = dh_cz_raster_bin((int32_t) v, K);
+        dh_cz_raster_columns(K, tpad, cbin[ch], re.data(), im.data());
+        const size_t pitch = sizeof(float) * ncols;
+        if (be.upload2d(d_bmat + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
+            be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
+            be.upload(d_cbin + ch, &cbin[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B)) return DH_EDEVICE;
+        return be.sync() ? DH_EDEVICE : DH_OK;
+    }
+    // raster: the push's no outputs slab by slab -- fold, then DFT + rotation
+    int push_raster(const float* w, size_t n_in, float* out, size_t out_stride, uint32_t no) {
+        fold.win = w; fold.win_n = (uint32_t) (hist + n_in);
+        ras.g.out = out; ras.g.out_stride = out_stride;
+        ras.m0 = (uint32_t) ((outputs(n0) * D + (D - 1u)) % K);
+        const uint32_t wj = hist + (uint32_t) (D - 1 - n0 % D);        // window index of x[n_j] of the push's first row
+        for (uint32_t row = 0; row < no; row += slab_rows) {
+            fold.wj0 = wj + row * D; fold.nrows = std::min(slab_rows, no - row);
+            ras.row0 = row; ras.g.n_out = fold.nrows;
+            if (dh_be_cz_fold(fold, stream) || dh_be_cz_gemm_raster(ras, stream)) return DH_EDEVICE;
+        }
+        return DH_OK;
+    }
+    int init(const dh_channelizer_config& c, uint32_t interp, uint32_t raster) {
+        if (raster) return init_raster(c);
         B = c.n_channels; D = c.decimation; L = interp; tpad = dh_cz_tpad_rat(c.n_taps, L); ncols = dh_cz_ncols(B); max_input = c.max_input;
+        hist = tpad - 1u;
         cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
         taps.assign((size_t) L * tpad, 0.0f);
         for (uint32_t p = 0; p < L; p++) {
@@ -326,6 +410,7 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         return be.sync() ? DH_EDEVICE : DH_OK;           // (the host copies above are released on return)
     }
     int retune(uint32_t ch, uint32_t u) {
+        if (K) return retune_raster(ch, u);
         std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
         inc[ch] = u;
         const size_t pitch = sizeof(float) * ncols;
@@ -380,10 +465,13 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
             src = d_stage;
         }
         float* w = d_win[cur];
-        if (dh_be_cz_window(w, d_win[cur ^ 1], prev_n, src, cf32, tpad - 1, n_in, stream)) return DH_EDEVICE;
+        if (dh_be_cz_window(w, d_win[cur ^ 1], prev_n, src, cf32, hist, n_in, stream)) return DH_EDEVICE;
         if (no) {
             rat.g.win = w; rat.g.out = out; rat.g.out_stride = out_stride;
-            if (L == 1) {
+            if (K) {
+                const int rc = push_raster(w, n_in, out, out_stride, (uint32_t) no);
+                if (rc != DH_OK) return rc;
+            } else if (L == 1) {
                 rat.g.j0 = j0; rat.g.off0 = (uint32_t) (D - 1 - n0 % D); rat.g.n_out = (uint32_t) no;
                 if (dh_be_cz_gemm(rat.g, stream)) return DH_EDEVICE;
             } else {
@@ -409,15 +497,24 @@ int dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out
     // interpolation was appended to the struct: a caller built against the older header passes the older size and means L = 1
     const bool has_interp = c.struct_size >= offsetof(dh_channelizer_config, interpolation) + sizeof(c.interpolation);
     const uint32_t L = has_interp && c.interpolation ? c.interpolation : 1u;
+    // raster and bins were appended after it.  raster sits in what was the older struct's tail padding, which that struct's
+    // size covers and its callers never wrote, so raster is read only from a struct_size that covers bins as well: every
+    // smaller size, or raster = 0, is the fixed-offset bank
+    const bool has_raster = c.struct_size >= offsetof(dh_channelizer_config, bins) + sizeof(c.bins);
+    const uint32_t K = has_raster ? c.raster : 0u;
     if (c.struct_size < offsetof(dh_channelizer_config, interpolation) || c.decimation < 1 || c.decimation > 1024 ||
-        L > DH_CZ_MAX_L || L > c.decimation || std::gcd(L, c.decimation) != 1u || c.n_taps < 1 || c.n_taps > 16384u * L ||
-        c.n_channels < 1 || c.n_channels > 65536 || c.max_input < 1 || c.max_input > (1u << 28) || !c.taps || !c.increments ||
+        L > DH_CZ_MAX_L || L > c.decimation || std::gcd(L, c.decimation) != 1u || c.n_taps < 1 ||
+        c.n_channels < 1 || c.n_channels > 65536 || c.max_input < 1 || c.max_input > (1u << 28) || !c.taps ||
         (c.input_format != DH_CZ_CS16 && c.input_format != DH_CZ_CF32) || (c.output_mode != DH_CZ_IQ_F32 && c.output_mode != DH_CZ_FM) ||
         (c.dcblock && c.output_mode != DH_CZ_FM))
         return DH_EINVAL;
+    if (K ? !c.bins || K < 2 || K > DH_CZ_MAX_RASTER || L != 1u ||
+            c.n_taps > (uint64_t) DH_CZ_MAX_FOLD_P * K || c.n_taps > DH_CZ_MAX_RASTER_TAPS
+          : c.n_taps > 16384u * L || !c.increments)
+        return DH_EINVAL;
     for (uint32_t k = 0; k < c.n_taps; k++)
         if (!(c.taps[k] - c.taps[k] == 0.0f)) return DH_EINVAL;        // finite taps only
-    return dh_create(c, out, [&](dh_channelizer& z) { return z.init(c, L); });
+    return dh_create(c, out, [&](dh_channelizer& z) { return z.init(c, L, K); });
 }
 void dh_channelizer_destroy(dh_channelizer* z) { dh_destroy(z); }
 

@@ -54,6 +54,38 @@
 //             of its own: DhCzPhase has its row count, the window index of its first row and that row's n_j.  A GEMM
 //             workgroup tile belongs to one slot (k_cz_gemm_rat; host body dh_cz_output_rat).
 //
+// ---- Uniform raster (raster = K != 0): every channel on a multiple of input_rate / K, so all channels share ONE polyphase
+// fold of the prototype and differ only in a K-point DFT.  The specification; tests/cz_raster_restate.c restates it from this
+// text alone.  Everything not mentioned is as at the top (input formats, P(phi), FM, dcblock, the power blocks / gate /
+// counts in terms of the output index j, denormals kept, reset). ----
+//   Raster    K = raster, 2 <= K <= 16384.  Channel b sits at bins[b] * input_rate / K; c_b = bins[b] mod K reduced into
+//             [0, K).  Any subset of bins, in any order, with duplicates; B <= 65536 as above.
+//   Phase     for 0 <= q < K:  Phi(q) = (uint32) ((((uint64) q << 32) + K / 2) / K)   (integer division).  Phasors are
+//             P(Phi(q)) of the tables above.  A phase is always formed as (c * m) mod K in integer arithmetic and then
+//             mapped through Phi, never by multiplying a rounded increment: the fold relies on exact K-periodicity.
+//   Prototype h[0..T) zero-padded to P K, P = ceil(T / K); 1 <= T <= 64 K and T <= 2^20.  The history is H = P K - 1 input
+//             samples, x[n < 0] = 0.
+//   Output j  at n_j = j D + D - 1, exactly as at the top; a push yields the D-blocks it completes and the results do not
+//             depend on how the stream is cut into pushes.
+//   Fold      for r = 0 .. K-1 two chains over p = 0 .. P-1 in increasing p from +0, all P terms added, the padded ones too:
+//               vr = fma(h[r + p K], xr, vr)      vi = fma(h[r + p K], xi, vi)      with x = x[n_j - r - p K]
+//             v is zero-padded to K' = 16 ceil(K / 16).
+//   DFT       G_b[r] = P(Phi((c_b r) mod K)) for r < K and 0 for K <= r < K'.  The two chains of the top over r = 0 .. K'-1
+//             from +0, the padded terms added:
+//               yr = fma(vi, -Gi, fma(vr, Gr, yr))      yi = fma(vi, Gr, fma(vr, Gi, yi))
+//             -- the k-ordered chain that v_mfma_f32_16x16x4_f32 computes, with v in the place of x and K' in that of T'.
+//   Rotation  z = P(Phi((K - (c_b (n_j mod K)) mod K) mod K)) (x) y, products rounded, then the sum, as at the top.  n_j is
+//             taken from the 64-bit stream position, not modulo 2^32.
+//   Retune    of channel b gives it a new bin (dh_channelizer_retune's value read as a two's-complement int32) and
+//             recomputes its column of G; it zeroes what a retune zeroes at the top; the input history is untouched.
+//   Not with  interpolation > 1: DH_EINVAL.
+//   Work      (1) the window with H = P K - 1; then per slab of at most DH_CZ_FOLD_SLAB_BYTES of folded rows (a multiple of
+//             the GEMM's 128-row tile): (2a) dh_cz_fold_item, one (output instant, r) per lane -- row i of the slab keeps
+//             v[r] at fold[i K' + K' - 1 - r], so that (2b) the GEMM tile of the top, reading "the window" at
+//             (K' - 1) + i K' - k against the B operand [2 K'][ncols] built from G, computes the DFT chains unchanged
+//             (k_cz_gemm_raster; host body dh_cz_output_raster) and dh_cz_emit_raster rotates.  FM, tail and power then
+//             run once over the push.
+//
 // ---- Block power and the squelch gate (optional; dh_channelizer_power_enable).  The specification; tests/cz_power_restate.c
 // restates it from this text alone. ----
 //   Blocks    enabled once per channelizer with a block length L, 1 <= L <= 65536 outputs (L = 480: 10 ms at 48 kS/s).  j is
@@ -93,7 +125,7 @@
 // Work per push (host code in abi_impl.hpp): (1) dh_cz_window_item -- the window [H = T'-1 history samples ++ the new ones]
 // as complex floats; (2) the GEMM + rotation, tiled over 128 output instants x 64 channels (k_cz_gemm; host body
 // dh_cz_output); FM mode then (3) dh_cz_fm_item, one output per lane, and (4) dh_cz_tail_channel, one channel per lane:
-// the DC blocker's recurrence and the carried z[j-1].
+// the DC blocker's recurrence and the carried z[j-1].  On a uniform raster (2) is the fold and the DFT, slab by slab (above).
 #pragma once
 
 #include <math.h>
@@ -107,6 +139,13 @@
 #define DH_CZ_STATE_WORDS 4       // per channel: z[j-1] (re, im), x_prev, y_prev of the DC blocker
 #define DH_CZ_PSTATE_WORDS 4      // per channel, only with power enabled (an array of its own): S (float bits), open, quiet, S of this push
 #define DH_CZ_MAX_L 64            // interpolation: phases of a rational rate
+#define DH_CZ_MAX_RASTER 16384    // raster: K, the steps per input rate
+#define DH_CZ_MAX_FOLD_P 64       // raster: T <= 64 K ...
+#define DH_CZ_MAX_RASTER_TAPS (1u << 20)       // ... and T <= 2^20
+#define DH_CZ_FOLD_SLAB_BYTES (32u << 20)      // raster: the fold buffer, whatever max_input is
+#define DH_CZ_FOLD_ROWS 16        // output instants per k_cz_fold workgroup (one accumulator pair each, per lane)
+#define DH_CZ_FOLD_LANES 256      // ... and its r extent, one r per lane
+#define DH_CZ_FOLD_LDS 6144       // complex samples of input span it stages at a time (48 KB)
 
 // Column of the real GEMM for channel b, component c (0: the real output, 1: the imaginary one).  Sixteen channels' real
 // columns, then their sixteen imaginary ones: a 16 x 16 MFMA tile holds one component of sixteen channels, and the lane
@@ -204,6 +243,63 @@ DH_HD void dh_cz_output_rat(const DhCzRatParams& R, uint32_t s, uint32_t i, uint
     float yr, yi;
     dh_cz_chains(R.g, dh_cz_bank(R.g, ph.bank), ph.wbase + i * R.g.D, b, yr, yi);
     dh_cz_emit_at(R.g, s + R.L * i, b, ph.nj0 + i * R.g.D, yr, yi);
+}
+
+// ---- uniform raster: the fold, the DFT's B operand, the rotation (the header comment) -------------------------------------
+DH_HD uint32_t dh_cz_raster_phi(uint32_t q, uint32_t K) { return (uint32_t) ((((uint64_t) q << 32) + K / 2u) / K); }
+DH_HD uint32_t dh_cz_raster_bin(int32_t bin, uint32_t K) { const int32_t m = bin % (int32_t) K; return (uint32_t) (m < 0 ? m + (int32_t) K : m); }
+// rows of folded v one slab holds: a multiple of the GEMM's row tile, at least one tile (K' = 16384: 16 MiB)
+DH_HD uint32_t dh_cz_fold_slab_rows(uint32_t kpad) {
+    const uint32_t rows = DH_CZ_FOLD_SLAB_BYTES / (8u * kpad) / DH_CZ_TM * DH_CZ_TM;
+    return rows ? rows : (uint32_t) DH_CZ_TM;
+}
+
+struct DhCzFoldParams {
+    const float* win;             // [H + n_in][2], H = P K - 1
+    const float* h;               // [P K] the prototype, zero-padded
+    float* fold;                  // [slab rows][K'][2]: row i's v[r] at i K' + K' - 1 - r
+    uint32_t K, kpad, P, D;
+    uint32_t wj0;                 // window index of x[n_j] of the slab's first row
+    uint32_t nrows;               // rows of this slab
+    uint32_t win_n;               // H + n_in
+};
+// the two fold chains of (row, r) of a slab, r < K'; the padding K <= r < K' is written as zeros
+DH_HD void dh_cz_fold_item(const DhCzFoldParams& F, uint32_t row, uint32_t r) {
+    float vr = 0.0f, vi = 0.0f;
+    if (r < F.K) {
+        const float* x = F.win + 2 * ((size_t) F.wj0 + (size_t) row * F.D - r);
+        for (uint32_t p = 0; p < F.P; p++, x -= 2 * (size_t) F.K) {
+            const float hv = F.h[r + (size_t) p * F.K];
+            vr = __builtin_fmaf(hv, x[0], vr); vi = __builtin_fmaf(hv, x[1], vi);
+        }
+    }
+    float* q = F.fold + 2 * ((size_t) row * F.kpad + (F.kpad - 1u - r));
+    q[0] = vr; q[1] = vi;
+}
+
+struct DhCzRasterParams {
+    DhCzParams g;                 // win = the fold buffer, tpad = K', n_out = the slab's rows; inc, j0 and off0 unused
+    const uint32_t* cbin;         // [B] c_b
+    const uint32_t* phi;          // [K] Phi(q)
+    uint32_t K;
+    uint32_t row0;                // push row of the slab's first row
+    uint32_t m0;                  // n_j mod K of the PUSH's first row (host, from the 64-bit position)
+};
+// the rotation and the store of slab row i of channel b
+DH_HD void dh_cz_emit_raster(const DhCzRasterParams& R, uint32_t i, uint32_t b, float yr, float yi) {
+    const uint32_t row = R.row0 + i, m = (R.m0 + row * R.g.D) % R.K, t = (R.cbin[b] * m) % R.K;
+    float pr, pi;
+    dh_cz_phasor(R.phi[t ? R.K - t : 0u], R.g.coarse, R.g.fine, pr, pi);
+    const float a = pr * yr, c = pi * yi, d = pr * yi, e = pi * yr;
+    const float zr = a - c, zi = d + e;
+    float* q = R.g.fm ? R.g.zbuf + 2 * ((size_t) row * R.g.B + b) : R.g.out + 2 * ((size_t) b * R.g.out_stride + row);
+    q[0] = zr; q[1] = zi;
+}
+// Host body of the raster GEMM: slab row i
+DH_HD void dh_cz_output_raster(const DhCzRasterParams& R, uint32_t i, uint32_t b) {
+    float yr, yi;
+    dh_cz_chains(R.g, R.g.bmat, i * R.g.tpad + (R.g.tpad - 1u), b, yr, yi);
+    dh_cz_emit_raster(R, i, b, yr, yi);
 }
 
 // element e of this push's window: the last H samples of the previous window, then the new samples converted
@@ -360,6 +456,17 @@ inline void dh_cz_columns(const float* h, uint32_t tpad, uint32_t u, float* re_c
     }
 }
 
+// raster: the two GEMM columns of the channel on bin c (0 <= c < K): re_col / im_col [2 K'] (rows 2r, 2r + 1), G zero beyond K
+inline void dh_cz_raster_columns(uint32_t K, uint32_t kpad, uint32_t c, float* re_col, float* im_col) {
+    const float* t = dh_cz_host_tables();
+    for (uint32_t r = 0; r < kpad; r++) {
+        float gr = 0.0f, gi = 0.0f;
+        if (r < K) dh_cz_phasor(dh_cz_raster_phi((uint32_t) (((uint64_t) c * r) % K), K), t, t + 8192, gr, gi);
+        re_col[2 * r] = gr; re_col[2 * r + 1] = -gi;
+        im_col[2 * r] = gi; im_col[2 * r + 1] = gr;
+    }
+}
+
 #if !DH_DEVICE_BUILD
 // ---- host backends of the CPU test harness (engine.hip defines the gfx950 ones) --------------------------------------
 static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void*) {
@@ -375,6 +482,16 @@ static int dh_be_cz_gemm_rat(const DhCzRatParams& R, void*) {
     for (uint32_t s = 0; s < R.nslots; s++)
         for (uint32_t b = 0; b < R.g.B; b++)
             for (uint32_t i = 0; i < R.ph[s].count; i++) dh_cz_output_rat(R, s, i, b);
+    return 0;
+}
+static int dh_be_cz_fold(const DhCzFoldParams& F, void*) {
+    for (uint32_t row = 0; row < F.nrows; row++)
+        for (uint32_t r = 0; r < F.kpad; r++) dh_cz_fold_item(F, row, r);
+    return 0;
+}
+static int dh_be_cz_gemm_raster(const DhCzRasterParams& R, void*) {
+    for (uint32_t b = 0; b < R.g.B; b++)
+        for (uint32_t i = 0; i < R.g.n_out; i++) dh_cz_output_raster(R, i, b);
     return 0;
 }
 static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void*) {

@@ -892,8 +892,8 @@ __global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev
 //   D lane (n, g = l >> 4), register r = (row 4 g + r, col n).  Column tile 2 c holds sixteen channels' real parts and tile
 //   2 c + 1 their imaginary parts (dh_cz_col), so each lane rotates and stores its own outputs.
 // One tile of a decimating converter bank: rows row0 .. row0 + 127 of nrows, row i reading the window at wbase + i step - k
-// against the B operand bmat; emit(i, b, yr, yi) gets each finished pair of chains.  k_cz_gemm (L = 1) and k_cz_gemm_rat (one
-// phase of a rational rate) are its two instantiations.
+// against the B operand bmat; emit(i, b, yr, yi) gets each finished pair of chains.  k_cz_gemm (L = 1), k_cz_gemm_rat (one
+// phase of a rational rate) and k_cz_gemm_raster (the DFT over folded rows) are its three instantiations.
 #define DH_CZ_AS 36
 #define DH_CZ_BS 144
 template <class Emit>
@@ -988,6 +988,77 @@ __global__ __launch_bounds__(256) void k_cz_gemm_rat(const DhCzRatParams R) {
     if (row0 >= ph.count) return;
     dh_cz_gemm_tile(R.g, dh_cz_bank(R.g, ph.bank), ph.wbase, R.g.D, row0, ph.count,
                     [&](uint32_t i, uint32_t b, float yr, float yi) { dh_cz_emit_at(R.g, s + R.L * i, b, ph.nj0 + i * R.g.D, yr, yi); });
+}
+
+// Uniform raster (channelizer_core.hpp): the DFT stage is the tile above with the folded rows in the window's place -- row i's
+// v[r] at i K' + K' - 1 - r, so wbase = K' - 1, step = K' and tpad = K' make it the specification's chain over r.
+__global__ __launch_bounds__(256) void k_cz_gemm_raster(const DhCzRasterParams R) {
+    dh_cz_gemm_tile(R.g, R.g.bmat, R.g.tpad - 1u, R.g.tpad, blockIdx.x * DH_CZ_TM, R.g.n_out,
+                    [&](uint32_t i, uint32_t b, float yr, float yi) { dh_cz_emit_raster(R, i, b, yr, yi); });
+}
+
+// The polyphase fold of raster mode (host body dh_cz_fold_item).  A workgroup takes DH_CZ_FOLD_ROWS = 16 consecutive output
+// instants (blockIdx.x) and 256 consecutive r (blockIdx.y), lane = r: one accumulator pair per (instant, r) in registers, p
+// walked in increasing order with one load of h[r + p K] per sixteen instants.  Every input sample serves about T / D
+// instants, so the span the tile needs goes through LDS: for the taps p0 <= p < p1 that is the (16 - 1) D + (p1 - p0 - 1) K
+// + 256 samples below x[n_row0 - r0 - p0 K], and p advances in chunks of as many p as DH_CZ_FOLD_LDS = 6144 complex samples
+// (48 KB: three workgroups per CU) hold; the accumulators stay in registers across chunks.  One p always fits while
+// 15 D + 256 <= 6144, that is D <= 392, for every K and P; a larger D reads the window through L2 instead (its instants
+// share almost nothing: a tile's rows are then > 392 samples apart and K <= 256 of them are used per p).
+// LDS layout: the span as consecutive 8-byte samples.  A lane reads sample (255 - lane) + const, so the 32 lanes of a
+// ds_read_b64 group cover 256 contiguous bytes, all 64 banks once: no conflicts whatever D and K are; the staging stores
+// are lane-contiguous too.
+__global__ __launch_bounds__(DH_CZ_FOLD_LANES) void k_cz_fold(const DhCzFoldParams F) {
+    __shared__ __attribute__((aligned(16))) float2 xs[DH_CZ_FOLD_LDS];
+    const uint32_t tid = threadIdx.x, r0 = blockIdx.y * DH_CZ_FOLD_LANES, r = r0 + tid, row0 = blockIdx.x * DH_CZ_FOLD_ROWS;
+    const bool live = r < F.K;
+    const float2* win = (const float2*) F.win;
+    const int32_t top = (int32_t) (F.wj0 + row0 * F.D) - (int32_t) r0;          // window index of x[n_row0 - r0]
+    const uint32_t rowspan = (DH_CZ_FOLD_ROWS - 1u) * F.D;
+    float2 acc[DH_CZ_FOLD_ROWS];
+#pragma unroll
+    for (int i = 0; i < DH_CZ_FOLD_ROWS; i++) acc[i] = make_float2(0.0f, 0.0f);
+    if (rowspan + DH_CZ_FOLD_LANES <= DH_CZ_FOLD_LDS) {
+        const uint32_t pc = dh_min(F.P, 1u + (DH_CZ_FOLD_LDS - rowspan - DH_CZ_FOLD_LANES) / F.K);
+        for (uint32_t p0 = 0; p0 < F.P; p0 += pc) {
+            const uint32_t p1 = dh_min(F.P, p0 + pc);
+            const uint32_t len = rowspan + (p1 - p0 - 1u) * F.K + DH_CZ_FOLD_LANES;
+            const int32_t lo = top - (int32_t) (DH_CZ_FOLD_LANES - 1u) - (int32_t) ((p1 - 1u) * F.K);
+            __syncthreads();                            // the previous chunk has been read
+            for (uint32_t t = tid; t < len; t += DH_CZ_FOLD_LANES) {
+                const int32_t idx = lo + (int32_t) t;   // below the window: r >= K lanes; above: the rows past nrows
+                xs[t] = idx >= 0 && (uint32_t) idx < F.win_n ? win[idx] : make_float2(0.0f, 0.0f);
+            }
+            __syncthreads();
+            if (live)
+                for (uint32_t p = p0; p < p1; p++) {
+                    const float hv = F.h[r + p * F.K];
+                    const float2* s = xs + (DH_CZ_FOLD_LANES - 1u - tid) + (p1 - 1u - p) * F.K;
+#pragma unroll
+                    for (int i = 0; i < DH_CZ_FOLD_ROWS; i++) {
+                        const float2 x = s[(uint32_t) i * F.D];
+                        acc[i].x = __builtin_fmaf(hv, x.x, acc[i].x); acc[i].y = __builtin_fmaf(hv, x.y, acc[i].y);
+                    }
+                }
+        }
+    } else if (live) {
+        for (uint32_t p = 0; p < F.P; p++) {
+            const float hv = F.h[r + p * F.K];
+            const int32_t base = top - (int32_t) tid - (int32_t) (p * F.K);
+#pragma unroll
+            for (int i = 0; i < DH_CZ_FOLD_ROWS; i++) {
+                if (row0 + (uint32_t) i < F.nrows) {
+                    const float2 x = win[base + (int32_t) ((uint32_t) i * F.D)];
+                    acc[i].x = __builtin_fmaf(hv, x.x, acc[i].x); acc[i].y = __builtin_fmaf(hv, x.y, acc[i].y);
+                }
+            }
+        }
+    }
+    if (r >= F.kpad) return;
+    float2* out = (float2*) F.fold + (size_t) row0 * F.kpad + (F.kpad - 1u - r);
+#pragma unroll
+    for (int i = 0; i < DH_CZ_FOLD_ROWS; i++)
+        if (row0 + (uint32_t) i < F.nrows) out[(size_t) i * F.kpad] = live ? acc[i] : make_float2(0.0f, 0.0f);
 }
 
 __global__ __launch_bounds__(256) void k_cz_fm(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out) {
@@ -1253,6 +1324,20 @@ static int dh_be_cz_gemm(const DhCzParams& P, void* stream) {
 static int dh_be_cz_gemm_rat(const DhCzRatParams& R, void* stream) {
     if (!R.nslots) return DH_OK;
     hipLaunchKernelGGL(k_cz_gemm_rat, dim3((R.ph[0].count + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC), R.nslots), dim3(256), 0,
+                       (hipStream_t) stream, R);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_cz_fold(const DhCzFoldParams& F, void* stream) {
+    if (!F.nrows) return DH_OK;
+    hipLaunchKernelGGL(k_cz_fold, dim3((F.nrows + DH_CZ_FOLD_ROWS - 1) / DH_CZ_FOLD_ROWS, (F.kpad + DH_CZ_FOLD_LANES - 1) / DH_CZ_FOLD_LANES),
+                       dim3(DH_CZ_FOLD_LANES), 0, (hipStream_t) stream, F);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+static int dh_be_cz_gemm_raster(const DhCzRasterParams& R, void* stream) {
+    if (!R.g.n_out) return DH_OK;
+    hipLaunchKernelGGL(k_cz_gemm_raster, dim3((R.g.n_out + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC)), dim3(256), 0,
                        (hipStream_t) stream, R);
     HIP_TRY(hipGetLastError());
     return DH_OK;

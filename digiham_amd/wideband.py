@@ -31,11 +31,13 @@ def ysf_audio(seed, n_frames=30):
     return synth.shape(synth.ysf_stream(seed, n_frames))
 
 
-def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak=0.9, keying=None):
+def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak=0.9, keying=None, noise_device=None):
     """carriers: list of (offset_hz, level_db, audio48) -- each FM-modulated at 48 kS/s x decimation (audio linearly
     interpolated), level relative to the strongest; the sum is scaled so that it never clips, complex Gaussian noise of
     `noise_lsb` rms per component is added, and the result rounded to int16.  `keying`: per carrier None (always on) or
-    (start_s, stop_s) -- the carrier's amplitude is 0 outside [start, stop) and its audio begins at start.  Returns
+    (start_s, stop_s) -- the carrier's amplitude is 0 outside [start, stop) and its audio begins at start.
+    `noise_device`: where the noise generator runs (default: on `device`; a generator's stream depends on its device, so
+    "cpu" makes a seed name the same noise whatever `device` is).  Returns
     int16 [n][2] (a numpy array, or a torch tensor on `device` when that is not the CPU)."""
     import torch
     rate = AUDIO_RATE * decimation
@@ -60,8 +62,9 @@ def composite(decimation, carriers, n, noise_lsb=2.0, seed=0, device="cpu", peak
             t_s = t_out / AUDIO_RATE
             on = ((t_s >= key[0]) & (t_s < key[1])).double()
             acc += scale * a * torch.polar(on, ph)
-    g = torch.Generator(device=dev).manual_seed(seed)
-    noise = torch.randn((n, 2), generator=g, dtype=torch.float64, device=dev) * noise_lsb
+    ndev = dev if noise_device is None else torch.device(noise_device)
+    g = torch.Generator(device=ndev).manual_seed(seed)
+    noise = torch.randn((n, 2), generator=g, dtype=torch.float64, device=ndev).to(dev) * noise_lsb
     iq = torch.stack((acc.real, acc.imag), 1) + noise
     q = iq.round().clamp(-32768, 32767).to(torch.int16)
     return q.cpu().numpy() if dev.type == "cpu" else q

@@ -356,6 +356,14 @@ int dh_frontend_s16(const int16_t* d_in, size_t in_stride, float* d_out, size_t 
  * floor((j * decimation + decimation - 1) / L), and after N input samples exactly floor(L N / decimation) outputs exist.
  * Limits: L <= 64, L <= decimation, gcd(L, decimation) = 1, n_taps <= 16384 L.  Wherever "max_input / decimation" sizes
  * something below, read max_input * L / decimation.
+ * Uniform raster: raster = K != 0 puts every channel on a multiple of input_rate / K -- channel b at bins[b] * input_rate / K,
+ * bins taken mod K, any subset in any order, duplicates allowed -- and computes all of them as ONE polyphase fold of the
+ * prototype followed by a K-point DFT on the matrix cores: the matrix work per output is 8 B K instead of 8 B n_taps.
+ * increments is then ignored and may be NULL; bins must not be.  Phases are the integers (c m) mod K mapped through
+ * Phi(q) = ((q << 32) + K / 2) / K, so the arithmetic (channelizer_core.hpp, "Uniform raster") is not bit for bit that of
+ * the same channels given as increments; both are the same converter bank to within rounding.  The fixed-offset form stays
+ * the general case, for channels off any raster.  Limits: 2 <= raster <= 16384, 1 <= n_taps <= 64 raster and <= 2^20 (in
+ * place of 16384).  raster together with interpolation > 1 is DH_EINVAL: a raster has no rational rates yet.
  * ---------------------------------------------------------------------- */
 enum { DH_CZ_CS16 = 1, DH_CZ_CF32 = 2 };
 enum { DH_CZ_IQ_F32 = 1, DH_CZ_FM = 2 };
@@ -374,13 +382,19 @@ typedef struct {
     uint32_t max_input;            /* complex samples per push */
     void*    stream;               /* hipStream_t; NULL = default stream */
     uint32_t interpolation;        /* L of a rational rate; 0 and 1 (and a struct_size that ends before this field): L = 1 */
+    uint32_t raster;               /* K of a uniform raster; 0 (and every struct_size below the whole struct): fixed offsets */
+    const int32_t* bins;           /* raster != 0: host [n_channels], copied at create */
 } dh_channelizer_config;
+/* raster took the place of the tail padding that the struct had when it ended with interpolation: that struct's size covers
+ * it, and its callers never wrote it.  raster is therefore read only when struct_size covers bins as well, i.e. is at least
+ * sizeof(dh_channelizer_config); every smaller struct_size means fixed offsets whatever bytes follow interpolation. */
 
 int  dh_channelizer_create(const dh_channelizer_config* cfg, dh_channelizer** out);
 void dh_channelizer_destroy(dh_channelizer* c);
 /* back to sample 0: zero input history and channel states (taps and increments stay) */
 int  dh_channelizer_reset(dh_channelizer* c);
-/* channel `channel` takes `increment` from the next push on; its FM / DC-blocker state restarts, the input history stays */
+/* channel `channel` takes `increment` from the next push on; its FM / DC-blocker state restarts, the input history stays.
+ * On a uniform raster `increment` is the channel's new bin, read as a two's-complement int32 (pass (uint32_t) bin). */
 int  dh_channelizer_retune(dh_channelizer* c, uint32_t channel, uint32_t increment);
 /* n_in (<= max_input, any length, 0 included) complex samples; *n_out = outputs completed by this push, known without a
  * sync.  d_out [n_channels][out_stride] (out_stride in output samples: complex pairs for IQ_F32, floats for FM, >= *n_out)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""tools/channelizer_model.py [--interpolation L] [--decimation M] [--rows R] [--seconds S] [--seed N] [--device cuda|cpu]:
+"""tools/channelizer_model.py [--interpolation L] [--decimation M] [--rows R] [--seconds S] [--seed N] [--device cuda|cpu]
+[--raster HZ]:
 a float64 model of the rational-rate channelizer on the end-to-end fixture of tests/test_channelizer_rational.py, next to
 the library.
 
@@ -11,7 +12,13 @@ h_p[k] = h[r_p + k L] of the prototype (FFT, complex128), take z[j] = (h_p * x)[
 first 512 outputs.  The last line says whether the model decodes every row as test_end_to_end_wideband_gpu asks (ids in
 every non-empty DMR row's LCs, at least as many syncs as superframes, no syncs in the empty rows); the exit status is 1 if
 it does not.  A fixture for that test has to be one this model passes; --seed 8 is the test's.  --seed 7 on the device
-gives row 10 a sixth LC with wrong ids in the model and in the library alike."""
+gives row 10 a sixth LC with wrong ids in the model and in the library alike.
+
+--raster HZ (with --decimation D; no interpolation): the fixture of tests/test_channelizer_raster.py instead -- 48 kS/s * D,
+channels on multiples of HZ, Channelizer(raster_hz=HZ) -- and the model is the raster mode's own formula in double: the
+polyphase fold v[r] = sum_p h[r + p K] x[n_j - r - p K], the K-point DFT over r and the rotation e^(-2 pi i c n_j / K), then
+the discriminator and the DC blocker as above.  That fixture's noise comes from the CPU generator whatever --device is, so
+a seed checked here with --device cpu names the noise test_end_to_end_raster_gpu gets."""
 import argparse
 import os
 import sys
@@ -45,6 +52,38 @@ def model_rows(x, rate, raster, h, L, M):
     return out
 
 
+def model_rows_raster(x, rate, raster_hz, raster, h, D, block=8192):
+    """float64 FM + DC rows [len(raster)][n // D] of the int16 composite x [n][2]: fold + DFT + rotation."""
+    from scipy.signal import lfilter
+    K = int(round(rate / raster_hz))
+    P = -(-len(h) // K)
+    hp = np.zeros(P * K)
+    hp[:len(h)] = h
+    hp = hp.reshape(P, K)
+    n = len(x)
+    n_out = n // D
+    H = P * K
+    xs = np.concatenate([np.zeros(H, complex), (x[:, 0].astype(np.float64) + 1j * x[:, 1]) / 32768.0])
+    c = np.mod(np.round(np.array(raster) / raster_hz).astype(np.int64), K)
+    r = np.arange(K)
+    E = np.exp(2j * np.pi * np.outer(r, c) / K)                 # [K][rows]
+    z = np.zeros((len(raster), n_out), complex)
+    for j0 in range(0, n_out, block):
+        j1 = min(n_out, j0 + block)
+        nj = np.arange(j0, j1) * D + D - 1
+        v = np.zeros((j1 - j0, K), complex)
+        for p in range(P):                                      # x[n_j - r - p K]: rows D apart, r descending
+            first = xs[H + nj[0] - p * K:]
+            a = np.lib.stride_tricks.as_strided(first, shape=(j1 - j0, K), strides=(D * xs.itemsize, -xs.itemsize), writeable=False)
+            v += hp[p][None, :] * a
+        z[:, j0:j1] = (v @ E).T * np.exp(-2j * np.pi * np.outer(c, nj % K) / K)
+    out = np.zeros((len(raster), n_out), np.float64)
+    for i in range(len(raster)):
+        w = z[i] * np.conj(np.concatenate([[0], z[i, :-1]]))
+        out[i] = lfilter([1.0, -1.0], [1.0, -0.995], np.angle(w) / np.pi)
+    return out
+
+
 def decode(audio, meta, O, api):
     """per row: (syncs, LCs, LCs with wrong ids) of the oracle's DMR chain."""
     ref = O.chain(np.ascontiguousarray(audio, np.float32), proto=1)
@@ -75,22 +114,29 @@ def main():
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--seed", type=int, default=8)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--raster", type=float, default=0.0)
     a = ap.parse_args()
     from digiham_amd import api
     from oracle import oracle as O
     import test_channelizer_rational as T
     O.build()
     L, M = a.interpolation, a.decimation
-    f = T.end_to_end_fixture(L, M, a.rows, a.seconds, a.device, a.seed)
+    if a.raster:
+        import test_channelizer_raster as TR
+        L = 1
+        f = TR.end_to_end_fixture(M, a.raster, a.rows, a.seconds, a.device, a.seed)
+    else:
+        f = T.end_to_end_fixture(L, M, a.rows, a.seconds, a.device, a.seed)
     on_device = a.device != "cpu"
     x = f["x"].cpu().numpy() if on_device else f["x"]
     lib = None
     if on_device:
-        cz = api.Channelizer(f["rate"], M, f["raster"], f["h"], input="cs16", output="fm", dcblock=True, max_input=f["n"], interpolation=L)
+        cz = api.Channelizer(f["rate"], M, f["raster"], f["h"], input="cs16", output="fm", dcblock=True, max_input=f["n"],
+                             **(dict(raster_hz=a.raster) if a.raster else dict(interpolation=L)))
         rows, k = cz.push(f["x"])
         lib = rows[:, :k].cpu().numpy().astype(np.float64)
         cz.close()
-    model = model_rows(x, f["rate"], f["raster"], f["h"], L, M)
+    model = model_rows_raster(x, f["rate"], a.raster, f["raster"], f["h"], M) if a.raster else model_rows(x, f["rate"], f["raster"], f["h"], L, M)
     rm = decode(model, f["meta"], O, api)
     rl = decode(lib, f["meta"], O, api) if lib is not None else None
     start = 512                                                 # outputs skipped: the filter's and the DC blocker's start-up
@@ -101,7 +147,8 @@ def main():
             line += "  library %s  max |FM difference| %.3g" % (rl[r], float(np.abs(lib[r] - model[r])[start:].max()))
         print(line, flush=True)
     ok = passes(rm, f)
-    print("seed %d, %s noise: the model %s every row%s" % (a.seed, a.device, "decodes" if ok else "does NOT decode",
+    print("%sseed %d, %s noise: the model %s every row%s" % ("raster %g Hz, D %d, %d rows, %g s: " % (a.raster, M, a.rows, a.seconds) if a.raster else "", a.seed,
+             "cpu" if a.raster else a.device, "decodes" if ok else "does NOT decode",
           "" if rl is None else "; the library %s; counts %s" % ("does too" if passes(rl, f) else "does NOT", "agree" if rl == rm else "differ")))
     return 0 if ok else 1
 
