@@ -1541,8 +1541,8 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
         // symbols) of phase i = 3 r + j -- three phases per DPP row, so that the five partial sums of a phase are five neighbouring
         // lanes of one row and meet through row_shr (lane g = 4 of each group: ((s4 + s3) + (s2 + s1)) + s0, three roundings
         // where the exchange form has four: the tolerance derived below covers it).  The ten lanes that then hold a phase form
-        // its interval; `above` (ruled out by the smallest upper end) and `fine` (guard holds, estimate not exactly 0, and the
-        // lane is either ruled out or positive and below 5e6) are the only votes: one candidate and every lane fine is the case
+        // its interval; `above` (ruled out by the smallest upper end) and the two kinds of `fine` (guard holds and estimate not exactly
+        // 0: fine when ruled out; also positive and below 5e6: fine as a candidate) are the only votes: one candidate and every lane fine is the case
         // decided here -- everything else (an estimate of exactly 0, NaN / overflow, ties) is left to the full form below, which
         // starts over.  ~100 instructions instead of ~260 per block.
         if (SPS == 10 && !P.ordered_timing) {
@@ -1563,7 +1563,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 DH_LA(gs, lane)[0] = act ? s2.x + s2.y : 0.0f; DH_LA(gq, lane)[0] = act ? q2.x + q2.y : 0.0f;
             }
             DH_LANE_ARRAY(float, lo, 1); DH_LANE_ARRAY(float, hi, 1);
-            uint64_t vote_above = 0, vote_fine = 0;
+            uint64_t vote_above = 0, fine_cand = 0, fine_out = 0;
 #if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
             {
                 float s = gs[0], q = gq[0], t1, t2, u1, u2;
@@ -1601,8 +1601,9 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 if (BOUNDED && e_blk > 0.0f) tol += 8.0f * e_blk * dh_sqrt_upper(__builtin_fmaxf(v, 0.0f) + 4.0f * e_blk * e_blk) + 8.0f * e_blk * e_blk;      // (see the full form below)
                 const float l = own ? v - tol : DH_FLT_MAX, h = own ? v + tol : DH_FLT_MAX;
                 DH_LA(lo, lane)[0] = l; DH_LA(hi, lane)[0] = h;
-                DH_LA(gs, lane)[0] = own ? ((e < 1e30f && v != 0.0f && l > 0.0f && h < 4999999.0f) ? 1.0f : 0.0f) : 1.0f;      // fine as a candidate
-                DH_LA(gq, lane)[0] = own ? ((e < 1e30f && v != 0.0f) ? 1.0f : 0.0f) : 1.0f;                                      // fine when ruled out
+                const bool sane = e < 1e30f && v != 0.0f;
+                DH_BALLOT_ACC(fine_cand, !own || (sane && l > 0.0f && h < 4999999.0f), lane);      // fine as a candidate
+                DH_BALLOT_ACC(fine_out, !own || sane, lane);                                       // fine when ruled out
             }
             float hmin;
 #if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
@@ -1612,16 +1613,17 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
             for (int q = 0; q < DH_WAVE; q++) hmin = dh_fmin_(hmin, hi[q][0]);
 #endif
             DH_FOR_LANES_FRESH(lane) {
-                const bool above = DH_LA(lo, lane)[0] > hmin;
-                DH_BALLOT_ACC(vote_above, above, lane);
-                DH_BALLOT_ACC(vote_fine, (above ? DH_LA(gq, lane)[0] : DH_LA(gs, lane)[0]) != 0.0f, lane);
+                DH_BALLOT_ACC(vote_above, DH_LA(lo, lane)[0] > hmin, lane);
             }
+            // The verdict is scalar logic on the three ballots: every lane fine for what it is (ruled out / candidate) and exactly
+            // one candidate.  A lone candidate is one of the ten lanes that hold a phase (the other lanes share one interval: all of
+            // them candidates or none), lane 16 r + 5 j + 4 for phase 3 r + j: phases 1 .. 4 step up, 5 .. 8 down, 0 and 9 stay.
             const uint64_t cand = ~vote_above;
-            if (DH_LIKELY(vote_fine == ~0ull && cand != 0 && (cand & (cand - 1)) == 0)) {
+            const uint64_t unfit = (vote_above & ~fine_out) | (cand & ~fine_cand);
+            if (DH_LIKELY((unfit | (cand & (cand - 1))) == 0 && cand != 0)) {
                 est_done = true; ordered = false;
-                const uint32_t b = (uint32_t) dh_ffs64(cand), vmin_pos = 3u * (b >> 4) + ((b & 15u) - 4u) / 5u;
-                if (vmin_pos > 0 && vmin_pos < 5) new_off = +1;
-                else if (vmin_pos >= 5 && vmin_pos < 9) new_off = -1;
+                constexpr uint64_t UP = (1ull << 9) | (1ull << 14) | (1ull << 20) | (1ull << 25), DOWN = (1ull << 30) | (1ull << 36) | (1ull << 41) | (1ull << 46);
+                new_off = (cand & UP) ? +1 : (cand & DOWN) ? -1 : 0;
             }
         }
         if (SPS == 10 && !P.ordered_timing && !est_done) {
@@ -1925,13 +1927,14 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
 // ---------------------------------------------------------------------------------------------
 // ---- P5: thresholds + slice (gfsk_demodulator.cpp:88-106 / fsk_demodulator.cpp:89-99)
 // error-bounded mode: a comparison whose two sides are closer than T cannot be trusted to come out as the
-// reference's; those symbols are not stored here but decided exactly below
+// reference's; those symbols are decided exactly below, and that decision replaces the dibit stored here
 // TWO symbols per lane, q = 2 lane and 2 lane + 1 (a run has at most 100): their AGC extremes, window sums and everything
 // derived from them are pairs, so centre, average, the two thresholds and the three distances are packed operations for
 // both symbols -- one pass of ~40 vector instructions instead of two of ~37.  Every operation is the one the one-symbol
 // form performs (same operands, same order), so the dibits and the doubts are the same.
 // `out`: where symbol 0 of the run goes; `agc` (device): the scan's own results for the lane's two symbols, used when the run starts its
-// block.  Doubtful symbols are not stored; their votes come back in vote_a (symbols 2 l) and vote_b (2 l + 1).
+// block.  Doubtful symbols are stored provisionally and overwritten by dh_settle_doubts; their votes come back in vote_a (symbols 2 l)
+// and vote_b (2 l + 1).
 struct DhSliceSetup { bool four_levels, e_pos, width_pow2, pair_store; float T_eff, inv_width; };
 template <int SPS, int LV, bool BOUNDED>
 DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, const DhAgcPair agc, uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
@@ -1976,11 +1979,16 @@ DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, const DhAgcPai
 #ifdef DH_IGNORE_DOUBT
         doubt_a = false; doubt_b = false;
 #endif
-        // the lane's two dibits are neighbours: one 16-bit store when the row position is even (wave-uniform) and both are decided
-        if (pair_store && va && !doubt_a && vb && !doubt_b) *reinterpret_cast<uint16_t*>(out + qa) = (uint16_t) ((uint32_t) sa | ((uint32_t) sb << 8));
-        else {
-            if (va && !doubt_a) out[qa] = sa;
-            if (vb && !doubt_b) out[qa + 1u] = sb;
+        // Every valid symbol's dibit is stored, doubtful or not: dh_settle_doubts stores out[q] again for every vote it is handed --
+        // later in program order, from this wavefront, to the same address (and behind waits for its own loads, which this store
+        // precedes in the memory counter).  The lane's two dibits are neighbours: one 16-bit store when the row position is even
+        // (wave-uniform); an odd last symbol of such a run (m odd: wave-uniform too) goes as a byte.
+        if (DH_LIKELY(pair_store)) {
+            if (vb) *reinterpret_cast<uint16_t*>(out + qa) = (uint16_t) ((uint32_t) sa | ((uint32_t) sb << 8));
+            if (DH_UNLIKELY((m & 1u) != 0u)) { if (qa + 1u == m) out[qa] = sa; }
+        } else {
+            if (va) out[qa] = sa;
+            if (vb) out[qa + 1u] = sb;
         }
         DH_BALLOT_ACC(vote_a, doubt_a, lane);
         DH_BALLOT_ACC(vote_b, doubt_b, lane);
@@ -2200,6 +2208,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     const float* in = P.in + (size_t) ch * P.in_stride + part_lo;
     uint8_t* syms = P.syms + (size_t) ch * P.sym_stride;
     const float* in_end = P.in + (size_t) (P.n_channels - 1u) * P.in_stride + P.n;    // end of the readable input
+    // a whole window (DH_FTILE + NZ samples) from input index i lies inside the readable input iff i < win_lim: the pointer compare
+    // in + i + (DH_FTILE + NZ) <= in_end, taken once per push (an index is below n_new <= 2^32 - 1, so the clamp loses nothing)
+    const ptrdiff_t in_room = (in_end - in) - (ptrdiff_t) (DH_FTILE + NZ);
+    const uint32_t win_lim = dh_uniform(in_room < 0 ? 0u : in_room >= (ptrdiff_t) 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t) in_room + 1u);
 
     DH_PHASE_MARK_BEGIN();
     // ---- load carried state
@@ -2210,6 +2222,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     const uint32_t n_new = dh_min<uint32_t>(n_push, part_hi) > part_lo ? dh_min<uint32_t>(n_push, part_hi) - part_lo : 0u;
     const uint32_t nv = tc + n_new;                     // length of the virtual input stream
     const uint32_t nf = nv >= NZ ? nv - NZ : 0u;        // filtered samples available this push
+    const uint32_t pf_lim = dh_uniform(dh_min<uint32_t>(win_lim, n_new));        // the next window may be fetched ahead from input indices below this
     DH_FOR_LANES(lane) {
         for (uint32_t j = lane; j < DH_SCAN_N; j += DH_WAVE) {
             S.vol_old[j] = j < DH_VOLUME_RB_SIZE ? st[DH_ST_VOL + j] : 0.0f;
@@ -2249,7 +2262,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     // error-bounded mode (see "Error-bounded FIR" above): the tail then starts with DH_ST_P0 samples of HISTORY, so that the
     // raw samples behind every entry of the 100-symbol rings are still at hand when a comparison has to be settled exactly
     uint32_t p = BOUNDED ? sth[DH_ST_P0] : 0u;          // read position in the filtered stream
-    bool staged = false; uint32_t staged_p = 0;         // the LDS window already holds V[staged_p ...) (prefetch)
+    uint32_t staged_p = 0xFFFFFFFFu;                    // the LDS window already holds V[staged_p ...) (prefetch); 0xFFFFFFFF: it does not (no run starts there: p < nv)
     // the next window fetched into registers behind P3 and put into the window block in P7: the split-f16 kernels (as two arrays of
     // halves, with the constants of its run below) and the kernels without an RRC stage (as it is: they have the registers, and staged
     // from L2 at the start of the next run every run waited out an L2 round trip: POCSAG slicer 4.86 -> 4.34 ms, D-Star chain 3.94 -> 3.65,
@@ -2334,9 +2347,9 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         // 16 B per LDS store (a group of four never straddles a pad slot: pads sit every 16 elements).
         // From the second run on, the window was already put there by the previous iteration's prefetch (the kernels that fetch it into
         // registers: PF_REG; the others have had it pulled into L2).
-        if (DH_LIKELY(staged && staged_p == p)) {
+        if (DH_LIKELY(staged_p == p)) {
             if (PF_REG && MF16) { f16_staged = true; xmax_done = true; e_run = st_e_run; k1 = st_k1; k2 = st_k2; }      // (put there by P7 of the previous run)
-        } else if (p >= tc && in + (p - tc) + (DH_FTILE + NZ) <= in_end) {
+        } else if (p - tc < pf_lim) {                   // (p < nv in every run: its first symbol fits)
             // whole window inside the input buffer: unconditional loads (all in flight together, see the prefetch
             // below for why that matters), samples past the end of the stream zeroed afterwards
             const float* src = in + (p - tc);
@@ -2541,13 +2554,13 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 
         // ---- the raw window of the NEXT run: planned here, fetched behind P3 (dh_issue_next_window), stored in P7 (dh_store_next_window)
         const uint32_t p_next = last_start + sps + ((k0 == 0 && m == 1) ? (uint32_t) step_off : 0u);
-        const bool pf_ok = p_next >= tc && p_next < nv;
-        const uint32_t pf_have = pf_ok ? dh_min<uint32_t>(DH_FTILE + NZ, nv - p_next) : 0u;
+        const uint32_t pf_have = dh_min<uint32_t>(DH_FTILE + NZ, nv - p_next);        // (read in P7, under pf_reg only: p_next < nv there)
         DH_LANE_ARRAY(dh_f4, pfr, PF_REG ? DH_PF_N : 1);  // split-f16 kernels: the next window, parked in registers through P4 - P6
         // Only when the whole window lies inside the input buffer (every run but the last ones of the last
         // channel): the loads are then unconditional, there is nothing to merge, and all five are in flight
         // together; samples past pf_have are zeroed in P7.  Otherwise the next iteration stages in P1.
-        const bool pf_plain = pf_ok && (in + (p_next - tc) + (DH_FTILE + NZ) <= in_end);
+        // (tc <= p_next < nv and the window inside the input, as one unsigned compare: p_next - tc wraps past every n_new when p_next < tc)
+        const bool pf_plain = p_next - tc < pf_lim;
         const bool pf_reg = PF_REG && pf_plain && P.exact_mode != 2;
         if constexpr (KEEPF) {
             // This run's filtered samples [p, p_next) leave as they stand in LDS (each store instruction a run of 64 consecutive
@@ -2618,16 +2631,18 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         DH_PHASE_MARK(5);
         // ---- P7: commit the run (wave-uniform bookkeeping) and fold new volumes into the ring
         DH_FOR_LANES_FRESH(lane) {
-            // a run has at most 100 symbols: two predicated copies per lane, both loads in flight together (as a loop this was
-            // two trips of exec-mask bookkeeping with a wait in each)
+            // a run has at most 100 symbols: two copies per lane, both loads in flight together (as a loop this was two trips of
+            // exec-mask bookkeeping with a wait in each).  A lane beyond the run copies the run's first slot again -- the value lane 0
+            // writes there -- so the stores need no predicate: no exec-mask region, no skip branch.
             const uint32_t ka = k0 + (uint32_t) lane, kb = ka + DH_WAVE, ke = k0 + m;
-            const float va_ = S.vol_new[ka < ke ? ka : k0], vb_ = S.vol_new[kb < ke ? kb : k0];
-            if (ka < ke) S.vol_old[ka] = va_;
-            if (kb < ke) S.vol_old[kb] = vb_;
+            const uint32_t ia = ka < ke ? ka : k0, ib = kb < ke ? kb : k0;
+            const float va_ = S.vol_new[ia], vb_ = S.vol_new[ib];
+            S.vol_old[ia] = va_;
+            S.vol_old[ib] = vb_;
         }
-        staged = false;
+        staged_p = 0xFFFFFFFFu;
         if (DH_LIKELY(pf_reg)) {
-            if constexpr (PF_REG && MF16) { staged = dh_stage_f16<NZ>(P, S, pfr, pf_have, st_e_run, st_k1, st_k2); staged_p = p_next; }
+            if constexpr (PF_REG && MF16) { if (DH_LIKELY(dh_stage_f16<NZ>(P, S, pfr, pf_have, st_e_run, st_k1, st_k2))) staged_p = p_next; }
             else if constexpr (PF_PLAIN) {
                 // no RRC stage: the window is the 1 024 samples themselves (four groups of four per lane, unpadded), zeros beyond the stream's end
                 static_assert(!PF_PLAIN || (DH_FTILE == 4u * DH_WAVE * (DH_PF_N - 1)), "four full groups cover the window");
@@ -2641,7 +2656,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                         dh_store4(ldst + 4 * DH_WAVE * r, w);
                     }
                 }
-                staged = true; staged_p = p_next;
+                staged_p = p_next;
             }
         }
         DH_BARRIER();
