@@ -18,42 +18,7 @@
 
 #include "../../include/digiham_amd.h"     // dh_event, DH_EV_*
 
-// one value per lane that outlives a lane loop: a register on the GPU, a [lane] array in the harness; DH_LV_READ
-// fetches the value of lane k (wave-uniform k) -- v_readlane
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_LANE_VALUE(type, name) type name
-#define DH_LV(name, lane) name
-#define DH_LV_READ(name, k) ((uint32_t) __builtin_amdgcn_readlane((int) (name), (int) (k)))
-#define DH_LV_DOWN(name, lane, d) ((uint32_t) __shfl_down((int) (name), (unsigned) (d), DH_WAVE))      // the value of lane + d
-#else
-#define DH_LANE_VALUE(type, name) type name[DH_WAVE]
-#define DH_LV(name, lane) name[lane]
-#define DH_LV_READ(name, k) ((uint32_t) name[k])
-#define DH_LV_DOWN(name, lane, d) ((uint32_t) name[((lane) + (d)) < DH_WAVE ? (lane) + (d) : (lane)])
-#endif
-// the same for a struct of per-lane values (registers on the GPU, an array of structs in the harness); DH_LS_READ fetches a
-// field of lane k (wave-uniform k: v_readlane), DH_LS_WRITE sets it (v_writelane)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_LANE_STRUCT(type, name) type name
-#define DH_LANE_STRUCT_REF(type, name) type& name
-#define DH_LS(name, lane) name
-#define DH_LS_READ(name, field, k) ((uint32_t) __builtin_amdgcn_readlane((int) (name).field, (int) (k)))
-// (v_writelane takes value and lane from scalar registers, a VOP3 of gfx9 reads at most one: the lane select goes through m0,
-// which belongs to the compiler -- saved and restored around the write, as in DhState::set)
-static __device__ __forceinline__ uint32_t dh_writelane(uint32_t reg, uint32_t lane, uint32_t v) {
-    const uint32_t sv = (uint32_t) __builtin_amdgcn_readfirstlane((int) v), si = (uint32_t) __builtin_amdgcn_readfirstlane((int) lane);
-    uint32_t keep;
-    asm("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1" : "+v"(reg), "=&s"(keep) : "s"(sv), "s"(si));
-    return reg;
-}
-#define DH_LS_WRITE(name, field, k, v) (name).field = dh_writelane((name).field, (uint32_t) (k), (uint32_t) (v))
-#else
-#define DH_LANE_STRUCT(type, name) type name[DH_WAVE]
-#define DH_LANE_STRUCT_REF(type, name) type* name
-#define DH_LS(name, lane) name[lane]
-#define DH_LS_READ(name, field, k) ((uint32_t) (name)[k].field)
-#define DH_LS_WRITE(name, field, k, v) (name)[k].field = (uint32_t) (v)
-#endif
+// (per-lane values that outlive a lane loop -- DH_LANE_VALUE / DH_LV*, DH_LANE_STRUCT / DH_LS* -- are dh_portable.hpp's)
 
 #define DH_SYM_CARRY_MAX 512          // symbols a decoder may leave unread between pushes (<= 480)
 #define DH_DSTAR_CARRY_MAX 704        // D-Star: the header phase waits for more than 660 bits (dstar_phase.hpp:52)
@@ -155,44 +120,9 @@ DH_HD int dh_dmr_sync_type(const DhPlanes& p, int start) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The 32 state words of a channel while its wavefront runs: ONE vector register, word i in lane i.  The frame
-// state machines index them with run-time (wave-uniform) indices such as DS_SYNC_TYPE0 + slot; v_readlane /
-// v_writelane take the index from a scalar register, so a read or write is a single instruction with no memory
-// round trip (an LDS copy costs ~100 cycles of latency per access on this serial path, a register array would
-// go to scratch).  s[i] reads, s[i] = v writes; the harness build is a plain array.
-struct DhState {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    uint32_t reg;
-    __device__ __forceinline__ uint32_t get(uint32_t i) const { return (uint32_t) __builtin_amdgcn_readlane((int) reg, (int) i); }
-    __device__ __forceinline__ void set(uint32_t i, uint32_t v) {
-        const uint32_t sv = dh_uniform(v), si = dh_uniform(i);         // v_writelane takes value and lane from scalar registers
-        // gfx9 VOP3 reads at most one SGPR, so the lane select goes through m0; m0 is reserved for the compiler
-        // (a clobber would be ignored), hence saved and restored around the write
-        uint32_t keep;
-        asm("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
-            : "+v"(reg), "=&s"(keep) : "s"(sv), "s"(si));
-    }
-    __device__ __forceinline__ void load(const uint32_t* g) { reg = threadIdx.x < DH_DEC_STATE_WORDS ? g[threadIdx.x] : 0u; }
-    __device__ __forceinline__ void store(uint32_t* g) const { if (threadIdx.x < DH_DEC_STATE_WORDS) g[threadIdx.x] = reg; }
-    __device__ __forceinline__ void store_words(uint32_t* g, uint32_t first, uint32_t n) const { if (threadIdx.x - first < n) g[threadIdx.x - first] = reg; }     // words [first, first + n)
-#else
-    uint32_t w[DH_DEC_STATE_WORDS];
-    uint32_t get(uint32_t i) const { return w[i]; }
-    void set(uint32_t i, uint32_t v) { w[i] = v; }
-    void load(const uint32_t* g) { for (int i = 0; i < DH_DEC_STATE_WORDS; i++) w[i] = g[i]; }
-    void store(uint32_t* g) const { for (int i = 0; i < DH_DEC_STATE_WORDS; i++) g[i] = w[i]; }
-    void store_words(uint32_t* g, uint32_t first, uint32_t n) const { for (uint32_t i = 0; i < n; i++) g[i] = w[first + i]; }
-#endif
-    struct Ref {
-        DhState* st; uint32_t i;
-        DH_HD operator uint32_t() const { return st->get(i); }
-        DH_HD Ref& operator=(uint32_t v) { st->set(i, v); return *this; }
-        DH_HD Ref& operator=(const Ref& o) { st->set(i, (uint32_t) o); return *this; }
-        DH_HD uint32_t operator++(int) { const uint32_t v = st->get(i); st->set(i, v + 1u); return v; }
-    };
-    DH_HD Ref operator[](uint32_t i) { return Ref{this, i}; }
-    DH_HD Ref operator[](int i) { return Ref{this, (uint32_t) i}; }
-};
+// The state words of a channel while its wavefront runs: ONE vector register, word i in lane i (DhState, dh_portable.hpp).
+// The frame state machines index them with run-time (wave-uniform) indices such as DS_SYNC_TYPE0 + slot: s[i] reads, s[i] = v writes.
+static_assert(DH_DEC_STATE_WORDS == DH_WAVE, "a channel's state row is one word per lane");
 
 struct DhDecCtx {
     const DhDecParams* P;
@@ -400,11 +330,7 @@ DH_HD void dh_channel_open(DhDecCtx& c, DhState& s, DhSymView& syms, const DhDec
     c.ev = P.events ? P.events + (size_t) ch * P.ev_stride : nullptr;
     c.nout = dh_uniform(append ? P.out_count[ch] : 0u); c.nev = dh_uniform(append && P.ev_count ? P.ev_count[ch] : 0u); c.overflow = false;
     c.consumed = s[DS_CONSUMED];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    c.writer = threadIdx.x == 0;
-#else
-    c.writer = true;
-#endif
+    c.writer = dh_is_writer_lane();
     syms.carry = lds_carry; syms.nc = s[DS_CARRY]; syms.fresh = P.syms + (size_t) ch * P.sym_stride + sym_base;
     syms.nfresh = P.sym_count[ch] - sym_base; syms.win = S.symwin; syms.wbase = 0; syms.wlen = 0;
     dh_stage_decoder_lds(P, S, lds_carry, P.carry + (size_t) ch * P.carry_stride, syms.nc, tables);
@@ -453,11 +379,6 @@ DH_HD void dh_channel_close(DhDecCtx& c, DhState& s, DhSymView& syms, const DhDe
 //           (staged in LDS, stored coalesced)
 // The SyncPhase search (dmr_phase.cpp:35-47) is unchanged.
 // =============================================================================================
-#if defined(DH_ASM_MARKERS) && DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_DMARK(text) asm volatile("; DH_DMARK " text ::: "memory")      // (tools/asm_census.py: the decoder's regions in the assembly)
-#else
-#define DH_DMARK(text) ((void) 0)
-#endif
 struct DhDmrLane {
     uint32_t hw[5], lw[5];        // the burst's dibits: dibit i = bit i & 31 of word i >> 5 (hw: bit 1, lw: bit 0)
     uint32_t summary;             // pass A -> B, C (DH_DS_*)
@@ -825,20 +746,6 @@ DH_HD uint32_t dh_dmr_pass_b(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_LAN
     return to_sync ? k - 1u : k;
 }
 
-// index of the highest set bit, x != 0
-DH_HD int dh_top64(uint64_t x) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return 63 - __clzll((long long) x);
-#else
-    return 63 - __builtin_clzll(x);
-#endif
-}
-// a field of lane j, j a per-lane value (ds_bpermute; every lane of the wave takes part)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_LS_GATHER(name, field, j) ((uint32_t) __shfl((int) (name).field, (int) (j), DH_WAVE))
-#else
-#define DH_LS_GATHER(name, field, j) ((uint32_t) (name)[j].field)
-#endif
 
 // pass B, lane-parallel: the same bookkeeping for a REGULAR chunk, one burst per lane as in passes A and C.  A chunk is regular when,
 // from the state on entry, slot != -1; every burst has a TACT that names the expected slot (the slot alternates, no switch, no
@@ -993,12 +900,6 @@ DH_HD bool dh_dmr_pass_b_lanes(DhDmrMachine& M, DhState& s, DhDecShared& S, DH_L
     return true;
 }
 
-// exclusive prefix sum over the lanes of a small per-lane count (< 16), by votes
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_LANES_BELOW(mask, lane) ((uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) ((mask) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) (mask), 0u)))
-#else
-#define DH_LANES_BELOW(mask, lane) ((uint32_t) dh_popc64((mask) & (((uint64_t) 1 << (lane)) - 1u)))
-#endif
 
 DH_HD void dh_dmr_channel(const DhDecParams& P, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
     DhDecCtx c; DhState s; DhSymView syms;
@@ -1280,7 +1181,7 @@ DH_HD void dh_viterbi_finish(DhDecShared& S, const int* sizes, int fin) {
 // four codewords of a pass clean or nothing -- lost in the YSF pipe: 8 % of the passes qualified.  profiles/r04_b_ab_logs.txt.)
 
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
 // One trellis step of the forward pass below; C = step & 63 = the lane of the decision registers that takes its vote, an
 // IMMEDIATE of v_writelane (the steps are spelled out, not looped over: as a loop variable the lane went through m0 --
 // three scalar moves per step and 64 scalar registers of constants, which the decoders then spilled).  The vote comes
@@ -2405,60 +2306,41 @@ DH_HD uint32_t dh_bits_range(const uint64_t* w, uint32_t start, uint32_t cnt) {
 struct DhDstarScratch { uint64_t dbits[11]; uint32_t dec[44]; uint32_t out[12]; };
 static_assert(sizeof(DhDstarScratch) <= DH_SYM_CARRY_MAX, "D-Star header scratch");
 
-// Header::parseFromHeader (header.cpp:24-58) on the 660 bits at `pos`: true when the path metric is <= 10 and the CRC
-// holds; the 41 header bytes are then in X.out (little-endian words)
-DH_HD bool dh_dstar_header_parse(const DhSymView& syms, uint32_t pos, DhDstarScratch& X) {
-    // descramble + de-interleave (header.cpp:26-30, :60-72): de-interleaved bit idx = 24 k + i comes from received
-    // bit i * 28 + k (i < 12) or 12 + i * 27 + k; 64 bits per vote
-    for (uint32_t c = 0; c < 11u; c++) {
-        uint64_t m = 0;
-        DH_FOR_LANES(lane) {
-            const uint32_t idx = c * 64u + (uint32_t) lane;
-            uint32_t bit = 0;
-            if (idx < 660u) {
-                const uint32_t k = idx / 24u, i = idx % 24u;
-                const uint32_t src = i < 12u ? i * 28u + k : 12u + i * 27u + k;
-                bit = (dh_view_at(syms, pos + src) & 1u) ^ dh_dstar_pn(src);
-            }
-            DH_BALLOT_ACC(m, bit != 0u, lane);
-        }
-        X.dbits[c] = m;
-    }
-    DH_BARRIER();
-    // Header::viterbi_decode (:86-150) as add-compare-select + decision bits + traceback: the reference carries the
-    // four survivor byte strings instead, which is the same path under the same tie rules (k = 0 wins ties, the
-    // lowest end state wins).  State i = (newest bit << 1) | previous bit; predecessor ((i << 1) & 2) | k.
-    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    {
-        // the four states on the four lanes of every quad: lane i reads the metrics of its two predecessors through
-        // DPP quad permutes ([0,2,0,2] and [1,3,1,3]), its branch words are 00 / 10 / 11 / 01 for k = 0 and the
-        // complement for k = 1; sixteen 2-bit branch distances are computed at once per 32 received bits
-        const uint32_t st = threadIdx.x & 3u;
-        const uint32_t ca = (st == 1u || st == 2u) ? 0x55555555u : 0u;      // first bit of the k = 0 branch word
-        const uint32_t cb = st >= 2u ? 0x55555555u : 0u;                     // second bit
-        uint32_t m = 0;
-#define DH_DSTAR_ACS(q) do { \
+// The forward pass of Header::viterbi_decode (:86-150): add-compare-select over the 330 trellis steps of the de-interleaved bits
+// X.dbits, four decision bits per step into X.dec (step t: bits 4 (t & 7) .. + 3 of word t >> 3, bit i = new state i took k = 1),
+// the four end metrics in m0 .. m3.  State i = (newest bit << 1) | previous bit; predecessor ((i << 1) & 2) | k; k = 0 wins ties.
+// (Device: a macro, not a function -- as an inlined function the loop's exit test came out inverted in k_dstar.)  The four states
+// sit on the four lanes of every quad: lane i reads the metrics of its two predecessors through DPP quad permutes ([0,2,0,2] and
+// [1,3,1,3]), its branch words are 00 / 10 / 11 / 01 for k = 0 and the complement for k = 1 (ca / cb: first / second bit of the
+// k = 0 branch word); sixteen 2-bit branch distances are computed at once per 32 received bits; a round of the loop takes
+// 8 trellis steps = 16 received bits, the last one the steps 328, 329; lanes 0..3 of a vote = new states 0..3.
+#if DH_ON_GPU
+#define DH_DSTAR_ACS_STEP(q) do { \
             const uint32_t a_ = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) m, 0x88, 0xF, 0xF, true) + ((ha >> (2u * (q))) & 3u); \
             const uint32_t b_ = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) m, 0xDD, 0xF, 0xF, true) + ((hb >> (2u * (q))) & 3u); \
-            dw |= ((uint32_t) __ballot(b_ < a_) & 0xFu) << (4u * (q));      /* lanes 0..3 = new states 0..3 */ \
+            dw |= ((uint32_t) __ballot(b_ < a_) & 0xFu) << (4u * (q)); \
             m = b_ < a_ ? b_ : a_; } while (0)
-        for (uint32_t g = 0; g < 42u; g++) {                                 // 8 trellis steps = 16 received bits per round
-            const uint32_t seg = (uint32_t) (X.dbits[g >> 2] >> (16u * (g & 3u))) & 0xFFFFu;
-            const uint32_t ha = ((seg & 0x5555u) ^ (ca & 0x5555u)) + (((seg >> 1) & 0x5555u) ^ (cb & 0x5555u));
-            const uint32_t hb = 0xAAAAu - ha;
-            uint32_t dw = 0;
-            if (g < 41u) {
-                DH_DSTAR_ACS(0); DH_DSTAR_ACS(1); DH_DSTAR_ACS(2); DH_DSTAR_ACS(3);
-                DH_DSTAR_ACS(4); DH_DSTAR_ACS(5); DH_DSTAR_ACS(6); DH_DSTAR_ACS(7);
-            } else { DH_DSTAR_ACS(0); DH_DSTAR_ACS(1); }                     // steps 328, 329
-            X.dec[g] = dw;
-        }
-#undef DH_DSTAR_ACS
-        m0 = (uint32_t) __builtin_amdgcn_readlane((int) m, 0); m1 = (uint32_t) __builtin_amdgcn_readlane((int) m, 1);
-        m2 = (uint32_t) __builtin_amdgcn_readlane((int) m, 2); m3 = (uint32_t) __builtin_amdgcn_readlane((int) m, 3);
+#define DH_DSTAR_ACS(X, m0, m1, m2, m3) { \
+        const uint32_t st = threadIdx.x & 3u; \
+        const uint32_t ca = (st == 1u || st == 2u) ? 0x55555555u : 0u; \
+        const uint32_t cb = st >= 2u ? 0x55555555u : 0u; \
+        uint32_t m = 0; \
+        for (uint32_t g = 0; g < 42u; g++) { \
+            const uint32_t seg = (uint32_t) ((X).dbits[g >> 2] >> (16u * (g & 3u))) & 0xFFFFu; \
+            const uint32_t ha = ((seg & 0x5555u) ^ (ca & 0x5555u)) + (((seg >> 1) & 0x5555u) ^ (cb & 0x5555u)); \
+            const uint32_t hb = 0xAAAAu - ha; \
+            uint32_t dw = 0; \
+            if (g < 41u) { \
+                DH_DSTAR_ACS_STEP(0); DH_DSTAR_ACS_STEP(1); DH_DSTAR_ACS_STEP(2); DH_DSTAR_ACS_STEP(3); \
+                DH_DSTAR_ACS_STEP(4); DH_DSTAR_ACS_STEP(5); DH_DSTAR_ACS_STEP(6); DH_DSTAR_ACS_STEP(7); \
+            } else { DH_DSTAR_ACS_STEP(0); DH_DSTAR_ACS_STEP(1); } \
+            (X).dec[g] = dw; \
+        } \
+        m0 = (uint32_t) __builtin_amdgcn_readlane((int) m, 0); m1 = (uint32_t) __builtin_amdgcn_readlane((int) m, 1); \
+        m2 = (uint32_t) __builtin_amdgcn_readlane((int) m, 2); m3 = (uint32_t) __builtin_amdgcn_readlane((int) m, 3); \
     }
 #else
+inline void dh_dstar_acs_(DhDstarScratch& X, uint32_t& m0, uint32_t& m1, uint32_t& m2, uint32_t& m3) {
     for (uint32_t blk = 0; blk < 11u; blk++) {                     // 32 trellis steps per 64-bit word
         const uint64_t word = X.dbits[blk];
         uint32_t lo = dh_uniform((uint32_t) word), hi = dh_uniform((uint32_t) (word >> 32));
@@ -2483,7 +2365,35 @@ DH_HD bool dh_dstar_header_parse(const DhSymView& syms, uint32_t pos, DhDstarScr
           X.dec[blk * 4u + g] = dw;
         }
     }
+}
+#define DH_DSTAR_ACS(X, m0, m1, m2, m3) dh_dstar_acs_(X, m0, m1, m2, m3)
 #endif
+
+// Header::parseFromHeader (header.cpp:24-58) on the 660 bits at `pos`: true when the path metric is <= 10 and the CRC
+// holds; the 41 header bytes are then in X.out (little-endian words)
+DH_HD bool dh_dstar_header_parse(const DhSymView& syms, uint32_t pos, DhDstarScratch& X) {
+    // descramble + de-interleave (header.cpp:26-30, :60-72): de-interleaved bit idx = 24 k + i comes from received
+    // bit i * 28 + k (i < 12) or 12 + i * 27 + k; 64 bits per vote
+    for (uint32_t c = 0; c < 11u; c++) {
+        uint64_t m = 0;
+        DH_FOR_LANES(lane) {
+            const uint32_t idx = c * 64u + (uint32_t) lane;
+            uint32_t bit = 0;
+            if (idx < 660u) {
+                const uint32_t k = idx / 24u, i = idx % 24u;
+                const uint32_t src = i < 12u ? i * 28u + k : 12u + i * 27u + k;
+                bit = (dh_view_at(syms, pos + src) & 1u) ^ dh_dstar_pn(src);
+            }
+            DH_BALLOT_ACC(m, bit != 0u, lane);
+        }
+        X.dbits[c] = m;
+    }
+    DH_BARRIER();
+    // Header::viterbi_decode (:86-150) as add-compare-select + decision bits + traceback: the reference carries the
+    // four survivor byte strings instead, which is the same path under the same tie rules (k = 0 wins ties, the
+    // lowest end state wins).  State i = (newest bit << 1) | previous bit; predecessor ((i << 1) & 2) | k.
+    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    DH_DSTAR_ACS(X, m0, m1, m2, m3);
     DH_BARRIER();
     uint32_t state = 0, best = m0;
     if (m1 < best) { best = m1; state = 1; }

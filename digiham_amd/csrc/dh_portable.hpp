@@ -13,6 +13,15 @@
 // CPU-only test tier execute the exact wave algorithm (index maths, carries, block-parallel
 // timing recovery) against the oracle without a GPU.  The shipped library contains only the
 // gfx950 build; there is no CPU fallback in the product.
+//
+// THE SEAM.  Everything that differs between the two builds lives in this header and in wave_ops.hpp beside it (the
+// float-vector, LDS and DPP primitives), under ONE predicate, DH_ON_GPU.  Every primitive states once what it computes
+// (NaN behaviour and which lanes' results are defined included), has its gfx950 form and its CPU restatement side by side,
+// and carries the same name and signature in both builds.  The algorithm bodies (*_core.hpp) are a single program: new code
+// never writes a build conditional inside a body -- it adds a primitive here.  The only build conditionals outside the two
+// headers are whole-function pairs at namespace scope, a hand-scheduled kernel piece next to its plain restatement
+// (dh_fir_lane, dh_fir_mfma, dh_fir_f16, dh_agc_scan, the Viterbi forward passes); what the CPU tier proves about the device
+// code it proves through the agreement of these pairs.  tests/test_device_seam.py keeps the rule from eroding.
 #pragma once
 
 #include <stdint.h>
@@ -29,9 +38,23 @@
 #define DH_D inline
 #endif
 
+// the device pass of the gfx950 build: the one predicate of the seam (0 in the CPU harness and in hipcc's host pass)
+#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#define DH_ON_GPU 1
+#else
+#define DH_ON_GPU 0
+#endif
+
+// an expression that differs between the builds, both forms side by side
+#if DH_ON_GPU
+#define DH_GPU_ELSE(gpu, cpu) gpu
+#else
+#define DH_GPU_ELSE(gpu, cpu) cpu
+#endif
+
 #define DH_WAVE 64
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
 // DH_FOR_LANES_FRESH: the lane id passes through an empty volatile asm, so nothing derived from it (per-lane LDS
 // addresses, lane % 10, 64-bit row pointers) is loop-invariant to the compiler.  Left alone it hoists dozens of such
 // values out of the slicer's per-run loop, across the FIR where every register is taken, spills them to scratch and
@@ -48,43 +71,28 @@ static __device__ __forceinline__ int dh_fresh_lane_id_() { int l = (int) thread
 #define DH_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); \
                           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
 #define DH_BALLOT_ACC(mask, pred, lane) (mask) = __builtin_amdgcn_ballot_w64((bool) (pred))      /* (v_cmp straight into the scalar pair; __ballot((pred) ? 1 : 0) left a v_cndmask + v_cmp behind every vote) */
-#define DH_IS_LANE0(lane) ((lane) == 0)
 #else
 #define DH_FOR_LANES(lane) for (int lane = 0; lane < DH_WAVE; ++lane)
 #define DH_FOR_LANES_FRESH(lane) DH_FOR_LANES(lane)
 #define DH_BARRIER() ((void) 0)
 #define DH_BALLOT_ACC(mask, pred, lane) (mask) |= ((uint64_t) ((pred) ? 1 : 0) << (lane))
-#define DH_IS_LANE0(lane) ((lane) == 0)
 #endif
+#define DH_IS_LANE0(lane) ((lane) == 0)
+// DH_IS_LANE0 outside a lane loop: true in the ONE lane that performs a body's wave-uniform global stores (the CPU build runs
+// such code once, for all lanes)
+DH_HD bool dh_is_writer_lane() { return DH_GPU_ELSE(threadIdx.x == 0, true); }
 
 // A value every lane holds identically (loaded from LDS / memory at a wave-uniform address): moving it to a
 // scalar register lets the arithmetic that follows run on the scalar ALU instead of costing VALU issue cycles.
-DH_HD uint32_t dh_uniform(uint32_t x) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t) __builtin_amdgcn_readfirstlane((int) x);
-#else
-    return x;
-#endif
-}
+DH_HD uint32_t dh_uniform(uint32_t x) { return DH_GPU_ELSE((uint32_t) __builtin_amdgcn_readfirstlane((int) x), x); }
 
-DH_HD int dh_popc32(uint32_t x) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return __popc(x);
-#else
-    return __builtin_popcount(x);
-#endif
-}
-
-DH_HD int dh_popc64(uint64_t x) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return __popcll(x);
-#else
-    return __builtin_popcountll(x);
-#endif
-}
+DH_HD int dh_popc32(uint32_t x) { return DH_GPU_ELSE(__popc(x), __builtin_popcount(x)); }
+DH_HD int dh_popc64(uint64_t x) { return DH_GPU_ELSE(__popcll(x), __builtin_popcountll(x)); }
+DH_HD int dh_ffs64(uint64_t x) { return DH_GPU_ELSE(__ffsll((unsigned long long) x) - 1, __builtin_ctzll(x)); }      // index of the lowest set bit, x != 0
+DH_HD int dh_top64(uint64_t x) { return 63 - DH_GPU_ELSE(__clzll((long long) x), __builtin_clzll(x)); }              // index of the highest set bit, x != 0
 
 DH_HD uint32_t dh_brev32(uint32_t x) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
     return __brev(x);
 #else
     x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
@@ -95,17 +103,168 @@ DH_HD uint32_t dh_brev32(uint32_t x) {
 #endif
 }
 
-DH_HD int dh_ffs64(uint64_t x) {   // index of lowest set bit, x != 0
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return __ffsll((unsigned long long) x) - 1;
-#else
-    return __builtin_ctzll(x);
-#endif
-}
-
 template <typename T> DH_HD T dh_min(T a, T b) { return a < b ? a : b; }
 template <typename T> DH_HD T dh_max(T a, T b) { return a > b ? a : b; }
 
 // branch weights: what the register allocator keeps out of the hot path (spill code goes where the weights are low)
 #define DH_LIKELY(x) __builtin_expect(!!(x), 1)
 #define DH_UNLIKELY(x) __builtin_expect(!!(x), 0)
+
+// DH_TO_VGPR: a loop-invariant wave-uniform value that should live in a VGPR rather than compete for the 102 SGPRs
+// DH_COMPILER_FENCE: compiler-only memory fence -- values cached from memory before it must be re-read after it
+// (the CPU build: nothing, both)
+// DH_CONST_TABLE: a constant table both builds index at run time -- on the device it needs an address in device memory
+#if DH_ON_GPU
+#define DH_TO_VGPR(x) asm volatile("" : "+v"(x))
+#define DH_COMPILER_FENCE() asm volatile("" ::: "memory")
+#define DH_CONST_TABLE __device__ static constexpr
+#else
+#define DH_TO_VGPR(x) ((void) 0)
+#define DH_COMPILER_FENCE() ((void) 0)
+#define DH_CONST_TABLE static constexpr
+#endif
+
+// Markers: with -DDH_ASM_MARKERS (tools/asm_census.py) every phase boundary of the slicer (DH_PHASE_MARK*) and every region
+// of the decoders (DH_DMARK) leaves a comment in the assembly, which the census counts instructions between; nothing otherwise.
+// (Round 2-4's per-phase shader-clock builds used the same places; they went with round 5's prune.)
+#if defined(DH_ASM_MARKERS) && DH_ON_GPU
+#define DH_PHASE_MARK_BEGIN() asm volatile("; DH_PHASE begin" ::: "memory")
+#define DH_PHASE_MARK(i) asm volatile("; DH_PHASE " #i ::: "memory")
+#define DH_DMARK(text) asm volatile("; DH_DMARK " text ::: "memory")
+#else
+#define DH_PHASE_MARK_BEGIN() ((void) 0)
+#define DH_PHASE_MARK(i) ((void) 0)
+#define DH_DMARK(text) ((void) 0)
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// Values a lane holds across phases: registers on the GPU, [lane] arrays in the CPU build.
+//   DH_LANE_ARRAY(type, name, n) / DH_LA(name, lane)      n values per lane; DH_LA(name, lane)[i] is this lane's i-th
+//   DH_LANE_VALUE(type, name) / DH_LV(name, lane)         one value per lane
+//     DH_LV_READ(name, k)        the value of lane k, k wave-uniform (v_readlane)
+//     DH_LV_DOWN(name, lane, d)  the value of lane + d; the lane's own where lane + d > 63 (__shfl_down)
+//   DH_LANE_STRUCT(type, name) / DH_LS(name, lane)        a struct of 32-bit fields per lane; as a parameter: DH_LANE_STRUCT_REF, and
+//                                                          DH_LANE_STRUCT_IN for one only read (the device passes it by value)
+//     DH_LS_READ(name, field, k)      field of lane k, k wave-uniform (v_readlane)
+//     DH_LS_WRITE(name, field, k, v)  sets it, k and v wave-uniform (v_writelane: dh_writelane)
+//     DH_LS_GATHER(name, field, j)    field of lane j, j a per-lane value (ds_bpermute; every lane of the wave takes part)
+//   DH_LANES_BELOW(mask, lane)   the number of set bits of `mask` below this lane: an exclusive prefix count of a vote (v_mbcnt)
+#if DH_ON_GPU
+#define DH_LANE_ARRAY(type, name, n) type name[n]
+#define DH_LA(name, lane) name
+#define DH_LANE_VALUE(type, name) type name
+#define DH_LV(name, lane) name
+#define DH_LV_READ(name, k) ((uint32_t) __builtin_amdgcn_readlane((int) (name), (int) (k)))
+#define DH_LV_DOWN(name, lane, d) ((uint32_t) __shfl_down((int) (name), (unsigned) (d), DH_WAVE))
+#define DH_LANE_STRUCT(type, name) type name
+#define DH_LANE_STRUCT_REF(type, name) type& name
+#define DH_LANE_STRUCT_IN(type, name) const type name
+#define DH_LS(name, lane) name
+#define DH_LS_READ(name, field, k) ((uint32_t) __builtin_amdgcn_readlane((int) (name).field, (int) (k)))
+// (v_writelane takes value and lane from scalar registers, a VOP3 of gfx9 reads at most one: the lane select goes through m0,
+// which belongs to the compiler -- a clobber would be ignored -- hence saved and restored around the write)
+static __device__ __forceinline__ uint32_t dh_writelane(uint32_t reg, uint32_t lane, uint32_t v) {
+    const uint32_t sv = (uint32_t) __builtin_amdgcn_readfirstlane((int) v), si = (uint32_t) __builtin_amdgcn_readfirstlane((int) lane);
+    uint32_t keep;
+    asm("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1" : "+v"(reg), "=&s"(keep) : "s"(sv), "s"(si));
+    return reg;
+}
+#define DH_LS_WRITE(name, field, k, v) (name).field = dh_writelane((name).field, (uint32_t) (k), (uint32_t) (v))
+#define DH_LS_GATHER(name, field, j) ((uint32_t) __shfl((int) (name).field, (int) (j), DH_WAVE))
+#define DH_LANES_BELOW(mask, lane) ((uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) ((mask) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) (mask), 0u)))
+#else
+#define DH_LANE_ARRAY(type, name, n) type name[DH_WAVE][n]
+#define DH_LA(name, lane) name[lane]
+#define DH_LANE_VALUE(type, name) type name[DH_WAVE]
+#define DH_LV(name, lane) name[lane]
+#define DH_LV_READ(name, k) ((uint32_t) name[k])
+#define DH_LV_DOWN(name, lane, d) ((uint32_t) name[((lane) + (d)) < DH_WAVE ? (lane) + (d) : (lane)])
+#define DH_LANE_STRUCT(type, name) type name[DH_WAVE]
+#define DH_LANE_STRUCT_REF(type, name) type* name
+#define DH_LANE_STRUCT_IN(type, name) const type* name
+#define DH_LS(name, lane) name[lane]
+#define DH_LS_READ(name, field, k) ((uint32_t) (name)[k].field)
+#define DH_LS_WRITE(name, field, k, v) (name)[k].field = (uint32_t) (v)
+#define DH_LS_GATHER(name, field, j) ((uint32_t) (name)[j].field)
+#define DH_LANES_BELOW(mask, lane) ((uint32_t) dh_popc64((mask) & (((uint64_t) 1 << (lane)) - 1u)))
+#endif
+
+// DH_WAVE words of a wavefront in ONE vector register, word i in lane i, indexed with run-time (wave-uniform) indices:
+// v_readlane / v_writelane take the index from a scalar register, so a read or write is a single instruction with no memory
+// round trip (an LDS copy costs ~100 cycles of latency per access on a serial path, a register array would go to scratch).
+// s[i] reads, s[i] = v writes; load / store move all of them, store_words the words [first, first + n).  The CPU build is a
+// plain array.  (DhState: the decoders' channel state, decoder_core.hpp, is what it holds.)
+struct DhState {
+#if DH_ON_GPU
+    uint32_t reg;
+    __device__ __forceinline__ uint32_t get(uint32_t i) const { return (uint32_t) __builtin_amdgcn_readlane((int) reg, (int) i); }
+    __device__ __forceinline__ void set(uint32_t i, uint32_t v) { reg = dh_writelane(reg, i, v); }
+    __device__ __forceinline__ void load(const uint32_t* g) { reg = threadIdx.x < DH_WAVE ? g[threadIdx.x] : 0u; }
+    __device__ __forceinline__ void store(uint32_t* g) const { if (threadIdx.x < DH_WAVE) g[threadIdx.x] = reg; }
+    __device__ __forceinline__ void store_words(uint32_t* g, uint32_t first, uint32_t n) const { if (threadIdx.x - first < n) g[threadIdx.x - first] = reg; }
+#else
+    uint32_t w[DH_WAVE];
+    uint32_t get(uint32_t i) const { return w[i]; }
+    void set(uint32_t i, uint32_t v) { w[i] = v; }
+    void load(const uint32_t* g) { for (int i = 0; i < DH_WAVE; i++) w[i] = g[i]; }
+    void store(uint32_t* g) const { for (int i = 0; i < DH_WAVE; i++) g[i] = w[i]; }
+    void store_words(uint32_t* g, uint32_t first, uint32_t n) const { for (uint32_t i = 0; i < n; i++) g[i] = w[first + i]; }
+#endif
+    struct Ref {
+        DhState* st; uint32_t i;
+        DH_HD operator uint32_t() const { return st->get(i); }
+        DH_HD Ref& operator=(uint32_t v) { st->set(i, v); return *this; }
+        DH_HD Ref& operator=(const Ref& o) { st->set(i, (uint32_t) o); return *this; }
+        DH_HD uint32_t operator++(int) { const uint32_t v = st->get(i); st->set(i, v + 1u); return v; }
+    };
+    DH_HD Ref operator[](uint32_t i) { return Ref{this, i}; }
+    DH_HD Ref operator[](int i) { return Ref{this, (uint32_t) i}; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The same vocabulary for a workgroup of DH_OP_LANES lanes = DH_OP_WAVES wavefronts whose phases span the whole workgroup (the
+// scan of the packed read-out, outpack_core.hpp): the CPU build's lane loop runs over all 256 lanes, a per-lane value is an
+// array of 256, a per-wavefront value (a vote: a scalar pair on the device) an array of four.
+//   DH_OP_FOR(lane)                                    the lane loop
+//   DH_OP_VAL(type, name) / DH_OP_V(name, lane)        a value per lane: a register
+//   DH_OP_WAVE_VAL(type, name) / DH_OP_W(name, lane)   a value per wavefront, as the lane's wavefront holds it: a scalar pair
+//   DH_OP_VOTE(name, pred, lane)     the wavefront's vote on pred, bit l = its lane l; DH_OP_CLEAR_VOTES(name) before the loop that votes
+//   DH_OP_WAVE_SCAN(name)            inclusive prefix sum inside each wavefront (64-bit values): six steps of "add what the lane d
+//                                    below holds" (ds_bpermute)
+//   DH_OP_WAVE_MAX(dst, src)         the largest value (unsigned, 32 bits) of each wavefront, in all of its lanes
+#define DH_OP_LANES 256u                    /* lanes of the scan's workgroup = channels one pass of the scan covers */
+#define DH_OP_WAVES (DH_OP_LANES / DH_WAVE)
+#if DH_ON_GPU
+#define DH_OP_FOR(lane) for (uint32_t lane = threadIdx.x, dh_once_ = 1; dh_once_; dh_once_ = 0)
+#define DH_OP_VAL(type, name) type name[1]
+#define DH_OP_WAVE_VAL(type, name) type name[1]
+#define DH_OP_V(name, lane) name[0]
+#define DH_OP_W(name, lane) name[0]
+#define DH_OP_VOTE(name, pred, lane) name[0] = __builtin_amdgcn_ballot_w64((bool) (pred))
+#define DH_OP_CLEAR_VOTES(name) ((void) 0)
+#define DH_OP_WAVE_SCAN(name) do { \
+        const uint32_t wl_ = threadIdx.x & (DH_WAVE - 1u); \
+        for (uint32_t d_ = 1; d_ < DH_WAVE; d_ <<= 1) { \
+            const uint64_t t_ = (uint64_t) __shfl_up((unsigned long long) name[0], d_, DH_WAVE); \
+            if (wl_ >= d_) name[0] += t_; \
+        } } while (0)
+#define DH_OP_WAVE_MAX(dst, src) do { \
+        dst[0] = src[0]; \
+        for (uint32_t d_ = 1; d_ < DH_WAVE; d_ <<= 1) { const uint32_t t_ = (uint32_t) __shfl_xor((int) dst[0], (int) d_, DH_WAVE); if (t_ > dst[0]) dst[0] = t_; } \
+    } while (0)
+#else
+#define DH_OP_FOR(lane) for (uint32_t lane = 0; lane < DH_OP_LANES; ++lane)
+#define DH_OP_VAL(type, name) type name[DH_OP_LANES]
+#define DH_OP_WAVE_VAL(type, name) type name[DH_OP_WAVES]
+#define DH_OP_V(name, lane) name[lane]
+#define DH_OP_W(name, lane) name[(lane) / DH_WAVE]
+#define DH_OP_VOTE(name, pred, lane) name[(lane) / DH_WAVE] |= (uint64_t) ((pred) ? 1 : 0) << ((lane) % DH_WAVE)
+#define DH_OP_CLEAR_VOTES(name) do { for (uint32_t w_ = 0; w_ < DH_OP_WAVES; ++w_) name[w_] = 0; } while (0)
+#define DH_OP_WAVE_SCAN(name) do { for (uint32_t l_ = 1; l_ < DH_OP_LANES; ++l_) if (l_ % DH_WAVE) name[l_] += name[l_ - 1]; } while (0)
+#define DH_OP_WAVE_MAX(dst, src) do { \
+        for (uint32_t w_ = 0; w_ < DH_OP_WAVES; ++w_) { \
+            uint32_t m_ = 0; \
+            for (uint32_t l_ = 0; l_ < DH_WAVE; ++l_) if (src[w_ * DH_WAVE + l_] > m_) m_ = src[w_ * DH_WAVE + l_]; \
+            for (uint32_t l_ = 0; l_ < DH_WAVE; ++l_) dst[w_ * DH_WAVE + l_] = m_; \
+        } } while (0)
+#endif

@@ -20,6 +20,7 @@
 #pragma once
 
 #include "dh_portable.hpp"
+#include "wave_ops.hpp"
 
 #define DH_VARIANCE_SYMBOLS 100      // include/gfsk_demodulator.hpp:5
 #define DH_VOLUME_RB_SIZE 100        // include/gfsk_demodulator.hpp:6
@@ -162,28 +163,8 @@ DH_HD DhDspShared dh_dsp_carve(void* base, uint32_t sps, uint32_t nz = 0) {     
     return S;
 }
 
-// Phase markers: with -DDH_ASM_MARKERS (tools/asm_census.py) every phase boundary of the slicer leaves a comment in the assembly; nothing otherwise.
-// (Round 2-4's per-phase shader-clock builds used the same places; they went with round 5's prune.)
-#if defined(DH_ASM_MARKERS) && DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-// (static census of the phases in the assembly: tools/asm_census.py counts the instructions between these comments)
-#define DH_PHASE_MARK_BEGIN() asm volatile("; DH_PHASE begin" ::: "memory")
-#define DH_PHASE_MARK(i) asm volatile("; DH_PHASE " #i ::: "memory")
-#else
-#define DH_PHASE_MARK_BEGIN() ((void) 0)
-#define DH_PHASE_MARK(i) ((void) 0)
-#endif
-
 // (Wave priorities -- s_setprio around the FIR and in the decoder half -- were worth 2 % in round 2 and nothing since the FIR moved to
 // the matrix cores: removed in round 5; the policies and their A/B logs are in git history and profiles/r03_b_ab_logs.txt.)
-
-// per-lane values that must survive a barrier: registers on the GPU, [lane] arrays in the harness
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_LANE_ARRAY(type, name, n) type name[n]
-#define DH_LA(name, lane) name
-#else
-#define DH_LANE_ARRAY(type, name, n) type name[DH_WAVE][n]
-#define DH_LA(name, lane) name[lane]
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // (float)((double)acc / gain), the reference's `sum / gain` with a double gain, without paying an
@@ -226,47 +207,6 @@ DH_HD float dh_div_gain(float acc, double gain, double rgain) {
     return suspect ? dh_div_gain_exact(acc, gain) : y;
 }
 
-// x / d for a float constant d (the samples per symbol: `volume_sum / samplesPerSymbol`, gfsk_demodulator.cpp:83), r =
-// RN(1 / d): q0 = RN(x r) is within 1 ulp of x / d, the FMA delivers the residual x - d q0 exactly, and
-// RN(q0 + residual * r) is then the correctly rounded quotient (Markstein's theorem; it needs r correctly rounded and
-// no underflow / overflow on the way).  Three instructions instead of the eleven of an IEEE division; 0, tiny, huge
-// and non-finite x (anything outside 2^-100 <= |x| <= 2^100) take the real division.  tests/test_numerics.py runs all
-// 2^32 floats through it for d = 10 (and the other sps values on a sample).
-DH_HD float dh_div_const(float x, float d, float r) {
-    union { float f; uint32_t u; } a; a.f = x;
-    const uint32_t t = (a.u << 1) - 2u * 0x0D800000u;                   // bits(2^-100) = (127 - 100) << 23
-    if (t > 2u * (0x71800000u - 0x0D800000u)) return x / d;             // bits(2^100) = (127 + 100) << 23
-    const float q0 = x * r;
-    const float rem = __builtin_fmaf(-q0, d, x);
-    return __builtin_fmaf(rem, r, q0);
-}
-
-// the same for a pair of operands (device: v_pk_mul_f32 + two v_pk_fma_f32 for both; one range test on the larger of the two words)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-typedef float dh_f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ dh_f2v dh_div_const2(dh_f2v x, float d, float r) {
-    const uint32_t ta = (__float_as_uint(x.x) << 1) - 2u * 0x0D800000u, tb = (__float_as_uint(x.y) << 1) - 2u * 0x0D800000u;
-    if (__builtin_expect((ta > tb ? ta : tb) > 2u * (0x71800000u - 0x0D800000u), 0)) { dh_f2v q; q.x = dh_div_const(x.x, d, r); q.y = dh_div_const(x.y, d, r); return q; }
-    const dh_f2v rr = { r, r }, dd = { -d, -d };
-    const dh_f2v q0 = x * rr;
-    const dh_f2v rem = __builtin_elementwise_fma(q0, dd, x);
-    return __builtin_elementwise_fma(rem, rr, q0);
-}
-#endif
-
-// loop-invariant wave-uniform values that should live in VGPRs rather than compete for the 102 SGPRs
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_TO_VGPR(x) asm volatile("" : "+v"(x))
-#else
-#define DH_TO_VGPR(x) ((void) 0)
-#endif
-// compiler-only memory fence: values cached from memory before it must be re-read after it
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_COMPILER_FENCE() asm volatile("" ::: "memory")
-#else
-#define DH_COMPILER_FENCE() ((void) 0)
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // FIR pass: lane computes outputs [base, base+16) of the tile from the padded LDS window.
 //   x[e] = xs[DH_XPAD(e)] holds input sample (tile_start - NZ + e);  out[j] = sum_i c[i]*x[base+j+i]
@@ -276,60 +216,6 @@ __device__ __forceinline__ dh_f2v dh_div_const2(dh_f2v x, float d, float r) {
 // of group B.  The sliding window then holds pairs (x[t], x[t+8]); sliding by one tap renames
 // pairs instead of re-aligning them, and one ds_read2_b32 fills a pair.  Straight-line after
 // unrolling: 8 window pairs + 8 accumulator pairs + the taps (one VGPR each).
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-typedef float dh_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ dh_f2 dh_f2_make(float a, float b) { dh_f2 v; v.x = a; v.y = b; return v; }
-template <bool FAST> __device__ __forceinline__ dh_f2 dh_f2_mac(float c, dh_f2 w, dh_f2 acc) {
-    if (FAST) { const dh_f2 cc = dh_f2_make(c, c); return __builtin_elementwise_fma(cc, w, acc); }   // v_pk_fma_f32
-    const dh_f2 p = c * w;                                 // v_pk_mul_f32, rounded
-    return acc + p;                                        // v_pk_add_f32, rounded (-ffp-contract=off)
-}
-// The same with the tap as ONE HALF of a 64-bit scalar register pair (two taps per pair, chosen with op_sel): the
-// packed multiply takes the pair as its scalar operand, so the taps occupy 41 / 81 SGPRs instead of as many VGPRs.
-// Left to the compiler a scalar tap becomes a (c, c) pair -- two SGPRs per tap, which spills SGPRs into VGPR lanes
-// in the slicer kernel -- hence the explicit instruction.
-template <bool FAST, int HALF> __device__ __forceinline__ dh_f2 dh_f2_mac_pair(dh_f2 cc, dh_f2 w, dh_f2 acc) {
-    dh_f2 p;
-    if (FAST) {
-        if (HALF == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(p) : "s"(cc), "v"(w), "v"(acc));
-        else           asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(p) : "s"(cc), "v"(w), "v"(acc));
-        return p;
-    }
-    if (HALF == 0) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(p) : "s"(cc), "v"(w));
-    else           asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(p) : "s"(cc), "v"(w));
-    return acc + p;                                        // v_pk_add_f32, rounded (-ffp-contract=off)
-}
-#else
-struct dh_f2 { float x, y; };
-inline dh_f2 dh_f2_make(float a, float b) { dh_f2 v; v.x = a; v.y = b; return v; }
-template <bool FAST> inline dh_f2 dh_f2_mac(float c, dh_f2 w, dh_f2 acc) {
-    if (FAST) return dh_f2_make(__builtin_fmaf(c, w.x, acc.x), __builtin_fmaf(c, w.y, acc.y));
-    const float px = c * w.x, py = c * w.y;
-    return dh_f2_make(acc.x + px, acc.y + py);
-}
-#endif
-// element-wise pair arithmetic for both builds (device: v_pk_add_f32 / v_pk_fma_f32)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ dh_f2 dh_f2_add(dh_f2 a, dh_f2 b) { return a + b; }
-__device__ __forceinline__ dh_f2 dh_f2_sub(dh_f2 a, dh_f2 b) { return a - b; }
-__device__ __forceinline__ dh_f2 dh_f2_fma(dh_f2 a, dh_f2 b, dh_f2 c) { return __builtin_elementwise_fma(a, b, c); }
-#else
-inline dh_f2 dh_f2_add(dh_f2 a, dh_f2 b) { return dh_f2_make(a.x + b.x, a.y + b.y); }
-inline dh_f2 dh_f2_sub(dh_f2 a, dh_f2 b) { return dh_f2_make(a.x - b.x, a.y - b.y); }
-inline dh_f2 dh_f2_fma(dh_f2 a, dh_f2 b, dh_f2 c) { return dh_f2_make(__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)); }
-#endif
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ dh_f2 dh_f2_scale(dh_f2 a, float s) { const dh_f2 ss = { s, s }; return a * ss; }
-// min(|a|, |b|, |c|) in one instruction; a NaN operand is skipped (v_min3_f32), so callers that must notice a NaN distance make
-// sure ALL THREE are NaN then (they are: every distance of a symbol hangs on the same average and extremes) -- see P5
-__device__ __forceinline__ float dh_min3_abs(float a, float b, float c) { float r; asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-#else
-inline dh_f2 dh_f2_scale(dh_f2 a, float s) { return dh_f2_make(a.x * s, a.y * s); }
-inline float dh_min3_abs(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b)), __builtin_fabsf(c)); }
-#endif
-#if !(DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__))
-inline dh_f2 dh_div_const2(dh_f2 x, float d, float r) { return dh_f2_make(dh_div_const(x.x, d, r), dh_div_const(x.y, d, r)); }
-#endif
 #define DH_FIR_H (DH_FIR_L / 2)
 #define DH_XLOFF(e) ((e) + ((e) >> 4))                 // dword offset of window element e from the lane's base
 
@@ -337,16 +223,8 @@ inline dh_f2 dh_div_const2(dh_f2 x, float d, float r) { return dh_f2_make(dh_div
 template <bool FAST>
 DH_HD void dh_fir_finish(const float* acc, double gain, double rgain, float inv_gain, float* out16, bool* nonfinite = nullptr) {
     if (FAST) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        // one v_mul_f32 per output, from where the accumulator half lies to where the output is wanted: left to itself the
-        // compiler packs the multiplies and pays for it with ~29 register moves (halves gathered into pairs before, results
-        // copied into the outputs' registers after)
 #pragma unroll
-        for (int j = 0; j < DH_FIR_L; j++) asm("v_mul_f32 %0, %1, %2" : "=v"(out16[j]) : "s"(inv_gain), "v"(acc[j]));
-#else
-#pragma unroll
-        for (int j = 0; j < DH_FIR_L; j++) out16[j] = acc[j] * inv_gain;
-#endif
+        for (int j = 0; j < DH_FIR_L; j++) out16[j] = dh_mul_uniform(inv_gain, acc[j]);
         if (nonfinite) {                                  // NaN or infinity in any accumulator: 0 * acc is then NaN
             float t = 0.0f;
 #pragma unroll
@@ -373,7 +251,7 @@ DH_HD void dh_fir_finish(const float* acc, double gain, double rgain, float inv_
     }
 }
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
 // Window pairs come from LDS through inline asm: every sample is needed twice, 8 taps apart -- first as the high
 // half of a pair, then as the low half of another.  Given ordinary loads the compiler keeps the first copy, pairs
 // up adjacent addresses instead, and shuffles halves with ~2 v_mov per tap on the VALU, which is the bottleneck
@@ -382,24 +260,6 @@ DH_HD void dh_fir_finish(const float* acc, double gain, double rgain, float inv_
 // them, so each batch passes through an explicit `s_waitcnt lgkmcnt(0)` (robust against any other LDS / scalar
 // memory operation the compiler may have in flight) before its first use.
 #define DH_FIR_G 4
-template <int O0, int O1> __device__ __forceinline__ dh_f2 dh_lds_read2(uint32_t addr) {
-    static_assert(O0 < 256 && O1 < 256, "ds_read2_b32 offsets are 8-bit dword counts");
-    dh_f2 v;
-    asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v) : "v"(addr), "n"(O0), "n"(O1) : "memory");
-    return v;
-}
-// (eight bytes from a four-byte aligned address: the queue's LDS alignment mode is "unaligned" on this target)
-template <int OFF_BYTES> __device__ __forceinline__ dh_f2 dh_lds_read_b64(uint32_t addr) {
-    dh_f2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF_BYTES) : "memory");
-    return v;
-}
-typedef float dh_v4f __attribute__((ext_vector_type(4)));
-template <int OFF_BYTES> __device__ __forceinline__ dh_v4f dh_lds_read_b128(uint32_t addr) {
-    dh_v4f v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF_BYTES) : "memory");
-    return v;
-}
 // pair i of the slide sequence: (x[8 + i], x[16 + i]), consumed when tap i has been accumulated
 template <int NZ, int I> __device__ __forceinline__ void dh_fir_issue_one(uint32_t addr, dh_f2& d) {
     if constexpr (I < NZ) d = dh_lds_read2<DH_XLOFF(DH_FIR_H + I), DH_XLOFF(2 * DH_FIR_H + I)>(addr);
@@ -541,13 +401,6 @@ inline void dh_fir_lane(const float* taps, double gain, double rgain, float inv_
 }
 #endif
 
-// four consecutive floats from a 4-byte-aligned address (global_load_dwordx4: gfx950 allows dword alignment)
-struct __attribute__((aligned(4))) dh_f4 { float x, y, z, w; };
-struct alignas(16) dh_f4a { float x, y, z, w; };     // 16-byte aligned: one ds_read_b128
-DH_HD dh_f4 dh_load4_unaligned(const float* p) { dh_f4 v; __builtin_memcpy(&v, p, sizeof(v)); return v; }
-DH_HD void dh_store4(float* q, const dh_f4& v) { q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
-DH_HD void dh_store4_unaligned(float* q, const dh_f4& v) { __builtin_memcpy(q, &v, sizeof(v)); }   // global_store_dwordx4
-
 // ---------------------------------------------------------------------------------------------
 // The fused FIR on the matrix pipe (error-bounded and FAST wide-filter kernels): v_mfma_f32_16x16x4_f32 is bit for bit a
 // k-ordered chain of f32 FMAs, at the same FLOP rate as v_pk_fma_f32 -- but it issues beside the VALU, which the rest
@@ -569,8 +422,7 @@ DH_HD void dh_store4_unaligned(float* q, const dh_f4& v) { __builtin_memcpy(q, &
 // word o): sixteen ds_write_b32 at compile-time offsets from one per-lane base (2-way bank conflicts, which a 4-byte
 // store hides behind its own issue time).
 #define DH_MF_OUT(T, r, g, n) (128u * (uint32_t) (g) + (uint32_t) (n) + 32u * (uint32_t) (r) + 16u * ((uint32_t) (T) & 1u) + 512u * ((uint32_t) (T) >> 1))
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-typedef float dh_f32x4 __attribute__((ext_vector_type(4)));
+#if DH_ON_GPU
 // acc[4 T + r] of lane (n, g) = sum over the chain for output DH_MF_OUT(T, r, g, n); `tapsf` points at tap 0 of the
 // zero-framed table, `xs` at the padded window
 template <int NZ>
@@ -650,29 +502,6 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 #define DH_F16_ROW_BLOCK(m) (2u * ((uint32_t) (m) & 3u) + (((uint32_t) (m) >> 2) & 1u) + 8u * ((uint32_t) (m) >> 3))
 #define DH_F16_OUT(T, r, g, n) (256u * (uint32_t) (T) + 128u * ((uint32_t) (g) >> 1) + 32u * (uint32_t) (r) + 16u * ((uint32_t) (g) & 1u) + (uint32_t) (n))
 
-// IEEE binary16 <-> binary32 in integer arithmetic (host and harness; the device converts in hardware): round to nearest even
-DH_HD uint16_t dh_f16_bits(float f) {
-    union { float f; uint32_t u; } v; v.f = f;
-    const uint32_t sign = (v.u >> 16) & 0x8000u, a = v.u & 0x7FFFFFFFu;
-    if (a >= 0x7F800000u) return (uint16_t) (sign | (a > 0x7F800000u ? 0x7E00u : 0x7C00u));
-    if (a >= 0x477FF000u) return (uint16_t) (sign | 0x7C00u);                         // >= 65520 rounds to infinity
-    if (a < 0x33000001u) return (uint16_t) sign;                                      // <= 2^-25: zero (the tie goes to even = 0)
-    const int e = (int) (a >> 23) - 127;
-    uint32_t man = (a & 0x7FFFFFu) | 0x800000u, shift = e < -14 ? (uint32_t) (13 + (-14 - e)) : 13u;
-    uint32_t q = man >> shift; const uint32_t rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1u);
-    if (rem > half || (rem == half && (q & 1u))) q++;
-    const uint32_t bits = e < -14 ? q : ((uint32_t) (e + 15 - 1) << 10) + q;           // (the implicit bit of q carries into the exponent)
-    return (uint16_t) (sign | bits);
-}
-DH_HD float dh_f16_value(uint16_t h) {
-    const uint32_t sign = (uint32_t) (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
-    union { float f; uint32_t u; } v;
-    if (e == 31u) v.u = sign | 0x7F800000u | (m << 13);
-    else if (e == 0u) { v.f = (float) m * 5.9604644775390625e-08f; v.u |= sign; }     // m 2^-24
-    else v.u = sign | ((e + 112u) << 23) | (m << 13);
-    return v.f;
-}
-
 // the split of a tap and the per-lane B operands (host, once per engine): frag[f][lane][d], f = 0..2 the g1 slices, 3..5 the g2 slices
 struct DhF16Taps {
     uint32_t frag[2 * DH_F16_MAX_KSTEPS][DH_WAVE][4];        // the first 2 * DH_F16_KSTEPS_OF(nz) are used
@@ -724,26 +553,7 @@ inline float dh_f16_error_coefficient(const DhF16Taps& F, uint32_t nz, double ga
     return f;
 }
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-typedef _Float16 dh_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 dh_h4 __attribute__((ext_vector_type(4)));
-typedef uint32_t dh_u4 __attribute__((ext_vector_type(4)));
-// four samples -> four halves of h1 and of h2 (scale = 2^-k as a float)
-typedef _Float16 dh_h2 __attribute__((ext_vector_type(2)));
-// (Round 4 tried the second half as ONE fused operation per sample, h2 = f16(fma(x, 2^11 scale, -2^11 h1)) with v_fma_mixlo / mixhi_f16
-// reading 2^11 h1 as a half: bit-identical, two and a half instructions per sample instead of three and a half -- and no faster,
-// because v_fma_mix* issues at 8.2 cycles per wavefront against 4.2 for the conversions and packed operations it replaces
-// (tools/microbench/valu_rate.hip).  Dropped.)
-__device__ __forceinline__ void dh_f16_split4(const dh_f4& v, float scale, dh_h4& h1, dh_h4& h2) {
-    const float x[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float xs = x[i] * scale;                            // exact (power of two)
-        const _Float16 a = (_Float16) xs;                         // v_cvt_f16_f32: round to nearest even
-        const float r = xs - (float) a;                           // exact
-        h1[i] = a; h2[i] = (_Float16) (r * 2048.0f);
-    }
-}
+#if DH_ON_GPU
 // acc16[4 T + r] of lane (n, g) = y-before-gain of output DH_F16_OUT(T, r, g, n) in the scaled domain: main + 2^-11 second sum
 // is formed by the caller's fma (k1, k2).  `hw` = the window block (h1 at byte 0, h2 at DH_F16_H2_OFFSET words), G = the six
 // tap fragments of this lane.
@@ -793,15 +603,6 @@ __device__ __forceinline__ void dh_fir_f16(const float* hw, const dh_u4 (&G)[2 *
 #else
 // harness: the same split and the same sums as plain f32 chains (products of halves are exact in f32; a sequential chain of
 // 96 rounded additions stays inside what (H1) allows the hardware, so the decisions downstream are the same)
-inline void dh_f16_split4(const dh_f4& v, float scale, uint16_t* h1, uint16_t* h2) {
-    const float x[4] = { v.x, v.y, v.z, v.w };
-    for (int i = 0; i < 4; i++) {
-        const float xs = x[i] * scale;
-        h1[i] = dh_f16_bits(xs);
-        const float r = xs - dh_f16_value(h1[i]);
-        h2[i] = dh_f16_bits(r * 2048.0f);
-    }
-}
 template <int NZ>
 inline void dh_fir_f16(const float* hw, const uint32_t (*G)[DH_WAVE][4], int lane, float k1, float k2, float* out16) {
     constexpr int DH_F16_KSTEPS = DH_F16_KSTEPS_OF(NZ), DH_F16_H2_OFFSET = DH_F16_H2_OFFSET_OF(NZ);
@@ -824,39 +625,6 @@ inline void dh_fir_f16(const float* hw, const uint32_t (*G)[DH_WAVE][4], int lan
 }
 #endif
 
-// Four consecutive floats to LDS at `base` + a compile-time offset (the padded window is only dword aligned, so the
-// widest store the hardware takes is a dword pair; the compiler adds the offset to the base with one VALU instruction
-// per pair because a ds_write2_b32 offset only reaches 255 dwords -- four ds_write_b32 with 16-bit byte offsets cost
-// LDS issue slots, which this kernel has to spare, and no VALU at all).  The stores are invisible to the compiler's
-// wait-count tracking: dh_lds_stores_done() must come before the barrier that publishes them.
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-template <int OFF_WORDS> __device__ __forceinline__ void dh_lds_store4_at(float* base, const dh_f4& v) {
-    static_assert(4 * OFF_WORDS + 12 < 65536, "ds_write_b32 offsets are 16-bit byte counts");
-    const uint32_t addr = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) base;
-    asm volatile("ds_write_b32 %0, %1 offset:%5\n\tds_write_b32 %0, %2 offset:%6\n\tds_write_b32 %0, %3 offset:%7\n\tds_write_b32 %0, %4 offset:%8"
-                 :: "v"(addr), "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "n"(4 * OFF_WORDS), "n"(4 * OFF_WORDS + 4), "n"(4 * OFF_WORDS + 8), "n"(4 * OFF_WORDS + 12) : "memory");
-}
-__device__ __forceinline__ void dh_lds_stores_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// ten floats into one column of the transposed variance ring (row i is DH_VARIANCE_SYMBOLS words further; K = column offset):
-// ten ds_write_b32 with immediate offsets from one address, no vector arithmetic (see dh_lds_store4_at)
-template <int K> __device__ __forceinline__ void dh_lds_store_row10(float* base, float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, float a8, float a9) {
-    const uint32_t addr = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) base;
-    asm volatile("ds_write_b32 %0, %1 offset:%11\n\tds_write_b32 %0, %2 offset:%12\n\tds_write_b32 %0, %3 offset:%13\n\tds_write_b32 %0, %4 offset:%14\n\t"
-                 "ds_write_b32 %0, %5 offset:%15\n\tds_write_b32 %0, %6 offset:%16\n\tds_write_b32 %0, %7 offset:%17\n\tds_write_b32 %0, %8 offset:%18\n\t"
-                 "ds_write_b32 %0, %9 offset:%19\n\tds_write_b32 %0, %10 offset:%20"
-                 :: "v"(addr), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(a6), "v"(a7), "v"(a8), "v"(a9),
-                    "n"(4 * K), "n"(4 * (K + 100)), "n"(4 * (K + 200)), "n"(4 * (K + 300)), "n"(4 * (K + 400)), "n"(4 * (K + 500)), "n"(4 * (K + 600)),
-                    "n"(4 * (K + 700)), "n"(4 * (K + 800)), "n"(4 * (K + 900)) : "memory");
-}
-#else
-template <int K> inline void dh_lds_store_row10(float* base, float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, float a8, float a9) {
-    const float a[10] = { a0, a1, a2, a3, a4, a5, a6, a7, a8, a9 };
-    for (int i = 0; i < 10; i++) base[i * 100 + K] = a[i];
-}
-template <int OFF_WORDS> inline void dh_lds_store4_at(float* base, const dh_f4& v) { dh_store4(base + OFF_WORDS, v); }
-inline void dh_lds_stores_done() {}
-#endif
-
 // virtual input stream of a channel for this push: carried tail followed by the new samples
 DH_HD float dh_virtual_sample(const float* tail, uint32_t tc, const float* in, uint32_t idx) {
     return idx < tc ? tail[idx] : in[idx - tc];
@@ -867,84 +635,16 @@ DH_HD float dh_virtual_sample(const float* tail, uint32_t tc, const float* in, u
 // gfsk_demodulator.cpp:109-116): S.mn[k] / S.mx[k] = min / max over the volume ring as it stands
 // right after symbol k was written.  The reference seeds min with FLT_MAX and max with FLT_MIN
 // (sic: the smallest positive float), which are exactly the identities used for padding here.
-#define DH_FLT_MAX 3.402823466e+38f
-#define DH_DBL_MAX 1.7976931348623157e+308
-#define DH_FLT_MIN 1.175494351e-38f
-// an upper bound of sqrt(x), x >= 0 (a tolerance may be generous, never short): the hardware's v_sqrt_f32 (1 ulp, one
-// instruction -- the correctly rounded square root this file is compiled for is twenty) on an argument kept away from
-// the denormals, times 1 + 2^-20
-DH_HD float dh_sqrt_upper(float x) {
-    const float a = x > 1e-30f ? x : 1e-30f;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_sqrtf(a) * 1.00000095367431640625f;
-#else
-    return __builtin_sqrtf(a) * 1.00000095367431640625f;
-#endif
-}
-DH_HD float dh_fmin_(float a, float b) { return b < a ? b : a; }
-DH_HD float dh_fmax_(float a, float b) { return b > a ? b : a; }
-// the extremes of a lane's two symbols 2 l, 2 l + 1 (device: what the scan hands to the slicing phase in registers; the
-// harness's scan leaves its results in S.mn / S.mx only)
+// `agc`: the extremes of ring slots 2 l and 2 l + 1 once more, as a per-lane value -- what the scan hands to the slicing phase in
+// registers.  Defined for the slots k0 .. k1 - 1 (the others: some value of the block, never looked at).
 struct DhAgcPair { float mn0, mx0, mn1, mx1; };
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-// v_min_f32 / v_max_f32 return the operand that is not NaN -- exactly what `if (v < min) min = v` does with a
-// NaN entry (it is skipped) -- and cost one VALU instruction where compare + select cost two.
-__device__ __forceinline__ float dh_vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float dh_vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// Inclusive wave64 prefix min (mn) and max (mx) in lane order, on the VALU's DPP network: row_shr 1/2/4/8 inside
-// each row of 16, then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3.  Lanes without a source
-// keep their value.  A DPP read needs two wait states after the VALU write of its source: the min / max streams
-// are interleaved and padded with s_nop (inline asm gets no hazard handling from the compiler).
-__device__ __forceinline__ void dh_wave_prefix_minmax(float& mn, float& mx) {
-#define DH_SCAN_STEP(ctrl) \
-    "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 " ctrl "\n\tv_max_f32_dpp %1, %1, %1 " ctrl "\n\t"
-    asm volatile("s_nop 4\n\t"                 // a VALU write of EXEC just before would need 5 wait states ahead of a DPP op
-                 DH_SCAN_STEP("row_shr:1 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP("row_shr:2 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP("row_shr:4 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP("row_shr:8 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 DH_SCAN_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 1"
-                 : "+v"(mn), "+v"(mx));
-#undef DH_SCAN_STEP
-}
-// The same for TWO pairs at once (prefix and suffix scans of the AGC): four streams interleaved, so that a DPP read always finds its
-// source written three instructions earlier (two wait states are needed) -- no s_nop between the steps, 25 instructions instead of 40.
-__device__ __forceinline__ void dh_wave_prefix_minmax2(float& mn, float& mx, float& mn2, float& mx2) {
-#define DH_SCAN_STEP4(ctrl) \
-    "v_min_f32_dpp %0, %0, %0 " ctrl "\n\tv_max_f32_dpp %1, %1, %1 " ctrl "\n\tv_min_f32_dpp %2, %2, %2 " ctrl "\n\tv_max_f32_dpp %3, %3, %3 " ctrl "\n\t"
-    asm volatile("s_nop 4\n\t"
-                 DH_SCAN_STEP4("row_shr:1 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP4("row_shr:2 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP4("row_shr:4 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP4("row_shr:8 row_mask:0xf bank_mask:0xf")
-                 DH_SCAN_STEP4("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 DH_SCAN_STEP4("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 1"
-                 : "+v"(mn), "+v"(mx), "+v"(mn2), "+v"(mx2));
-#undef DH_SCAN_STEP4
-}
-// the previous lane's value of four registers at once (lane 0 keeps the identities it is given)
-__device__ __forceinline__ void dh_wave_prev4(float& a, float& b, float& c, float& d, float va, float vb, float vc, float vd) {
-    asm volatile("s_nop 4\n\tv_mov_b32_dpp %0, %4 wave_shr:1 row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %1, %5 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mov_b32_dpp %2, %6 wave_shr:1 row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %3, %7 wave_shr:1 row_mask:0xf bank_mask:0xf\n\ts_nop 1"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(va), "v"(vb), "v"(vc), "v"(vd));
-}
-// value of the previous lane (lane 0 keeps `first`): wave_shr:1
-__device__ __forceinline__ float dh_wave_prev(float v, float first) {
-    float r = first;
-    asm volatile("s_nop 4\n\tv_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf\n\ts_nop 1" : "+v"(r) : "v"(v));
-    return r;
-}
-
+#if DH_ON_GPU
 // lane l owns ring slots 2l and 2l+1 for the prefix part; the suffix part is the same scan over the ring read
 // backwards (lane l takes slots 126-2l and 127-2l), handed back to the owning lanes -- lane 63 - l -- by four ds_bpermute
 // (until round 5 through S.mn / S.mx: four stores, a barrier, four loads, a barrier -- one LDS round trip more).  The lane's
-// results (slots 2l and 2l+1) are also returned: the slicing phase of a run that starts its block takes them from there.
-__device__ __forceinline__ DhAgcPair dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1) {
+// results (slots 2l and 2l+1) also stay in registers: the slicing phase of a run that starts its block takes them from there.
+__device__ __forceinline__ void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc)) {
     const int lane = dh_fresh_lane_id_();
     const uint32_t e0 = 2u * (uint32_t) lane, e1 = e0 + 1u;
     // prefix source: old below k0, new in [k0, k1), identity above
@@ -975,10 +675,10 @@ __device__ __forceinline__ DhAgcPair dh_agc_scan(DhDspShared& S, uint32_t k0, ui
     r.mn0 = dh_vmin(dh_vmin(epmn, pmn0), s0n); r.mx0 = dh_vmax(dh_vmax(epmx, pmx0), s0x);
     r.mn1 = dh_vmin(pmn, s1n); r.mx1 = dh_vmax(pmx, s1x);
     S.mn[e0] = r.mn0; S.mx[e0] = r.mx0; S.mn[e1] = r.mn1; S.mx[e1] = r.mx1;
-    return r;
+    agc = r;
 }
 #else
-inline void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1) {
+inline void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc)) {
     // plain sequential statement of the same thing (harness only)
     float pmn = DH_FLT_MAX, pmx = DH_FLT_MIN;
     for (uint32_t j = 0; j < k0; j++) { pmn = dh_fmin_(pmn, S.vol_old[j]); pmx = dh_fmax_(pmx, S.vol_old[j]); }
@@ -988,18 +688,10 @@ inline void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1) {
         for (uint32_t j = k + 1; j < DH_VOLUME_RB_SIZE; j++) { smn = dh_fmin_(smn, S.vol_old[j]); smx = dh_fmax_(smx, S.vol_old[j]); }
         S.mn[k] = dh_fmin_(pmn, smn); S.mx[k] = dh_fmax_(pmx, smx);
     }
-}
-#endif
-
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-// minimum of lanes 0..15 (one DPP row), valid in lane 15 and returned wave-uniform: four v_min_f32 with row_shr
-__device__ __forceinline__ float dh_row_min_to_lane15(float v) {
-    asm volatile("s_nop 4\n\tv_min_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1"
-                 : "+v"(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 15));
+    for (uint32_t l = 0; l < DH_WAVE; l++) {
+        const uint32_t e0 = 2u * l, e1 = e0 + 1u, a = e0 >= k0 && e0 < k1 ? e0 : k0, b = e1 >= k0 && e1 < k1 ? e1 : k0;
+        agc[l] = DhAgcPair{ S.mn[a], S.mx[a], S.mn[b], S.mx[b] };
+    }
 }
 #endif
 
@@ -1071,34 +763,6 @@ DH_HD float dh_exact_filtered(const float* tail, uint32_t tc, const float* in, u
     }
     return dh_div_gain(acc, gain, rgain);
 }
-
-// maximum over the wavefront of a per-lane value (device: six ds_swizzle / bpermute exchanges)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-// (row_shr 1/2/4/8 inside each row of 16, row_bcast:15 / :31 across rows -- the running maximum ends up in lane 63;
-// v_max_f32 skips a NaN operand, which is what the caller wants: NaN samples are caught behind the FIR)
-__device__ __forceinline__ float dh_wave_max(float v) {
-#define DH_MAX_STEP(ctrl) "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 " ctrl "\n\t"
-    asm volatile("s_nop 4\n\t"
-                 DH_MAX_STEP("row_shr:1 row_mask:0xf bank_mask:0xf") DH_MAX_STEP("row_shr:2 row_mask:0xf bank_mask:0xf")
-                 DH_MAX_STEP("row_shr:4 row_mask:0xf bank_mask:0xf") DH_MAX_STEP("row_shr:8 row_mask:0xf bank_mask:0xf")
-                 DH_MAX_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf") DH_MAX_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 1" : "+v"(v));
-#undef DH_MAX_STEP
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-// max(|a|, |b|, c) in one instruction
-__device__ __forceinline__ float dh_max3_abs(float a, float b, float c) {
-    float r; asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
-}
-#define DH_WAVE_MAX(a) dh_wave_max((a)[0])             // of a DH_LANE_ARRAY(float, a, 1)
-#else
-inline float dh_wave_max_lanes(const float (&a)[DH_WAVE][1]) {
-    float m = 0.0f;
-    for (int l = 0; l < DH_WAVE; l++) m = __builtin_fmaxf(m, a[l][0]);
-    return m;
-}
-#define DH_WAVE_MAX(a) dh_wave_max_lanes(a)
-#endif
 
 // The rare paths of the error-bounded kernels (inlined: as real calls they would force the kernel's argument block into
 // scratch memory).  What they need to know lives in LDS between runs (DhBoundState), not in vector registers: all 128 are
@@ -1369,19 +1033,7 @@ DH_HD void dh_symbol_windows(DhDspShared& S, const float* fbuf, uint32_t k0, uin
         const float* srca = fbuf + (int32_t) (qa * 10u) + step_off;
         const float* srcb = l < 35u ? srca + 640 : fbuf;
         float v[10], w[10];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        {
-            const uint32_t aa = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) srca;
-            const uint32_t ab = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) srcb;
-            dh_f2 x0 = dh_lds_read_b64<0>(aa), x1 = dh_lds_read_b64<8>(aa), x2 = dh_lds_read_b64<16>(aa), x3 = dh_lds_read_b64<24>(aa), x4 = dh_lds_read_b64<32>(aa);
-            dh_f2 y0 = dh_lds_read_b64<0>(ab), y1 = dh_lds_read_b64<8>(ab), y2 = dh_lds_read_b64<16>(ab), y3 = dh_lds_read_b64<24>(ab), y4 = dh_lds_read_b64<32>(ab);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3), "+v"(y4) :: "memory");
-            v[0] = x0.x; v[1] = x0.y; v[2] = x1.x; v[3] = x1.y; v[4] = x2.x; v[5] = x2.y; v[6] = x3.x; v[7] = x3.y; v[8] = x4.x; v[9] = x4.y;
-            w[0] = y0.x; w[1] = y0.y; w[2] = y1.x; w[3] = y1.y; w[4] = y2.x; w[5] = y2.y; w[6] = y3.x; w[7] = y3.y; w[8] = y4.x; w[9] = y4.y;
-        }
-#else
-        for (int i = 0; i < 10; i++) { v[i] = srca[i]; w[i] = srcb[i]; }
-#endif
+        dh_lds_run10_pair(srca, srcb, v, w);
         float vola = v[0], volb = w[0];
 #pragma unroll
         for (int i = 1; i < 10; i++) { vola += v[i]; volb += w[i]; }
@@ -1408,17 +1060,7 @@ DH_HD void dh_symbol_windows(DhDspShared& S, const float* fbuf, uint32_t k0, uin
         const bool valid = q < m;
         const float* src = valid && q > 0u ? fbuf + (int32_t) (q * 20u) + step_off : fbuf;       // (lanes beyond the run read symbol 0 and store nothing)
         float v[20];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        {
-            const uint32_t a = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) src;
-            dh_v4f x0 = dh_lds_read_b128<0>(a), x1 = dh_lds_read_b128<16>(a), x2 = dh_lds_read_b128<32>(a), x3 = dh_lds_read_b128<48>(a), x4 = dh_lds_read_b128<64>(a);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4) :: "memory");
-            v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w; v[8] = x2.x; v[9] = x2.y;
-            v[10] = x2.z; v[11] = x2.w; v[12] = x3.x; v[13] = x3.y; v[14] = x3.z; v[15] = x3.w; v[16] = x4.x; v[17] = x4.y; v[18] = x4.z; v[19] = x4.w;
-        }
-#else
-        for (int i = 0; i < 20; i++) v[i] = src[i];
-#endif
+        dh_lds_run<20>(src, v);
         float vol = v[0];
 #pragma unroll
         for (int i = 1; i < 20; i++) vol += v[i];
@@ -1433,26 +1075,15 @@ DH_HD void dh_symbol_windows(DhDspShared& S, const float* fbuf, uint32_t k0, uin
         dh_lds_stores_done();
     }
     // sps 40 (a pass holds at most 25 symbols): the same with ten ds_read_b128 per symbol (a forty-word lane stride read one word at a
-    // time reaches four banks: eight-way conflicts in the general loop)
+    // time reaches four banks: eight-way conflicts in the general loop).  (Folded into the sps-20 body with the window bounds as
+    // constants, the sps-20 kernels came out with another instruction order: two bodies.)
     if (SPS == 40 && DH_STOP_AFTER >= 3) DH_FOR_LANES_FRESH(lane) {
         const uint32_t l = (uint32_t) lane;
         const uint32_t q = l < 63u ? l + 1u : 0u;
         const bool valid = q < m;
         const float* src = valid && q > 0u ? fbuf + (int32_t) (q * 40u) + step_off : fbuf;       // (lanes beyond the run read symbol 0 and store nothing)
         float v[40];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        {
-            const uint32_t a = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) src;
-            dh_v4f x0 = dh_lds_read_b128<0>(a), x1 = dh_lds_read_b128<16>(a), x2 = dh_lds_read_b128<32>(a), x3 = dh_lds_read_b128<48>(a), x4 = dh_lds_read_b128<64>(a);
-            dh_v4f x5 = dh_lds_read_b128<80>(a), x6 = dh_lds_read_b128<96>(a), x7 = dh_lds_read_b128<112>(a), x8 = dh_lds_read_b128<128>(a), x9 = dh_lds_read_b128<144>(a);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9) :: "memory");
-            const dh_v4f x[10] = { x0, x1, x2, x3, x4, x5, x6, x7, x8, x9 };
-#pragma unroll
-            for (int i = 0; i < 10; i++) { v[4 * i] = x[i].x; v[4 * i + 1] = x[i].y; v[4 * i + 2] = x[i].z; v[4 * i + 3] = x[i].w; }
-        }
-#else
-        for (int i = 0; i < 40; i++) v[i] = src[i];
-#endif
+        dh_lds_run<40>(src, v);
         float vol = v[0], mid = v[13];
 #pragma unroll
         for (int i = 1; i < 40; i++) vol += v[i];
@@ -1564,33 +1195,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
             }
             DH_LANE_ARRAY(float, lo, 1); DH_LANE_ARRAY(float, hi, 1);
             uint64_t vote_above = 0, fine_cand = 0, fine_out = 0;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            {
-                float s = gs[0], q = gq[0], t1, t2, u1, u2;
-                // (row_shr with bound_ctrl: lanes without a source read 0 -- only lanes 4, 9, 14 of a row are looked at, and theirs exist)
-                asm volatile("s_nop 4\n\t"               // (a VALU write of EXEC just before would need 5 wait states ahead of a DPP op)
-                             "v_add_f32_dpp %0, %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                             "v_add_f32_dpp %2, %5, %5 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                             "s_nop 0\n\t"                // (a DPP read needs two wait states after the write of its source: the other stream's add + this)
-                             "v_add_f32_dpp %1, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                             "v_add_f32_dpp %3, %2, %2 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                             "v_add_f32_dpp %1, %4, %1 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                             "v_add_f32_dpp %3, %5, %3 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-                             : "=&v"(t1), "=&v"(t2), "=&v"(u1), "=&v"(u2) : "v"(s), "v"(q));
-                gs[0] = t2; gq[0] = u2;
-            }
-#else
-            {
-                float ts[DH_WAVE], tq[DH_WAVE];
-                for (int l = 0; l < DH_WAVE; l++) {
-                    const int c = l & 15;
-                    auto at = [&](float (*arr)[1], int d) { return c - d >= 0 ? arr[l - d][0] : 0.0f; };
-                    ts[l] = ((at(gs, 0) + at(gs, 1)) + (at(gs, 2) + at(gs, 3))) + at(gs, 4);
-                    tq[l] = ((at(gq, 0) + at(gq, 1)) + (at(gq, 2) + at(gq, 3))) + at(gq, 4);
-                }
-                for (int l = 0; l < DH_WAVE; l++) { gs[l][0] = ts[l]; gq[l][0] = tq[l]; }
-            }
-#endif
+            dh_row_sum5_pair(gs, gq);
             DH_FOR_LANES_FRESH(lane) {
                 const uint32_t r = (uint32_t) lane >> 4, c = (uint32_t) lane & 15u;
                 const bool own = (((r == 3u ? 0x0010u : 0x4210u) >> c) & 1u) != 0u;      // this lane holds a phase: lane 4, 9 or 14 of its row (row 3: phase 9 only)
@@ -1605,13 +1210,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 DH_BALLOT_ACC(fine_cand, !own || (sane && l > 0.0f && h < 4999999.0f), lane);      // fine as a candidate
                 DH_BALLOT_ACC(fine_out, !own || sane, lane);                                       // fine when ruled out
             }
-            float hmin;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            hmin = -dh_wave_max(-hi[0]);
-#else
-            hmin = DH_FLT_MAX;
-            for (int q = 0; q < DH_WAVE; q++) hmin = dh_fmin_(hmin, hi[q][0]);
-#endif
+            const float hmin = DH_WAVE_MIN(hi);
             DH_FOR_LANES_FRESH(lane) {
                 DH_BALLOT_ACC(vote_above, DH_LA(lo, lane)[0] > hmin, lane);
             }
@@ -1703,13 +1302,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 const uint32_t nz = (uint32_t) (vote_nz | (vote_nz >> 10) | (vote_nz >> 20) | (vote_nz >> 30) | (vote_nz >> 40));
                 vote_zero = ~nz & ten;
             }
-            float hmin;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            hmin = dh_row_min_to_lane15(hi[0]);
-#else
-            hmin = DH_FLT_MAX;
-            for (int q = 0; q < 10; q++) hmin = dh_fmin_(hmin, hi[q][0]);
-#endif
+            const float hmin = DH_ROW0_MIN(hi);                 // (lanes 10 .. 15 hold FLT_MAX)
             DH_FOR_LANES_FRESH(lane) { DH_BALLOT_ACC(vote_above, DH_LA(lo, lane)[0] > hmin, lane); }
             const uint32_t above = (uint32_t) vote_above & ten;
             const uint32_t cand = ~above & ten;                 // phases whose interval reaches below hmin
@@ -1796,13 +1389,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 DH_BALLOT_ACC(v_small, h < 4999999.0f, lane);
                 DH_BALLOT_ACC(v_big, l > 5000001.0f, lane);
             }
-            float hmin;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            hmin = -dh_wave_max(-iv_hi[0]);
-#else
-            hmin = DH_FLT_MAX;
-            for (int q = 0; q < DH_WAVE; q++) hmin = dh_fmin_(hmin, iv_hi[q][0]);
-#endif
+            const float hmin = DH_WAVE_MIN(iv_hi);
             DH_FOR_LANES_FRESH(lane) { DH_BALLOT_ACC(v_above, DH_LA(iv_lo, lane)[0] > hmin, lane); }
             const uint64_t phases = sps >= 64u ? ~0ull : ((1ull << sps) - 1ull);
             const uint64_t cand = ~v_above & phases;                          // phases whose interval reaches below the smallest upper end
@@ -1842,8 +1429,6 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                     dh_exact_var_ring_staged<NZ>(C, S, sps, S.xf + 576, dh_dsp_xf_words(NZ) - 576u, chain_rows);
                     BS->n_exact_blocks++;
                     DH_BARRIER();
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#endif
                 }
                 DH_LANE_ARRAY(float, iv_lo, 1); DH_LANE_ARRAY(float, iv_hi, 1); DH_LANE_ARRAY(uint32_t, iv_ok, 1);
                 DH_FOR_LANES_FRESH(lane) {
@@ -1883,13 +1468,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
                 DH_BARRIER();
                 if (BOUNDED && SPS != 10 && attempt == 0) {
                     // is the reference's (arg-min, vmin <= 0, vmin > 5e6) beyond doubt?  One vote per question.
-                    float hmin;
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-                    hmin = -dh_wave_max(-iv_hi[0]);
-#else
-                    hmin = DH_FLT_MAX;
-                    for (int q = 0; q < DH_WAVE; q++) hmin = dh_fmin_(hmin, iv_hi[q][0]);
-#endif
+                    const float hmin = DH_WAVE_MIN(iv_hi);
                     uint64_t v_above = 0, v_ok = 0, v_pos = 0, v_small = 0, v_big = 0;
                     DH_FOR_LANES_FRESH(lane) {
                         const float l = DH_LA(iv_lo, lane)[0], h = DH_LA(iv_hi, lane)[0];
@@ -1932,28 +1511,24 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
 // derived from them are pairs, so centre, average, the two thresholds and the three distances are packed operations for
 // both symbols -- one pass of ~40 vector instructions instead of two of ~37.  Every operation is the one the one-symbol
 // form performs (same operands, same order), so the dibits and the doubts are the same.
-// `out`: where symbol 0 of the run goes; `agc` (device): the scan's own results for the lane's two symbols, used when the run starts its
+// `out`: where symbol 0 of the run goes; `agc`: the scan's own results for the lane's two symbols, used when the run starts its
 // block.  Doubtful symbols are stored provisionally and overwritten by dh_settle_doubts; their votes come back in vote_a (symbols 2 l)
 // and vote_b (2 l + 1).
 struct DhSliceSetup { bool four_levels, e_pos, width_pow2, pair_store; float T_eff, inv_width; };
 template <int SPS, int LV, bool BOUNDED>
-DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, const DhAgcPair agc, uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
+DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, DH_LANE_STRUCT_IN(DhAgcPair, agc), uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
                             const DhSliceSetup& U, uint64_t& vote_a, uint64_t& vote_b) {
-    (void) agc;
     const bool four_levels = U.four_levels, e_pos = U.e_pos, width_pow2 = U.width_pow2, pair_store = U.pair_store;
     const float T_eff = U.T_eff, inv_width = U.inv_width;
     DH_FOR_LANES_FRESH(lane) {
         const uint32_t qa = 2u * (uint32_t) lane;
         const bool va = qa < m, vb = qa + 1u < m;
         const uint32_t qq = va ? qa : 0u, k = k0 + qq;                            // (lanes beyond the run recompute symbols 0 / 1: in-range reads, no store)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
         // (a run that starts its block: the lane's symbols 2 l, 2 l + 1 are the ring slots the AGC scan left in its registers)
+        const DhAgcPair& own = DH_LS(agc, lane);
         dh_f2 mn, mx;
-        if (k0 == 0u) { mn = dh_f2_make(agc.mn0, agc.mn1); mx = dh_f2_make(agc.mx0, agc.mx1); }
+        if (k0 == 0u) { mn = dh_f2_make(own.mn0, own.mn1); mx = dh_f2_make(own.mx0, own.mx1); }
         else { mn = dh_f2_make(S.mn[k], S.mn[k + 1u]); mx = dh_f2_make(S.mx[k], S.mx[k + 1u]); }
-#else
-        const dh_f2 mn = dh_f2_make(S.mn[k], S.mn[k + 1u]), mx = dh_f2_make(S.mx[k], S.mx[k + 1u]);
-#endif
         const dh_f2 sumq = dh_f2_make(S.sum[qq], S.sum[qq + 1u]);
         const dh_f2 center = dh_f2_scale(dh_f2_add(mx, mn), 0.5f);                // (max + min) / 2.0f: the division by two is exact
         // (sps 20: the division by the window's six samples as reciprocal product + exact residual + correction, dh_div_const; tests/test_numerics.py)
@@ -2079,26 +1654,7 @@ DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f
                 DH_LA(varr, lane)[r] = dh_zero_beyond(DH_LA(varr, lane)[r], e, have);
             }
         }
-        float mx = 0.0f;                            // (a NaN is skipped here and caught behind the FIR)
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        {
-            // ten v_max3_f32 in ONE statement (as ten statements the compiler put an s_nop behind each)
-            static_assert(DH_PF_N == 5, "five groups of four");
-            const dh_f4 w0 = varr[0], w1 = varr[1], w2 = varr[2], w3 = varr[3], w4 = varr[4];
-            asm("v_max3_f32 %0, |%1|, |%2|, 0\n\tv_max3_f32 %0, |%3|, |%4|, %0\n\tv_max3_f32 %0, |%5|, |%6|, %0\n\tv_max3_f32 %0, |%7|, |%8|, %0\n\t"
-                "v_max3_f32 %0, |%9|, |%10|, %0\n\tv_max3_f32 %0, |%11|, |%12|, %0\n\tv_max3_f32 %0, |%13|, |%14|, %0\n\tv_max3_f32 %0, |%15|, |%16|, %0\n\t"
-                "v_max3_f32 %0, |%17|, |%18|, %0\n\tv_max3_f32 %0, |%19|, |%20|, %0"
-                : "=&v"(mx) : "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w),
-                              "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w));
-        }
-#else
-#pragma unroll
-        for (int r = 0; r < DH_PF_N; r++) {
-            const dh_f4 w = DH_LA(varr, lane)[r];
-            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.x), __builtin_fabsf(w.y)));
-            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.z), __builtin_fabsf(w.w)));
-        }
-#endif
+        const float mx = dh_max_abs_groups(DH_LA(varr, lane));      // (a NaN is skipped here and caught behind the FIR)
         DH_LA(xm, lane)[0] = mx;
     }
     const float xmax = DH_WAVE_MAX(xm);
@@ -2117,21 +1673,14 @@ DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f
     DH_FOR_LANES_FRESH(lane) {
         const bool in_last = (uint32_t) lane < LAST_LANES, in_store = (uint32_t) lane < STORE_LANES;
         if (STORE_LANES > LAST_LANES && !in_last) { dh_f4 z; z.x = 0.0f; z.y = 0.0f; z.z = 0.0f; z.w = 0.0f; DH_LA(varr, lane)[DH_PF_N - 1] = z; }
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
         dh_h4* d1 = reinterpret_cast<dh_h4*>(S.xf) + lane;                          // halves 4 lane .. 4 lane + 3 of group 0; group r is 256 halves on
         dh_h4* d2 = reinterpret_cast<dh_h4*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + lane;
 #pragma unroll
         for (int r = 0; r < DH_PF_N; r++) {
             dh_h4 a, b;
-            dh_f16_split4(varr[r], scale, a, b);
-            if (r < DH_PF_N - 1 || in_store) { d1[DH_WAVE * r] = a; d2[DH_WAVE * r] = b; }
+            dh_f16_split4(DH_LA(varr, lane)[r], scale, a, b);
+            if (r < DH_PF_N - 1 || in_store) { dh_h4_store(d1 + DH_WAVE * r, a); dh_h4_store(d2 + DH_WAVE * r, b); }
         }
-#else
-        uint16_t* d1 = reinterpret_cast<uint16_t*>(S.xf) + 4 * lane;
-        uint16_t* d2 = reinterpret_cast<uint16_t*>(S.xf + DH_F16_H2_OFFSET_OF(NZ)) + 4 * lane;
-        for (int r = 0; r < DH_PF_N; r++)
-            if (r < DH_PF_N - 1 || in_store) dh_f16_split4(varr[lane][r], scale, d1 + 4 * DH_WAVE * r, d2 + 4 * DH_WAVE * r);
-#endif
     }
     return true;
 }
@@ -2161,21 +1710,10 @@ DH_HD void dh_issue_next_window(DhDspShared& S, const float* const& in, const ui
     } else {
         // Register-free variant: one dword per 128-byte line of the next window is requested now, which pulls the
         // lines into L2; the next iteration's P1 then stages from L2 instead of HBM.  The dwords themselves are not
-        // wanted: global_load_lds_dword drops them (lane l -> m0 + 4 l) into a part of the window block that is dead
-        // until the next staging, so no vector register is tied to a load the compiler does not know about.  They
-        // have landed before the next P1 stores anything there (its own, younger loads are waited for first), and
-        // an explicit s_waitcnt follows the loop for the last one.
-        if (pf_plain) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-            const uint32_t pf_lane = (uint32_t) dh_fresh_lane_id_();       // not loop-invariant: a hoisted address is spilled
-            const float* line = in + (p_next - tc) + 32u * pf_lane;
-            const uint32_t sink = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) (S.xf + DH_PF_SINK);
-            uint32_t keep_m0;
-            if (32u * pf_lane < DH_FTILE + NZ)
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep_m0) : "s"(sink), "v"(line) : "memory");
-#endif
-        }
+        // wanted: they are dropped into a part of the window block that is dead until the next staging (dh_l2_touch_lines).
+        // They have landed before the next P1 stores anything there (its own, younger loads are waited for first), and
+        // an explicit wait follows the loop for the last one.
+        if (pf_plain) dh_l2_touch_lines(in + (p_next - tc), DH_FTILE + NZ, S.xf + DH_PF_SINK);
     }
 }
 
@@ -2279,25 +1817,12 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     const int32_t fast_sym_end = (P.sym_cap >= (uint32_t) DH_VARIANCE_SYMBOLS && P.sym_cap < 0x40000000u) ? (int32_t) (P.sym_cap - DH_VARIANCE_SYMBOLS) : -1;
 
     DH_PHASE_MARK(7);
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    // split-f16 FIR: this lane's six tap fragments -- 16-byte loads, 1 KiB per instruction, the same 6 KiB for every wavefront
-    // of the chip (L1 / L2 hits).  Requested one iteration ahead (here, and again at the end of every iteration, when the
-    // staging registers are free), so they have landed when P2 wants them.
-    dh_u4 tapfrag_regs[2 * DH_F16_KSTEPS_OF(NZ > 0 ? NZ : 80)];
-#define DH_TAPFRAG_LOAD() do { if constexpr (MF16) { const dh_u4* tf_ = reinterpret_cast<const dh_u4*>(P.tapfrag) + dh_fresh_lane_id_(); \
-        _Pragma("unroll") for (int f_ = 0; f_ < 2 * DH_F16_KSTEPS_OF(NZ > 0 ? NZ : 80); f_++) tapfrag_regs[f_] = tf_[DH_WAVE * f_]; } } while (0)
-    DH_TAPFRAG_LOAD();
-    // Every path through P2 must leave these loads landed, also the rare ones that never look at the fragments: otherwise the
-    // compiler's wait-count bookkeeping still sees them in flight further down, and the first instruction that reuses one of
-    // their registers -- in the slicing phase -- gets an s_waitcnt vmcnt(0), which also waits for the NEXT window's loads,
-    // requested after P3 precisely so that they can stay in flight through P4 - P6 (it cost 1 ms of a 6.8 ms step).
-#define DH_TAPFRAG_SETTLE() do { if constexpr (MF16) { _Pragma("unroll") for (int f_ = 0; f_ < 2 * DH_F16_KSTEPS_OF(NZ > 0 ? NZ : 80); f_++) \
-        asm volatile("" :: "v"(tapfrag_regs[f_])); } } while (0)
-#else
-    const uint32_t (* const tapfrag_regs)[DH_WAVE][4] = reinterpret_cast<const uint32_t (*)[DH_WAVE][4]>(P.tapfrag);     // (harness: the table itself)
-#define DH_TAPFRAG_LOAD() ((void) 0)
-#define DH_TAPFRAG_SETTLE() ((void) 0)
-#endif
+    // split-f16 FIR: this lane's six tap fragments -- the same 6 KiB for every wavefront of the chip (L1 / L2 hits).  Requested one
+    // iteration ahead (here, and again at the end of every iteration, when the staging registers are free), so they have landed
+    // when P2 wants them; every path through P2 leaves them settled (wave_ops.hpp: DH_TAPFRAG_*).
+    constexpr int NFRAG = 2 * DH_F16_KSTEPS_OF(NZ > 0 ? NZ : 80);
+    DH_TAPFRAG_REGS(tapfrag_regs, NFRAG, P.tapfrag);
+    DH_TAPFRAG_LOAD(tapfrag_regs, NFRAG, P.tapfrag, MF16);
     for (;;) {
         // ---- run planning (wave-uniform): symbols k0 .. k0+m-1 of the current variance block.
         // A symbol at filtered position s is produced iff nf - s > sps + 1 (gfsk_demodulator.cpp:18-22);
@@ -2381,12 +1906,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 #pragma unroll
                         for (int r = 0; r < DH_PF_N; r++) {
                             const dh_f4 w = DH_LA(v, lane)[r];
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
                             mx = dh_max3_abs(w.x, w.y, mx); mx = dh_max3_abs(w.z, w.w, mx);
-#else
-                            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.x), __builtin_fabsf(w.y)));
-                            mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(w.z), __builtin_fabsf(w.w)));
-#endif
                         }
                         DH_LA(xmax_lane, lane)[0] = mx;
                     }
@@ -2548,7 +2068,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             }
             DH_BARRIER();
         }
-        DH_TAPFRAG_SETTLE();
+        DH_TAPFRAG_SETTLE(tapfrag_regs, NFRAG, MF16);
         DH_PHASE_MARK(1);
         const float* fbuf = S.xf;
 
@@ -2602,12 +2122,8 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         dh_issue_next_window<NZ, PF_REG>(S, in, tc, p_next, pf_plain, pf_reg, pfr);
 
         // ---- P4: sliding AGC min/max as two wave scans
-        DhAgcPair agc = { 0.0f, 0.0f, 0.0f, 0.0f };
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-        if (DH_STOP_AFTER >= 4) agc = dh_agc_scan(S, k0, k0 + m);
-#else
-        if (DH_STOP_AFTER >= 4) dh_agc_scan(S, k0, k0 + m);
-#endif
+        DH_LANE_STRUCT(DhAgcPair, agc) = {};
+        if (DH_STOP_AFTER >= 4) dh_agc_scan(S, k0, k0 + m, agc);
         DH_BARRIER();
         DH_PHASE_MARK(3);
 
@@ -2673,13 +2189,11 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             else { e_cur = ec; e_count = cnt; }
             if (block_done) { BS->prev_start = cur_start; BS->prev_off = cur_off; blk_flags = (blk_flags & 1u) ? 2u : 0u; BS->blk_flags = blk_flags; }
         }
-        DH_TAPFRAG_LOAD();                              // for the next run
+        DH_TAPFRAG_LOAD(tapfrag_regs, NFRAG, P.tapfrag, MF16);      // for the next run
         DH_PHASE_MARK(6);
     }
 
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // a last L2-touch load may still be writing into the window block
-#endif
+    dh_global_loads_done();                             // a last L2-touch load may still be writing into the window block
     if constexpr (KEEPF) {
         // the outputs behind the last run (less than a symbol's worth, unless the symbol buffer is full): the reference's arithmetic,
         // sample by sample, while the tail it reads is still the old one
@@ -2810,19 +2324,13 @@ DH_HD void dh_rrc_tile(const DhRrcParams& R, uint32_t ch, uint32_t tile, DhDspSh
     }
     DH_BARRIER();
     DH_COMPILER_FENCE();                                // the taps become live after the staging registers are dead
-    float tv[NZ / 2 + 1];
-#pragma unroll
-    for (int i = 0; i <= NZ / 2; i++) tv[i] = R.taps[i];       // harness only: the GPU reads R.taps as scalar pairs (DhFirBatch SG)
+    // (the taps straight from the parameter block: the GPU reads R.taps as scalar pairs, DhFirBatch SG)
     // Each lane produces 16 consecutive outputs.  Stored straight from registers, one store instruction would touch
     // 64 separate 64-byte pieces of the row; instead the tile goes through the (now idle) window block and leaves
     // as four fully coalesced 1 KB stores.
     DH_LANE_ARRAY(float, fo, DH_FIR_L);
     DH_FOR_LANES(lane) {
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
         if ((uint32_t) lane * DH_FIR_L < cnt) dh_fir_lane<NZ, FAST, true>(R.taps, R.gain, R.rgain, R.inv_gain, S.xf, lane, DH_LA(fo, lane));
-#else
-        if ((uint32_t) lane * DH_FIR_L < cnt) dh_fir_lane<NZ, FAST>(tv, R.gain, R.rgain, R.inv_gain, S.xf, lane, DH_LA(fo, lane));
-#endif
     }
     DH_BARRIER();                                       // every lane has read its window
     DH_FOR_LANES(lane) {

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(DH_WAVE) void k_xcc_probe(uint32_t* out) {
 // aligned come back whole (the queues run with the LDS alignment mode "unaligned"; a mode that rounds the address down would slice wrong
 // symbols after every timing step of one sample).  HipBackend::lds_unaligned_probe looks once per device and process.
 __global__ __launch_bounds__(DH_WAVE) void k_lds_unaligned_probe(uint32_t* out) {
-#if defined(__HIP_DEVICE_COMPILE__)         // (the LDS read helpers only exist in the device pass)
+#if DH_ON_GPU         // (the LDS read helpers only exist in the device pass)
     __shared__ float w[DH_WAVE + 8];
     w[threadIdx.x] = (float) threadIdx.x;
     if (threadIdx.x < 8) w[DH_WAVE + threadIdx.x] = (float) (DH_WAVE + threadIdx.x);
@@ -328,7 +328,7 @@ __global__ void k_dvfilter(const int16_t* in, int16_t* out, float* state, size_t
 // (four dwords from a row that is only promised to be 4-byte aligned: the plain vector type would tell the compiler 16)
 typedef uint32_t dh_u4w __attribute__((ext_vector_type(4), aligned(4)));
 __global__ __launch_bounds__(320) void k_fe_fused(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
     // five wavefronts: the first runs the recurrence of tile k while the other four convert tile k + 1 into the second buffer
     __shared__ float tiles[2][DH_FE_CH][DH_FE_TS + 1];
     const int lane0 = threadIdx.x;                               // < 64: the recurrence wavefront
@@ -435,7 +435,7 @@ __global__ void k_div_const(const float* in, float* out, size_t n, float d, floa
 
 // one tile per wavefront: D = C + A x B with v_mfma_f32_16x16x32_f16 (dh_debug_mfma_f16)
 __global__ __launch_bounds__(DH_WAVE) void k_mfma_f16(const uint16_t* A, const uint16_t* B, const float* C, float* D) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
     const size_t t = blockIdx.x;
     const int l = threadIdx.x, m = l & 15, q = l >> 4;
     typedef unsigned short dh_us8 __attribute__((ext_vector_type(8)));
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(DH_WAVE) void k_mfma_f16(const uint16_t* A, const u
 #endif
 }
 __global__ void k_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
     for (size_t i = (blockIdx.x * (size_t) blockDim.x + threadIdx.x) * 4; i < n; i += (size_t) gridDim.x * blockDim.x * 4) {
         dh_f4 v; v.x = in[i]; v.y = i + 1 < n ? in[i + 1] : 0.0f; v.z = i + 2 < n ? in[i + 2] : 0.0f; v.w = i + 3 < n ? in[i + 3] : 0.0f;
         dh_h4 a, b;
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev
 template <class Emit>
 __device__ __forceinline__ void dh_cz_gemm_tile(const DhCzParams& P, const float* bmat, uint32_t wbase, uint32_t step, uint32_t row0,
                                                 uint32_t nrows, Emit emit) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if DH_ON_GPU
     __shared__ __attribute__((aligned(16))) float As[DH_CZ_TM * DH_CZ_AS];
     __shared__ __attribute__((aligned(16))) float Bs[32 * DH_CZ_BS];
     const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;

@@ -149,13 +149,8 @@ struct DhPn9Bytes {
         }
     }
 };
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-__device__ static constexpr DhCrc16Table dh_crc16_table{};
-__device__ static constexpr DhPn9Bytes dh_pn9_bytes{};
-#else
-static constexpr DhCrc16Table dh_crc16_table{};
-static constexpr DhPn9Bytes dh_pn9_bytes{};
-#endif
+DH_CONST_TABLE DhCrc16Table dh_crc16_table{};
+DH_CONST_TABLE DhPn9Bytes dh_pn9_bytes{};
 
 // four bytes of the whitening sequence as a little-endian word (byte 4 i in bits 0..7)
 constexpr uint32_t dh_pn9_le_word(int i) {

@@ -22,8 +22,7 @@
 #include "dh_portable.hpp"
 #include "../../include/digiham_amd.h"      // dh_outpack_header, dh_outpack_entry, dh_event
 
-#define DH_OP_LANES 256u                    /* lanes of the scan's workgroup = channels one pass of the scan covers */
-#define DH_OP_WAVES (DH_OP_LANES / DH_WAVE)
+// (DH_OP_LANES, DH_OP_WAVES and the DH_OP_* vocabulary of a 256-lane phase: dh_portable.hpp)
 
 struct DhOutpack {
     dh_outpack_header* hdr; dh_outpack_entry* entries; dh_event* events; uint8_t* frames;      // the pack
@@ -40,43 +39,6 @@ struct DhOpShared { uint64_t wave_v[DH_OP_WAVES], wave_f[DH_OP_WAVES]; uint32_t 
 struct alignas(16) DhOpQuad { uint32_t w[4]; };
 
 DH_HD uint64_t dh_op_pad16(uint32_t n) { return ((uint64_t) n + 15u) & ~(uint64_t) 15u; }
-
-#if DH_DEVICE_BUILD && defined(__HIP_DEVICE_COMPILE__)
-#define DH_OP_FOR(lane) for (uint32_t lane = threadIdx.x, dh_once_ = 1; dh_once_; dh_once_ = 0)
-#define DH_OP_VAL(type, name) type name[1]                      /* a value per lane: a register */
-#define DH_OP_WAVE_VAL(type, name) type name[1]                 /* a value per wavefront: a scalar pair */
-#define DH_OP_V(name, lane) name[0]
-#define DH_OP_W(name, lane) name[0]
-#define DH_OP_VOTE(name, pred, lane) name[0] = __builtin_amdgcn_ballot_w64((bool) (pred))
-#define DH_OP_CLEAR_VOTES(name) ((void) 0)
-// inclusive prefix sum inside each wavefront: six steps of "add what the lane d below holds" (ds_bpermute)
-#define DH_OP_WAVE_SCAN(name) do { \
-        const uint32_t wl_ = threadIdx.x & (DH_WAVE - 1u); \
-        for (uint32_t d_ = 1; d_ < DH_WAVE; d_ <<= 1) { \
-            const uint64_t t_ = (uint64_t) __shfl_up((unsigned long long) name[0], d_, DH_WAVE); \
-            if (wl_ >= d_) name[0] += t_; \
-        } } while (0)
-// the largest value of each wavefront, in all of its lanes
-#define DH_OP_WAVE_MAX(dst, src) do { \
-        dst[0] = src[0]; \
-        for (uint32_t d_ = 1; d_ < DH_WAVE; d_ <<= 1) { const uint32_t t_ = (uint32_t) __shfl_xor((int) dst[0], (int) d_, DH_WAVE); if (t_ > dst[0]) dst[0] = t_; } \
-    } while (0)
-#else
-#define DH_OP_FOR(lane) for (uint32_t lane = 0; lane < DH_OP_LANES; ++lane)
-#define DH_OP_VAL(type, name) type name[DH_OP_LANES]
-#define DH_OP_WAVE_VAL(type, name) type name[DH_OP_WAVES]
-#define DH_OP_V(name, lane) name[lane]
-#define DH_OP_W(name, lane) name[(lane) / DH_WAVE]
-#define DH_OP_VOTE(name, pred, lane) name[(lane) / DH_WAVE] |= (uint64_t) ((pred) ? 1 : 0) << ((lane) % DH_WAVE)
-#define DH_OP_CLEAR_VOTES(name) do { for (uint32_t w_ = 0; w_ < DH_OP_WAVES; ++w_) name[w_] = 0; } while (0)
-#define DH_OP_WAVE_SCAN(name) do { for (uint32_t l_ = 1; l_ < DH_OP_LANES; ++l_) if (l_ % DH_WAVE) name[l_] += name[l_ - 1]; } while (0)
-#define DH_OP_WAVE_MAX(dst, src) do { \
-        for (uint32_t w_ = 0; w_ < DH_OP_WAVES; ++w_) { \
-            uint32_t m_ = 0; \
-            for (uint32_t l_ = 0; l_ < DH_WAVE; ++l_) if (src[w_ * DH_WAVE + l_] > m_) m_ = src[w_ * DH_WAVE + l_]; \
-            for (uint32_t l_ = 0; l_ < DH_WAVE; ++l_) dst[w_ * DH_WAVE + l_] = m_; \
-        } } while (0)
-#endif
 
 // One append: candidates, fit rule, entries, header, scratch.  One workgroup of DH_OP_LANES lanes.
 DH_D void dh_outpack_scan(const DhOutpack& P, DhOpShared& S) {

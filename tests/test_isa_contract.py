@@ -2,7 +2,7 @@
 (it neither tracks loads issued from inline asm nor inserts hazard wait states inside asm blocks).  This test
 compiles the device code to assembly and verifies them on the generated ISA:
 
-* FIR window reads (dsp_core.hpp: dh_lds_read2 / dh_fir_arrived): between an asm `ds_read2_b32` and the next
+* FIR window reads (wave_ops.hpp: dh_lds_read2; dsp_core.hpp: dh_fir_arrived): between an asm `ds_read2_b32` and the next
   `s_waitcnt lgkmcnt(0)` no instruction may touch the destination registers (a register-allocator copy or spill
   there would read data that has not arrived yet);
 * every DPP instruction is at least two instructions (or an s_nop) away from the VALU write of its source;
