@@ -263,17 +263,19 @@ int dh_engine_sync(dh_engine* e) {
 //   dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream);
 //   dh_be_cz_power(const DhCzPowerParams& P, void* stream);      (only with power enabled: block power, then the gate and the counts)
 // (engine.hip defines the gfx950 ones; channelizer_core.hpp the CPU harness's.)  Two window buffers take turns: a push's
-// window is the last H = T' - 1 samples (raster: P K - 1) of the previous one followed by the new samples.
+// window is the last H samples of the previous one followed by the new samples.  The kind of bank -- fixed (L = 1), rational
+// (L > 1) or raster (K != 0) -- enters in init()'s geometry, in word_of() / columns() and in the GEMM step of push().
 struct dh_channelizer : dh_state {                      // (clear() and retune() act on what init() and power_enable() declare)
-    uint32_t B = 0, D = 0, L = 1, tpad = 0, ncols = 0, max_input = 0;      // rate = input L / D
+    uint32_t B = 0, D = 0, L = 1, tpad = 0, ncols = 0, max_input = 0;      // rate = input L / D; tpad: T', or K' on a raster
     uint32_t hist = 0;                                  // H: T' - 1, or P K - 1 on a raster
     int cf32 = 0, fm = 0, dcblock = 0;
-    std::vector<float> taps;                            // [L][T']: the phases h_p of h, each zero-padded to T'
-    std::vector<uint32_t> inc;
+    std::vector<float> taps;                            // [L][T']: the phases h_p of h, each zero-padded to T'; raster: h padded to P K
+    std::vector<uint32_t> word;                         // [B] a channel's word: u_b, or c_b on a raster
+    std::vector<float> cols;                            // [2][2 T'] the column pair in the making
     float* d_tables = nullptr;                          // coarse ++ fine
-    uint32_t* d_inc = nullptr;
+    uint32_t* d_word = nullptr;                         // [B]
     float* d_bmat = nullptr;                            // [L][2 T'][ncols]
-    float* d_win[2] = { nullptr, nullptr };             // [T' - 1 + max_input][2] each
+    float* d_win[2] = { nullptr, nullptr };             // [H + max_input][2] each
     float* d_state = nullptr;                           // [B][DH_CZ_STATE_WORDS]
     float* d_zbuf = nullptr;                            // FM: [max_input L / D + 1][B][2]
     uint8_t* d_stage = nullptr;                         // push_host's input
@@ -282,13 +284,11 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
     uint64_t n0 = 0;                                    // samples pushed since create / reset
     DhCzRatParams rat{};                                // rat.g: what init() fixes; a push adds its window, its output rows and its
                                                         // position (L = 1), or its slots (L > 1)
-    // uniform raster (K != 0; tpad = K', taps = h padded to P K, bmat = one bank built from G): the fold buffer and what the
-    // rotation reads; K = 0: nothing of it is allocated or launched
+    // what only a uniform raster owns (K != 0; bmat = one bank built from G): the fold buffer and what the rotation reads;
+    // K = 0: nothing of it is allocated or launched
     uint32_t K = 0;
-    std::vector<uint32_t> cbin;                         // [B] c_b
     float* d_taps = nullptr;                            // [P K]
     float* d_fold = nullptr;                            // [slab_rows][K'][2]
-    uint32_t* d_cbin = nullptr;                         // [B]
     uint32_t* d_phi = nullptr;                          // [K] Phi(q)
     uint32_t slab_rows = 0;
     DhCzFoldParams fold{};
@@ -305,58 +305,78 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
         return bufs.zero_all() ? DH_EDEVICE : DH_OK;
     }
-    // raster mode: the B operand is one bank [2 K'][ncols] of G, the windows hold H = P K - 1, one fold slab
-    int init_raster(const dh_channelizer_config& c) {
-        B = c.n_channels; D = c.decimation; L = 1; K = c.raster; tpad = dh_cz_tpad(K); ncols = dh_cz_ncols(B); max_input = c.max_input;
+    // a channel's word from the caller's value: the increment, or (a two's-complement int32) the bin reduced into [0, K)
+    uint32_t word_of(uint32_t v) const { return K ? dh_cz_raster_bin((int32_t) v, K) : v; }
+    // channel ch's column pair of bank p into `cols`
+    void columns(uint32_t p, uint32_t ch) {
+        float* re = cols.data(), * im = re + 2 * (size_t) tpad;
+        if (K) dh_cz_raster_columns(K, tpad, word[ch], re, im);
+        else dh_cz_columns(taps.data() + (size_t) p * tpad, tpad, word[ch], re, im);
+    }
+    // ... and from there into the B operand at bmat, every bank: put(a column's first element, its 2 T' values, pitch ncols)
+    template <class Put> int place(float* bmat, uint32_t ch, Put put) {
+        for (uint32_t p = 0; p < L; p++) {
+            columns(p, ch);
+            for (uint32_t c = 0; c < 2; c++)
+                if (put(bmat + p * bank() + dh_cz_col(ch, c), cols.data() + c * 2 * (size_t) tpad)) return DH_EDEVICE;
+        }
+        return DH_OK;
+    }
+    int init(const dh_channelizer_config& c, uint32_t interp, uint32_t raster) {
+        B = c.n_channels; D = c.decimation; L = interp; K = raster; ncols = dh_cz_ncols(B); max_input = c.max_input;
         cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
-        const uint32_t P = (c.n_taps + K - 1u) / K;
-        hist = P * K - 1u; slab_rows = dh_cz_fold_slab_rows(tpad);
-        taps.assign((size_t) P * K, 0.0f);
-        std::copy(c.taps, c.taps + c.n_taps, taps.begin());
-        cbin.resize(B);
-        for (uint32_t b = 0; b < B; b++) cbin[b] = dh_cz_raster_bin(c.bins[b], K);
-        const size_t bm = bank(), win = 2 * ((size_t) hist + max_input);
+        if (K) {                                        // geometry of a raster: one bank [2 K'][ncols] of G, one fold slab
+            fold.P = (c.n_taps + K - 1u) / K;
+            tpad = dh_cz_tpad(K); hist = fold.P * K - 1u; slab_rows = dh_cz_fold_slab_rows(tpad);
+            taps.assign((size_t) fold.P * K, 0.0f);
+            std::copy(c.taps, c.taps + c.n_taps, taps.begin());
+        } else {                                        // ... of L converter banks
+            tpad = dh_cz_tpad_rat(c.n_taps, L); hist = tpad - 1u;
+            taps.assign((size_t) L * tpad, 0.0f);
+            for (uint32_t p = 0; p < L; p++) {
+                const uint32_t r = (uint32_t) (((uint64_t) p * D + D - 1u) % L);
+                for (uint32_t k = 0; r + (uint64_t) k * L < c.n_taps; k++) taps[(size_t) p * tpad + k] = c.taps[r + k * L];
+            }
+        }
+        word.resize(B);
+        for (uint32_t b = 0; b < B; b++) word[b] = word_of(K ? (uint32_t) c.bins[b] : c.increments[b]);
+        cols.resize(4 * (size_t) tpad);
+        const size_t bm = L * bank(), win = 2 * ((size_t) hist + max_input);
         bool ok = bufs.alloc(d_tables, 4 * 4096);
-        ok &= bufs.alloc(d_cbin, B);
-        ok &= bufs.alloc(d_phi, K);
-        ok &= bufs.alloc(d_taps, taps.size());
+        ok &= bufs.alloc(d_word, B);
         ok &= bufs.alloc(d_bmat, bm);
         ok &= bufs.alloc(d_win[0], win, dh::ZERO_ON_RESET);
         ok &= bufs.alloc(d_win[1], win, dh::ZERO_ON_RESET);
-        ok &= bufs.alloc(d_fold, (size_t) 2 * slab_rows * tpad);
         ok &= bufs.alloc(d_state, (size_t) DH_CZ_STATE_WORDS * B, dh::ZERO_PER_CHANNEL);
         if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) outputs(max_input) + 1) * B);
         ok &= bufs.alloc(d_stage, in_bytes() * max_input);
+        if (K) ok &= bufs.alloc(d_phi, K) && bufs.alloc(d_taps, taps.size()) && bufs.alloc(d_fold, (size_t) 2 * slab_rows * tpad);
         if (!ok) return DH_ENOMEM;
-        DhCzParams& g = ras.g;
-        g.win = d_fold; g.bmat = d_bmat; g.coarse = d_tables; g.fine = d_tables + 8192; g.zbuf = d_zbuf;
-        g.D = D; g.tpad = tpad; g.B = B; g.ncols = ncols; g.fm = fm;
-        ras.cbin = d_cbin; ras.phi = d_phi; ras.K = K;
-        fold.h = d_taps; fold.fold = d_fold; fold.K = K; fold.kpad = tpad; fold.P = P; fold.D = D;
-        std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
-        for (uint32_t b = 0; b < B; b++) {
-            dh_cz_raster_columns(K, tpad, cbin[b], re.data(), im.data());
-            const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
-            for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bmat[r * ncols + cr] = re[r]; bmat[r * ncols + ci] = im[r]; }
-        }
-        std::vector<uint32_t> phi(K);
-        for (uint32_t q = 0; q < K; q++) phi[q] = dh_cz_raster_phi(q, K);
-        if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_cbin, cbin.data(), sizeof(uint32_t) * B) ||
-            be.upload(d_phi, phi.data(), sizeof(uint32_t) * K) || be.upload(d_taps, taps.data(), sizeof(float) * taps.size()) ||
+        DhCzParams& g = rat.g;
+        g.bmat = d_bmat; g.coarse = d_tables; g.fine = d_tables + 8192; g.inc = d_word; g.zbuf = d_zbuf;
+        g.D = D; g.tpad = tpad; g.B = B; g.ncols = ncols; g.fm = fm; rat.L = L;
+        std::vector<float> bmat(bm, 0.0f);
+        for (uint32_t b = 0; b < B; b++)
+            place(bmat.data(), b, [&](float* dst, const float* src) { for (size_t r = 0; r < 2 * (size_t) tpad; r++) dst[r * ncols] = src[r]; return 0; });
+        if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_word, word.data(), sizeof(uint32_t) * B) ||
             be.upload(d_bmat, bmat.data(), sizeof(float) * bm)) return DH_EDEVICE;
+        if (K) {
+            ras.g = g; ras.g.win = d_fold; ras.cbin = d_word; ras.phi = d_phi; ras.K = K;
+            fold.h = d_taps; fold.fold = d_fold; fold.K = K; fold.kpad = tpad; fold.D = D;
+            std::vector<uint32_t> phi(K);
+            for (uint32_t q = 0; q < K; q++) phi[q] = dh_cz_raster_phi(q, K);
+            if (be.upload(d_phi, phi.data(), sizeof(uint32_t) * K) || be.upload(d_taps, taps.data(), sizeof(float) * taps.size())) return DH_EDEVICE;
+        }
         const int rc = clear();
         if (rc != DH_OK) return rc;
-        return be.sync() ? DH_EDEVICE : DH_OK;
+        return be.sync() ? DH_EDEVICE : DH_OK;           // (the host copies above are released on return)
     }
-    // raster: v is the new bin, a two's-complement int32
-    int retune_raster(uint32_t ch, uint32_t v) {
-        std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
-        cbin[ch] = dh_cz_raster_bin((int32_t) v, K);
-        dh_cz_raster_columns(K, tpad, cbin[ch], re.data(), im.data());
-        const size_t pitch = sizeof(float) * ncols;
-        if (be.upload2d(d_bmat + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
-            be.upload2d(d_bmat + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()) ||
-            be.upload(d_cbin + ch, &cbin[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B)) return DH_EDEVICE;
+    // v: the channel's new increment, or its new bin
+    int retune(uint32_t ch, uint32_t v) {
+        word[ch] = word_of(v);
+        const size_t pitch = sizeof(float) * ncols, rows = 2 * (size_t) tpad;
+        if (place(d_bmat, ch, [&](float* dst, const float* src) { return be.upload2d(dst, pitch, src, sizeof(float), sizeof(float), rows); }) ||
+            be.upload(d_word + ch, &word[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B)) return DH_EDEVICE;
         return be.sync() ? DH_EDEVICE : DH_OK;
     }
     // raster: the push's no outputs slab by slab -- fold, then DFT + rotation
@@ -371,57 +391,6 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
             if (dh_be_cz_fold(fold, stream) || dh_be_cz_gemm_raster(ras, stream)) return DH_EDEVICE;
         }
         return DH_OK;
-    }
-    int init(const dh_channelizer_config& c, uint32_t interp, uint32_t raster) {
-        if (raster) return init_raster(c);
-        B = c.n_channels; D = c.decimation; L = interp; tpad = dh_cz_tpad_rat(c.n_taps, L); ncols = dh_cz_ncols(B); max_input = c.max_input;
-        hist = tpad - 1u;
-        cf32 = c.input_format == DH_CZ_CF32; fm = c.output_mode == DH_CZ_FM; dcblock = c.dcblock != 0;
-        taps.assign((size_t) L * tpad, 0.0f);
-        for (uint32_t p = 0; p < L; p++) {
-            const uint32_t r = (uint32_t) (((uint64_t) p * D + D - 1u) % L);
-            for (uint32_t k = 0; r + (uint64_t) k * L < c.n_taps; k++) taps[(size_t) p * tpad + k] = c.taps[r + k * L];
-        }
-        inc.assign(c.increments, c.increments + B);
-        const size_t bm = L * bank(), win = 2 * ((size_t) tpad - 1 + max_input);
-        bool ok = bufs.alloc(d_tables, 4 * 4096);
-        ok &= bufs.alloc(d_inc, B);
-        ok &= bufs.alloc(d_bmat, bm);
-        ok &= bufs.alloc(d_win[0], win, dh::ZERO_ON_RESET);
-        ok &= bufs.alloc(d_win[1], win, dh::ZERO_ON_RESET);
-        ok &= bufs.alloc(d_state, (size_t) DH_CZ_STATE_WORDS * B, dh::ZERO_PER_CHANNEL);
-        if (fm) ok &= bufs.alloc(d_zbuf, 2 * ((size_t) outputs(max_input) + 1) * B);
-        ok &= bufs.alloc(d_stage, in_bytes() * max_input);
-        if (!ok) return DH_ENOMEM;
-        rat.g.bmat = d_bmat; rat.g.coarse = d_tables; rat.g.fine = d_tables + 8192; rat.g.inc = d_inc; rat.g.zbuf = d_zbuf;
-        rat.g.D = D; rat.g.tpad = tpad; rat.g.B = B; rat.g.ncols = ncols; rat.g.fm = fm; rat.L = L;
-        std::vector<float> bmat(bm, 0.0f), re(2 * (size_t) tpad), im(2 * (size_t) tpad);
-        for (uint32_t p = 0; p < L; p++)
-            for (uint32_t b = 0; b < B; b++) {
-                dh_cz_columns(taps.data() + (size_t) p * tpad, tpad, inc[b], re.data(), im.data());
-                float* bank_p = bmat.data() + p * bank();
-                const uint32_t cr = dh_cz_col(b, 0), ci = dh_cz_col(b, 1);
-                for (size_t r = 0; r < 2 * (size_t) tpad; r++) { bank_p[r * ncols + cr] = re[r]; bank_p[r * ncols + ci] = im[r]; }
-            }
-        if (be.upload(d_tables, dh_cz_host_tables(), sizeof(float) * 4 * 4096) || be.upload(d_inc, inc.data(), sizeof(uint32_t) * B) ||
-            be.upload(d_bmat, bmat.data(), sizeof(float) * bm)) return DH_EDEVICE;
-        const int rc = clear();
-        if (rc != DH_OK) return rc;
-        return be.sync() ? DH_EDEVICE : DH_OK;           // (the host copies above are released on return)
-    }
-    int retune(uint32_t ch, uint32_t u) {
-        if (K) return retune_raster(ch, u);
-        std::vector<float> re(2 * (size_t) tpad), im(2 * (size_t) tpad);
-        inc[ch] = u;
-        const size_t pitch = sizeof(float) * ncols;
-        for (uint32_t p = 0; p < L; p++) {
-            dh_cz_columns(taps.data() + (size_t) p * tpad, tpad, u, re.data(), im.data());
-            if (be.upload2d(d_bmat + p * bank() + dh_cz_col(ch, 0), pitch, re.data(), sizeof(float), sizeof(float), re.size()) ||
-                be.upload2d(d_bmat + p * bank() + dh_cz_col(ch, 1), pitch, im.data(), sizeof(float), sizeof(float), im.size()))
-                return DH_EDEVICE;
-        }
-        if (be.upload(d_inc + ch, &inc[ch], sizeof(uint32_t)) || bufs.zero_row(ch, B)) return DH_EDEVICE;
-        return be.sync() ? DH_EDEVICE : DH_OK;
     }
     static bool level_ok(float v) { return v - v == 0.0f && v >= 0.0f; }       // finite and not negative
     int set_squelch(float open_level, float close_level, uint32_t hang) {

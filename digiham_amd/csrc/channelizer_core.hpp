@@ -175,7 +175,9 @@ struct DhCzParams {
     int fm;                       // 0: rotated z to the output rows, 1: to zbuf
 };
 
-// the rotation and the store of output `row` of channel b at input index nj (mod 2^32), y = the two chains
+// the rotation and the store of output `row` of channel b at input index nj (mod 2^32), y = the two chains.  (The rotation and
+// the store stand here and in dh_cz_emit_raster: behind one function of any shape tried, both GEMM kernels compile to
+// other instructions.)
 DH_HD void dh_cz_emit_at(const DhCzParams& P, uint32_t row, uint32_t b, uint32_t nj, float yr, float yi) {
     float pr, pi;
     dh_cz_phasor(0u - P.inc[b] * nj, P.coarse, P.fine, pr, pi);
@@ -321,6 +323,9 @@ DH_HD void dh_cz_fm_item(const float* zbuf, const float* state, float* out, size
     out[(size_t) b * out_stride + j] = dh_fe_atan2f_over_pi(wi, wr);
 }
 
+// one step of the DC blocker: y for the input x after (x_prev, y_prev)
+DH_HD float dh_cz_dc_step(float x, float xp, float yp) { const float d = x - xp; const float f = 0.995f * yp; return d + f; }
+
 // the serial part of FM mode, one channel: DC blocker over the channel's n_out outputs in place, then the carried state
 DH_HD void dh_cz_tail_channel(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, uint32_t b) {
     float* st = state + (size_t) b * DH_CZ_STATE_WORDS;
@@ -331,10 +336,10 @@ DH_HD void dh_cz_tail_channel(const float* zbuf, float* state, float* out, size_
         for (; j + 8 <= n_out; j += 8) {          // eight loads in flight ahead of the recurrence
             float v[8];
             for (int e = 0; e < 8; e++) v[e] = row[j + e];
-            for (int e = 0; e < 8; e++) { const float d = v[e] - xp; const float f = 0.995f * yp; const float y = d + f; xp = v[e]; yp = y; v[e] = y; }
+            for (int e = 0; e < 8; e++) { const float y = dh_cz_dc_step(v[e], xp, yp); xp = v[e]; yp = y; v[e] = y; }
             for (int e = 0; e < 8; e++) row[j + e] = v[e];
         }
-        for (; j < n_out; j++) { const float x = row[j]; const float d = x - xp; const float f = 0.995f * yp; const float y = d + f; xp = x; yp = y; row[j] = y; }
+        for (; j < n_out; j++) { const float x = row[j]; const float y = dh_cz_dc_step(x, xp, yp); xp = x; yp = y; row[j] = y; }
         st[2] = xp; st[3] = yp;
     }
     if (n_out) { const float* z = zbuf + 2 * ((size_t) (n_out - 1) * B + b); st[0] = z[0]; st[1] = z[1]; }
@@ -398,7 +403,9 @@ DH_HD void dh_cz_power_segment(const DhCzPowerParams& P, uint32_t b, uint32_t s)
     if (s + 1u == P.nseg) st[3] = complete ? 0u : dh_cz_f_bits(S);
 }
 
-// the gate recurrence of channel b over the n_blocks blocks this push completed; counts[b]; the carried (open, quiet)
+// the gate recurrence of channel b over the n_blocks blocks this push completed; counts[b]; the carried (open, quiet).  (The
+// step stands twice, in the unrolled eight and in the tail: behind one function or lambda k_cz_gate compiles to other
+// instructions.)
 DH_HD void dh_cz_gate_channel(const DhCzPowerParams& P, uint32_t b) {
     uint32_t* st = P.pstate + (size_t) b * DH_CZ_PSTATE_WORDS;
     uint32_t open = st[1], quiet = st[2], any = open;
@@ -444,15 +451,19 @@ inline const float* dh_cz_host_tables() {
     return t;
 }
 
+// the four B-operand entries of G[k] = (gr, gi): rows 2k (x real part) and 2k + 1 (x imaginary part) of a channel's two columns
+inline void dh_cz_column_entries(float gr, float gi, uint32_t k, float* re_col, float* im_col) {
+    re_col[2 * k] = gr; re_col[2 * k + 1] = -gi;
+    im_col[2 * k] = gi; im_col[2 * k + 1] = gr;
+}
+
 // the two GEMM columns of one channel: re_col / im_col [2 T'] (rows 2k, 2k + 1), h zero-padded to T'
 inline void dh_cz_columns(const float* h, uint32_t tpad, uint32_t u, float* re_col, float* im_col) {
     const float* t = dh_cz_host_tables();
     for (uint32_t k = 0; k < tpad; k++) {
         float pr, pi;
         dh_cz_phasor(u * k, t, t + 8192, pr, pi);
-        const float gr = h[k] * pr, gi = h[k] * pi;
-        re_col[2 * k] = gr; re_col[2 * k + 1] = -gi;
-        im_col[2 * k] = gi; im_col[2 * k + 1] = gr;
+        dh_cz_column_entries(h[k] * pr, h[k] * pi, k, re_col, im_col);
     }
 }
 
@@ -462,8 +473,7 @@ inline void dh_cz_raster_columns(uint32_t K, uint32_t kpad, uint32_t c, float* r
     for (uint32_t r = 0; r < kpad; r++) {
         float gr = 0.0f, gi = 0.0f;
         if (r < K) dh_cz_phasor(dh_cz_raster_phi((uint32_t) (((uint64_t) c * r) % K), K), t, t + 8192, gr, gi);
-        re_col[2 * r] = gr; re_col[2 * r + 1] = -gi;
-        im_col[2 * r] = gi; im_col[2 * r + 1] = gr;
+        dh_cz_column_entries(gr, gi, r, re_col, im_col);
     }
 }
 

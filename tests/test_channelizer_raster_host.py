@@ -1,8 +1,10 @@
-"""The channelizer's raster mode under AddressSanitizer, UndefinedBehaviorSanitizer and leak detection:
-tests/host_cpp/raster_lifecycle.cpp, a stand-alone program over the CPU backend -- invalid configurations with nothing
-allocated, create with the k-th backend allocation failing for every k, a configuration of the older struct size whose
-heap block ends where that struct ends, and ragged pushes with a retune and a reset in both output modes, where every
-window, fold-buffer and output index is the sanitizer's to check.  CPU tier only; nothing is loaded into this process."""
+"""The channelizer's host handle under AddressSanitizer, UndefinedBehaviorSanitizer and leak detection:
+tests/host_cpp/raster_lifecycle.cpp, a stand-alone program over the CPU backend -- the raster's invalid configurations with
+nothing allocated, a configuration of the older struct size whose heap block ends where that struct ends, and for each of
+the three kinds of bank (fixed offsets, rational rate, raster) create with the k-th backend allocation failing for every k
+and ragged pushes with a retune and a reset in both output modes, where every window, fold-buffer and output index is the
+sanitizer's to check; then the one slot of dh_cz_plan_rat at L = 1 against a fixed bank's position formulas, past 2^32
+included.  CPU tier only; nothing is loaded into this process."""
 import os
 import subprocess
 

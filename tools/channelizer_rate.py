@@ -30,7 +30,12 @@ measured"), in one run on one device:
   --config a --out F --lib variants/lib_parent.so --tag parent_1          --config a --out F --lib digiham_amd/libdigiham_amd.so --tag new_1
   --config a --out F --lib variants/lib_parent.so --tag parent_2          --config a --out F --lib digiham_amd/libdigiham_amd.so --tag new_2
 and the split between k_cz_fold and k_cz_gemm_raster: rocprofv3 --kernel-trace --stats -- python tools/channelizer_rate.py
---raster --modes iq, in a run of its own."""
+--raster --modes iq, in a run of its own.
+The lines of profiles/channelizer_one_gemm_rate.jsonl ("One GEMM entry measured, and not taken"; the
+lines tagged new_* are of a build, not kept, in which a fixed bank launched k_cz_gemm_rat with one slot), in one run on one
+device, for each of --config a, --config b and --config c-short --pushes 50 the four commands
+  --out F --lib variants/lib_parent.so --tag parent_1                     --out F --lib <that build> --tag new_1
+  --out F --lib variants/lib_parent.so --tag parent_2                     --out F --lib <that build> --tag new_2"""
 import argparse
 import json
 import os
