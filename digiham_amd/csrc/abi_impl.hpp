@@ -4,11 +4,18 @@
 // shipped and never loaded by the digiham_amd package).
 //
 // Before inclusion the includer defines DH_BACKEND (the duck-typed interface listed in engine_impl.hpp; which instantiation
-// a launch_* runs is not the backend's to decide: launch_plan.hpp) and these free functions:
+// a launch_* runs is not the backend's to decide: launch_plan.hpp) and these free functions of its own:
 //   int  dh_be_device_count();
 //   const char* dh_be_last_error();
 //   int  dh_be_alloc(int device, size_t bytes, void** out); int dh_be_free(void*);
 //   int  dh_be_copy(void* dst, const void* src, size_t bytes, int to_host);
+//   int  dh_be_frontend(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock, void* stream);
+//   int  dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, float* d, size_t tiles, void* stream);
+//   int  dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream);
+//   dh_be_cz_gemm / dh_be_cz_gemm_rat / dh_be_cz_fold / dh_be_cz_gemm_raster               the channelizer's matrix-core stages
+//   dh_be_monitor_open, dh_be_reset_channels                                               step A of the band monitor, the masked reset
+// (kernels with barriers, LDS staging, matrix-core tiles or wave votes: engine.hip defines the gfx950 launches, the harness and
+// the *_core.hpp files the CPU restatements) -- and includes helper_launches.hpp, which with the core headers states ONCE, for both builds:
 //   int  dh_be_fec_block(int code, void* words, uint8_t* ok, size_t n, void* stream);
 //   int  dh_be_bptc(const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n, void* stream);
 //   int  dh_be_trellis(const uint8_t* in, size_t in_stride, int n_dibits, uint8_t* out, size_t out_stride, uint8_t* metric, size_t n, void* stream);
@@ -17,17 +24,12 @@
 //   int  dh_be_dvfilter(const int16_t* in, int16_t* out, float* state, size_t B, size_t stride, size_t n, void* stream);
 //   int  dh_be_div_gain(const float* in, float* out, size_t n, int narrow, void* stream);
 //   int  dh_be_div_const(const float* in, float* out, size_t n, unsigned divisor, void* stream);
-//   int  dh_be_frontend(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock, void* stream);
-//   int  dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, float* d, size_t tiles, void* stream);
 //   int  dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* stream);
-//   int  dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream);
-// and the launches of the four later handles, each listed at the head of its section below:
-//   dh_be_cz_window / dh_be_cz_gemm / dh_be_cz_gemm_rat / dh_be_cz_fm / dh_be_cz_power      the channelizer
-//   dh_be_cz_fold / dh_be_cz_gemm_raster                                                   ... in raster mode
+// and the other launches of the four later handles, each listed at the head of its section below:
+//   dh_be_cz_window / dh_be_cz_fm / dh_be_cz_power                                         the channelizer
 //   dh_be_preroll_append / dh_be_preroll_gather                                            the pre-roll ring
 //   dh_be_outpack_scan / dh_be_outpack_copy                                                the packed read-out
-//   dh_be_monitor_open / dh_be_monitor_assign, dh_be_reset_channels                        the band monitor, the masked reset
-// (engine.hip defines the gfx950 ones; the *_core.hpp files the CPU harness's.)
+//   dh_be_monitor_assign / dh_be_monitor_close                                             steps B and C of the band monitor
 //
 // A handle kind is a struct over dh_place (device, stream) with a backend `be`, scope() and release(), an init() that
 // allocates through its DeviceBuffers, and a dh_*_create that validates its configuration and calls dh_create; dh_destroy,

@@ -130,6 +130,7 @@
 
 #include <math.h>
 
+#include "../../include/digiham_amd.h"
 #include "frontend_core.hpp"
 
 #define DH_CZ_TAP_STEP 16         // T' = a multiple of the K extent of one LDS chunk of the GEMM (16 taps = 32 real K)
@@ -478,11 +479,7 @@ inline void dh_cz_raster_columns(uint32_t K, uint32_t kpad, uint32_t c, float* r
 }
 
 #if !DH_DEVICE_BUILD
-// ---- host backends of the CPU test harness (engine.hip defines the gfx950 ones) --------------------------------------
-static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void*) {
-    for (size_t e = 0; e < H + n_in; e++) dh_cz_window_item(cur, prev, prev_n, in, cf32, H, e);
-    return 0;
-}
+// ---- CPU restatements of the matrix-core stages (engine.hip has the gfx950 kernels; the other launches follow, one text for both builds)
 static int dh_be_cz_gemm(const DhCzParams& P, void*) {
     for (uint32_t b = 0; b < P.B; b++)
         for (uint32_t row = 0; row < P.n_out; row++) dh_cz_output(P, row, b);
@@ -504,16 +501,54 @@ static int dh_be_cz_gemm_raster(const DhCzRasterParams& R, void*) {
         for (uint32_t i = 0; i < R.g.n_out; i++) dh_cz_output_raster(R, i, b);
     return 0;
 }
-static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void*) {
-    for (uint32_t b = 0; b < B; b++)
-        for (uint32_t j = 0; j < n_out; j++) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
-    for (uint32_t b = 0; b < B; b++) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
-    return 0;
-}
-static int dh_be_cz_power(const DhCzPowerParams& P, void*) {
-    for (uint32_t s = P.nseg; s-- > 0;)                                 // last segment first: the lanes of a launch have no order
-        for (uint32_t b = 0; b < P.B; b++) dh_cz_power_segment(P, b, s);
-    for (uint32_t b = 0; b < P.B; b++) dh_cz_gate_channel(P, b);
-    return 0;
-}
 #endif
+
+// ---------------------------------------------------------------------------------- channelizer (channelizer_core.hpp)
+namespace {
+
+__global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n) {
+    for (size_t e = blockIdx.x * (size_t) blockDim.x + threadIdx.x; e < n; e += (size_t) gridDim.x * blockDim.x)
+        dh_cz_window_item(cur, prev, prev_n, in, cf32, H, e);
+}
+
+__global__ __launch_bounds__(256) void k_cz_fm(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_out) return;
+    for (uint32_t b = blockIdx.y; b < B; b += gridDim.y) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_cz_tail(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock) {
+    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
+    if (b < B) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
+}
+
+// Block power (channelizer_core.hpp): one lane per (channel, block segment of this push).  FM mode: lanes on consecutive
+// channels of zbuf [n_out][B][2]; IQ mode: lanes on consecutive segments of one channel's row.
+__global__ __launch_bounds__(256) void k_cz_power(const DhCzPowerParams P) {
+    const size_t n = (size_t) P.B * P.nseg;
+    for (size_t t = (size_t) blockIdx.x * 256u + threadIdx.x; t < n; t += (size_t) gridDim.x * 256u) {
+        const uint32_t b = (uint32_t) (P.fm ? t % P.B : t / P.nseg), s = (uint32_t) (P.fm ? t / P.B : t % P.nseg);
+        dh_cz_power_segment(P, b, s);
+    }
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_cz_gate(const DhCzPowerParams P) {
+    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
+    if (b < P.B) dh_cz_gate_channel(P, b);
+}
+
+}  // namespace
+
+static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream) {
+    const size_t n = H + n_in;
+    return dh_launch(k_cz_window, dim3(grid_for(n, 256)), dim3(256), 0, stream, "k_cz_window", cur, prev, prev_n, in, cf32, H, n) ? DH_EDEVICE : DH_OK;
+}
+static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream) {
+    if (!n_out) return DH_OK;
+    if (dh_launch(k_cz_fm, dim3((n_out + 255) / 256, B < 65535u ? B : 65535u), dim3(256), 0, stream, "k_cz_fm", zbuf, state, out, out_stride, B, n_out)) return DH_EDEVICE;
+    return dh_launch(k_cz_tail, dim3((B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, stream, "k_cz_tail", zbuf, state, out, out_stride, B, n_out, dcblock) ? DH_EDEVICE : DH_OK;
+}
+static int dh_be_cz_power(const DhCzPowerParams& P, void* stream) {
+    if (P.nseg && dh_launch(k_cz_power, dim3(grid_for((size_t) P.B * P.nseg, 256)), dim3(256), 0, stream, "k_cz_power", P)) return DH_EDEVICE;
+    return dh_launch(k_cz_gate, dim3((P.B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, stream, "k_cz_gate", P) ? DH_EDEVICE : DH_OK;
+}

@@ -103,6 +103,55 @@ DH_HD uint32_t dh_brev32(uint32_t x) {
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// The launch vocabulary of the helper kernels (at the end of the core header that owns their bodies; helper_launches.hpp for
+// the batch FEC and stand-alone stages): their __global__ wrappers and launch statements are one text for both builds.  A
+// launcher ends in dh_launch(kernel, grid, block, lds_bytes, stream, what, args...), 0 = launched.  hipcc gives the words their usual meaning (in its host pass too, hence DH_DEVICE_BUILD here); in the
+// CPU build __global__ is a plain function, blockIdx / threadIdx / blockDim / gridDim are thread-local (tests push from several
+// host threads), __shared__ is storage that outlives the call, the atomics on the monitor's summary words are plain updates,
+// and dh_launch is a loop: the kernel called once per (block, thread) of the grid the launcher computed, LAST FIRST --
+// the lanes of a launch have no order, and nothing may come to rest on one.
+//   dh_workgroup(lanes)   the block of a kernel whose body runs its own lane loops (DH_FOR_LANES, DH_OP_FOR): dim3(lanes) on
+//                         the device; the CPU build visits such a block once
+#if DH_DEVICE_BUILD
+static inline dim3 dh_workgroup(unsigned lanes) { return dim3(lanes); }
+// (engine.hip defines it: hipLaunchKernelGGL, then the one launch-failure check, whose message is `what`)
+template <class K, class... A>
+static int dh_launch(K kernel, dim3 grid, dim3 block, size_t lds_bytes, void* stream, const char* what, const A&... args);
+#else
+struct dim3 {
+    unsigned x, y, z; bool lanes_in_body = false;
+    dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
+};
+static inline dim3 dh_workgroup(unsigned lanes) { dim3 d(lanes); d.lanes_in_body = true; return d; }
+struct DhLaunchIndex { unsigned x, y, z; };
+inline thread_local DhLaunchIndex blockIdx, threadIdx, blockDim, gridDim;
+#define __global__ static
+#define __launch_bounds__(...)
+#define __shared__ static thread_local
+template <class T> inline T atomicAdd(T* p, T v) { const T old = *p; *p = old + v; return old; }
+template <class T> inline T atomicMin(T* p, T v) { const T old = *p; if (v < old) *p = v; return old; }
+template <class K, class... A>
+inline int dh_launch(K kernel, dim3 grid, dim3 block, size_t /* lds_bytes */, void* /* stream */, const char* /* what */, const A&... args) {
+    const dim3 threads = block.lanes_in_body ? dim3(1) : block;
+    gridDim = { grid.x, grid.y, grid.z }; blockDim = { block.x, block.y, block.z };
+    for (unsigned bz = grid.z; bz-- > 0;) for (unsigned by = grid.y; by-- > 0;) for (unsigned bx = grid.x; bx-- > 0;)
+        for (unsigned tz = threads.z; tz-- > 0;) for (unsigned ty = threads.y; ty-- > 0;) for (unsigned tx = threads.x; tx-- > 0;) {
+            blockIdx = { bx, by, bz }; threadIdx = { tx, ty, tz };
+            kernel(args...);
+        }
+    return 0;
+}
+#endif
+// the stream of a back end; a back end without one (the stand-alone test programs') launches on the null stream
+template <class BE> static auto dh_be_stream(BE& be, int) -> decltype((void*) be.ms()) { return (void*) be.ms(); }
+template <class BE> static void* dh_be_stream(BE&, long) { return nullptr; }
+// the grid of a one-item-per-lane kernel with a grid-stride loop
+inline unsigned grid_for(size_t n, unsigned block) {
+    const size_t g = (n + block - 1) / block;
+    return (unsigned) (g < 1 ? 1 : (g > 8192 ? 8192 : g));      // 256 CUs x 32 resident workgroups, grid-stride beyond
+}
+
 template <typename T> DH_HD T dh_min(T a, T b) { return a < b ? a : b; }
 template <typename T> DH_HD T dh_max(T a, T b) { return a > b ? a : b; }
 

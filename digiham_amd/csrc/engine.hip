@@ -5,6 +5,8 @@
 // data, so the workgroup -> XCD round-robin of the dispatcher needs no remapping: each XCD's L2
 // only ever holds its own channels' rows, and 16 384-channel grids give 64 workgroups per CU.
 // Batch FEC kernels are one item per lane, 256-lane workgroups, grid-stride.
+// The helper kernels and their launches stand at the ends of the core headers and in helper_launches.hpp, one text for this build and the
+// CPU harness; here are the kernels that need barriers, LDS staging, matrix cores or wave votes.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 // (no FMA contraction anywhere: products and sums of the exact paths round separately, as the
@@ -34,6 +36,21 @@ int hip_fail(hipError_t e, const char* what) {
 }
 #define DH_OPAQUE_SGPR(x) asm volatile("" : "+s"(x))        // an opaque copy: the compiler must not tie it to an earlier computation of the same value
 #define HIP_TRY(expr) do { if (hip_fail((expr), #expr)) return DH_EDEVICE; } while (0)
+
+}  // namespace
+
+// The launch of a helper kernel (the core headers and helper_launches.hpp state each one, for this build and the CPU harness; declared in dh_portable.hpp): the one place a
+// launch failure is looked for, and its message names the kernel.
+template <class K, class... A>
+static int dh_launch(K kernel, dim3 grid, dim3 block, size_t lds_bytes, void* stream, const char* what, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t) stream, args...);
+    return hip_fail(hipGetLastError(), what);
+}
+static int dh_fec_tables(const DhFecTables** out);
+static int dh_be_golay(const DhFecTables* T, int which, uint32_t* words, uint8_t* ok, size_t n, void* stream);
+#include "helper_launches.hpp"
+
+namespace {
 
 #define DH_TILE_LB 3
 #define DH_TILES_PER_WG 4
@@ -188,49 +205,6 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_TILE_LB)) voi
         dh_rrc_tile<NZ, FAST>(R, blockIdx.y, t, S);
 }
 
-__global__ __launch_bounds__(DH_WAVE) void k_rrc_generic(const DhRrcGenParams G) {
-    __shared__ float win[DH_GEN_WINDOW];
-    __shared__ float taps[DH_MAX_NZ + 1];
-    dh_rrc_generic_tile(G, blockIdx.y, blockIdx.x, win, taps);
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz) {
-    __shared__ float sh[DH_MAX_NZ];
-    dh_rrc_hist_channel(hist, in, in_stride, n, n_per, nz, blockIdx.x, sh);
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_dmr(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_dmr_channel(P, blockIdx.x, S);
-}
-
-__global__ __launch_bounds__(DH_WAVE, 4) void k_ysf(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_ysf_channel(P, blockIdx.x, S);
-}
-
-__global__ __launch_bounds__(DH_WAVE, 4) void k_nxdn(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_nxdn_channel(P, blockIdx.x, S);
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_pocsag(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_pocsag_channel(P, blockIdx.x, S);
-}
-
-// protocol scan: nine sync tests at every symbol position, no frame state machine (decoder_core.hpp, dh_scan_channel)
-__global__ __launch_bounds__(DH_WAVE) void k_scan(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_scan_channel(P, blockIdx.x, S);
-}
-
-#define DH_DSTAR_LB 4
-__global__ __launch_bounds__(DH_WAVE, DH_DSTAR_LB) void k_dstar(const DhDecParams P) {
-    __shared__ DhDecShared S;
-    dh_dstar_channel(P, blockIdx.x, S);
-}
-
 // which XCD workgroup i of a launch runs on (HipBackend::tail_split_probe)
 __global__ __launch_bounds__(DH_WAVE) void k_xcc_probe(uint32_t* out) {
     if (threadIdx.x == 0) out[blockIdx.x] = dh_xcc_id();
@@ -258,21 +232,6 @@ __global__ __launch_bounds__(DH_WAVE) void k_lds_unaligned_probe(uint32_t* out) 
 #endif
 }
 
-__global__ void k_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B) {
-    const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch < B) dh_init_state_channel(dsp_state, state_words, tail0, dec_state, slot_filter, ch);
-}
-
-__global__ void k_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B) {
-    const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch < B) dh_set_slot_filter_channel(dec_state, filter, ch);
-}
-
-__global__ void k_fec_block(const DhFecTables* T, int code, void* words, uint8_t* ok, size_t n) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        dh_fec_block_item(*T, code, words, ok, i);
-}
-
 // Golay: syndrome LUT (16 KiB) staged in LDS once per workgroup, then grid-stride over the words
 __global__ __launch_bounds__(256) void k_golay(const DhFecTables* T, int which, uint32_t* words, uint8_t* ok, size_t n) {
     __shared__ uint32_t lut[4096];
@@ -287,32 +246,6 @@ __global__ __launch_bounds__(256) void k_golay(const DhFecTables* T, int which, 
         words[i] = w;
         ok[i] = r ? 1 : 0;
     }
-}
-
-__global__ void k_bptc(const DhFecTables* T, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        dh_bptc_item(*T, in, out, ok, i);
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_trellis(const uint8_t* in, size_t in_stride, int n_dibits, uint8_t* out, size_t out_stride,
-                                                     uint8_t* metric, size_t n) {
-    __shared__ DhDecShared S;
-    dh_trellis_wave(in, in_stride, n_dibits, out, out_stride, metric, n, blockIdx.x, S);
-}
-
-__global__ void k_crc16(const uint8_t* in, size_t stride, int count, uint16_t* out, size_t n) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        dh_crc16_item(in, stride, count, out, i);
-}
-
-__global__ void k_whitening(const uint8_t* in, uint8_t* out, size_t stride, int n_bits, size_t n) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        dh_whitening_item(in, out, stride, n_bits, i);
-}
-
-__global__ void k_dvfilter(const int16_t* in, int16_t* out, float* state, size_t B, size_t stride, size_t n) {
-    const size_t ch = blockIdx.x * (size_t) blockDim.x + threadIdx.x;
-    if (ch < B) dh_dvfilter_channel(in + ch * stride, out + ch * stride, state + ch * 22, n);
 }
 
 // The front-end in ONE launch (round 3): a workgroup of five wavefronts takes DH_FE_CH channels through tiles of DH_FE_TS
@@ -423,16 +356,6 @@ __global__ __launch_bounds__(320) void k_fe_fused(const int16_t* in, size_t in_s
 #endif
 }
 
-__global__ void k_div_gain(const float* in, float* out, size_t n, double gain, double rgain) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        out[i] = dh_div_gain(in[i], gain, rgain);
-}
-
-__global__ void k_div_const(const float* in, float* out, size_t n, float d, float r) {
-    for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        out[i] = dh_div_const(in[i], d, r);
-}
-
 // one tile per wavefront: D = C + A x B with v_mfma_f32_16x16x32_f16 (dh_debug_mfma_f16)
 __global__ __launch_bounds__(DH_WAVE) void k_mfma_f16(const uint16_t* A, const uint16_t* B, const float* C, float* D) {
 #if DH_ON_GPU
@@ -447,19 +370,6 @@ __global__ __launch_bounds__(DH_WAVE) void k_mfma_f16(const uint16_t* A, const u
     for (int r = 0; r < 4; r++) D[t * 256 + (4 * q + r) * 16 + m] = c[r];
 #endif
 }
-__global__ void k_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale) {
-#if DH_ON_GPU
-    for (size_t i = (blockIdx.x * (size_t) blockDim.x + threadIdx.x) * 4; i < n; i += (size_t) gridDim.x * blockDim.x * 4) {
-        dh_f4 v; v.x = in[i]; v.y = i + 1 < n ? in[i + 1] : 0.0f; v.z = i + 2 < n ? in[i + 2] : 0.0f; v.w = i + 3 < n ? in[i + 3] : 0.0f;
-        dh_h4 a, b;
-        dh_f16_split4(v, scale, a, b);
-        uint16_t t1[4], t2[4];
-        __builtin_memcpy(t1, &a, sizeof(t1)); __builtin_memcpy(t2, &b, sizeof(t2));      // the four halves as the kernels store them (one 8-byte vector)
-        for (int j = 0; j < 4 && i + j < n; j++) { h1[i + j] = t1[j]; h2[i + j] = t2[j]; }
-    }
-#endif
-}
-
 // dh_debug_copy: the streaming ceiling of the lease (16 bytes per lane, non-temporal both ways, four pieces in flight per lane)
 typedef uint32_t dh_u4s __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void k_copy16(const dh_u4s* __restrict__ src, dh_u4s* __restrict__ dst, size_t n16) {
@@ -490,11 +400,6 @@ __global__ __launch_bounds__(256) void k_read16(const dh_u4s* __restrict__ src, 
     }
     for (; i < n16; i += stride) acc ^= __builtin_nontemporal_load(src + i);
     if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u && acc.x == 0x9E3779B9u) { volatile uint32_t* sink = g_read_sink; sink[0] = acc.x; sink[1] = acc.y; }      // (volatile: the variable has internal linkage and no reader -- a plain store, and with it the whole kernel, is dead code)
-}
-
-inline unsigned grid_for(size_t n, unsigned block) {
-    const size_t g = (n + block - 1) / block;
-    return (unsigned) (g < 1 ? 1 : (g > 8192 ? 8192 : g));      // 256 CUs x 32 resident workgroups, grid-stride beyond
 }
 
 // ---------------------------------------------------------------------------------- FEC tables
@@ -843,45 +748,9 @@ struct HipBackend {
     int launch_rrc_tiles(const DhRrcParams& R, uint32_t nz, bool fast) {
         return dh_plan_rrc_tiles(nz, fast, [&](auto i) { using I = decltype(i); return go_rrc_tiles<I::NZ, I::FAST>(R); });
     }
-    int launch_rrc_generic(const DhRrcGenParams& G) {
-        for (uint32_t b0 = 0; b0 < G.n_channels; b0 += 65535u) {      // channels on grid.y: at most 65 535 per launch
-            DhRrcGenParams Q = G;
-            Q.n_channels = std::min<uint32_t>(G.n_channels - b0, 65535u);
-            Q.in = G.in + (size_t) b0 * G.in_stride; Q.out = G.out + (size_t) b0 * G.out_stride; Q.hist = G.hist + (size_t) b0 * G.nz;
-            hipLaunchKernelGGL(k_rrc_generic, dim3((G.n + DH_FTILE - 1) / DH_FTILE, Q.n_channels), dim3(DH_WAVE), 0, ms(), Q);
-            if (launched("k_rrc_generic")) return -1;
-        }
-        return 0;
-    }
-    int launch_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B) {
-        hipLaunchKernelGGL(k_rrc_hist, dim3(B), dim3(DH_WAVE), 0, ms(), hist, in, in_stride, n, n_per, nz);
-        return launched("k_rrc_hist");
-    }
-    int launch_decoder(const DhDecParams& P, int proto) {
-        if (proto == DH_PROTO_DMR) hipLaunchKernelGGL(k_dmr, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        else if (proto == DH_PROTO_YSF) hipLaunchKernelGGL(k_ysf, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        else if (proto == DH_PROTO_NXDN) hipLaunchKernelGGL(k_nxdn, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        else if (proto == DH_PROTO_POCSAG) hipLaunchKernelGGL(k_pocsag, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        else if (proto == DH_PROTO_SCAN) hipLaunchKernelGGL(k_scan, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        else hipLaunchKernelGGL(k_dstar, dim3(P.n_channels), dim3(DH_WAVE), 0, ms(), P);
-        return launched("k_decoder");
-    }
-    int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B) {
-        hipLaunchKernelGGL(k_init_state, dim3((B + 255) / 256), dim3(256), 0, ms(), dsp_state, state_words, tail0, dec_state, slot_filter, B);
-        return launched("k_init_state");
-    }
-    int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B) {
-        hipLaunchKernelGGL(k_set_slot_filter, dim3((B + 255) / 256), dim3(256), 0, ms(), dec_state, filter, B);
-        return launched("k_set_slot_filter");
-    }
 };
 
 // ---------------------------------------------------------------------------------- channelizer (channelizer_core.hpp)
-__global__ __launch_bounds__(256) void k_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n) {
-    for (size_t e = blockIdx.x * (size_t) blockDim.x + threadIdx.x; e < n; e += (size_t) gridDim.x * blockDim.x)
-        dh_cz_window_item(cur, prev, prev_n, in, cf32, H, e);
-}
-
 // The channelizer's GEMM on v_mfma_f32_16x16x4_f32 (bit for bit the k-ordered fmaf chain of dh_cz_output).  A workgroup of
 // four wavefronts computes DH_CZ_TM = 128 output instants x 128 real columns (64 channels); wavefront w takes rows 64 (w & 1)
 // and columns 64 (w >> 1) onwards as 4 x 4 tiles of 16 x 16.  K runs over the taps in chunks of DH_CZ_TAP_STEP = 16 (32 real
@@ -1061,67 +930,12 @@ __global__ __launch_bounds__(DH_CZ_FOLD_LANES) void k_cz_fold(const DhCzFoldPara
         if (row0 + (uint32_t) i < F.nrows) out[(size_t) i * F.kpad] = live ? acc[i] : make_float2(0.0f, 0.0f);
 }
 
-__global__ __launch_bounds__(256) void k_cz_fm(const float* zbuf, const float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out) {
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n_out) return;
-    for (uint32_t b = blockIdx.y; b < B; b += gridDim.y) dh_cz_fm_item(zbuf, state, out, out_stride, B, b, j);
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_cz_tail(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock) {
-    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
-    if (b < B) dh_cz_tail_channel(zbuf, state, out, out_stride, B, n_out, dcblock, b);
-}
-
-// Block power (channelizer_core.hpp): one lane per (channel, block segment of this push).  FM mode: lanes on consecutive
-// channels of zbuf [n_out][B][2]; IQ mode: lanes on consecutive segments of one channel's row.
-__global__ __launch_bounds__(256) void k_cz_power(const DhCzPowerParams P) {
-    const size_t n = (size_t) P.B * P.nseg;
-    for (size_t t = (size_t) blockIdx.x * 256u + threadIdx.x; t < n; t += (size_t) gridDim.x * 256u) {
-        const uint32_t b = (uint32_t) (P.fm ? t % P.B : t / P.nseg), s = (uint32_t) (P.fm ? t / P.B : t % P.nseg);
-        dh_cz_power_segment(P, b, s);
-    }
-}
-
-__global__ __launch_bounds__(DH_WAVE) void k_cz_gate(const DhCzPowerParams P) {
-    const uint32_t b = blockIdx.x * DH_WAVE + threadIdx.x;
-    if (b < P.B) dh_cz_gate_channel(P, b);
-}
-
-// ---------------------------------------------------------------------------------- pre-roll ring (preroll_core.hpp)
-// One workgroup per (1 024-sample tile, channel), blockIdx.y looping over the channels as in k_cz_fm.  Lane l of the 256
-// takes samples l, l + 256, l + 512, l + 768 of the tile: every wave instruction moves one contiguous 256-byte piece on
-// both sides, except the one piece per tile that may straddle the ring's seam.  The tile-0 workgroup of a channel is
-// the only one that touches that channel's open_at (append) or count (gather).
-__global__ __launch_bounds__(256) void k_preroll_append(const DhPrAppend A) {
-    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
-    for (uint32_t b = blockIdx.y; b < A.B; b += gridDim.y) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) dh_pr_append_open(A, b);
-#pragma unroll
-        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
-            const uint32_t i = i0 + 256u * k;
-            if (i < A.n) dh_pr_append_item(A, b, i);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_preroll_gather(const DhPrGather G) {
-    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
-    for (uint32_t b = blockIdx.y; b < G.B; b += gridDim.y) {
-        uint32_t pos;
-        const uint32_t count = dh_pr_count(G, b, pos);
-        if (blockIdx.x == 0 && threadIdx.x == 0) G.counts[b] = count;
-#pragma unroll
-        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
-            const uint32_t i = i0 + 256u * k;
-            if (i < count) dh_pr_gather_item(G, b, pos, i);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------- band monitor (monitor_core.hpp)
-// Steps A, B and C of a round: one lane per channel, 256-thread workgroups, the loop bound the same for every lane of a
-// workgroup so that the votes below see whole wavefronts.  Ordinary vector stores for the state and the per-channel
-// outputs; the summary block takes one vector atomic per wavefront and non-zero count (A), per newly named channel (B, C).
+// Step A of a round (B and C: monitor_core.hpp): one lane per channel, 256-thread workgroups, the loop bound the same for
+// every lane of a workgroup so that the votes below see whole wavefronts.  Ordinary vector stores for the state and the
+// per-channel outputs; the summary block takes one vector atomic per wavefront and non-zero count.  (Written in the 256-lane
+// vocabulary of dh_portable.hpp, so that the CPU tier could run it, its prologue comes out scheduled differently: DESIGN.md
+// section 4.  It stays as it is, with its restatement in monitor_core.hpp.)
 __global__ __launch_bounds__(256) void k_monitor_open(const DhMonOpen A) {
     const bool first = (threadIdx.x & (DH_WAVE - 1)) == 0;
     for (uint32_t base = blockIdx.x * 256u; base < A.B; base += gridDim.x * 256u) {
@@ -1136,45 +950,6 @@ __global__ __launch_bounds__(256) void k_monitor_open(const DhMonOpen A) {
             if (first && n_live) atomicAdd(&A.sum->n_live[p], n_live);
         }
     }
-}
-
-__global__ __launch_bounds__(256) void k_monitor_assign(const DhMonAssign S) {
-    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < S.B; b += gridDim.x * 256u) {
-        uint64_t start;
-        const uint32_t p = dh_mon_assign_channel(S, b, start);
-        if (p) {
-            atomicAdd(&S.sum->n_new[p], 1u);
-            atomicMin((unsigned long long*) &S.sum->min_start[p], (unsigned long long) start);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_monitor_close(const DhMonClose C) {
-    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < C.B; b += gridDim.x * 256u) {
-        uint64_t start;
-        const uint32_t p = dh_mon_close_channel(C, b, start);
-        if (p) {
-            atomicAdd(&C.sum->n_new[p], 1u);
-            atomicMin((unsigned long long*) &C.sum->min_start[p], (unsigned long long) start);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------- packed read-out (outpack_core.hpp)
-// k_outpack_scan: ONE workgroup of 256 lanes walks the engine's B channels 256 at a time -- B is at most a few tens of
-// thousands of 8-byte reads -- so that the order rule is exact without any hand-over between workgroups: candidate vote
-// and popcount below the lane, two shuffle scans per wavefront, the wavefronts' totals through 48 bytes of LDS, a running
-// carry across passes.  Ordinary vector stores only.
-// k_outpack_copy: a fixed grid, workgroup i takes entries i, i + gridDim.x, ... of THIS append while i < n_new; n_new and
-// the first entry's index are the two scratch words the scan left, the same for every lane.
-__global__ __launch_bounds__(DH_OP_LANES) void k_outpack_scan(const DhOutpack P) {
-    __shared__ DhOpShared S;
-    dh_outpack_scan(P, S);
-}
-
-__global__ __launch_bounds__(256) void k_outpack_copy(const DhOutpack P) {
-    const uint32_t first = P.scratch[0], n_new = P.scratch[1];
-    for (uint32_t i = blockIdx.x; i < n_new; i += gridDim.x) dh_outpack_copy_entry(P, first + i, threadIdx.x, 256u);
 }
 
 // Masked reset of an engine: workgroup i takes channels i, i + gridDim.x, ...; a channel whose flag is 0 costs one byte
@@ -1211,198 +986,57 @@ static int dh_be_copy(void* dst, const void* src, size_t bytes, int to_host) {
     HIP_TRY(hipMemcpy(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice));
     return DH_OK;
 }
-static int dh_be_fec_block(int code, void* words, uint8_t* ok, size_t n, void* stream) {
-    if (!n) return DH_OK;
-    if (!words || !ok) return DH_EINVAL;
-    const DhFecTables* T = nullptr;
-    int rc = tables_for_current_device(&T);
-    if (rc) return rc;
-    if (code == 5 || code == 6)
-        hipLaunchKernelGGL(k_golay, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t) stream, T, code == 6 ? 1 : 0, (uint32_t*) words, ok, n);
-    else
-        hipLaunchKernelGGL(k_fec_block, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, T, code, words, ok, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+// (the helper kernels' hooks: the core headers and helper_launches.hpp.  Here: what those launches take from this build, and the kernels whose
+// device form a thread-at-a-time visit cannot run -- the CPU harness has restatements of these)
+static int dh_fec_tables(const DhFecTables** out) { return tables_for_current_device(out); }
+static int dh_be_golay(const DhFecTables* T, int which, uint32_t* words, uint8_t* ok, size_t n, void* stream) {
+    return dh_launch(k_golay, dim3(grid_for(n, 256 * 8)), dim3(256), 0, stream, "k_golay", T, which, words, ok, n) ? DH_EDEVICE : DH_OK;
 }
-static int dh_be_bptc(const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n, void* stream) {
-    if (!n) return DH_OK;
-    const DhFecTables* T = nullptr;
-    int rc = tables_for_current_device(&T);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_bptc, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, T, in, out, ok, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_trellis(const uint8_t* in, size_t in_stride, int n_dibits, uint8_t* out, size_t out_stride, uint8_t* metric, size_t n, void* stream) {
-    if (!n) return DH_OK;
-    hipLaunchKernelGGL(k_trellis, dim3((unsigned) ((n + 3) / 4)), dim3(DH_WAVE), 0, (hipStream_t) stream, in, in_stride, n_dibits, out, out_stride, metric, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_crc16(const uint8_t* in, size_t stride, int count, uint16_t* out, size_t n, void* stream) {
-    if (!n) return DH_OK;
-    hipLaunchKernelGGL(k_crc16, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, in, stride, count, out, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_whitening(const uint8_t* in, uint8_t* out, size_t stride, int n_bits, size_t n, void* stream) {
-    if (!n) return DH_OK;
-    hipLaunchKernelGGL(k_whitening, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, in, out, stride, n_bits, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_dvfilter(const int16_t* in, int16_t* out, float* state, size_t B, size_t stride, size_t n, void* stream) {
-    if (!B) return DH_OK;
-    hipLaunchKernelGGL(k_dvfilter, dim3((unsigned) ((B + 63) / 64)), dim3(64), 0, (hipStream_t) stream, in, out, state, B, stride, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
 static int dh_be_frontend(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock, void* stream) {
     if (!B || !n) return DH_OK;
-    hipLaunchKernelGGL(k_fe_fused, dim3((unsigned) ((B + DH_FE_CH - 1) / DH_FE_CH)), dim3(320), 0, (hipStream_t) stream, in, in_stride, out, out_stride, state, B, n, mode, dcblock);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_fe_fused, dim3((unsigned) ((B + DH_FE_CH - 1) / DH_FE_CH)), dim3(320), 0, stream, "k_fe_fused", in, in_stride, out, out_stride, state, B, n, mode, dcblock) ? DH_EDEVICE : DH_OK;
 }
-
-static int dh_be_div_const(const float* in, float* out, size_t n, unsigned divisor, void* stream) {
-    if (!n) return DH_OK;
-    const float d = (float) divisor;
-    hipLaunchKernelGGL(k_div_const, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, in, out, n, d, 1.0f / d);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
-static int dh_be_div_gain(const float* in, float* out, size_t n, int narrow, void* stream) {
-    if (!n) return DH_OK;
-    const double gain = narrow ? DH_RRC_NARROW_GAIN : DH_RRC_WIDE_GAIN;
-    hipLaunchKernelGGL(k_div_gain, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, in, out, n, gain, 1.0 / gain);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
 static int dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, float* d, size_t tiles, void* stream) {
     if (!tiles) return DH_OK;
-    hipLaunchKernelGGL(k_mfma_f16, dim3((unsigned) tiles), dim3(DH_WAVE), 0, (hipStream_t) stream, a, b, c, d);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_mfma_f16, dim3((unsigned) tiles), dim3(DH_WAVE), 0, stream, "k_mfma_f16", a, b, c, d) ? DH_EDEVICE : DH_OK;
 }
-static int dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* stream) {
-    if (!n) return DH_OK;
-    hipLaunchKernelGGL(k_f16_split, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t) stream, in, h1, h2, n, scale);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
 static int dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void* stream) {
     if (!n_bytes) return DH_OK;
     const size_t n16 = n_bytes / 16;
     if (!dst) {
         const unsigned rgrid = (unsigned) std::min<size_t>((n16 + 255) / 256, 8192);
-        hipLaunchKernelGGL(k_read16, dim3(rgrid), dim3(256), 0, (hipStream_t) stream, (const dh_u4s*) src, n16);
-        HIP_TRY(hipGetLastError());
-        return DH_OK;
+        return dh_launch(k_read16, dim3(rgrid), dim3(256), 0, stream, "k_read16", (const dh_u4s*) src, n16) ? DH_EDEVICE : DH_OK;
     }
     const unsigned grid = (unsigned) std::min<size_t>((n16 + 255) / 256, 2048);      // 256 CUs x 8 resident workgroups of 256
-    hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(256), 0, (hipStream_t) stream, (const dh_u4s*) src, (dh_u4s*) dst, n16);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_copy16, dim3(grid), dim3(256), 0, stream, "k_copy16", (const dh_u4s*) src, (dh_u4s*) dst, n16) ? DH_EDEVICE : DH_OK;
 }
 
-static int dh_be_cz_window(float* cur, const float* prev, uint32_t prev_n, const void* in, int cf32, uint32_t H, size_t n_in, void* stream) {
-    const size_t n = H + n_in;
-    hipLaunchKernelGGL(k_cz_window, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t) stream, cur, prev, prev_n, in, cf32, H, n);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
 static int dh_be_cz_gemm(const DhCzParams& P, void* stream) {
     if (!P.n_out) return DH_OK;
-    hipLaunchKernelGGL(k_cz_gemm, dim3((P.n_out + DH_CZ_TM - 1) / DH_CZ_TM, P.ncols / (2u * DH_CZ_TNC)), dim3(256), 0, (hipStream_t) stream, P);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_cz_gemm, dim3((P.n_out + DH_CZ_TM - 1) / DH_CZ_TM, P.ncols / (2u * DH_CZ_TNC)), dim3(256), 0, stream, "k_cz_gemm", P) ? DH_EDEVICE : DH_OK;
 }
 static int dh_be_cz_gemm_rat(const DhCzRatParams& R, void* stream) {
     if (!R.nslots) return DH_OK;
-    hipLaunchKernelGGL(k_cz_gemm_rat, dim3((R.ph[0].count + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC), R.nslots), dim3(256), 0,
-                       (hipStream_t) stream, R);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_cz_gemm_rat, dim3((R.ph[0].count + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC), R.nslots), dim3(256), 0,
+                     stream, "k_cz_gemm_rat", R) ? DH_EDEVICE : DH_OK;
 }
 static int dh_be_cz_fold(const DhCzFoldParams& F, void* stream) {
     if (!F.nrows) return DH_OK;
-    hipLaunchKernelGGL(k_cz_fold, dim3((F.nrows + DH_CZ_FOLD_ROWS - 1) / DH_CZ_FOLD_ROWS, (F.kpad + DH_CZ_FOLD_LANES - 1) / DH_CZ_FOLD_LANES),
-                       dim3(DH_CZ_FOLD_LANES), 0, (hipStream_t) stream, F);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_cz_fold, dim3((F.nrows + DH_CZ_FOLD_ROWS - 1) / DH_CZ_FOLD_ROWS, (F.kpad + DH_CZ_FOLD_LANES - 1) / DH_CZ_FOLD_LANES),
+                     dim3(DH_CZ_FOLD_LANES), 0, stream, "k_cz_fold", F) ? DH_EDEVICE : DH_OK;
 }
 static int dh_be_cz_gemm_raster(const DhCzRasterParams& R, void* stream) {
     if (!R.g.n_out) return DH_OK;
-    hipLaunchKernelGGL(k_cz_gemm_raster, dim3((R.g.n_out + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC)), dim3(256), 0,
-                       (hipStream_t) stream, R);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
-static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_stride, uint32_t B, uint32_t n_out, int dcblock, void* stream) {
-    if (!n_out) return DH_OK;
-    hipLaunchKernelGGL(k_cz_fm, dim3((n_out + 255) / 256, B < 65535u ? B : 65535u), dim3(256), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cz_tail, dim3((B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, zbuf, state, out, out_stride, B, n_out, dcblock);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_cz_power(const DhCzPowerParams& P, void* stream) {
-    if (P.nseg) {
-        hipLaunchKernelGGL(k_cz_power, dim3(grid_for((size_t) P.B * P.nseg, 256)), dim3(256), 0, (hipStream_t) stream, P);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_cz_gate, dim3((P.B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, (hipStream_t) stream, P);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
-static int dh_be_preroll_append(const DhPrAppend& A, void* stream) {
-    if (!A.n) return DH_OK;
-    hipLaunchKernelGGL(k_preroll_append, dim3((A.n + DH_PR_TILE - 1) / DH_PR_TILE, A.B < 65535u ? A.B : 65535u), dim3(256), 0, (hipStream_t) stream, A);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_preroll_gather(const DhPrGather& G, void* stream) {
-    if (!G.max_n) return DH_OK;
-    hipLaunchKernelGGL(k_preroll_gather, dim3((G.max_n + DH_PR_TILE - 1) / DH_PR_TILE, G.B < 65535u ? G.B : 65535u), dim3(256), 0, (hipStream_t) stream, G);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_cz_gemm_raster, dim3((R.g.n_out + DH_CZ_TM - 1) / DH_CZ_TM, R.g.ncols / (2u * DH_CZ_TNC)), dim3(256), 0,
+                     stream, "k_cz_gemm_raster", R) ? DH_EDEVICE : DH_OK;
 }
 
 static int dh_be_monitor_open(const DhMonOpen& A, void* stream) {
-    hipLaunchKernelGGL(k_monitor_open, dim3(grid_for(A.B, 256)), dim3(256), 0, (hipStream_t) stream, A);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_monitor_assign(const DhMonAssign& S, void* stream) {
-    hipLaunchKernelGGL(k_monitor_assign, dim3(grid_for(S.B, 256)), dim3(256), 0, (hipStream_t) stream, S);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-static int dh_be_monitor_close(const DhMonClose& C, void* stream) {
-    hipLaunchKernelGGL(k_monitor_close, dim3(grid_for(C.B, 256)), dim3(256), 0, (hipStream_t) stream, C);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+    return dh_launch(k_monitor_open, dim3(grid_for(A.B, 256)), dim3(256), 0, stream, "k_monitor_open", A) ? DH_EDEVICE : DH_OK;
 }
 // (on the engine's stream, behind whatever the engine has in flight on streams of its own: HipBackend::ms)
 static int dh_be_reset_channels(HipBackend& be, const DhResetChannels& R) {
-    hipLaunchKernelGGL(k_reset_channels, dim3(R.B < 2048u ? R.B : 2048u), dim3(256), 0, be.ms(), R);
-    return be.launched("k_reset_channels");
-}
-
-// (both on the engine's stream, behind whatever the engine has in flight on streams of its own: HipBackend::ms)
-static int dh_be_outpack_scan(HipBackend& be, const DhOutpack& P) {
-    hipLaunchKernelGGL(k_outpack_scan, dim3(1), dim3(DH_OP_LANES), 0, be.ms(), P);
-    return be.launched("k_outpack_scan");
-}
-static int dh_be_outpack_copy(HipBackend& be, const DhOutpack& P) {
-    hipLaunchKernelGGL(k_outpack_copy, dim3(P.B < 1024u ? P.B : 1024u), dim3(256), 0, be.ms(), P);
-    return be.launched("k_outpack_copy");
+    return dh_launch(k_reset_channels, dim3(R.B < 2048u ? R.B : 2048u), dim3(256), 0, be.ms(), "k_reset_channels", R);
 }
 
 #define DH_BACKEND HipBackend

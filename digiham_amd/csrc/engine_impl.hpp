@@ -113,14 +113,16 @@ inline void fill_taps(int rrc, P& p) {
 //   int timing_read_split(float* first_ms, uint32_t* first_channels, uint32_t* n); bool overlap_pushes;
 //   int launch_rrc_demod(const DhDspParams&, uint32_t nz, bool fast);
 //   int launch_rrc_tiles(const DhRrcParams&, uint32_t nz, bool fast);
-//   int launch_rrc_generic(const DhRrcGenParams&);
-//   int launch_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B);
 //   int launch_chain(const DhDspParams&, const DhDecParams&, uint32_t nz, bool fast, int proto);   // 1 = unavailable
-//   int launch_decoder(const DhDecParams&, int proto);
-//   int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
-//   int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B);
-// and, beside it, the free function dh_be_reset_channels(BE&, const DhResetChannels&) (monitor_core.hpp: the CPU harness's;
-// engine.hip: the gfx950 one).
+//   void* / hipStream_t ms();                                // the engine's stream, behind what the engine has in flight on its own
+// The engine's helper launches are free functions over the backend, one text for both builds (kernels_core.hpp), on be.ms():
+//   dh_be_rrc_generic(be, const DhRrcGenParams&);
+//   dh_be_rrc_hist(be, float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B);
+//   dh_be_decoder(be, const DhDecParams&, int proto);
+//   dh_be_init_state(be, uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
+//   dh_be_set_slot_filter(be, uint32_t* dec_state, uint32_t filter, uint32_t B);
+// and dh_be_reset_channels(BE&, const DhResetChannels&) (a barrier inside: engine.hip has the gfx950 one, monitor_core.hpp
+// the CPU harness's).
 
 // The device buffers of one handle (an engine, a channelizer).  Every buffer is allocated through alloc() and stated
 // nowhere else: free_all() frees what was allocated, zero_all() and zero_row() clear what was declared as state.
@@ -275,7 +277,7 @@ struct Engine {
     int reset() {
         int rc = bufs.zero_all();
         // the fused slicer starts with nz zero samples of history in its tail (RrcFilter's delay line)
-        rc |= be.launch_init_state(dsp_state, L.state_words, L.fused ? L.nz : 0u, dec_state, slot_filter, L.B);
+        rc |= dh_be_init_state(be, dsp_state, L.state_words, L.fused ? L.nz : 0u, dec_state, slot_filter, L.B);
         last_n = 0;
         return rc ? DH_EDEVICE : DH_OK;
     }
@@ -290,24 +292,24 @@ struct Engine {
     int set_slot_filter(uint32_t f) {
         if (L.proto != DH_PROTO_DMR) return DH_EINVAL;
         slot_filter = filter_word(f);
-        return be.launch_set_slot_filter(dec_state, slot_filter, L.B) ? DH_EDEVICE : DH_OK;
+        return dh_be_set_slot_filter(be, dec_state, slot_filter, L.B) ? DH_EDEVICE : DH_OK;
     }
     // one channel only (a module instance attached to a shared engine: include/digiham/shared_engine.hpp)
     int set_slot_filter_channel(uint32_t ch, uint32_t f) {
         if (L.proto != DH_PROTO_DMR || ch >= L.B) return DH_EINVAL;
-        return be.launch_set_slot_filter(dec_state + (size_t) ch * DH_DEC_STATE_WORDS, filter_word(f), 1) ? DH_EDEVICE : DH_OK;
+        return dh_be_set_slot_filter(be, dec_state + (size_t) ch * DH_DEC_STATE_WORDS, filter_word(f), 1) ? DH_EDEVICE : DH_OK;
     }
     // back to the freshly-constructed state of ONE channel (the others keep streaming)
     int reset_channel(uint32_t ch) {
         if (ch >= L.B) return DH_EINVAL;
         int rc = bufs.zero_row(ch, L.B);
-        rc |= be.launch_init_state(dsp_state ? dsp_state + (size_t) ch * L.state_words : nullptr, L.state_words, L.fused ? L.nz : 0u,
+        rc |= dh_be_init_state(be, dsp_state ? dsp_state + (size_t) ch * L.state_words : nullptr, L.state_words, L.fused ? L.nz : 0u,
                                    dec_state ? dec_state + (size_t) ch * DH_DEC_STATE_WORDS : nullptr, slot_filter, 1);
         return rc ? DH_EDEVICE : DH_OK;
     }
 
     // ... of every channel with d_flags[b] != 0 ([B] bytes on the device), in one launch: the rows zero_row() clears, then
-    // what launch_init_state writes.  The buffer table travels in the kernel's arguments.
+    // what k_init_state writes.  The buffer table travels in the kernel's arguments.
     int reset_channels(const uint8_t* d_flags) {
         if (!d_flags) return DH_EINVAL;
         DhResetChannels R{};
@@ -344,12 +346,12 @@ struct Engine {
         be.timing_mark(0);
         if (L.rrc == DH_RRC_CUSTOM) {
             gen.in = d_in; gen.in_stride = stride; gen.n = (uint32_t) n;
-            if (n) rc |= be.launch_rrc_generic(gen);
-            if (n) rc |= be.launch_rrc_hist(rrc_hist, d_in, stride, (uint32_t) n, nullptr, L.nz, L.B);
+            if (n) rc |= dh_be_rrc_generic(be, gen);
+            if (n) rc |= dh_be_rrc_hist(be, rrc_hist, d_in, stride, (uint32_t) n, nullptr, L.nz, L.B);
         } else if (L.rrc && !L.fused) {
             rrcp.in = d_in; rrcp.in_stride = stride; rrcp.n = (uint32_t) n; rrcp.n_per = d_counts;
             if (n) rc |= be.launch_rrc_tiles(rrcp, L.nz, fast);
-            if (n) rc |= be.launch_rrc_hist(rrc_hist, d_in, stride, (uint32_t) n, d_counts, L.nz, L.B);
+            if (n) rc |= dh_be_rrc_hist(be, rrc_hist, d_in, stride, (uint32_t) n, d_counts, L.nz, L.B);
         }
         be.timing_mark(1);
         if (L.demod) {
@@ -366,7 +368,7 @@ struct Engine {
             decoder_done = chained == 0;
         }
         be.timing_mark(2);
-        if (L.proto && L.demod && !decoder_done) rc |= be.launch_decoder(dec, L.proto);
+        if (L.proto && L.demod && !decoder_done) rc |= dh_be_decoder(be, dec, L.proto);
         be.timing_mark(3);
         be.timing_next();
         return rc ? DH_EDEVICE : DH_OK;
@@ -390,7 +392,7 @@ struct Engine {
         if (!L.proto || L.demod || !d_syms || !d_count) return DH_EINVAL;
         last_counts = nullptr;
         dec.syms = d_syms; dec.sym_stride = stride; dec.sym_count = d_count;
-        return be.launch_decoder(dec, L.proto) ? DH_EDEVICE : DH_OK;
+        return dh_be_decoder(be, dec, L.proto) ? DH_EDEVICE : DH_OK;
     }
 
     int check_overflow() {

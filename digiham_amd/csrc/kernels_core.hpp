@@ -3,6 +3,7 @@
 // test harness.
 #pragma once
 
+#include "../../include/digiham_amd.h"
 #include "dsp_core.hpp"
 #include "frontend_core.hpp"
 #include "channelizer_core.hpp"
@@ -222,6 +223,88 @@ DH_HD void dh_dvfilter_channel(const int16_t* in, int16_t* out, float* st, size_
         out[t] = (int16_t) (uint16_t) ((uint32_t) iv & 0xFFFFu);
     }
     for (int i = 0; i < 11; i++) { st[i] = xv[i]; st[11 + i] = yv[i]; }
+}
+
+// ---------------------------------------------------------------------------------- the engine's small kernels
+namespace {
+
+__global__ __launch_bounds__(DH_WAVE) void k_rrc_generic(const DhRrcGenParams G) {
+    __shared__ float win[DH_GEN_WINDOW];
+    __shared__ float taps[DH_MAX_NZ + 1];
+    dh_rrc_generic_tile(G, blockIdx.y, blockIdx.x, win, taps);
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz) {
+    __shared__ float sh[DH_MAX_NZ];
+    dh_rrc_hist_channel(hist, in, in_stride, n, n_per, nz, blockIdx.x, sh);
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_dmr(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_dmr_channel(P, blockIdx.x, S);
+}
+
+__global__ __launch_bounds__(DH_WAVE, 4) void k_ysf(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_ysf_channel(P, blockIdx.x, S);
+}
+
+__global__ __launch_bounds__(DH_WAVE, 4) void k_nxdn(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_nxdn_channel(P, blockIdx.x, S);
+}
+
+__global__ __launch_bounds__(DH_WAVE) void k_pocsag(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_pocsag_channel(P, blockIdx.x, S);
+}
+
+// protocol scan: nine sync tests at every symbol position, no frame state machine (decoder_core.hpp, dh_scan_channel)
+__global__ __launch_bounds__(DH_WAVE) void k_scan(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_scan_channel(P, blockIdx.x, S);
+}
+
+#define DH_DSTAR_LB 4
+__global__ __launch_bounds__(DH_WAVE, DH_DSTAR_LB) void k_dstar(const DhDecParams P) {
+    __shared__ DhDecShared S;
+    dh_dstar_channel(P, blockIdx.x, S);
+}
+
+__global__ void k_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B) {
+    const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch < B) dh_init_state_channel(dsp_state, state_words, tail0, dec_state, slot_filter, ch);
+}
+
+__global__ void k_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B) {
+    const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch < B) dh_set_slot_filter_channel(dec_state, filter, ch);
+}
+
+}  // namespace
+
+template <class BE> static int dh_be_rrc_generic(BE& be, const DhRrcGenParams& G) {
+    for (uint32_t b0 = 0; b0 < G.n_channels; b0 += 65535u) {      // channels on grid.y: at most 65 535 per launch
+        DhRrcGenParams Q = G;
+        Q.n_channels = dh_min<uint32_t>(G.n_channels - b0, 65535u);
+        Q.in = G.in + (size_t) b0 * G.in_stride; Q.out = G.out + (size_t) b0 * G.out_stride; Q.hist = G.hist + (size_t) b0 * G.nz;
+        if (dh_launch(k_rrc_generic, dim3((G.n + DH_FTILE - 1) / DH_FTILE, Q.n_channels), dh_workgroup(DH_WAVE), 0, dh_be_stream(be, 0), "k_rrc_generic", Q)) return -1;
+    }
+    return 0;
+}
+template <class BE> static int dh_be_rrc_hist(BE& be, float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B) {
+    return dh_launch(k_rrc_hist, dim3(B), dh_workgroup(DH_WAVE), 0, dh_be_stream(be, 0), "k_rrc_hist", hist, in, in_stride, n, n_per, nz);
+}
+template <class BE> static int dh_be_decoder(BE& be, const DhDecParams& P, int proto) {
+    void (*const k)(const DhDecParams) = proto == DH_PROTO_DMR ? k_dmr : proto == DH_PROTO_YSF ? k_ysf : proto == DH_PROTO_NXDN ? k_nxdn :
+                                         proto == DH_PROTO_POCSAG ? k_pocsag : proto == DH_PROTO_SCAN ? k_scan : k_dstar;
+    return dh_launch(k, dim3(P.n_channels), dh_workgroup(DH_WAVE), 0, dh_be_stream(be, 0), "k_decoder", P);
+}
+template <class BE> static int dh_be_init_state(BE& be, uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B) {
+    return dh_launch(k_init_state, dim3((B + 255) / 256), dim3(256), 0, dh_be_stream(be, 0), "k_init_state", dsp_state, state_words, tail0, dec_state, slot_filter, B);
+}
+template <class BE> static int dh_be_set_slot_filter(BE& be, uint32_t* dec_state, uint32_t filter, uint32_t B) {
+    return dh_launch(k_set_slot_filter, dim3((B + 255) / 256), dim3(256), 0, dh_be_stream(be, 0), "k_set_slot_filter", dec_state, filter, B);
 }
 
 #include "monitor_core.hpp"       // (needs dh_init_state_channel)

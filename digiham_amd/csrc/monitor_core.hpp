@@ -1,6 +1,6 @@
 // monitor_core.hpp -- the band monitor's per-round bookkeeping (include/digiham_amd.h, "Band monitor"): which channels
 // the scanner sees, which one is named and from where its decoder is fed, which ones an engine forgets.  Bodies shared by
-// the gfx950 kernels in engine.hip and by the CPU test harness.  No arithmetic on samples: three small words of state per
+// the gfx950 build and the CPU test harness (kernels of steps B and C: the end of this file; k_monitor_open, k_reset_channels: engine.hip).  No arithmetic on samples: three small words of state per
 // channel (a fourth, `opened`, for naming on close), nine statistics records read per scanned or closing channel, and one
 // fixed-size summary block that is all the host reads per round.
 #pragma once
@@ -204,7 +204,8 @@ DH_HD void dh_rst_init(const DhResetChannels& R, uint32_t b) {
 }
 
 #if !DH_DEVICE_BUILD
-// ---- host backends of the CPU test harness (engine.hip defines the gfx950 ones) --------------------------------------
+// ---- CPU restatements of the masked reset (a barrier between its two steps) and of step A (counted per wavefront with
+// votes); engine.hip has the gfx950 kernels; the monitor's other launches follow, one text for both builds ---------------
 template <class BE>
 static int dh_be_reset_channels(BE&, const DhResetChannels& R) {
     for (uint32_t b = R.B; b-- > 0;)
@@ -219,20 +220,41 @@ static int dh_be_monitor_open(const DhMonOpen& A, void*) {
     }
     return 0;
 }
-static int dh_be_monitor_assign(const DhMonAssign& S, void*) {
-    for (uint32_t b = S.B; b-- > 0;) {
+#endif
+
+// ---------------------------------------------------------------------------------- band monitor (monitor_core.hpp)
+// Steps B and C of a round: one lane per channel, 256-thread workgroups.  Ordinary vector stores for the state and the
+// per-channel outputs; the summary block takes one vector atomic per newly named channel.  (Step A, k_monitor_open, counts per
+// wavefront with votes: engine.hip, its CPU restatement in monitor_core.hpp.)
+namespace {
+
+__global__ __launch_bounds__(256) void k_monitor_assign(const DhMonAssign S) {
+    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < S.B; b += gridDim.x * 256u) {
         uint64_t start;
         const uint32_t p = dh_mon_assign_channel(S, b, start);
-        if (p) { S.sum->n_new[p] += 1u; if (start < S.sum->min_start[p]) S.sum->min_start[p] = start; }
+        if (p) {
+            atomicAdd(&S.sum->n_new[p], 1u);
+            atomicMin((unsigned long long*) &S.sum->min_start[p], (unsigned long long) start);
+        }
     }
-    return 0;
 }
-static int dh_be_monitor_close(const DhMonClose& C, void*) {
-    for (uint32_t b = C.B; b-- > 0;) {
+
+__global__ __launch_bounds__(256) void k_monitor_close(const DhMonClose C) {
+    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < C.B; b += gridDim.x * 256u) {
         uint64_t start;
         const uint32_t p = dh_mon_close_channel(C, b, start);
-        if (p) { C.sum->n_new[p] += 1u; if (start < C.sum->min_start[p]) C.sum->min_start[p] = start; }
+        if (p) {
+            atomicAdd(&C.sum->n_new[p], 1u);
+            atomicMin((unsigned long long*) &C.sum->min_start[p], (unsigned long long) start);
+        }
     }
-    return 0;
 }
-#endif
+
+}  // namespace
+
+static int dh_be_monitor_assign(const DhMonAssign& S, void* stream) {
+    return dh_launch(k_monitor_assign, dim3(grid_for(S.B, 256)), dim3(256), 0, stream, "k_monitor_assign", S) ? DH_EDEVICE : DH_OK;
+}
+static int dh_be_monitor_close(const DhMonClose& C, void* stream) {
+    return dh_launch(k_monitor_close, dim3(grid_for(C.B, 256)), dim3(256), 0, stream, "k_monitor_close", C) ? DH_EDEVICE : DH_OK;
+}

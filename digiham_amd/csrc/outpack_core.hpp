@@ -1,7 +1,7 @@
 // outpack_core.hpp -- the packed read-out (include/digiham_amd.h, "Packed read-out"): what one engine push produced, moved
 // from the engine's dense [B][out_cap] / [B][ev_cap] rows into three compact device areas behind one header, appendable
-// across the pushes and engines of a round.  Bodies shared by the gfx950 kernels in engine.hip (k_outpack_scan,
-// k_outpack_copy) and by the CPU test harness.  No arithmetic on the data: counts are added up, bytes move as 16-byte
+// across the pushes and engines of a round.  Bodies of the kernels k_outpack_scan and
+// k_outpack_copy (at the end of this file), which both builds compile.  No arithmetic on the data: counts are added up, bytes move as 16-byte
 // pieces.
 //
 // The scan is ONE workgroup of DH_OP_LANES lanes (four wavefronts) that walks the B channels DH_OP_LANES at a time, in
@@ -143,17 +143,30 @@ DH_HD void dh_outpack_copy_entry(const DhOutpack& P, uint32_t idx, uint32_t lane
     }
 }
 
-#if !DH_DEVICE_BUILD
-// ---- host back ends of the CPU test harness (engine.hip defines the gfx950 ones) -------------------------------------
-template <class BE>
-static int dh_be_outpack_scan(BE&, const DhOutpack& P) {
-    DhOpShared S;
+// ---------------------------------------------------------------------------------- packed read-out (outpack_core.hpp)
+// k_outpack_scan: ONE workgroup of 256 lanes walks the engine's B channels 256 at a time -- B is at most a few tens of
+// thousands of 8-byte reads -- so that the order rule is exact without any hand-over between workgroups: candidate vote
+// and popcount below the lane, two shuffle scans per wavefront, the wavefronts' totals through 48 bytes of LDS, a running
+// carry across passes.  Ordinary vector stores only.
+// k_outpack_copy: a fixed grid, workgroup i takes entries i, i + gridDim.x, ... of THIS append while i < n_new; n_new and
+// the first entry's index are the two scratch words the scan left, the same for every lane.
+namespace {
+
+__global__ __launch_bounds__(DH_OP_LANES) void k_outpack_scan(const DhOutpack P) {
+    __shared__ DhOpShared S;
     dh_outpack_scan(P, S);
-    return 0;
 }
-template <class BE>
-static int dh_be_outpack_copy(BE&, const DhOutpack& P) {
-    for (uint32_t i = P.scratch[1]; i-- > 0;) dh_outpack_copy_entry(P, P.scratch[0] + i, 0u, 1u);      // (the workgroups of a launch have no order)
-    return 0;
+
+__global__ __launch_bounds__(256) void k_outpack_copy(const DhOutpack P) {
+    const uint32_t first = P.scratch[0], n_new = P.scratch[1];
+    for (uint32_t i = blockIdx.x; i < n_new; i += gridDim.x) dh_outpack_copy_entry(P, first + i, threadIdx.x, 256u);
 }
-#endif
+
+}  // namespace
+
+template <class BE> static int dh_be_outpack_scan(BE& be, const DhOutpack& P) {
+    return dh_launch(k_outpack_scan, dim3(1), dh_workgroup(DH_OP_LANES), 0, dh_be_stream(be, 0), "k_outpack_scan", P);
+}
+template <class BE> static int dh_be_outpack_copy(BE& be, const DhOutpack& P) {
+    return dh_launch(k_outpack_copy, dim3(P.B < 1024u ? P.B : 1024u), dim3(256), 0, dh_be_stream(be, 0), "k_outpack_copy", P);
+}

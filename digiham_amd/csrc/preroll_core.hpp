@@ -1,6 +1,6 @@
 // preroll_core.hpp -- the pre-roll ring (include/digiham_amd.h, "Pre-roll"): every channel's last `depth` samples, kept on
 // the device so that a channel that has just been named is decoded from where its squelch opened.  Index arithmetic
-// shared by the gfx950 kernels in engine.hip and by the CPU test harness; no arithmetic on the samples at all -- they move
+// shared by the gfx950 build and the CPU test harness, as are the kernels and their launches at the end of this file; no arithmetic on the samples at all -- they move
 // as 32-bit words, so NaN payloads, -0 and subnormals arrive as they were sent.
 //
 // Stream index t of a channel lives at ring[b][t mod depth].  The host knows `total` (the same for every channel), so the
@@ -8,6 +8,7 @@
 // and the kernels wrap with one compare.
 #pragma once
 
+#include "../../include/digiham_amd.h"
 #include "dh_portable.hpp"
 
 #define DH_PR_NONE 0xFFFFFFFFFFFFFFFFull      /* DH_PREROLL_NONE */
@@ -72,22 +73,46 @@ DH_HD void dh_pr_gather_item(const DhPrGather& G, uint32_t b, uint32_t pos, uint
     G.out[(size_t) b * G.out_stride + i] = G.ring[(size_t) b * G.depth + p];
 }
 
-#if !DH_DEVICE_BUILD
-// ---- host backends of the CPU test harness (engine.hip defines the gfx950 ones) --------------------------------------
-static int dh_be_preroll_append(const DhPrAppend& A, void*) {
-    for (uint32_t b = 0; b < A.B; b++) {
-        dh_pr_append_open(A, b);
-        for (uint32_t i = A.n; i-- > 0;) dh_pr_append_item(A, b, i);        // last sample first: the lanes of a launch have no order
+// ---------------------------------------------------------------------------------- pre-roll ring (preroll_core.hpp)
+// One workgroup per (1 024-sample tile, channel), blockIdx.y looping over the channels as in k_cz_fm.  Lane l of the 256
+// takes samples l, l + 256, l + 512, l + 768 of the tile: every wave instruction moves one contiguous 256-byte piece on
+// both sides, except the one piece per tile that may straddle the ring's seam.  The tile-0 workgroup of a channel is
+// the only one that touches that channel's open_at (append) or count (gather).
+namespace {
+
+__global__ __launch_bounds__(256) void k_preroll_append(const DhPrAppend A) {
+    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
+    for (uint32_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) dh_pr_append_open(A, b);
+#pragma unroll
+        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
+            const uint32_t i = i0 + 256u * k;
+            if (i < A.n) dh_pr_append_item(A, b, i);
+        }
     }
-    return 0;
 }
-static int dh_be_preroll_gather(const DhPrGather& G, void*) {
-    for (uint32_t b = 0; b < G.B; b++) {
+
+__global__ __launch_bounds__(256) void k_preroll_gather(const DhPrGather G) {
+    const uint32_t i0 = blockIdx.x * DH_PR_TILE + threadIdx.x;
+    for (uint32_t b = blockIdx.y; b < G.B; b += gridDim.y) {
         uint32_t pos;
         const uint32_t count = dh_pr_count(G, b, pos);
-        G.counts[b] = count;
-        for (uint32_t i = count; i-- > 0;) dh_pr_gather_item(G, b, pos, i);
+        if (blockIdx.x == 0 && threadIdx.x == 0) G.counts[b] = count;
+#pragma unroll
+        for (uint32_t k = 0; k < DH_PR_TILE / 256u; k++) {
+            const uint32_t i = i0 + 256u * k;
+            if (i < count) dh_pr_gather_item(G, b, pos, i);
+        }
     }
-    return 0;
 }
-#endif
+
+}  // namespace
+
+static int dh_be_preroll_append(const DhPrAppend& A, void* stream) {
+    if (!A.n) return DH_OK;
+    return dh_launch(k_preroll_append, dim3((A.n + DH_PR_TILE - 1) / DH_PR_TILE, A.B < 65535u ? A.B : 65535u), dim3(256), 0, stream, "k_preroll_append", A) ? DH_EDEVICE : DH_OK;
+}
+static int dh_be_preroll_gather(const DhPrGather& G, void* stream) {
+    if (!G.max_n) return DH_OK;
+    return dh_launch(k_preroll_gather, dim3((G.max_n + DH_PR_TILE - 1) / DH_PR_TILE, G.B < 65535u ? G.B : 65535u), dim3(256), 0, stream, "k_preroll_gather", G) ? DH_EDEVICE : DH_OK;
+}

@@ -1,8 +1,12 @@
 // harness.cpp -- CPU wave-emulation build of the kernel bodies (TEST INFRASTRUCTURE ONLY).
 //
 // Compiles digiham_amd/csrc/*_core.hpp with a plain C++ compiler: DH_FOR_LANES becomes a
-// 64-iteration loop, DH_BARRIER a no-op, "device memory" is the host heap and a "kernel launch"
-// is a loop over workgroups.  It exports the same C ABI as libdigiham_amd.so so the CPU-only test
+// 64-iteration loop, DH_BARRIER a no-op and "device memory" is the host heap.  The helper kernels
+// and their launches are the device's own text (the ends of the core headers, digiham_amd/csrc/helper_launches.hpp): a launch
+// visits every block and thread of the grid the launcher computed.  What is written here is the
+// backend's plumbing, the three planned launches (a loop over workgroups each) and the
+// restatements of the kernels a thread-at-a-time visit cannot run (front-end, MFMA probe, copy).
+// It exports the same C ABI as libdigiham_amd.so so the CPU-only test
 // tier can run the engine's orchestration and the exact wave algorithms against the oracle.
 // Which instantiation serves which configuration comes from digiham_amd/csrc/launch_plan.hpp, as
 // on the device: every route the device chains or splits is chained or split here.
@@ -14,17 +18,10 @@
 #include <vector>
 
 #include "../../include/digiham_amd.h"
-#include "../../digiham_amd/csrc/kernels_core.hpp"
+#include "../../digiham_amd/csrc/helper_launches.hpp"
 #include "../../digiham_amd/csrc/launch_plan.hpp"
-#include "../../digiham_amd/csrc/fec_tables.hpp"
-#include "../../digiham_amd/csrc/rrc_taps.h"
 
 namespace {
-
-const DhFecTables& host_tables() {
-    static DhFecTables* T = [] { auto* t = new DhFecTables; dh::build_fec_tables(*t); return t; }();
-    return *T;
-}
 
 // test only (tests/host_cpp/handle_lifecycle.cpp): k > 0 makes the k-th backend allocation from now fail, once
 int g_alloc_fail_in = 0;
@@ -48,6 +45,7 @@ struct HostBackend {
     }
     int download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int sync() { return 0; }
+    void* ms() { return nullptr; }
     void timing_mark(int) {}
     void timing_next() {}
     int timing_enable(uint32_t) { return 0; }
@@ -76,17 +74,6 @@ struct HostBackend {
     }
     int launch_rrc_tiles(const DhRrcParams& R, uint32_t nz, bool fast) {
         return dh_plan_rrc_tiles(nz, fast, [&](auto i) { return run_rrc_tiles<decltype(i)>(R); });
-    }
-    int launch_rrc_generic(const DhRrcGenParams& G) {
-        static float win[DH_GEN_WINDOW], taps[DH_MAX_NZ + 1];
-        for (uint32_t ch = 0; ch < G.n_channels; ch++)
-            for (uint32_t t = 0; t * DH_FTILE < G.n; t++) dh_rrc_generic_tile(G, ch, t, win, taps);
-        return 0;
-    }
-    int launch_rrc_hist(float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B) {
-        float sh[DH_MAX_NZ];
-        for (uint32_t ch = 0; ch < B; ch++) dh_rrc_hist_channel(hist, in, in_stride, n, n_per, nz, ch, sh);
-        return 0;
     }
     // One chain instantiation, in the device kernel's order of work: channel by channel, slicer then decoder.
     // The tail split of the device's chain launches (engine.hip, k_chain), on every route the device splits: DH_TAIL_SPLIT
@@ -124,20 +111,6 @@ struct HostBackend {
     int launch_chain(const DhDspParams& P, const DhDecParams& D, uint32_t nz, bool fast, int proto) {
         return dh_plan_chain(P, nz, fast, proto, [&](auto i) { return run_chain<decltype(i)>(P, D); });
     }
-    int launch_decoder(const DhDecParams& P, int proto) {
-        DhDecShared* S = new DhDecShared;
-        for (uint32_t ch = 0; ch < P.n_channels; ch++) dh_decode_channel(proto, P, ch, *S);
-        delete S;
-        return 0;
-    }
-    int launch_init_state(uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B) {
-        for (uint32_t ch = 0; ch < B; ch++) dh_init_state_channel(dsp_state, state_words, tail0, dec_state, slot_filter, ch);
-        return 0;
-    }
-    int launch_set_slot_filter(uint32_t* dec_state, uint32_t filter, uint32_t B) {
-        for (uint32_t ch = 0; ch < B; ch++) dh_set_slot_filter_channel(dec_state, filter, ch);
-        return 0;
-    }
 };
 
 }  // namespace
@@ -147,39 +120,6 @@ static const char* dh_be_last_error() { return "host emulation"; }
 static int dh_be_alloc(int, size_t bytes, void** out) { *out = calloc(1, bytes ? bytes : 1); return *out ? 0 : DH_ENOMEM; }
 static int dh_be_free(void* p) { free(p); return 0; }
 static int dh_be_copy(void* dst, const void* src, size_t bytes, int) { if (bytes) memcpy(dst, src, bytes); return 0; }
-static int dh_be_fec_block(int code, void* words, uint8_t* ok, size_t n, void*) {
-    for (size_t i = 0; i < n; i++) dh_fec_block_item(host_tables(), code, words, ok, i);
-    return 0;
-}
-static int dh_be_bptc(const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n, void*) {
-    for (size_t i = 0; i < n; i++) dh_bptc_item(host_tables(), in, out, ok, i);
-    return 0;
-}
-static int dh_be_trellis(const uint8_t* in, size_t in_stride, int n_dibits, uint8_t* out, size_t out_stride, uint8_t* metric, size_t n, void*) {
-    DhDecShared* S = new DhDecShared;
-    for (size_t w = 0; w < (n + 3) / 4; w++) dh_trellis_wave(in, in_stride, n_dibits, out, out_stride, metric, n, w, *S);
-    delete S;
-    return 0;
-}
-static int dh_be_crc16(const uint8_t* in, size_t stride, int count, uint16_t* out, size_t n, void*) {
-    for (size_t i = 0; i < n; i++) dh_crc16_item(in, stride, count, out, i);
-    return 0;
-}
-static int dh_be_whitening(const uint8_t* in, uint8_t* out, size_t stride, int n_bits, size_t n, void*) {
-    for (size_t i = 0; i < n; i++) dh_whitening_item(in, out, stride, n_bits, i);
-    return 0;
-}
-static int dh_be_dvfilter(const int16_t* in, int16_t* out, float* state, size_t B, size_t stride, size_t n, void*) {
-    for (size_t ch = 0; ch < B; ch++) dh_dvfilter_channel(in + ch * stride, out + ch * stride, state + ch * 22, n);
-    return 0;
-}
-
-static int dh_be_div_gain(const float* in, float* out, size_t n, int narrow, void*) {
-    const double gain = narrow ? DH_RRC_NARROW_GAIN : DH_RRC_WIDE_GAIN, rgain = 1.0 / gain;
-    for (size_t i = 0; i < n; i++) out[i] = dh_div_gain(in[i], gain, rgain);
-    return 0;
-}
-
 static int dh_be_frontend(const int16_t* in, size_t in_stride, float* out, size_t out_stride, float* state, size_t B, size_t n, int mode, int dcblock, void*) {
     for (size_t ch = 0; ch < B; ch++) dh_frontend_channel(in + ch * in_stride, out + ch * out_stride, state + ch * DH_FE_STATE_WORDS, n, mode, dcblock);
     return 0;
@@ -194,21 +134,6 @@ static int dh_be_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, 
     }
     return 0;
 }
-static int dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void*) {
-    for (size_t i = 0; i < n; i += 4) {
-        dh_f4 v; v.x = in[i]; v.y = i + 1 < n ? in[i + 1] : 0.0f; v.z = i + 2 < n ? in[i + 2] : 0.0f; v.w = i + 3 < n ? in[i + 3] : 0.0f;
-        uint16_t a[4], b[4];
-        dh_f16_split4(v, scale, a, b);
-        for (int j = 0; j < 4 && i + j < n; j++) { h1[i + j] = a[j]; h2[i + j] = b[j]; }
-    }
-    return 0;
-}
 static int dh_be_copy_kernel(const void* src, void* dst, size_t n_bytes, void*) { if (dst) __builtin_memcpy(dst, src, n_bytes); return 0; }
-static int dh_be_div_const(const float* in, float* out, size_t n, unsigned divisor, void*) {
-    const float d = (float) divisor, r = 1.0f / d;
-    for (size_t i = 0; i < n; i++) out[i] = dh_div_const(in[i], d, r);
-    return 0;
-}
-
 #define DH_BACKEND HostBackend
 #include "../../digiham_amd/csrc/abi_impl.hpp"

@@ -391,6 +391,23 @@ def test_custom_rrc_table(ctx, oracle):
     for b in range(x.shape[0]):
         assert sc[b] == ref["sym_count"][b] and (s[b, :sc[b]] == ref["syms"][b, :sc[b]]).all()
         assert fc[b] == ref["out_count"][b] and (f[b, :fc[b]] == ref["out"][b, :fc[b]]).all()
+    # across the launch's channel chunks: 65 537 channels go out as 65 535 + 2 (channels sit on grid.y), each chunk with its
+    # own offsets into the input, the output and the history rows.  Row b is one of seven streams, b mod 7 -- the chunk
+    # boundary falls at 65 535 mod 7 = 1, so a chunk that starts at the wrong row shows in every channel behind it; one
+    # tile of samples per push, two pushes (the second filters over the first one's history).
+    B, nz, gain = 65537, 7, 0.37
+    taps = rng.normal(0, 1, nz + 1).astype(np.float32)
+    seven = rng.normal(0, 1, (7, 101)).astype(np.float32)
+    ref = np.stack([oracle.Rrc(taps=taps, gain=gain).process(row) for row in seven])
+    sel = np.arange(B) % 7
+    eng = api.Engine(B, 64, rrc="custom", taps=taps, gain=gain, demod="none", proto="none", ctx=ctx)
+    for lo, hi in ((0, 64), (64, 101)):
+        eng.push(np.ascontiguousarray(seven[sel, lo:hi]))
+        got = eng.filtered()[:, :hi - lo]
+        for k in range(7):
+            assert (got[sel == k].view(np.uint32) == ref[k, lo:hi].view(np.uint32)).all(), (k, lo)
+        assert got[65534].tobytes() == ref[65534 % 7, lo:hi].tobytes() and got[65535].tobytes() == ref[65535 % 7, lo:hi].tobytes()
+    eng.close()
 
 
 @pytest.mark.parametrize("kw,oproto", [(dict(proto="dmr"), 1), (dict(proto="ysf"), 2), (dict(proto="none", keep_filtered=True), 0),

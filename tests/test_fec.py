@@ -198,10 +198,14 @@ def test_trellis_error_clusters_at_the_edges_of_the_repair_window_vs_reference(c
     assert (o1 == o2).all()
 
 
-def test_crc_whitening_golden(ctx, golden):
+def test_crc_whitening_golden(ctx, golden, oracle):
     g = golden["fec"]
     for cnt in (4, 10, 20):
         assert (ctx.crc16(g["crc_in"], cnt) == g["crc%d" % cnt]).all()
+    # one item more than one pass of the launch's grid (8 192 workgroups of 256 lanes): one lane's grid-stride loop turns twice
+    n = 8192 * 256 + 1
+    d = ((np.arange(n, dtype=np.uint64) * 2654435761) >> 13).astype(np.uint8).reshape(n, 1)
+    assert (ctx.crc16(d, 1) == oracle.crc16(d, 1)).all()
     for nb in (100, 104, 160):
         k = (nb + 7) // 8
         assert (ctx.whitening(g["crc_in"], nb)[:, :k] == g["whiten%d" % nb]).all()

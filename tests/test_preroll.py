@@ -160,6 +160,25 @@ def test_open_at(ctx):
     pre.close()
 
 
+def test_channels_beyond_one_turn_of_grid_y(ctx):
+    """The channels of an append or a gather sit on grid.y, 65 535 workgroups at most, each looping b += gridDim.y.  65 536
+    channels is the most dh_preroll_create takes (65 537 is refused: test_errors): workgroup 0 then takes a second turn, for
+    channel 65 535 -- the only second turn there can be.  depth = 8, appends of 3: the ring wraps in every channel."""
+    B, depth, n = 65536, 8, 3
+    rng = np.random.default_rng(65536)
+    pre, m = api.Preroll(B, depth, ctx=ctx), Model(B, depth)
+    counts = (np.arange(B) % 3 != 1).astype(np.uint32) * n
+    for k in range(4):
+        c = None if k == 1 else np.roll(counts, k)
+        m.append(append_slice(ctx, pre, words(rng, (B, n + 2)), n, counts=c), c)
+        assert pre.total == m.total and (pre.open_at() == m.open_at).all(), k
+    from_ = np.where(np.arange(B) % 5 == 2, NONE64, (np.arange(B) % 7).astype(np.uint64))
+    from_[[0, B - 1]] = 5, 6
+    check_gather(ctx, pre, m, from_, 0, depth)
+    check_gather(ctx, pre, m, from_, 2, n)
+    pre.close()
+
+
 def test_errors(ctx):
     lib, mem = ctx.lib, ctx.mem
     for kw in (dict(n_channels=4, depth=0), dict(n_channels=0, depth=10), dict(n_channels=65537, depth=10), dict(n_channels=1, depth=(1 << 24) + 1)):
