@@ -1717,6 +1717,9 @@ DH_HD void dh_issue_next_window(DhDspShared& S, const float* const& in, const ui
     }
 }
 
+#define DH_TAIL_GROUPS 8              // write-back of the raw tail: 16-byte groups per lane and pass (dh_rrc_demod_channel)
+#define DH_RING_GROUPS 16             // the sps-10 variance ring (1 000 words) as words per lane: the prologue's loads, all in flight together
+
 // ---------------------------------------------------------------------------------------------
 // One channel, one push.  `S` is this wavefront's LDS block.  Called by all 64 lanes (device) or
 // once (host harness; the DH_FOR_LANES loops then iterate the lanes).
@@ -1752,21 +1755,62 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     const uint32_t win_lim = dh_uniform(in_room < 0 ? 0u : in_room >= (ptrdiff_t) 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t) in_room + 1u);
 
     DH_PHASE_MARK_BEGIN();
-    // ---- load carried state
+    // ---- load carried state.  Every global load of the prologue -- header, volume ring, variance ring, taps -- is issued before
+    // the first of them is waited for: taken one loop after the other they were nine round trips in a row at the start of every
+    // part of a push (the rings of the kernels with a run-time or larger samples-per-symbol keep their loops).
+    // (A ragged push adds one full wait: n_per[ch] is wanted as a scalar for the part's bounds, and the wait for it is a wait for
+    // everything issued before it.  All of the loads are in flight by then.)
     uint32_t k0 = sth[DH_ST_K];
     int32_t off = (int32_t) sth[DH_ST_OFF];
     const uint32_t tc = sth[DH_ST_TAIL];
+    const uint32_t h_p0 = BOUNDED ? sth[DH_ST_P0] : 0u;
+    uint32_t h_cur_start = 0, h_cur_off = 0, h_prev_start = 0, h_prev_off = 0, h_blk_flags = 0, h_e_count = 0;
+    float h_e_cur = 0.0f, h_e_prev = 0.0f, h_e_block = 0.0f;
+    if (BOUNDED) {
+        h_cur_start = sth[DH_ST_CUR_START]; h_cur_off = sth[DH_ST_CUR_OFF]; h_prev_start = sth[DH_ST_PREV_START]; h_prev_off = sth[DH_ST_PREV_OFF];
+        h_blk_flags = sth[DH_ST_BLOCK_FLAGS]; h_e_count = sth[DH_ST_E_COUNT];
+        h_e_cur = st[DH_ST_E_CUR]; h_e_prev = st[DH_ST_E_PREV]; h_e_block = st[DH_ST_E_BLOCK];
+    }
+    constexpr bool RING_REGS = SPS == 10;               // DH_VARIANCE_SYMBOLS * 10 words: DH_RING_GROUPS per lane
+    constexpr bool TAPS_REGS = NZ > 0 && NZ <= 80;      // NZ + 1 + 2 DH_TAP_LEAD words: two per lane
+    static_assert(DH_VOLUME_RB_SIZE > DH_WAVE && DH_SCAN_N == 2 * DH_WAVE && DH_VARIANCE_SYMBOLS * 10 <= DH_WAVE * DH_RING_GROUPS && 80 + 1 + 2 * DH_TAP_LEAD <= 2 * DH_WAVE, "words per lane of the prologue's loads");
+    DH_LANE_ARRAY(float, vol_v, 2);
+    DH_LANE_ARRAY(float, ring_v, RING_REGS ? DH_RING_GROUPS : 1);
+    DH_LANE_ARRAY(float, tap_v, 2);
+    DH_FOR_LANES(lane) {
+        // (a lane beyond the end of a table reads its last word and drops it)
+        DH_LA(vol_v, lane)[0] = st[DH_ST_VOL + (uint32_t) lane];
+        DH_LA(vol_v, lane)[1] = st[DH_ST_VOL + dh_min<uint32_t>((uint32_t) lane + DH_WAVE, DH_VOLUME_RB_SIZE - 1u)];
+        if constexpr (RING_REGS) {
+#pragma unroll
+            for (int r = 0; r < DH_RING_GROUPS; r++) DH_LA(ring_v, lane)[r] = st[DH_ST_VAR + dh_min<uint32_t>((uint32_t) lane + DH_WAVE * (uint32_t) r, DH_VARIANCE_SYMBOLS * 10u - 1u)];
+        }
+        if constexpr (TAPS_REGS) {
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const int k = lane + DH_WAVE * i - DH_TAP_LEAD, kc = k < 0 ? 0 : k > NZ ? NZ : k;
+                DH_LA(tap_v, lane)[i] = P.taps[kc <= NZ / 2 ? kc : NZ - kc];
+            }
+        }
+    }
     const uint32_t n_push = P.n_per ? dh_min<uint32_t>(dh_uniform(P.n_per[ch]), P.n) : P.n;
     const uint32_t n_new = dh_min<uint32_t>(n_push, part_hi) > part_lo ? dh_min<uint32_t>(n_push, part_hi) - part_lo : 0u;
     const uint32_t nv = tc + n_new;                     // length of the virtual input stream
     const uint32_t nf = nv >= NZ ? nv - NZ : 0u;        // filtered samples available this push
     const uint32_t pf_lim = dh_uniform(dh_min<uint32_t>(win_lim, n_new));        // the next window may be fetched ahead from input indices below this
     DH_FOR_LANES(lane) {
-        for (uint32_t j = lane; j < DH_SCAN_N; j += DH_WAVE) {
-            S.vol_old[j] = j < DH_VOLUME_RB_SIZE ? st[DH_ST_VOL + j] : 0.0f;
-            S.vol_new[j] = 0.0f;
+        S.vol_old[lane] = DH_LA(vol_v, lane)[0];
+        S.vol_old[lane + DH_WAVE] = (uint32_t) lane + DH_WAVE < DH_VOLUME_RB_SIZE ? DH_LA(vol_v, lane)[1] : 0.0f;
+        S.vol_new[lane] = 0.0f; S.vol_new[lane + DH_WAVE] = 0.0f;
+        if constexpr (RING_REGS) {
+#pragma unroll
+            for (int r = 0; r < DH_RING_GROUPS; r++) {
+                const uint32_t j = (uint32_t) lane + DH_WAVE * (uint32_t) r;
+                if (DH_WAVE * (r + 1) <= DH_VARIANCE_SYMBOLS * 10 || j < DH_VARIANCE_SYMBOLS * 10u) S.var_rb[j] = DH_LA(ring_v, lane)[r];      // (only the last group is partial)
+            }
+        } else {
+            for (uint32_t j = lane; j < DH_VARIANCE_SYMBOLS * sps; j += DH_WAVE) S.var_rb[j] = st[DH_ST_VAR + j];
         }
-        for (uint32_t j = lane; j < DH_VARIANCE_SYMBOLS * sps; j += DH_WAVE) S.var_rb[j] = st[DH_ST_VAR + j];
     }
     DH_BARRIER();
 
@@ -1779,19 +1823,20 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     uint32_t blk_flags = 0, e_count = 0; float e_cur = 0.0f, e_prev = 0.0f, e_blk_run = 0.0f;
     int32_t cur_start = 0, cur_off = 0;
     if (BOUNDED) {
-        cur_start = (int32_t) dh_uniform(sth[DH_ST_CUR_START]); cur_off = (int32_t) dh_uniform(sth[DH_ST_CUR_OFF]);
+        cur_start = (int32_t) dh_uniform(h_cur_start); cur_off = (int32_t) dh_uniform(h_cur_off);
         BS->cur_start = cur_start; BS->cur_off = cur_off;
-        BS->prev_start = (int32_t) sth[DH_ST_PREV_START]; BS->prev_off = (int32_t) sth[DH_ST_PREV_OFF];
-        blk_flags = dh_uniform(sth[DH_ST_BLOCK_FLAGS]); e_count = dh_uniform(sth[DH_ST_E_COUNT]);
-        e_cur = dh_uniform_f(st[DH_ST_E_CUR]); e_prev = dh_uniform_f(st[DH_ST_E_PREV]); e_blk_run = dh_uniform_f(st[DH_ST_E_BLOCK]);
+        BS->prev_start = (int32_t) h_prev_start; BS->prev_off = (int32_t) h_prev_off;
+        blk_flags = dh_uniform(h_blk_flags); e_count = dh_uniform(h_e_count);
+        e_cur = dh_uniform_f(h_e_cur); e_prev = dh_uniform_f(h_e_prev); e_blk_run = dh_uniform_f(h_e_block);
         BS->blk_flags = blk_flags; BS->n_uncertain = 0; BS->n_exact_runs = 0; BS->n_exact_blocks = 0;
     }
     DH_FOR_LANES(lane) {
         if (NZ > 80) { for (int i = lane; i <= NZ / 2; i += DH_WAVE) S.tapsf[i] = P.taps[i]; }
         else if (NZ > 0) {                              // the whole response between two runs of zeros (see DhDspShared)
-            for (int j = lane; j < NZ + 1 + 2 * DH_TAP_LEAD; j += DH_WAVE) {
-                const int k = j - DH_TAP_LEAD;
-                S.tapsf[k] = (k >= 0 && k <= NZ) ? P.taps[k <= NZ / 2 ? k : NZ - k] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const int j = lane + DH_WAVE * i, k = j - DH_TAP_LEAD;
+                if (j < NZ + 1 + 2 * DH_TAP_LEAD) S.tapsf[k] = (k >= 0 && k <= NZ) ? DH_LA(tap_v, lane)[i] : 0.0f;
             }
         }
         if (lane < 2) S.stats[lane] = 0;
@@ -1799,7 +1844,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
 
     // error-bounded mode (see "Error-bounded FIR" above): the tail then starts with DH_ST_P0 samples of HISTORY, so that the
     // raw samples behind every entry of the 100-symbol rings are still at hand when a comparison has to be settled exactly
-    uint32_t p = BOUNDED ? sth[DH_ST_P0] : 0u;          // read position in the filtered stream
+    uint32_t p = h_p0;                                  // read position in the filtered stream
     uint32_t staged_p = 0xFFFFFFFFu;                    // the LDS window already holds V[staged_p ...) (prefetch); 0xFFFFFFFF: it does not (no run starts there: p < nv)
     // the next window fetched into registers behind P3 and put into the window block in P7: the split-f16 kernels (as two arrays of
     // halves, with the constants of its run below) and the kernels without an RRC stage (as it is: they have the registers, and staged
@@ -2214,9 +2259,36 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         for (uint32_t j = lane; j < DH_VOLUME_RB_SIZE; j += DH_WAVE) st[DH_ST_VOL + j] = S.vol_old[j];
         for (uint32_t j = lane; j < DH_VARIANCE_SYMBOLS * sps; j += DH_WAVE) st[DH_ST_VAR + j] = S.var_rb[j];
     }
-    // the tail may overlap its own source when base < tc: in chunks through LDS (a chunk is read completely before any of
+    const uint32_t tail_n = new_tc < tail_max ? new_tc : tail_max;
+    if (base >= tc && tail_n >= 4u) {
+        // Every push longer than a tail: the new tail lies in the input row, which nothing writes.  Whole 16-byte groups, the
+        // loads of a pass (DH_TAIL_GROUPS per lane, 2 048 samples) unconditional and all in flight before the first store --
+        // element by element through LDS (below) every pair of loads was waited for, eleven round trips to L2 in a row at the
+        // end of every part.  The last group is the last four samples, wherever they start: it may overlap the one before
+        // it (the same values twice); a lane beyond the tail loads that group once more and stores nothing.
+        const float* src = in + (base - tc);
+        for (uint32_t c0 = 0; c0 < tail_n; c0 += 4u * DH_WAVE * DH_TAIL_GROUPS) {
+            DH_LANE_ARRAY(dh_f4, tv, DH_TAIL_GROUPS);
+            DH_FOR_LANES(lane) {
+#pragma unroll
+                for (int r = 0; r < DH_TAIL_GROUPS; r++) {
+                    const uint32_t e = c0 + 4u * ((uint32_t) lane + DH_WAVE * (uint32_t) r);
+                    DH_LA(tv, lane)[r] = dh_load4_unaligned(src + dh_min<uint32_t>(e, tail_n - 4u));
+                }
+            }
+            dh_global_loads_done();
+            DH_FOR_LANES(lane) {
+#pragma unroll
+                for (int r = 0; r < DH_TAIL_GROUPS; r++) {
+                    const uint32_t e = c0 + 4u * ((uint32_t) lane + DH_WAVE * (uint32_t) r);
+                    if (e < tail_n) dh_store4_unaligned(tail + dh_min<uint32_t>(e, tail_n - 4u), DH_LA(tv, lane)[r]);
+                }
+            }
+        }
+    }
+    // otherwise the tail overlaps its own source: in chunks through LDS (a chunk is read completely before any of
     // it is written, and later chunks only read further ahead)
-    for (uint32_t c0 = 0; c0 < new_tc && c0 < tail_max; c0 += DH_FTILE) {
+    else for (uint32_t c0 = 0; c0 < new_tc && c0 < tail_max; c0 += DH_FTILE) {
         DH_BARRIER();
         DH_FOR_LANES(lane) {
             for (uint32_t j = c0 + lane; j < new_tc && j < tail_max && j < c0 + DH_FTILE; j += DH_WAVE) S.xf[j - c0] = dh_virtual_sample(tail, tc, in, base + j);
@@ -2231,6 +2303,8 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             // (timing blocks completed by this call: the symbol counter of the block wraps at 100 exactly when one ends -- counted here,
             // from the counter as the call found it, not with a read-modify-write of LDS by one lane in every run)
             // (sym_base is not kept through the loop: a later part finds it where it read it, until P.sym_count is stored below)
+            // (the counters below are read again here and written back, not carried through the loop in registers: the compiler issues
+            // these loads together and stores the header as dwordx4 -- one more batch of loads per part)
             const uint32_t produced = nsym - (part_lo ? P.sym_count[ch] : 0u);
             sth[DH_ST_BLOCKS] += (sth[DH_ST_K] + produced) / DH_VARIANCE_SYMBOLS;
             sth[DH_ST_K] = k0;
