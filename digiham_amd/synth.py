@@ -791,7 +791,7 @@ def dstar_stream(seed, n_transmissions, lead_in=41, ber=0.0):
         if kind == 7:                                                  # a header beyond repair: 40 errors in its 660 bits
             at = 64 + 15 + rng.choice(660, 40, replace=False)
             b = b.copy(); b[at] ^= 1
-        infos.append({"kind": kind, "my": my, "message": msg, "header": h, "simple": simple, "frames": len(voice)})
+        infos.append({"kind": kind, "my": my, "message": msg, "header": h, "simple": simple, "frames": len(voice), "voice": voice})
         out += [b, rng.integers(0, 2, int(rng.integers(30, 400))).astype(np.uint8)]
     bits = np.concatenate(out)
     if ber > 0:

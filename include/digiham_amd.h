@@ -181,7 +181,10 @@ typedef struct {
 /* Decoder event: one record per call the reference makes into its MetaCollector,
  * plus the FEC-corrected words feeding it (BPTC LC, slot type, EMB, FICH, DCH). */
 typedef struct {
-    uint32_t sym_index;       /* absolute symbol index of the frame start (mod 2^32) */
+    uint32_t sym_index;       /* absolute symbol index of the frame start (mod 2^32): the first symbol of the burst, frame or
+                               * codeword that raises the event.  The events raised between frames carry the first symbol not
+                               * yet consumed: D-Star HEADER (radio header) and VOICE_START, raised once the 660 header bits /
+                               * the voice sync pattern are behind, carry the first symbol of the first voice frame */
     uint8_t  type;            /* DH_EV_* */
     uint8_t  a;               /* DMR slot / YSF frame number or CSD index */
     uint8_t  b;               /* sub-type (sync type, data type, lcss, reset cause) */
