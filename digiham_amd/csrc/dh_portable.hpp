@@ -67,7 +67,7 @@ static __device__ __forceinline__ int dh_fresh_lane_id_() { int l = (int) thread
 // GLOBAL memory, which makes the compiler wait (s_waitcnt vmcnt(0)) for every global load in flight -- the next window's
 // loads, requested a phase earlier precisely so that they can stay in flight through the phases that follow (round 3: the wait
 // sat in front of the slicing phase and cost 1 ms of a 6.8 ms step).  Where a body hands data to another one through global
-// memory the caller fences explicitly (k_chain: __syncthreads() between slicer and decoder, workgroup scope).
+// memory the caller fences explicitly (chain_core.hpp: dh_barrier_global() between slicer and decoder, workgroup scope).
 #define DH_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); \
                           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
 #define DH_BALLOT_ACC(mask, pred, lane) (mask) = __builtin_amdgcn_ballot_w64((bool) (pred))      /* (v_cmp straight into the scalar pair; __ballot((pred) ? 1 : 0) left a v_cndmask + v_cmp behind every vote) */
@@ -85,6 +85,48 @@ DH_HD bool dh_is_writer_lane() { return DH_GPU_ELSE(threadIdx.x == 0, true); }
 // A value every lane holds identically (loaded from LDS / memory at a wave-uniform address): moving it to a
 // scalar register lets the arithmetic that follows run on the scalar ALU instead of costing VALU issue cycles.
 DH_HD uint32_t dh_uniform(uint32_t x) { return DH_GPU_ELSE((uint32_t) __builtin_amdgcn_readfirstlane((int) x), x); }
+
+// ---------------------------------------------------------------------------------------------
+// A word in global memory that workgroups of ONE launch hand a channel over through (chain_core.hpp: the flag word of the tail
+// split).  Nothing here orders anything by itself: the word is read and merged relaxed, at agent scope, and the two fences
+// stand on either side of it.  The CPU build runs the workgroups of a launch one after the other, in index order, in one
+// thread: every access is a plain one, a fence is nothing.
+//   dh_agent_load(p)              the word
+//   dh_agent_cas(p, seen, want)   stores `want` if the word is still `seen` (true); otherwise `seen` becomes what it holds now
+//   dh_agent_add(p, v)            adds v to the word (a statistic: nobody waits for it)
+//   dh_nap()                      between two looks at a word that another workgroup will store (s_sleep 64: ~2 us)
+//   dh_acquire_behind_flag()      after the word was seen: nothing older than it stays in this CU's L1 (buffer_inv) or scalar cache
+//   dh_release_before_flag()      in front of the store of the word: everything this workgroup stored has reached the XCD's L2
+//                                 (s_waitcnt, no write-back: the workgroup that reads the word runs on the same XCD)
+//   dh_xcc_id()                   the XCD this wavefront runs on (HW_REG_XCC_ID; the CPU build: 0)
+//   dh_opaque_scalar(x)           x, as a scalar the compiler cannot tie to an earlier computation of the same value
+//   dh_barrier_global()           the workgroup's barrier that also fences GLOBAL memory at workgroup scope (__syncthreads; DH_BARRIER
+//                                 orders LDS only): one body's global stores, read back by the body behind it in the same wavefront
+DH_HD uint32_t dh_agent_load(const uint32_t* p) { return DH_GPU_ELSE(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), *p); }
+DH_HD bool dh_agent_cas(uint32_t* p, uint32_t& seen, uint32_t want) {
+#if DH_ON_GPU
+    return __hip_atomic_compare_exchange_strong(p, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    if (*p == seen) { *p = want; return true; }
+    seen = *p;
+    return false;
+#endif
+}
+DH_HD void dh_agent_add(uint32_t* p, uint32_t v) { DH_GPU_ELSE(__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), *p += v); }
+DH_HD uint32_t dh_xcc_id() { return DH_GPU_ELSE(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u, 0u); }
+#if DH_ON_GPU
+__device__ __forceinline__ void dh_nap() { __builtin_amdgcn_s_sleep(64); }
+__device__ __forceinline__ void dh_acquire_behind_flag() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); __builtin_amdgcn_s_dcache_inv(); }
+__device__ __forceinline__ void dh_release_before_flag() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); }
+__device__ __forceinline__ uint32_t dh_opaque_scalar(uint32_t x) { asm volatile("" : "+s"(x)); return x; }
+__device__ __forceinline__ void dh_barrier_global() { __syncthreads(); }
+#else
+inline void dh_nap() {}
+inline void dh_acquire_behind_flag() {}
+inline void dh_release_before_flag() {}
+inline uint32_t dh_opaque_scalar(uint32_t x) { return x; }
+inline void dh_barrier_global() {}
+#endif
 
 DH_HD int dh_popc32(uint32_t x) { return DH_GPU_ELSE(__popc(x), __builtin_popcount(x)); }
 DH_HD int dh_popc64(uint64_t x) { return DH_GPU_ELSE(__popcll(x), __builtin_popcountll(x)); }

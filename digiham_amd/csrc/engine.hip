@@ -6,7 +6,8 @@
 // only ever holds its own channels' rows, and 16 384-channel grids give 64 workgroups per CU.
 // Batch FEC kernels are one item per lane, 256-lane workgroups, grid-stride.
 // The helper kernels and their launches stand at the ends of the core headers and in helper_launches.hpp, one text for this build and the
-// CPU harness; here are the kernels that need barriers, LDS staging, matrix cores or wave votes.
+// CPU harness; the chain workgroup (slicer, decoder, the hand-over of the tail split) is chain_core.hpp, one text likewise, and
+// k_chain its launch-shape wrapper; here are the kernels that need barriers, LDS staging, matrix cores or wave votes.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 // (no FMA contraction anywhere: products and sums of the exact paths round separately, as the
@@ -21,7 +22,7 @@
 #include "../../include/digiham_amd.h"
 #include "kernels_core.hpp"
 #include "outpack_core.hpp"
-#include "launch_plan.hpp"
+#include "chain_core.hpp"
 #include "fec_tables.hpp"
 #include "rrc_taps.h"
 
@@ -34,7 +35,6 @@ int hip_fail(hipError_t e, const char* what) {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
     return -1;
 }
-#define DH_OPAQUE_SGPR(x) asm volatile("" : "+s"(x))        // an opaque copy: the compiler must not tie it to an earlier computation of the same value
 #define HIP_TRY(expr) do { if (hip_fail((expr), #expr)) return DH_EDEVICE; } while (0)
 
 }  // namespace
@@ -63,13 +63,6 @@ namespace {
 #ifndef DH_LB
 #define DH_LB 4          // minimum waves per SIMD the wide-filter kernels are register-budgeted for (128 VGPRs)
 #endif
-// The hand-over flag word of a split push (DH_ST_PART of a channel's state; k_chain below):
-// epoch of the push (24 bits) | parts written back << 24 | a later part gave up << 26 | XCC id << 28
-#define DH_PF_GAVE_UP (1u << 26)
-__device__ __forceinline__ bool dh_pf_of_push(uint32_t v, uint32_t epoch) { return (v & 0x00FFFFFFu) == epoch; }
-__device__ __forceinline__ uint32_t dh_pf_done(uint32_t v) { return (v >> 24) & 3u; }
-__device__ __forceinline__ uint32_t dh_pf_xcc(uint32_t v) { return v >> 28; }
-__device__ __forceinline__ uint32_t dh_xcc_id() { return __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u; }      // HW_REG_XCC_ID
 // ---------------------------------------------------------------------------------- kernels
 // second launch-bounds argument = minimum waves per SIMD: caps the VGPR budget at 128 (wide) / 256 (narrow)
 // KEEPF: the launch also delivers the filtered samples (DhDspParams::filt_out; BASELINE configs[1] in one kernel)
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_r
 // The whole chain of one channel in one wavefront: slice this push's samples, then run the protocol decoder over
 // the symbols just produced.  The decoder is latency-bound (scalar control, LDS round trips); inside this kernel
 // its stalls are covered by the other wavefronts' FIR arithmetic instead of by nothing, as in a separate launch.
-// The two stages use the LDS block one after the other.
+// The two stages use the LDS block one after the other.  The body, and the tail split's hand-over in it: dh_chain_workgroup (chain_core.hpp).
 // SPS = 10 is the specialised slicer of the DMR / YSF / D-Star pipes, SPS = 0 takes the run-time value (NXDN: 20).
 // PART only names the launch: with DH_FLAG_OVERLAP_PUSHES a push of a large engine goes out as two launches (PART 0 =
 // the first channels on the engine's high-priority stream, PART 1 = the rest on its normal-priority one; see
@@ -91,108 +84,7 @@ __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_r
 template <int NZ, bool FAST, int PROTO, int SPS = 10, int PART = 0>
 __global__ __launch_bounds__(DH_WAVE, (NZ > 80 ? DH_LB_NARROW : DH_LB)) void k_chain(const DhDspParams P, const DhDecParams D) {
     extern __shared__ __attribute__((aligned(16))) char dh_smem[];
-    // Tail split (HipBackend::go_chain): two (or three) workgroups per channel.  Workgroup c takes the first split_n0
-    // samples of channel c's push, workgroup split_pad + c the rest (up to split_n1, where workgroup 2 split_pad + c takes
-    // over), each starting from the state the one before wrote back -- a part is a push, and results do not depend on where
-    // pushes end.  Workgroups are dispatched in index order, so every first part is on the machine (most have long
-    // finished) before any second part is; the short later parts are what the launch drains with.  Hand-over: the
-    // workgroups of a channel run on the same XCD (workgroup i goes to XCD i mod 8, split_pad is a multiple of 8), so a
-    // part's stores only have to reach that XCD's L2 (s_waitcnt, no write-back) and the next part only has to drop its
-    // CU's L1 / scalar cache; the flag word carries the epoch of the push, the number of parts written back and the XCC
-    // id.  None of this is promised by HIP: HipBackend::open probes the placement once per device and switches the split off
-    // where it does not hold, and a part that finds another XCC id, or no flag within its patience, touches nothing and
-    // leaves -- the fix-up launch that follows every split launch (split_fixup, below) then finishes that channel's row.
-    uint32_t bid = blockIdx.x, part = 0, sym_base = 0, part_lo = 0, part_hi = 0xFFFFFFFFu;
-    const uint32_t last_part = P.split_n0 ? (P.split_n1 ? 2u : 1u) : 0u;
-    if (P.split_n0 && !P.split_fixup) {
-        while (part < last_part && bid >= P.split_pad) { part++; bid -= P.split_pad; }
-        if (bid >= P.n_channels) return;                // padding between the parts of the grid
-        part_lo = part == 0 ? 0u : part == 1 ? P.split_n0 : P.split_n1;
-        part_hi = part == 0 ? P.split_n0 : (part == 1 && P.split_n1) ? P.split_n1 : 0xFFFFFFFFu;       // (= dh_part_lo / dh_part_hi, launch_plan.hpp)
-    }
-    const uint32_t ch = bid + P.ch_base;
-    uint32_t* const part_flag = reinterpret_cast<uint32_t*>(P.state) + (size_t) ch * P.state_stride + DH_ST_PART;
-    if (P.split_n0 && P.split_fixup) {
-        // The launch behind a split launch (HipBackend::go_chain), one workgroup per channel.  The kernel boundary in front of
-        // it has made everything the split launch stored visible; a channel whose flag word says that all parts were written
-        // back -- every channel, unless a hand-over failed -- is left alone.  Otherwise the rest of the row is done here in
-        // one piece, starting behind the last part that was completed.
-        const uint32_t v = dh_uniform(__hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const uint32_t done = dh_pf_of_push(v, P.part_epoch) ? dh_pf_done(v) : 0u;
-        if (done > last_part) return;
-        part = done;
-        part_lo = part == 0 ? 0u : part == 1 ? P.split_n0 : P.split_n1;
-        if (part) sym_base = dh_uniform(__hip_atomic_load(P.sym_count + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    } else if (part) {
-        const uint32_t xcc = dh_xcc_id();
-        bool ok = false, told = false;
-        const bool forced = P.split_force_fail && part == 1u && ch % P.split_force_fail == 1u;     // (tests: this hand-over "fails"; a third part then has to notice)
-        for (uint32_t spin = 0; spin < (1u << 16) && !forced; spin++) {                 // (a first part takes ~1.5 ms; 2^16 x ~2 us)
-            const uint32_t v = dh_uniform(__hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (dh_pf_of_push(v, P.part_epoch)) {
-                if (v & DH_PF_GAVE_UP) { told = true; break; }                              // the part in front of this one gave up
-                if (dh_pf_done(v) >= part) { ok = dh_pf_xcc(v) == xcc; break; }
-            }
-            __builtin_amdgcn_s_sleep(64);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // buffer_inv: this CU's L1 holds nothing older than the flag
-        __builtin_amdgcn_s_dcache_inv();
-        if (!ok) {
-            // No hand-over (never seen on an MI355X in SPX mode, where the probe of HipBackend::open holds): nothing of this
-            // channel has been touched by this workgroup, the fix-up launch behind this one finishes the row.
-            if (threadIdx.x == 0) {
-                // "gave up" is published as a word of THIS push: when the part in front has not published yet the word still carries an older
-                // epoch, and a bit set on that would be dropped by that part's compare-and-swap below (it only keeps the bit of a word of its
-                // own push) -- the part behind this one would then spin through its whole patience instead of leaving at once
-                uint32_t seen = __hip_atomic_load(part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                for (;;) {
-                    const uint32_t want = (dh_pf_of_push(seen, P.part_epoch) ? seen : P.part_epoch) | DH_PF_GAVE_UP;
-                    if (__hip_atomic_compare_exchange_strong(part_flag, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                }
-                if (P.overflow) __hip_atomic_fetch_add(P.overflow + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (a statistic: dh_engine_debug_header(202))
-                if (P.overflow && told) __hip_atomic_fetch_add(P.overflow + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ... of which: told so by the part in front (203)
-            }
-            return;
-        }
-        sym_base = dh_uniform(__hip_atomic_load(P.sym_count + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-    {
-        DhDspShared L = dh_dsp_carve(dh_smem, SPS ? (uint32_t) SPS : P.sps, NZ);
-        constexpr int LV = PROTO == DH_PROTO_DSTAR ? 2 : 4;
-        static_assert(LV == DhChainInst<NZ, FAST, PROTO, SPS>::LV, "the plan routes by these levels (launch_plan.hpp)");
-        dh_rrc_demod_channel<NZ, FAST, SPS, LV>(P, ch, L, part_lo, part_hi, sym_base);      // (dh_plan_chain checked P.levels)
-    }
-    // This wavefront's symbol / count stores are read back by its own decoder half below: a WORKGROUP-scope fence (part of
-    // __syncthreads) orders them.  A device-scope __threadfence() here made every wavefront write back its XCD's L2 --
-    // 16 384 times per launch, 0.7 ms of a push of 4 752 samples (tools/push_size.py).
-    __syncthreads();
-    DhDecShared& S = *reinterpret_cast<DhDecShared*>(dh_smem);
-#ifdef DH_SKIP_DECODER                      // diagnostic builds (tools/phase_budget.sh): the slicer half alone (the hand-over of the tail split still takes place)
-    if (!P.n_channels)
-#endif
-    dh_decode_channel(PROTO, D, ch, S, sym_base, part != 0);
-    // (which part this is, and its flag word, worked out again: nothing of the hand-over stays live through the two halves)
-    uint32_t part_end = 0, bid_end = blockIdx.x;
-    DH_OPAQUE_SGPR(bid_end);
-    const uint32_t last_end = P.split_n0 ? (P.split_n1 ? 2u : 1u) : 0u;
-    if (P.split_n0 && P.split_fixup) part_end = last_end;                                 // the fix-up launch finishes the row
-    else while (P.split_n0 && part_end < last_end && bid_end >= P.split_pad) { part_end++; bid_end -= P.split_pad; }
-    if (P.split_n0) {                                   // (the last part publishes too: the fix-up launch reads how far the row got)
-        uint32_t* const flag_end = reinterpret_cast<uint32_t*>(P.state) + (size_t) (bid_end + P.ch_base) * P.state_stride + DH_ST_PART;
-        // everything this workgroup stored is in the XCD's L2 before the flag is
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (threadIdx.x == 0) {
-            // (a later part that has given up meanwhile set bit 26 with a fetch_or: a plain store would wipe it out and leave the part
-            // behind that one spinning through its whole patience -- compare-and-swap keeps the bit when the word is of this push)
-            const uint32_t mine = P.part_epoch | (part_end + 1u) << 24 | dh_xcc_id() << 28;
-            uint32_t seen = __hip_atomic_load(flag_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (;;) {
-                const uint32_t want = mine | (dh_pf_of_push(seen, P.part_epoch) ? (seen & DH_PF_GAVE_UP) : 0u);
-                if (__hip_atomic_compare_exchange_strong(flag_end, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-            }
-        }
-    }
+    dh_chain_workgroup<NZ, FAST, PROTO, SPS>(P, D, blockIdx.x, dh_smem);
 }
 
 template <int NZ, bool FAST>
@@ -486,71 +378,69 @@ struct HipBackend {
     // tail split of the chain launches (go_chain): share of a push, in percent, that the first workgroup of a channel
     // takes; 0 = off.  DH_TAIL_SPLIT in the environment overrides it when the engine is created (A/B runs).
     uint32_t tail_split_pct = DH_TAIL_SPLIT_PCT, tail_split_pct2 = DH_TAIL_SPLIT_PCT2, part_epoch = 0, tail_split_force_fail = 0;
-    // What the tail split's cheap hand-over rests on, checked once per device and process: the part is a gfx950 and the
-    // workgroups of a launch land on XCD (index mod 8) -- a probe launch of 4 096 workgroups records HW_REG_XCC_ID per index.
-    // (Dispatch in index order cannot be probed; a hand-over that does not come is caught at run time, see k_chain.)
-    bool tail_split_probe() {
-        static std::mutex m; static int verdict[64] = { 0 };         // 0 unknown, 1 holds, -1 does not
-        if (device < 0 || device >= 64) return false;
-        std::lock_guard<std::mutex> lock(m);
-        if (verdict[device]) return verdict[device] > 0;
-        // (a verdict is only recorded once the placement has actually been looked at: an allocation, launch or copy that fails
-        // here leaves it unknown -- the split stays off for THIS engine, the next engine probes again.  The probe runs on a
-        // stream of its own: the caller's may be capturing, or hold work this must not wait for.)
+    // One probe launch per device and process: `grid` one-wavefront workgroups of `kernel` leave a word each, `judge` makes 1 (holds),
+    // -1 (does not) or 0 (no finding) of them.  Only a finding is recorded in `verdict` (0 unknown; the caller holds its lock): a HIP
+    // call that fails leaves it unknown and `why` names the call -- the next engine probes again.  The probe runs on a stream of
+    // its own: the caller's may be capturing, or hold work this must not wait for.
+    template <class Judge> int run_probe(int (&verdict)[64], const char* name, void (*kernel)(uint32_t*), const char* launch, uint32_t grid, const char** why, Judge judge) {
         Scope on_device(device);
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess) { (void) hipGetLastError(); return false; }
-        if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) { verdict[device] = -1; return false; }
-        constexpr uint32_t N = 4096;
-        uint32_t* d = nullptr; std::vector<uint32_t> h(N, 0xFFu);
-        hipStream_t probe = nullptr;
-        if (hipStreamCreateWithFlags(&probe, hipStreamNonBlocking) != hipSuccess) { (void) hipGetLastError(); return false; }
-        if (hipMalloc((void**) &d, sizeof(uint32_t) * N) != hipSuccess) { (void) hipGetLastError(); (void) hipStreamDestroy(probe); return false; }
-        hipLaunchKernelGGL(k_xcc_probe, dim3(N), dim3(DH_WAVE), 0, probe, d);
-        const bool ran = hipGetLastError() == hipSuccess && hipStreamSynchronize(probe) == hipSuccess &&
-                         hipMemcpy(h.data(), d, sizeof(uint32_t) * N, hipMemcpyDeviceToHost) == hipSuccess;
-        (void) hipFree(d);
-        (void) hipStreamDestroy(probe);
-        if (!ran) { (void) hipGetLastError(); return false; }
-        bool ok = true;
-        for (uint32_t i = 0; i < N && ok; i++) ok = h[i] < 8u && h[i] == h[i & 7u];
-        for (uint32_t i = 0; i < 8 && ok; i++) for (uint32_t j = 0; j < i; j++) ok = ok && h[i] != h[j];      // eight XCDs, each index class its own
-        verdict[device] = ok ? 1 : -1;
-        return ok;
-    }
-    // see k_lds_unaligned_probe.  1 = unaligned reads come back whole, -1 = they do not (measured), 0 = the probe could not run (`why` says
-    // which HIP call failed: an out-of-memory or a launch failure is not an alignment finding, and is not cached)
-    int lds_unaligned_probe(const char** why) {
-        static std::mutex m; static int verdict[64] = { 0 };         // 0 unknown, 1 holds, -1 does not
-        if (device < 0 || device >= 64) { *why = "the LDS alignment probe keeps verdicts for device indices below 64"; return 0; }
-        std::lock_guard<std::mutex> lock(m);
-        if (std::getenv("DH_LDS_PROBE_FORCE_FAIL")) return -1;        // tests: what an engine on a device without unaligned LDS reads is told
-        if (verdict[device]) return verdict[device];
-        Scope on_device(device);
-        uint32_t* d = nullptr; uint32_t h = 0;
+        uint32_t* d = nullptr; std::vector<uint32_t> h(grid, 0u);
         hipStream_t probe = nullptr;
         static thread_local char msg[160];
         auto failed = [&](hipError_t e, const char* call) {
             if (e == hipSuccess) return false;
-            std::snprintf(msg, sizeof(msg), "the LDS alignment probe could not run: %s: %s", call, hipGetErrorString(e));
+            std::snprintf(msg, sizeof(msg), "the %s probe could not run: %s: %s", name, call, hipGetErrorString(e));
             (void) hipGetLastError();
             *why = msg;
             return true;
         };
         if (failed(hipStreamCreateWithFlags(&probe, hipStreamNonBlocking), "hipStreamCreateWithFlags")) return 0;
-        bool bad = failed(hipMalloc((void**) &d, sizeof(uint32_t)), "hipMalloc");
-        if (!bad) bad = failed(hipMemsetAsync(d, 0, sizeof(uint32_t), probe), "hipMemsetAsync");
+        bool bad = failed(hipMalloc((void**) &d, sizeof(uint32_t) * grid), "hipMalloc");
+        if (!bad) bad = failed(hipMemsetAsync(d, 0, sizeof(uint32_t) * grid, probe), "hipMemsetAsync");
         if (!bad) {
-            hipLaunchKernelGGL(k_lds_unaligned_probe, dim3(1), dim3(DH_WAVE), 0, probe, d);
-            bad = failed(hipGetLastError(), "launch of k_lds_unaligned_probe") || failed(hipStreamSynchronize(probe), "hipStreamSynchronize") ||
-                  failed(hipMemcpy(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(DH_WAVE), 0, probe, d);
+            bad = failed(hipGetLastError(), launch) || failed(hipStreamSynchronize(probe), "hipStreamSynchronize") ||
+                  failed(hipMemcpy(h.data(), d, sizeof(uint32_t) * grid, hipMemcpyDeviceToHost), "hipMemcpy");
         }
         if (d) (void) hipFree(d);
         (void) hipStreamDestroy(probe);
         if (bad) return 0;
-        if (h == 0u) { *why = "the LDS alignment probe could not run: the probe kernel left no result"; return 0; }
-        verdict[device] = h == 1u ? 1 : -1;
-        return verdict[device];
+        const int v = judge(h.data());
+        if (v) verdict[device] = v;
+        return v;
+    }
+    // What the tail split's cheap hand-over rests on: the part is a gfx950 and the workgroups of a launch land on XCD (index
+    // mod 8) -- 4 096 workgroups record HW_REG_XCC_ID per index.  A probe that could not run leaves the split off for THIS engine.
+    // (Dispatch in index order cannot be probed; a hand-over that does not come is caught at run time, see chain_core.hpp.)
+    bool tail_split_probe() {
+        static std::mutex m; static int verdict[64] = { 0 };
+        if (device < 0 || device >= 64) return false;
+        std::lock_guard<std::mutex> lock(m);
+        if (verdict[device]) return verdict[device] > 0;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) { (void) hipGetLastError(); return false; }
+        if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) { verdict[device] = -1; return false; }
+        constexpr uint32_t N = 4096;
+        const char* why = nullptr;
+        return run_probe(verdict, "XCD placement", k_xcc_probe, "launch of k_xcc_probe", N, &why, [](const uint32_t* h) {
+            bool ok = true;
+            for (uint32_t i = 0; i < N && ok; i++) ok = h[i] < 8u && h[i] == h[i & 7u];
+            for (uint32_t i = 0; i < 8 && ok; i++) for (uint32_t j = 0; j < i; j++) ok = ok && h[i] != h[j];      // eight XCDs, each index class its own
+            return ok ? 1 : -1;
+        }) > 0;
+    }
+    // see k_lds_unaligned_probe.  1 = unaligned reads come back whole, -1 = they do not (measured), 0 = the probe could not run (`why` says
+    // which HIP call failed: an out-of-memory or a launch failure is not an alignment finding, and is not cached)
+    int lds_unaligned_probe(const char** why) {
+        static std::mutex m; static int verdict[64] = { 0 };
+        if (device < 0 || device >= 64) { *why = "the LDS alignment probe keeps verdicts for device indices below 64"; return 0; }
+        std::lock_guard<std::mutex> lock(m);
+        if (std::getenv("DH_LDS_PROBE_FORCE_FAIL")) return -1;        // tests: what an engine on a device without unaligned LDS reads is told
+        if (verdict[device]) return verdict[device];
+        return run_probe(verdict, "LDS alignment", k_lds_unaligned_probe, "launch of k_lds_unaligned_probe", 1u, why, [&](const uint32_t* h) {
+            if (h[0] == 0u) *why = "the LDS alignment probe could not run: the probe kernel left no result";
+            return h[0] == 0u ? 0 : h[0] == 1u ? 1 : -1;
+        });
     }
     hipStream_t side = nullptr, side_lo = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join_lo = nullptr;
@@ -703,25 +593,21 @@ struct HipBackend {
             }
         }
         if constexpr (MAY_SPLIT) {
-            // Tail split (see k_chain): a launch of one workgroup per channel ends with a drain of about one workgroup's
+            // Tail split (see chain_core.hpp): a launch of one workgroup per channel ends with a drain of about one workgroup's
             // duration during which the chip runs half empty (start / end stamps of every wavefront, profiles/r03_d_*: 0.65 ms of a 6.2 ms step).  With the
             // last quarter of every row handed to a second workgroup of the same launch the drain consists of workgroups a
             // third as long.  Only for launches that fill the chip several times over and pushes long enough to be worth
             // two prologues.
             if (tail_split_pct > 0 && P.n_channels >= DH_TAIL_SPLIT_MIN_CHANNELS && P.n >= DH_TAIL_SPLIT_MIN_SAMPLES) {
                 DhDspParams Q = P;
-                dh_tail_split_points(P.n, tail_split_pct, tail_split_pct2, Q.split_n0, Q.split_n1);
-                Q.split_pad = (P.n_channels + 7u) & ~7u;
-                part_epoch = (part_epoch % 0x00FFFFFEu) + 1u;
-                Q.part_epoch = part_epoch;
-                Q.split_force_fail = tail_split_force_fail;
-                hipLaunchKernelGGL((k_chain<NZ, FAST, PROTO, SPS, 0>), dim3((Q.split_n1 ? 2u : 1u) * Q.split_pad + P.n_channels), dim3(DH_WAVE), lds, ms(), Q, D);
+                const DhSplitGrids G = dh_plan_split(Q, tail_split_pct, tail_split_pct2, part_epoch, tail_split_force_fail);      // (launch_plan.hpp)
+                hipLaunchKernelGGL((k_chain<NZ, FAST, PROTO, SPS, 0>), dim3(G.split), dim3(DH_WAVE), lds, ms(), Q, D);
                 if (launched("k_chain")) return -1;
                 // The fix-up launch (PART 1 only names it for profilers): one workgroup per channel looks at the channel's flag
                 // word and leaves -- a few microseconds for the whole grid -- unless a hand-over of the launch above failed, in
                 // which case it finishes that row unsplit.  Stream order makes it see everything the split launch stored.
                 Q.split_fixup = 1u;
-                hipLaunchKernelGGL((k_chain<NZ, FAST, PROTO, SPS, 1>), dim3(P.n_channels), dim3(DH_WAVE), lds, ms(), Q, D);
+                hipLaunchKernelGGL((k_chain<NZ, FAST, PROTO, SPS, 1>), dim3(G.fixup), dim3(DH_WAVE), lds, ms(), Q, D);
                 return launched("k_chain (fix-up)");
             }
         }

@@ -3,7 +3,8 @@
 // Both backends (HipBackend in engine.hip, the lane-loop HostBackend of tests/host_harness) go through these ladders; each
 // passes a callable that runs ONE instantiation, called as go(Tag{}) and returning the backend's status.  Nothing here
 // launches, allocates or emulates anything.  Also here, once: the protocol switch behind a slicer and the host-side
-// arithmetic of the tail split (grammar of DH_TAIL_SPLIT, bounds of a part).  When to split is each backend's own policy.
+// arithmetic of the tail split (grammar of DH_TAIL_SPLIT, parameters of a split launch; the parts themselves and the chain
+// workgroup: chain_core.hpp, which this header brings with it, at its end).  When to split is each backend's own policy.
 // tests/host_cpp/plan_test.cpp holds the routes as a literal table: a route changed here is changed there, on purpose.
 #pragma once
 
@@ -59,8 +60,7 @@ template <class Go> int dh_plan_rrc_tiles(uint32_t nz, bool fast, Go&& go) {
 }
 
 // The decoder of one channel; sym_base / append are the tail split's (POCSAG and the protocol scan are never chained and take neither).
-// k_chain calls it with its PROTO template constant, so the switch folds.  It keeps its own part bounds (below): stated through
-// these functions the NXDN chain kernels allocate registers differently, and the device code is not this header's to change.
+// dh_chain_workgroup (chain_core.hpp) calls it with its PROTO template constant, so the switch folds.
 DH_HD void dh_decode_channel(int proto, const DhDecParams& D, uint32_t ch, DhDecShared& S, uint32_t sym_base = 0, bool append = false) {
     if (proto == DH_PROTO_DMR) dh_dmr_channel(D, ch, S, sym_base, append);
     else if (proto == DH_PROTO_DSTAR) dh_dstar_channel(D, ch, S, sym_base, append);
@@ -70,7 +70,7 @@ DH_HD void dh_decode_channel(int proto, const DhDecParams& D, uint32_t ch, DhDec
     else dh_ysf_channel(D, ch, S, sym_base, append);
 }
 
-// ---- tail split (engine.hip, k_chain): the parts of a push
+// ---- tail split (chain_core.hpp): how a push is cut and launched
 // DH_TAIL_SPLIT = "80" or "75,93": percent of a push where the second / third part of a channel starts, "0" = off.
 // DH_TAIL_SPLIT_FORCE_FAIL = k (tests): see DhDspParams::split_force_fail.
 struct DhTailSplitEnv { bool set; uint32_t pct, pct2, force_fail; };
@@ -91,7 +91,24 @@ inline void dh_tail_split_points(uint32_t n, uint32_t pct, uint32_t pct2, uint32
     n0 = (uint32_t) ((uint64_t) n * pct / 100u);
     n1 = pct2 > pct ? (uint32_t) ((uint64_t) n * pct2 / 100u) : 0u;
 }
-// part p = 0, 1, 2 takes the samples [lo, hi) of the row; the fix-up behind a failed hand-over takes [lo of the first
-// unfinished part, dh_part_hi(2, ...) = the end of the row)
-DH_HD uint32_t dh_part_lo(uint32_t part, uint32_t n0, uint32_t n1) { return part == 0 ? 0u : part == 1 ? n0 : n1; }
-DH_HD uint32_t dh_part_hi(uint32_t part, uint32_t n0, uint32_t n1) { return part == 0 ? n0 : (part == 1 && n1) ? n1 : 0xFFFFFFFFu; }
+// The parameters of a split launch of Q's push, stated once for both backends (when to split is theirs): the parts' bounds
+// (a first part of at least one sample, a third that does not start in front of the second: nothing to clamp at the device's
+// thresholds), the pad between the parts of the grid -- a multiple of 8, so that the workgroups of a channel land on one XCD --
+// and the next epoch of the engine's counter.  Returns the grid of the split launch and of the fix-up launch behind it
+// (the same Q with split_fixup = 1).
+inline uint32_t dh_next_epoch(uint32_t e) { return (e % 0x00FFFFFEu) + 1u; }         // 24 bits, never 0
+struct DhSplitGrids { uint32_t split, fixup; };
+inline DhSplitGrids dh_plan_split(DhDspParams& Q, uint32_t pct, uint32_t pct2, uint32_t& epoch, uint32_t force_fail) {
+    dh_tail_split_points(Q.n, pct, pct2, Q.split_n0, Q.split_n1);
+    if (Q.split_n0 < 1u) Q.split_n0 = 1u;
+    if (pct2 > pct && Q.split_n1 < Q.split_n0) Q.split_n1 = Q.split_n0;
+    Q.split_pad = (Q.n_channels + 7u) & ~7u;
+    Q.part_epoch = epoch = dh_next_epoch(epoch);
+    Q.split_fixup = 0u;
+    Q.split_force_fail = force_fail;
+    return { (Q.split_n1 ? 2u : 1u) * Q.split_pad + Q.n_channels, Q.n_channels };
+}
+
+// The chain workgroup the chain routes launch, and the parts of a split push (dh_part_lo / dh_part_hi, the flag word): whoever
+// has the plan has them.  At the end: chain_core.hpp uses DhChainInst and dh_decode_channel above (either header may come first).
+#include "chain_core.hpp"

@@ -4,13 +4,14 @@
 // bytes), so the plan itself is asked: for every (nz, sps, fast, proto, levels, filt_out) an engine can hand to a backend
 // (engine_impl.hpp, make_layout) a recording callable notes the tag it was called with, and the note is compared with the
 // first matching row below (-1 = any; no row = no instantiation).  A route that changes in launch_plan.hpp changes here
-// too: this is the one place where that has to be done twice.
+// too: this is the one place where that has to be done twice.  Also here: the host-visible pieces of the tail split
+// (digiham_amd/csrc/chain_core.hpp) -- the locator, the bounds, the flag word and its merge, the parameters of a split launch.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "../../digiham_amd/csrc/launch_plan.hpp"
+#include "../../digiham_amd/csrc/chain_core.hpp"
 
 namespace {
 
@@ -131,6 +132,61 @@ int main() {
           dh_part_lo(2, n0, n1) == 65100u && dh_part_hi(2, n0, n1) == 0xFFFFFFFFu, "three parts");
     dh_tail_split_points(0xFFFFFFFFu, 99u, 0u, n0, n1);
     check(n0 == 4252017622u, "points: 64-bit product");
+
+    // which part of which channel a block of a split launch is; the blocks between the parts are padding
+    const struct { uint32_t channels, pad; } GRIDS[] = { { 1, 8 }, { 7, 8 }, { 8, 8 }, { 9, 16 } };
+    for (const auto& g : GRIDS) for (uint32_t parts = 2; parts <= 3; parts++) {
+        DhDspParams Q{}; Q.n = 1000u; Q.n_channels = g.channels; Q.ch_base = 0u;
+        uint32_t epoch = 41u;
+        const DhSplitGrids G = dh_plan_split(Q, 40u, parts == 3 ? 90u : 0u, epoch, 5u);
+        check(Q.split_pad == g.pad && Q.split_pad % 8u == 0u && Q.split_pad >= g.channels, "pad: the next multiple of 8");
+        check(G.split == (parts - 1u) * g.pad + g.channels && G.fixup == g.channels, "grids of the split and the fix-up launch");
+        check(Q.split_n0 == 400u && Q.split_n1 == (parts == 3 ? 900u : 0u) && Q.part_epoch == 42u && epoch == 42u &&
+              Q.split_force_fail == 5u && Q.split_fixup == 0u, "parameters of a split launch");
+        uint32_t real = 0;
+        for (uint32_t bid = 0; bid < G.split; bid++) {
+            const DhBlockPart B = dh_part_of_block(Q, bid);
+            const uint32_t part = bid / g.pad, local = bid % g.pad;       // (no block lies beyond the last part's channels)
+            check(B.part == part && B.bid == local && B.padding == (local >= g.channels), "dh_part_of_block");
+            real += B.padding ? 0u : 1u;
+        }
+        check(real == parts * g.channels, "every part of every channel has one block");
+        Q.split_fixup = 1u;                                             // the fix-up launch: block b is channel b
+        for (uint32_t bid = 0; bid < G.fixup; bid++) {
+            const DhBlockPart B = dh_part_of_block(Q, bid);
+            check(B.part == 0u && B.bid == bid && !B.padding, "dh_part_of_block (fix-up)");
+        }
+    }
+    {   // (the harness's pushes: a first part of at least one sample, a third not in front of the second)
+        DhDspParams Q{}; Q.n = 2u; Q.n_channels = 4u;
+        uint32_t epoch = 0u;
+        const DhSplitGrids G = dh_plan_split(Q, 1u, 40u, epoch, 0u);
+        check(Q.split_n0 == 1u && Q.split_n1 == 1u && G.split == 20u && epoch == 1u, "bounds of a two-sample push");
+    }
+    // the epoch: 24 bits, never 0
+    check(dh_next_epoch(0u) == 1u && dh_next_epoch(1u) == 2u && dh_next_epoch(0x00FFFFFDu) == 0x00FFFFFEu && dh_next_epoch(0x00FFFFFEu) == 1u, "epoch step");
+    // the flag word
+    for (uint32_t epoch : { 1u, 0x00ABCDEFu, 0x00FFFFFEu }) for (uint32_t part = 0; part < 3; part++) for (uint32_t xcc = 0; xcc < 16; xcc++) {
+        const uint32_t v = dh_pf_pack(epoch, part, xcc);
+        check(dh_pf_of_push(v, epoch) && !dh_pf_of_push(v, dh_next_epoch(epoch)) && dh_pf_done(v) == part + 1u && dh_pf_xcc(v) == xcc &&
+              !(v & DH_PF_GAVE_UP), "flag word round trip");
+        check(dh_pf_of_push(v | DH_PF_GAVE_UP, epoch) && dh_pf_done(v | DH_PF_GAVE_UP) == part + 1u && dh_pf_xcc(v | DH_PF_GAVE_UP) == xcc, "flag word with the give-up bit");
+    }
+    {   // its merge, both keep rules, on a word of this push (epoch 7) and on words of older pushes
+        const uint32_t E = 7u, gave_up = E | DH_PF_GAVE_UP;
+        const uint32_t done1 = dh_pf_pack(E, 0u, 5u), old = dh_pf_pack(6u, 1u, 3u) | DH_PF_GAVE_UP;
+        uint32_t w;
+        // the give-up write: the whole word of this push stays, an older one is replaced by the bare epoch
+        w = done1; dh_pf_publish(&w, E, gave_up, 0xFFFFFFFFu); check(w == (done1 | DH_PF_GAVE_UP), "give-up on a word of this push");
+        w = old; dh_pf_publish(&w, E, gave_up, 0xFFFFFFFFu); check(w == gave_up, "give-up on a word of an older push");
+        w = 0u; dh_pf_publish(&w, E, gave_up, 0xFFFFFFFFu); check(w == gave_up, "give-up on a fresh word");
+        // the done write: only the give-up bit of a word of this push stays
+        const uint32_t done2 = dh_pf_pack(E, 1u, 2u);
+        w = done1; dh_pf_publish(&w, E, done2, DH_PF_GAVE_UP); check(w == done2, "done over a done word of this push");
+        w = done1 | DH_PF_GAVE_UP; dh_pf_publish(&w, E, done2, DH_PF_GAVE_UP); check(w == (done2 | DH_PF_GAVE_UP), "done keeps the give-up bit of this push");
+        w = gave_up; dh_pf_publish(&w, E, done1, DH_PF_GAVE_UP); check(w == (done1 | DH_PF_GAVE_UP), "done behind an early give-up");
+        w = old; dh_pf_publish(&w, E, done1, DH_PF_GAVE_UP); check(w == done1, "done drops everything of an older push");
+    }
 
     printf("%d routes checked, %d failures\n", routes, failures);
     return failures ? 1 : 0;

@@ -4,12 +4,15 @@
 // 64-iteration loop, DH_BARRIER a no-op and "device memory" is the host heap.  The helper kernels
 // and their launches are the device's own text (the ends of the core headers, digiham_amd/csrc/helper_launches.hpp): a launch
 // visits every block and thread of the grid the launcher computed.  What is written here is the
-// backend's plumbing, the three planned launches (a loop over workgroups each) and the
+// backend's plumbing, the three planned launches (a loop over workgroups each; the chain's runs
+// digiham_amd/csrc/chain_core.hpp, the device's chain workgroup, over the device's grids) and the
 // restatements of the kernels a thread-at-a-time visit cannot run (front-end, MFMA probe, copy).
 // It exports the same C ABI as libdigiham_amd.so so the CPU-only test
 // tier can run the engine's orchestration and the exact wave algorithms against the oracle.
 // Which instantiation serves which configuration comes from digiham_amd/csrc/launch_plan.hpp, as
-// on the device: every route the device chains or splits is chained or split here.
+// on the device: every route the device chains or splits is chained or split here, a split
+// push as the split launch and its fix-up launch -- what is exercised is the hand-over itself
+// (flag word, give-up, told, fix-up), in index order, not only the part arithmetic.
 // It is built into tests/host_harness/libdh_hostemu.so, is never installed, and the digiham_amd
 // package has no code path that loads it: the product fails loudly without the gfx950 library.
 #include <stdlib.h>
@@ -19,7 +22,7 @@
 
 #include "../../include/digiham_amd.h"
 #include "../../digiham_amd/csrc/helper_launches.hpp"
-#include "../../digiham_amd/csrc/launch_plan.hpp"
+#include "../../digiham_amd/csrc/chain_core.hpp"
 
 namespace {
 
@@ -75,41 +78,32 @@ struct HostBackend {
     int launch_rrc_tiles(const DhRrcParams& R, uint32_t nz, bool fast) {
         return dh_plan_rrc_tiles(nz, fast, [&](auto i) { return run_rrc_tiles<decltype(i)>(R); });
     }
-    // One chain instantiation, in the device kernel's order of work: channel by channel, slicer then decoder.
-    // The tail split of the device's chain launches (engine.hip, k_chain), on every route the device splits: DH_TAIL_SPLIT
-    // = percent of a push where the later parts start, in launch_plan.hpp's grammar and bounds.  The policy is this
-    // backend's own -- split whenever the variable is set and the push has two samples, the first part at least one (the
-    // tests are far below the device's thresholds).  Here the parts of a channel simply run one after the other: what
-    // is exercised is the part arithmetic of the kernel bodies (offsets into the rows, appended symbols / frames / events).
-    template <class I> static int run_chain(const DhDspParams& P, const DhDecParams& D) {
-        const uint32_t sps = I::SPS ? (uint32_t) I::SPS : P.sps;
-        std::vector<float> lds(dh_dsp_shared_bytes(sps, I::NZ) / sizeof(float));
-        DhDspShared S = dh_dsp_carve(lds.data(), sps, I::NZ);
-        DhDecShared* DS = new DhDecShared;
+    // One chain instantiation: the grids the device launches, workgroup by workgroup in ASCENDING index order (not dh_launch,
+    // which visits a grid last first: the hand-over of the tail split rests on index-order dispatch), every workgroup the
+    // device's own text (chain_core.hpp), slicer and decoder sharing one block as they share the LDS.  The tail split, on every
+    // route the device splits: DH_TAIL_SPLIT = percent of a push where the later parts start, launch_plan.hpp's grammar and
+    // launch parameters.  The policy is this backend's own -- split whenever the variable is set and the push has two samples
+    // (the tests are far below the device's thresholds).  The split launch, then the fix-up launch: flag words, give-ups
+    // (DH_TAIL_SPLIT_FORCE_FAIL) and the fix-up's resumption are the real protocol, run sequentially.
+    uint32_t part_epoch = 0;
+    template <class I> int run_chain(const DhDspParams& P, const DhDecParams& D) {
+        static_assert(alignof(DhDecShared) <= 16, "operator new aligns the block");
+        std::vector<float> lds((std::max(dh_dsp_shared_bytes(I::SPS ? (uint32_t) I::SPS : P.sps, I::NZ), sizeof(DhDecShared)) + 3) / sizeof(float));     // as go_chain sizes it
+        auto launch = [&](const DhDspParams& Q, uint32_t grid) {
+            for (uint32_t bid = 0; bid < grid; bid++) dh_chain_workgroup<I::NZ, I::FAST, I::PROTO, I::SPS>(Q, D, bid, lds.data());
+        };
         const DhTailSplitEnv env = dh_tail_split_env();
-        uint32_t n0 = 0, n1 = 0;
         if (I::MAY_SPLIT && env.pct && P.n >= 2) {
-            dh_tail_split_points(P.n, env.pct, env.pct2, n0, n1);
-            n0 = std::max<uint32_t>(1u, n0);
-            n1 = env.pct2 ? std::max<uint32_t>(n0, n1) : 0u;
-        }
-        const uint32_t parts = n0 ? (n1 ? 3u : 2u) : 1u;
-        for (uint32_t ch = 0; ch < P.n_channels; ch++)
-            for (uint32_t part = 0; part < parts; part++) {
-                const uint32_t sym_base = part ? P.sym_count[ch] : 0u;
-                // DH_TAIL_SPLIT_FORCE_FAIL = k: the later parts of the channels with ch % k == 1 "fail" their hand-over, and what the
-                // device's fix-up launch does is done here -- the rest of the row in one piece behind the first part
-                const bool fixup = env.force_fail && ch % env.force_fail == 1u && part;
-                const uint32_t hi = parts == 1u || fixup ? 0xFFFFFFFFu : dh_part_hi(part, n0, n1);
-                dh_rrc_demod_channel<I::NZ, I::FAST, I::SPS, I::LV>(P, ch, S, dh_part_lo(part, n0, n1), hi, sym_base);
-                dh_decode_channel(I::PROTO, D, ch, *DS, sym_base, part != 0);
-                if (fixup) break;
-            }
-        delete DS;
+            DhDspParams Q = P;
+            const DhSplitGrids G = dh_plan_split(Q, env.pct, env.pct2, part_epoch, env.force_fail);
+            launch(Q, G.split);
+            Q.split_fixup = 1u;
+            launch(Q, G.fixup);
+        } else launch(P, P.n_channels);
         return 0;
     }
     int launch_chain(const DhDspParams& P, const DhDecParams& D, uint32_t nz, bool fast, int proto) {
-        return dh_plan_chain(P, nz, fast, proto, [&](auto i) { return run_chain<decltype(i)>(P, D); });
+        return dh_plan_chain(P, nz, fast, proto, [&](auto i) { return this->template run_chain<decltype(i)>(P, D); });
     }
 };
 

@@ -3,7 +3,8 @@
 One chained launch and two separate launches give the same bytes, so no output test can tell which route a push took: a
 backend that loses a route still passes them all.  tests/host_cpp/plan_test.cpp asks the plan itself, for every
 configuration an engine can hand to a backend, and compares with a table written out by hand; it also checks the grammar
-of DH_TAIL_SPLIT and the bounds of the parts, which the device backend and the wave emulation take from the same header.
+of DH_TAIL_SPLIT, the parameters of a split launch and the tail split's locator, part bounds and flag word
+(digiham_amd/csrc/chain_core.hpp), which the device backend and the wave emulation take from the same headers.
 """
 import os
 import subprocess

@@ -1,11 +1,11 @@
-"""The tail split of the chain launches (engine.hip: k_chain, HipBackend::go_chain).
+"""The tail split of the chain launches (chain_core.hpp: dh_chain_workgroup; engine.hip: k_chain, HipBackend::go_chain).
 
 A launch of one workgroup per channel drains for about one workgroup's duration; the chain kernels therefore hand the
 last part of every row to a second workgroup of the same launch, which starts from the state the first one wrote back and
 appends its symbols, frames and events.  A part is a push, so nothing may change: these tests compare split launches with
 whole ones and with the oracle -- on the CPU tier through the wave emulation (tests/host_harness/harness.cpp runs the
-parts of a channel one after the other, on every route the device splits -- DMR, YSF, NXDN, D-Star, taken from the same
-launch_plan.hpp: the part arithmetic of the kernel bodies), on the GPU at a size where the
+device's chain workgroup, chain_core.hpp, over the split launch's grid in index order and then over the fix-up launch's, on
+every route the device splits -- DMR, YSF, NXDN, D-Star: the hand-over protocol and the part arithmetic), on the GPU at a size where the
 engine really splits (>= 8192 channels, >= 65536 samples per push), with a channel count that is not a multiple of 8
 (the grid is padded), ragged counts on both sides of the split point and a short push (not split) in between.
 """
@@ -50,7 +50,8 @@ def test_split_pushes_on_the_wave_emulation(emu_ctx, oracle, monkeypatch, proto,
     x = _channels(proto, [31, 32, 33, 34])
     B, n = x.shape
     ref = oracle.chain(x, proto=oproto, **okw)
-    if pct.endswith(":fail"):                   # channels 1 and 3 lose their hand-over: the rest of the row in one piece (the fix-up launch's arithmetic)
+    fail = pct.endswith(":fail")
+    if fail:                                    # channels 1 and 3 lose their hand-over: the second part gives up, a third is told, the fix-up launch finishes the row
         pct = pct[:-5]
         monkeypatch.setenv("DH_TAIL_SPLIT_FORCE_FAIL", "2")
     monkeypatch.setenv("DH_TAIL_SPLIT", str(pct))
@@ -69,6 +70,14 @@ def test_split_pushes_on_the_wave_emulation(emu_ctx, oracle, monkeypatch, proto,
         eng.push(buf, n=int(cnt.max()), counts=cnt)
         pos += cnt
         _collect(eng, B, acc)
+    # the statistics of the hand-over, as on the GPU: a failing channel of a split push gives up once with two parts, twice
+    # with three -- the second time because it was told
+    gave_up, told = int(eng.debug_header(202)[0]), int(eng.debug_header(203)[0])
+    assert (gave_up > 0) == fail, (pct, gave_up)
+    if fail and "," in pct:
+        assert told > 0 and 2 * told == gave_up, (told, gave_up)
+    else:
+        assert told == 0, (pct, told)
     eng.close()
     for b in range(B):
         gs, gf, ge = (np.concatenate(acc[k][b]) for k in range(3))
