@@ -473,6 +473,13 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 //   taps      c = g1 + 2^-11 g2 + delta, g1 = f16(c), g2 = f16((c - g1) 2^11)   (host, once per engine; delta known exactly)
 //   products  M = sum g1 h1  (3 MFMAs of K = 32 per tile of 256 outputs),  R = sum (g2 h1 + g1 h2)  (6 MFMAs),
 //             y = (M + 2^-11 R) / (gain 2^-k)  as  fma(R, k2, M k1);   the g2 h2 products (2^-22) are dropped
+//   ONE CHAIN (dh_f16_one_chain: the wide filter's kernels that do not hand out their floats).  The two scales are a convention,
+//             and the two accumulators, the 2^11 of h2 and the fma they cost buy nothing: there the main sum's tap fragments
+//             hold g1' = 2^11 g1 (exact in f16 for the table: the host checks it), staging stores h2' = f16(x_s - h1) as it
+//             stands (dh_f16_split4_plain: the same |eps| <= 2^-24), and all nine MFMAs of a tile add into ONE accumulator on the
+//             2^11 scale, smallest first:  A = sum g2 h1 (3), + sum g1' h1 (3), + sum g1' h2' (3);  y = A kc,  kc = k1 2^-11 (exact).
+//             One multiplication per output, one accumulator quad per tile.  The price is in the radius: the six MFMAs that
+//             follow the small ones run at the main sum's magnitude, where the two-chain form had three (below).
 // f16 x f16 products are exact in f32; what the hardware does to their sum is not documented, so the bound rests on a
 // stated assumption, checked on the device by tests/test_numerics.py (known-answer probes + 10^6 random dot products):
 //   (H1) inside one MFMA every addend (32 products and C) enters the sum with an alignment error below 2^-24 mu, and each
@@ -481,7 +488,8 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 //        product of their group of eight, groups are added in order with a final round to nearest; worst case over 10^6
 //        random sums 3.5 u (|C| + sum |a b|) -- a tenth of what (H1) allows.)
 // dh_f16_error_coefficient() adds it all up (reference chain gamma_82 + its division; 123 u for the three chained MFMAs of
-// M; the split residuals; the dropped products; the two roundings of the combine) and keeps the 1.44 of head room for the
+// M; the split residuals; the dropped products; the two roundings of the combine -- in the one-chain form 246 u for the six
+// MFMAs at full magnitude and one rounding of the combine) and keeps the 1.44 of head room for the
 // slicer's own roundings that the f32 bound has.  Toeplitz layout as in dh_fir_mfma, natural block order:
 //   A: lane (m = l & 15, q = l >> 4) holds h[16 (16 T + b(m)) + 32 s + 8 q + j], j = 0..7 -- ONE ds_read_b128 from the plain f16
 //      window (32 bytes per row, 16 per q: conflict-free in every lane group of a b128 read); b(m) = DH_F16_ROW_BLOCK(m), a
@@ -502,15 +510,26 @@ inline void dh_fir_mfma(const float* tapsf, const float* xs, int lane, float* ac
 #define DH_F16_ROW_BLOCK(m) (2u * ((uint32_t) (m) & 3u) + (((uint32_t) (m) >> 2) & 1u) + 8u * ((uint32_t) (m) >> 3))
 #define DH_F16_OUT(T, r, g, n) (256u * (uint32_t) (T) + 128u * ((uint32_t) (g) >> 1) + 32u * (uint32_t) (r) + 16u * ((uint32_t) (g) & 1u) + (uint32_t) (n))
 
-// the split of a tap and the per-lane B operands (host, once per engine): frag[f][lane][d], f = 0..2 the g1 slices, 3..5 the g2 slices
+// Which kernels filter in the one-chain form (above): the wide filter's, unless they also deliver their filtered samples
+// (`keepf`: KEEPF of dh_rrc_demod_channel, fused_keep of an engine -- that path promises 2.5e-6 on its floats and keeps the form
+// it was measured with).  An engine launches either the KEEPF slicer or the others, so the host builds the fragments and
+// the coefficient ONCE, by the predicate the kernel is compiled with.
+constexpr bool dh_f16_one_chain(uint32_t nz, int keepf) { return nz == 80 && !keepf; }
+
+// the split of a tap and the per-lane B operands (host, once per engine): frag[f][lane][d], f = 0..2 the g1 slices (one chain:
+// of g1' = 2^11 g1), 3..5 the g2 slices
 struct DhF16Taps {
     uint32_t frag[2 * DH_F16_MAX_KSTEPS][DH_WAVE][4];        // the first 2 * DH_F16_KSTEPS_OF(nz) are used
     uint32_t ksteps;
-    double l1, l1_g1, l1_g2, sum_delta;
+    bool one_chain;
+    double l1, l1_g1, l1_g2, sum_delta;                      // (l1_g1: of g1 itself in either form)
 };
-inline void dh_f16_tap_fragments(const float* taps_half, uint32_t nz, DhF16Taps& F) {
+// false: a one-chain table whose 2^11 g1 is not a finite half equal to it (neither built-in table; nothing is usable then)
+inline bool dh_f16_tap_fragments(const float* taps_half, uint32_t nz, bool one_chain, DhF16Taps& F) {
     uint16_t g1[DH_MAX_NZ + 1], g2[DH_MAX_NZ + 1];
     F.l1 = F.l1_g1 = F.l1_g2 = F.sum_delta = 0.0;
+    F.one_chain = one_chain;
+    bool ok = true;
     for (uint32_t i = 0; i <= nz; i++) {
         const float c = taps_half[i <= nz / 2 ? i : nz - i];
         g1[i] = dh_f16_bits(c);
@@ -520,6 +539,12 @@ inline void dh_f16_tap_fragments(const float* taps_half, uint32_t nz, DhF16Taps&
         const double delta = r - v2 / 2048.0;
         F.l1 += c < 0 ? -(double) c : (double) c; F.l1_g1 += __builtin_fabs((double) dh_f16_value(g1[i]));
         F.l1_g2 += __builtin_fabs(v2); F.sum_delta += __builtin_fabs(delta);
+        if (one_chain) {                                                               // g1 becomes g1' = 2^11 g1
+            const float v1 = dh_f16_value(g1[i]);
+            g1[i] = dh_f16_bits(v1 * 2048.0f);
+            const float s1 = dh_f16_value(g1[i]);
+            if (!(s1 == v1 * 2048.0f) || (g1[i] & 0x7C00u) == 0x7C00u) ok = false;     // exact and finite (the product itself is exact in f32)
+        }
     }
     const int KS = (int) DH_F16_KSTEPS_OF(nz);
     F.ksteps = (uint32_t) KS;
@@ -533,6 +558,7 @@ inline void dh_f16_tap_fragments(const float* taps_half, uint32_t nz, DhF16Taps&
         }
         F.frag[f][lane][d] = w;
     }
+    return ok;
 }
 // error radius of a filtered sample per unit of max |x| for this path (see above; everything in units of u / gain):
 //   reference: (taps + 1) (gamma, + second order) L1 + 1.0001 L1 (its division and rounding): 82 for the wide filter
@@ -542,11 +568,23 @@ inline void dh_f16_tap_fragments(const float* taps_half, uint32_t nz, DhF16Taps&
 //              2 (2^-22 L1(g2) / 2 + sum |delta| (1 + 2^-12) + u L1) / u
 //   combine:   3.1 L1 (fl32(1 / gain), the multiply, the fma)
 // times 1.44 for the slicer's own roundings, as in dh_fir_error_coefficient.
+// One chain (everything divided by the 2^11 the accumulator carries; mu of (H1) is what the accumulator can hold BY THEN):
+//   MFMAs 1..KS, g2 h1:        mu = L1(g2) (1 + 2^-11)                                    -> 2^-11 41 KS L1(g2) (1 + 2^-11)
+//   MFMAs KS+1..2KS, g1' h1:   mu = (2^11 L1(g1) + L1(g2)) (1 + 2^-11)                    -> 41 KS (L1(g1) + 2^-11 L1(g2)) (1 + 2^-11)
+//   MFMAs 2KS+1..3KS, g1' h2': the same + 2^11 L1(g1) 2^-12, per unit of max |x_s| >= 1/2 at most 2^-11 of the main sum more
+//                                                                                         -> the same + 2^-11 41 KS L1(g1)
+//   together  82 KS L1(g1) (1 + 2^-11)  [246 for the wide filter, where the two chains had 123]
+//           + 2^-11 41 KS (3 L1(g2) (1 + 2^-11) + L1(g1))
+//   residuals: as above (h2' is within 2^-24 of x_s - h1 like 2^-11 h2; the dropped g2 h2' products are the same numbers)
+//   combine:   2.1 L1 (fl32(1 / gain) and ONE multiplication; kc = k1 2^-11 is exact)
+// Any other order -- the main sums between the small ones -- puts up to eight MFMAs at full magnitude.
 inline float dh_f16_error_coefficient(const DhF16Taps& F, uint32_t nz, double gain) {
     const double u = 5.9604644775390625e-08;
     const double ks = (double) F.ksteps, nref = 2.0 + (double) nz;                     // gamma_(taps + 1) for the reference's chain
-    const double kl1 = (nref + 0.01) * F.l1 + 1.0001 * F.l1 + 41.0 * ks * F.l1_g1 * (1.0 + 1.0 / 2048.0) + 82.0 * ks / 2048.0 * (F.l1_g2 + 0.5 * F.l1_g1)
-                     + 2.0 * (0.5 * F.l1_g2 / 4194304.0 + F.sum_delta * (1.0 + 1.0 / 4096.0) + u * F.l1) / u + 3.1 * F.l1;
+    const double mfma = F.one_chain ? 82.0 * ks * F.l1_g1 * (1.0 + 1.0 / 2048.0) + 41.0 * ks / 2048.0 * (3.0 * F.l1_g2 * (1.0 + 1.0 / 2048.0) + F.l1_g1)
+                                    : 41.0 * ks * F.l1_g1 * (1.0 + 1.0 / 2048.0) + 82.0 * ks / 2048.0 * (F.l1_g2 + 0.5 * F.l1_g1);
+    const double kl1 = (nref + 0.01) * F.l1 + 1.0001 * F.l1 + mfma
+                     + 2.0 * (0.5 * F.l1_g2 / 4194304.0 + F.sum_delta * (1.0 + 1.0 / 4096.0) + u * F.l1) / u + (F.one_chain ? 2.1 : 3.1) * F.l1;
     const double coef = 1.44 * kl1 * u / (gain < 0 ? -gain : gain) * 1.0001;
     float f = (float) coef;
     if ((double) f < coef) { union { float f; uint32_t u; } b; b.f = f; b.u++; f = b.f; }
@@ -556,8 +594,8 @@ inline float dh_f16_error_coefficient(const DhF16Taps& F, uint32_t nz, double ga
 #if DH_ON_GPU
 // acc16[4 T + r] of lane (n, g) = y-before-gain of output DH_F16_OUT(T, r, g, n) in the scaled domain: main + 2^-11 second sum
 // is formed by the caller's fma (k1, k2).  `hw` = the window block (h1 at byte 0, h2 at DH_F16_H2_OFFSET words), G = the six
-// tap fragments of this lane.
-template <int NZ>
+// tap fragments of this lane.  ONE: the one-chain form -- G[0..2] hold g1', the h2 array holds h2', k1 is kc and k2 is not used.
+template <int NZ, bool ONE>
 __device__ __forceinline__ void dh_fir_f16(const float* hw, const dh_u4 (&G)[2 * DH_F16_KSTEPS_OF(NZ)], int lane, float k1, float k2, float* out16) {
     constexpr int DH_F16_KSTEPS = DH_F16_KSTEPS_OF(NZ), DH_F16_FRAGS = 2 * DH_F16_KSTEPS, DH_F16_H2_OFFSET = DH_F16_H2_OFFSET_OF(NZ);
     const int m = lane & 15, q = lane >> 4;
@@ -575,35 +613,68 @@ __device__ __forceinline__ void dh_fir_f16(const float* hw, const dh_u4 (&G)[2 *
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int s = 0; s < DH_F16_KSTEPS; s++) a1[t][s] = *reinterpret_cast<const dh_h8*>(base + 512 * (TT + t) + 64 * s);
-        dh_f32x4 mn[2] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } }, sc[2] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+        if constexpr (ONE) {
+            // one accumulator per tile, two tiles alternating; the order is the one the radius was derived for (dh_f16_error_coefficient):
+            // the small sum first, then the two at the main sum's magnitude
+            dh_f32x4 acc[2] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
 #pragma unroll
-        for (int s = 0; s < DH_F16_KSTEPS; s++) {
+            for (int s = 0; s < DH_F16_KSTEPS; s++)
 #pragma unroll
-            for (int t = 0; t < 2; t++) sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[DH_F16_KSTEPS + s], sc[t], 0, 0, 0);
+                for (int t = 0; t < 2; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[DH_F16_KSTEPS + s], acc[t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < 2; t++) mn[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[s], mn[t], 0, 0, 0);
+            for (int s = 0; s < DH_F16_KSTEPS; s++) {
 #pragma unroll
-            for (int t = 0; t < 2; t++) a2[t][s] = *reinterpret_cast<const dh_h8*>(base + 512 * (TT + t) + 64 * s + 4 * DH_F16_H2_OFFSET);
+                for (int t = 0; t < 2; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[s], acc[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 2; t++) a2[t][s] = *reinterpret_cast<const dh_h8*>(base + 512 * (TT + t) + 64 * s + 4 * DH_F16_H2_OFFSET);
+            }
+#pragma unroll
+            for (int s = 0; s < DH_F16_KSTEPS; s++)
+#pragma unroll
+                for (int t = 0; t < 2; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[t][s], g[s], acc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) out16[4 * (TT + t) + r] = acc[t][r] * k1;
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * DH_F16_KSTEPS, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2 * DH_F16_KSTEPS, 0);
+#pragma unroll
+            for (int s = 0; s < DH_F16_KSTEPS; s++) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
+            __builtin_amdgcn_sched_group_barrier(0x008, 2 * DH_F16_KSTEPS, 0);
+            (void) k2;
+        } else {
+            dh_f32x4 mn[2] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } }, sc[2] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+#pragma unroll
+            for (int s = 0; s < DH_F16_KSTEPS; s++) {
+#pragma unroll
+                for (int t = 0; t < 2; t++) sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[DH_F16_KSTEPS + s], sc[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 2; t++) mn[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[t][s], g[s], mn[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 2; t++) a2[t][s] = *reinterpret_cast<const dh_h8*>(base + 512 * (TT + t) + 64 * s + 4 * DH_F16_H2_OFFSET);
+            }
+#pragma unroll
+            for (int s = 0; s < DH_F16_KSTEPS; s++)
+#pragma unroll
+                for (int t = 0; t < 2; t++) sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[t][s], g[s], sc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) out16[4 * (TT + t) + r] = __builtin_fmaf(sc[t][r], k2, mn[t][r] * k1);
+            // scheduling groups (DS read = 0x100, MFMA = 0x008): the order written above
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * DH_F16_KSTEPS, 0);
+#pragma unroll
+            for (int s = 0; s < DH_F16_KSTEPS; s++) { __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
+            __builtin_amdgcn_sched_group_barrier(0x008, 2 * DH_F16_KSTEPS, 0);
         }
-#pragma unroll
-        for (int s = 0; s < DH_F16_KSTEPS; s++)
-#pragma unroll
-            for (int t = 0; t < 2; t++) sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[t][s], g[s], sc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) out16[4 * (TT + t) + r] = __builtin_fmaf(sc[t][r], k2, mn[t][r] * k1);
-        // scheduling groups (DS read = 0x100, MFMA = 0x008): the order written above
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * DH_F16_KSTEPS, 0);
-#pragma unroll
-        for (int s = 0; s < DH_F16_KSTEPS; s++) { __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * DH_F16_KSTEPS, 0);
     }
 }
 #else
 // harness: the same split and the same sums as plain f32 chains (products of halves are exact in f32; a sequential chain of
 // 96 rounded additions stays inside what (H1) allows the hardware, so the decisions downstream are the same)
-template <int NZ>
+// (ONE: one chain in the device's order -- the taps' second halves, the main sum, the samples' second halves; 288 rounded additions
+// at the magnitudes the nine MFMAs see are inside the 369 u (H1) allows those)
+template <int NZ, bool ONE>
 inline void dh_fir_f16(const float* hw, const uint32_t (*G)[DH_WAVE][4], int lane, float k1, float k2, float* out16) {
     constexpr int DH_F16_KSTEPS = DH_F16_KSTEPS_OF(NZ), DH_F16_H2_OFFSET = DH_F16_H2_OFFSET_OF(NZ);
     const uint16_t* h1 = reinterpret_cast<const uint16_t*>(hw);
@@ -612,15 +683,17 @@ inline void dh_fir_f16(const float* hw, const uint32_t (*G)[DH_WAVE][4], int lan
     for (int T = 0; T < 4; T++) for (int r = 0; r < 4; r++) {
         const uint32_t o = DH_F16_OUT(T, r, g, n), b16 = o - (uint32_t) n;
         float mn = 0.0f, sc = 0.0f;
-        for (int pass = 0; pass < 3; pass++)                       // main; taps' second halves; samples' second halves (the device's order)
+        for (int i = 0; i < 3; i++) {                              // two chains: main (0); taps' second halves (1); samples' second halves (2).  ONE: 1, 0, 2 -- the device's order either way
+            const int pass = ONE ? (i == 0 ? 1 : i == 1 ? 0 : 2) : i;
             for (int s = 0; s < DH_F16_KSTEPS; s++) for (int qq = 0; qq < 4; qq++) for (int j = 0; j < 8; j++) {
                 const int kk = 8 * qq + j;                         // B fragment of lane (n, qq): element j
                 const uint32_t w = G[(pass == 1 ? DH_F16_KSTEPS : 0) + s][16 * qq + n][j >> 1];
                 const float tap = dh_f16_value((uint16_t) (w >> (16 * (j & 1))));
                 const uint16_t hv = (pass == 2 ? h2 : h1)[b16 + 32u * (uint32_t) s + (uint32_t) kk];
-                if (pass == 0) mn = __builtin_fmaf(dh_f16_value(hv), tap, mn); else sc = __builtin_fmaf(dh_f16_value(hv), tap, sc);
+                if (pass == 0 && !ONE) mn = __builtin_fmaf(dh_f16_value(hv), tap, mn); else sc = __builtin_fmaf(dh_f16_value(hv), tap, sc);
             }
-        out16[4 * T + r] = __builtin_fmaf(sc, k2, mn * k1);
+        }
+        out16[4 * T + r] = ONE ? sc * k1 : __builtin_fmaf(sc, k2, mn * k1);
     }
 }
 #endif
@@ -1640,8 +1713,13 @@ template <int NZ> struct DhWindowGroups {
         } } while (0)
 // split-f16 FIR: the window held in `varr` (five 16-byte groups per lane, as loaded) -> zeros beyond `have`, max |x| of the
 // wavefront, the power-of-two scale that puts it into [0.5, 1), the two arrays of halves in the window block.  Returns
-// false (nothing stored) when max |x| is outside the range the bound covers.
-template <int NZ>
+// false (nothing stored) when max |x| is outside the range the bound covers -- or NaN: the maximum is taken so that ONE NaN sample
+// makes it NaN (dh_max_abs_groups, DH_WAVE_MAX_NAN), and a NaN fails every comparison below.  An infinite sample is above the
+// range.  So what reaches the FIR is finite and at most 1e15, and with L1(taps) / gain about 1.45 nothing in it can overflow:
+// there is no look at its outputs afterwards.
+// ONE (dh_f16_one_chain): the second halves on the scale of the first (dh_f16_split4_plain), k1_out is the one factor kc of
+// y = A kc, and k2_out is not used.
+template <int NZ, bool ONE>
 DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f4, (&varr), DH_PF_N), uint32_t have, float& e_out, float& k1_out, float& k2_out) {
     constexpr uint32_t LAST_LANES = DhWindowGroups<NZ>::LAST_LANES, STORE_LANES = DhWindowGroups<NZ>::STORE_LANES;
     DH_LANE_ARRAY(float, xm, 1);
@@ -1654,20 +1732,20 @@ DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f
                 DH_LA(varr, lane)[r] = dh_zero_beyond(DH_LA(varr, lane)[r], e, have);
             }
         }
-        const float mx = dh_max_abs_groups(DH_LA(varr, lane));      // (a NaN is skipped here and caught behind the FIR)
+        const float mx = dh_max_abs_groups(DH_LA(varr, lane));
         DH_LA(xm, lane)[0] = mx;
     }
-    const float xmax = DH_WAVE_MAX(xm);
+    const float xmax = DH_WAVE_MAX_NAN(xm);
     float scale = 1.0f;
     if (xmax == 0.0f) { e_out = 0.0f; k1_out = P.inv_gain; }                       // all zeros in, all zeros out
     else if (xmax >= DH_BOUND_XMAX_LO && xmax <= DH_BOUND_XMAX_HI) {
         union { float f; uint32_t u; } b; b.f = xmax;
         const uint32_t ex = b.u >> 23;                                              // xmax in [2^(ex - 127), 2^(ex - 126))
         b.u = (253u - ex) << 23; scale = b.f;                                       // 2^(126 - ex)
-        b.u = (ex + 1u) << 23; k1_out = P.inv_gain * b.f;                           // fl32(1 / gain) 2^(ex - 126): exact scaling
+        b.u = (ex + 1u - (ONE ? 11u : 0u)) << 23; k1_out = P.inv_gain * b.f;        // fl32(1 / gain) 2^(ex - 126) (one chain: 2^-11 of it): exact scaling (ex >= 43)
         e_out = P.err_coef_f16 * xmax;
-    } else return false;                                                            // tiny, huge or infinite samples: outside the bound's assumptions
-    k2_out = k1_out * 0.00048828125f;                                               // 2^-11
+    } else return false;                                                            // tiny, huge, infinite or NaN samples: outside the bound's assumptions
+    k2_out = ONE ? 0.0f : k1_out * 0.00048828125f;                                  // 2^-11
     // (the arrays are as long as the last block's K range reaches: the halves behind the window, under zero taps, must be
     // finite -- the lanes of the last group beyond the window store zeros there)
     DH_FOR_LANES_FRESH(lane) {
@@ -1678,7 +1756,7 @@ DH_HD bool dh_stage_f16(const DhDspParams& P, DhDspShared& S, DH_LANE_ARRAY(dh_f
 #pragma unroll
         for (int r = 0; r < DH_PF_N; r++) {
             dh_h4 a, b;
-            dh_f16_split4(DH_LA(varr, lane)[r], scale, a, b);
+            if constexpr (ONE) dh_f16_split4_plain(DH_LA(varr, lane)[r], scale, a, b); else dh_f16_split4(DH_LA(varr, lane)[r], scale, a, b);
             if (r < DH_PF_N - 1 || in_store) { dh_h4_store(d1 + DH_WAVE * r, a); dh_h4_store(d2 + DH_WAVE * r, b); }
         }
     }
@@ -1739,6 +1817,8 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
     static_assert(SPS == 0 || SPS == 10 || SPS == 20 || SPS == 40, "0 = run-time samples per symbol; 10 has its own window and timing code, 20 / 40 are the generic code with the constant folded in");
     constexpr bool BOUNDED = DhIsBounded<NZ, FAST, SPS>::value;                      // see "Error-bounded FIR" above
     constexpr bool MF16 = BOUNDED && (NZ == 80 || NZ == 160) && KEEPF != 2;           // its fused FIR as a split-f16 product on the matrix cores
+    constexpr bool ONE_CHAIN = dh_f16_one_chain(NZ, KEEPF);                           // ... in the one-chain form (the host built the fragments by the same predicate)
+    constexpr bool F16_KEEPS_VOTE = MF16 && NZ == 160;                                // ... still followed by the vote on its outputs: the narrow filter's kernels, for their register allocation's sake (P2)
     DhBoundState* const BS = DH_BOUND_STATE(S);
     float* st = P.state + (size_t) ch * P.state_stride;
     uint32_t* sth = (uint32_t*) st;
@@ -1946,7 +2026,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                             DH_LA(v, lane)[r] = dh_zero_beyond(DH_LA(v, lane)[r], e, have);
                         }
                     }
-                    if (BOUNDED) {                     // max |x| of the window (a NaN is skipped here and caught behind the FIR)
+                    if (BOUNDED) {                     // max |x| of the window (NaN when a sample is NaN)
                         float mx = 0.0f;
 #pragma unroll
                         for (int r = 0; r < DH_PF_N; r++) {
@@ -1960,7 +2040,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
             if (MF16 && !use_exact) {
                 // split-f16 FIR: the window goes to LDS as two arrays of halves (dh_stage_f16)
                 xmax_done = true;
-                if (dh_stage_f16<NZ>(P, S, v, have, e_run, k1, k2)) f16_staged = true; else use_exact = true;
+                if (dh_stage_f16<NZ, ONE_CHAIN>(P, S, v, have, e_run, k1, k2)) f16_staged = true; else use_exact = true;
             }
             if (!f16_staged) {
                 DH_FOR_LANES_FRESH(lane) {
@@ -1994,7 +2074,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 }
             }
             xmax_done = true;
-            if (dh_stage_f16<NZ>(P, S, v, have, e_run, k1, k2)) f16_staged = true;
+            if (dh_stage_f16<NZ, ONE_CHAIN>(P, S, v, have, e_run, k1, k2)) f16_staged = true;
             else {
                 use_exact = true;
                 dh_gather_window<NZ>(S, tail, tc, in, nv, p);
@@ -2020,10 +2100,10 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         }
         DH_BARRIER();
         if (BOUNDED && !use_exact && !xmax_done) {
-            const float xmax = DH_WAVE_MAX(xmax_lane);
+            const float xmax = DH_WAVE_MAX_NAN(xmax_lane);
             if (xmax == 0.0f) e_run = 0.0f;             // all zeros in, all zeros out of either FIR
             else if (xmax >= DH_BOUND_XMAX_LO && xmax <= DH_BOUND_XMAX_HI) e_run = P.err_coef * xmax;
-            else use_exact = true;                      // tiny, huge or infinite samples: outside the bound's assumptions
+            else use_exact = true;                      // tiny, huge, infinite or NaN samples: outside the bound's assumptions
         }
         DH_PHASE_MARK(0);
 
@@ -2044,12 +2124,18 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                 if (DH_LIKELY(!use_exact)) {
                     if constexpr (MF16) {
                         // (f16_staged holds: every staging path that does not fill the two arrays of halves sets use_exact)
+                        // Nothing looks at the outputs: staging has seen max |x| of exactly these samples, NaN included, and lets only
+                        // finite windows of at most 1e15 through (dh_stage_f16), which cannot overflow in here.
+                        // (The narrow filter's kernels keep the vote behind the FIR they had -- sixteen v_fma and a ballot: without it
+                        // the NXDN chain kernel came out with a scratch load on the run loop's hot path, tools/asm_census.py.)
                         DH_FOR_LANES_FRESH(lane) {
-                            float t = 0.0f;
-                            dh_fir_f16<MF16 ? NZ : 80>(S.xf, tapfrag_regs, lane, k1, k2, DH_LA(fo, lane));
+                            dh_fir_f16<MF16 ? NZ : 80, ONE_CHAIN>(S.xf, tapfrag_regs, lane, k1, k2, DH_LA(fo, lane));
+                            if constexpr (F16_KEEPS_VOTE) {
+                                float t = 0.0f;
 #pragma unroll
-                            for (int j = 0; j < DH_FIR_L; j++) t = __builtin_fmaf(DH_LA(fo, lane)[j], 0.0f, t);       // NaN or infinity anywhere: 0 * y is NaN
-                            DH_BALLOT_ACC(vote_bad, !(t == 0.0f), lane);
+                                for (int j = 0; j < DH_FIR_L; j++) t = __builtin_fmaf(DH_LA(fo, lane)[j], 0.0f, t);       // NaN or infinity anywhere: 0 * y is NaN
+                                DH_BALLOT_ACC(vote_bad, !(t == 0.0f), lane);
+                            }
                         }
                         mf_layout = 2;
                     } else if constexpr (MFMA) {
@@ -2063,7 +2149,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
                         mf_layout = 1;
                     } else static_assert(!BOUNDED, "every error-bounded kernel filters on the matrix cores (launch_plan.hpp instantiates none without MF16 or MFMA)");
                 }
-                if (DH_UNLIKELY(use_exact || vote_bad)) {            // a NaN / infinity among the samples: the reference's arithmetic decides
+                if (DH_UNLIKELY(use_exact || vote_bad)) {            // samples outside the bound's range, a NaN / infinity among them: the reference's arithmetic decides
                     use_exact = true; e_run = 0.0f; BS->n_exact_runs++; mf_layout = 0;
                     if (MF16 && f16_staged) {           // the window block holds halves: the reference's FIR wants the raw samples back
                         DH_BARRIER();
@@ -2203,7 +2289,7 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         }
         staged_p = 0xFFFFFFFFu;
         if (DH_LIKELY(pf_reg)) {
-            if constexpr (PF_REG && MF16) { if (DH_LIKELY(dh_stage_f16<NZ>(P, S, pfr, pf_have, st_e_run, st_k1, st_k2))) staged_p = p_next; }
+            if constexpr (PF_REG && MF16) { if (DH_LIKELY((dh_stage_f16<NZ, ONE_CHAIN>(P, S, pfr, pf_have, st_e_run, st_k1, st_k2)))) staged_p = p_next; }
             else if constexpr (PF_PLAIN) {
                 // no RRC stage: the window is the 1 024 samples themselves (four groups of four per lane, unpadded), zeros beyond the stream's end
                 static_assert(!PF_PLAIN || (DH_FTILE == 4u * DH_WAVE * (DH_PF_N - 1)), "four full groups cover the window");

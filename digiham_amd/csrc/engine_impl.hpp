@@ -223,7 +223,8 @@ struct Engine {
         if (tapfrag) {
             DhF16Taps* F = new (std::nothrow) DhF16Taps;
             if (!F) return DH_ENOMEM;
-            dh_f16_tap_fragments(dsp.taps, L.nz, *F);
+            // (one form per engine: it launches either the slicer that keeps its floats or the others, dh_f16_one_chain)
+            if (!dh_f16_tap_fragments(dsp.taps, L.nz, dh_f16_one_chain(L.nz, L.fused_keep), *F)) { delete F; return DH_EINVAL; }
             dsp.err_coef_f16 = dh_f16_error_coefficient(*F, L.nz, dsp.gain);
             rc = be.upload(tapfrag, F->frag, sizeof(F->frag)) || be.sync();       // (the first 2 KS fragments are the ones a kernel reads)
             delete F;

@@ -131,37 +131,42 @@ DH_HD float dh_sqrt_upper(float x) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Minima and maxima that SKIP a NaN operand (the result is the other operand; NaN only when every operand is NaN).
+// Minima and maxima that SKIP a NaN operand (the result is the other operand; NaN only when every operand is NaN) -- and
+// the one that does not: dh_max3_abs, whose callers take max |x| of a window and want to SEE a NaN sample.
 //   dh_fmin_ / dh_fmax_(a, b)   `if (b < a) a = b`, the reference's own statement: a NaN b is skipped, a NaN a stays
 //   dh_vmin / dh_vmax(a, b)     v_min_f32 / v_max_f32: the operand that is not NaN -- for a NaN ENTRY b exactly what
 //                               `if (v < min) min = v` does -- at one VALU instruction where compare + select cost two
 //   dh_min3_abs(a, b, c)        min(|a|, |b|, |c|) in one instruction (v_min3_f32).  Callers that must notice a NaN
 //                               distance make sure ALL THREE are NaN then (they are: every distance of a symbol hangs
 //                               on the same average and extremes) -- see P5
-//   dh_max3_abs(a, b, c)        max(|a|, |b|, c) in one instruction (v_max3_f32)
+//   dh_max3_abs(a, b, c)        max(|a|, |b|, c), c >= 0 or NaN, in one instruction; NaN when ANY operand is NaN (v_maximum3_f32,
+//                               the gfx950 form that propagates a NaN where v_max3_f32 drops it)
 DH_HD float dh_fmin_(float a, float b) { return b < a ? b : a; }
 DH_HD float dh_fmax_(float a, float b) { return b > a ? b : a; }
 #if DH_ON_GPU
 __device__ __forceinline__ float dh_vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float dh_vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float dh_min3_abs(float a, float b, float c) { float r; asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float dh_max3_abs(float a, float b, float c) { float r; asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ float dh_max3_abs(float a, float b, float c) { float r; asm("v_maximum3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 #else
 inline float dh_vmin(float a, float b) { return __builtin_fminf(a, b); }
 inline float dh_vmax(float a, float b) { return __builtin_fmaxf(a, b); }
 inline float dh_min3_abs(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b)), __builtin_fabsf(c)); }
-inline float dh_max3_abs(float a, float b, float c) { return __builtin_fmaxf(c, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b))); }
+inline float dh_max3_abs(float a, float b, float c) {
+    if (a != a || b != b || c != c) return __builtin_nanf("");
+    return __builtin_fmaxf(c, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b)));
+}
 #endif
-// max |x| over a lane's N groups of four, 0 for none; a NaN is skipped.  Device: 2 N v_max3_f32 in ONE statement (as
-// separate statements the compiler put an s_nop behind each)
+// max |x| over a lane's N groups of four, 0 for none; NaN when one of them is NaN (dh_max3_abs).  Device: 2 N v_maximum3_f32 in
+// ONE statement (as separate statements the compiler put an s_nop behind each)
 template <int N> DH_HD float dh_max_abs_groups(const dh_f4 (&w)[N]) {
 #if DH_ON_GPU
     static_assert(N == 5, "five groups of four");
     float mx;
     const dh_f4 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-    asm("v_max3_f32 %0, |%1|, |%2|, 0\n\tv_max3_f32 %0, |%3|, |%4|, %0\n\tv_max3_f32 %0, |%5|, |%6|, %0\n\tv_max3_f32 %0, |%7|, |%8|, %0\n\t"
-        "v_max3_f32 %0, |%9|, |%10|, %0\n\tv_max3_f32 %0, |%11|, |%12|, %0\n\tv_max3_f32 %0, |%13|, |%14|, %0\n\tv_max3_f32 %0, |%15|, |%16|, %0\n\t"
-        "v_max3_f32 %0, |%17|, |%18|, %0\n\tv_max3_f32 %0, |%19|, |%20|, %0"
+    asm("v_maximum3_f32 %0, |%1|, |%2|, 0\n\tv_maximum3_f32 %0, |%3|, |%4|, %0\n\tv_maximum3_f32 %0, |%5|, |%6|, %0\n\tv_maximum3_f32 %0, |%7|, |%8|, %0\n\t"
+        "v_maximum3_f32 %0, |%9|, |%10|, %0\n\tv_maximum3_f32 %0, |%11|, |%12|, %0\n\tv_maximum3_f32 %0, |%13|, |%14|, %0\n\tv_maximum3_f32 %0, |%15|, |%16|, %0\n\t"
+        "v_maximum3_f32 %0, |%17|, |%18|, %0\n\tv_maximum3_f32 %0, |%19|, |%20|, %0"
         : "=&v"(mx) : "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w),
                       "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w));
     return mx;
@@ -217,6 +222,35 @@ DH_HD void dh_f16_split4(const dh_f4& v, float scale, dh_h4& h1, dh_h4& h2) {
         h2[i] = dh_f16_bits(r * 2048.0f);
 #endif
     }
+}
+// The same split with the second half left on the first one's scale: h2 = f16(x_s - h1).  For |x_s| <= 1 the residual is at most
+// 2^-12 in magnitude, where a half's spacing is 2^-24 (subnormals, and normals below 2^-13) or 2^-23: h2 is within 2^-24 of it, the
+// same x_s = h1 + h2 + eps, |eps| <= 2^-24, as above -- without the multiplication.  The FIR that reads these halves carries the
+// 2^11 in its taps instead (dsp_core.hpp: the one-chain form of dh_fir_f16).
+// Device: the difference as two v_pk_add_f32 with the second operand negated, written out -- left to the compiler, the
+// subtraction and the conversion behind it became one v_fma_mixlo_f16 per sample (8 cycles a wavefront against 4) with scalar
+// multiplications and subtractions around it, nine instructions per window MORE than the scaled split: four samples are two packed
+// multiplications, two packed conversions, four conversions back, two packed additions and two packed conversions.
+DH_HD void dh_f16_split4_plain(const dh_f4& v, float scale, dh_h4& h1, dh_h4& h2) {
+#if DH_ON_GPU
+    dh_v4f xs; xs.x = v.x; xs.y = v.y; xs.z = v.z; xs.w = v.w;
+    xs = xs * scale;                                              // exact (power of two)
+    const dh_h4 a = __builtin_convertvector(xs, dh_h4);           // v_cvt_pk_f16_f32: round to nearest even
+    const dh_v4f af = __builtin_convertvector(a, dh_v4f);
+    const dh_f2 x01 = xs.xy, x23 = xs.zw, a01 = af.xy, a23 = af.zw;
+    dh_f2 r01, r23;                                               // xs - a: exact
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r01) : "v"(x01), "v"(a01));
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r23) : "v"(x23), "v"(a23));
+    dh_v4f r; r.xy = r01; r.zw = r23;
+    h1 = a; h2 = __builtin_convertvector(r, dh_h4);
+#else
+    const float x[4] = { v.x, v.y, v.z, v.w };
+    for (int i = 0; i < 4; i++) {
+        const float xs = x[i] * scale;                            // exact (power of two)
+        h1[i] = dh_f16_bits(xs);
+        h2[i] = dh_f16_bits(xs - dh_f16_value(h1[i]));
+    }
+#endif
 }
 // *dst = v for four halves: one 8-byte store (the CPU build's dh_h4 is an array of four bit patterns, which has no assignment)
 DH_HD void dh_h4_store(dh_h4* dst, const dh_h4& v) { __builtin_memcpy(dst, &v, sizeof(dh_h4)); }
@@ -388,8 +422,8 @@ __device__ __forceinline__ void dh_wave_prev4(float& a, float& b, float& c, floa
 }
 
 // maximum over the wavefront of a per-lane value, wave-uniform (row_shr 1/2/4/8 inside each row of 16, row_bcast:15 / :31
-// across rows -- the running maximum ends up in lane 63; v_max_f32 skips a NaN operand, which is what the callers want:
-// NaN samples are caught behind the FIR)
+// across rows -- the running maximum ends up in lane 63; v_max_f32 skips a NaN operand.  max |x| of a window, which must
+// not lose a NaN, goes through dh_wave_max_nan below)
 __device__ __forceinline__ float dh_wave_max(float v) {
 #define DH_MAX_STEP(ctrl) "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 " ctrl "\n\t"
     asm volatile("s_nop 4\n\t"
@@ -399,6 +433,20 @@ __device__ __forceinline__ float dh_wave_max(float v) {
                  "s_nop 1" : "+v"(v));
 #undef DH_MAX_STEP
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// The same reduction for a maximum that must not lose a NaN (max |x| of a window: dh_max3_abs hands a NaN on, this does too):
+// on the BIT PATTERNS, v_max_u32.  The values are magnitudes -- sign bit clear -- so unsigned order is float order, with every
+// NaN above infinity; a NaN in any lane is the result.
+__device__ __forceinline__ float dh_wave_max_nan(float f) {
+    uint32_t v = __float_as_uint(f);
+#define DH_MAX_STEP(ctrl) "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 " ctrl "\n\t"
+    asm volatile("s_nop 4\n\t"
+                 DH_MAX_STEP("row_shr:1 row_mask:0xf bank_mask:0xf") DH_MAX_STEP("row_shr:2 row_mask:0xf bank_mask:0xf")
+                 DH_MAX_STEP("row_shr:4 row_mask:0xf bank_mask:0xf") DH_MAX_STEP("row_shr:8 row_mask:0xf bank_mask:0xf")
+                 DH_MAX_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf") DH_MAX_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                 "s_nop 1" : "+v"(v));
+#undef DH_MAX_STEP
+    return __int_as_float(__builtin_amdgcn_readlane((int) v, 63));
 }
 // minimum of lanes 0..15 (one DPP row), valid in lane 15 and returned wave-uniform: four v_min_f32 with row_shr
 __device__ __forceinline__ float dh_row_min_to_lane15(float v) {
@@ -415,22 +463,31 @@ inline float dh_wave_max_lanes(const float (&a)[DH_WAVE][1]) {
     for (int l = 0; l < DH_WAVE; l++) m = __builtin_fmaxf(m, a[l][0]);
     return m;
 }
+inline float dh_wave_max_nan_lanes(const float (&a)[DH_WAVE][1]) {
+    uint32_t m = 0;
+    for (int l = 0; l < DH_WAVE; l++) { union { float f; uint32_t u; } b; b.f = a[l][0]; if (b.u > m) m = b.u; }
+    union { float f; uint32_t u; } r; r.u = m;
+    return r.f;
+}
 inline float dh_wave_min_lanes(const float (&a)[DH_WAVE][1], int lanes) {
     float m = DH_FLT_MAX;
     for (int l = 0; l < lanes; l++) m = dh_fmin_(m, a[l][0]);
     return m;
 }
 #endif
-// Reductions of a DH_LANE_ARRAY(float, a, 1), wave-uniform results, NaN lanes skipped:
+// Reductions of a DH_LANE_ARRAY(float, a, 1), wave-uniform results; NaN lanes are skipped, except by DH_WAVE_MAX_NAN:
 //   DH_WAVE_MAX(a)   the largest value of the 64 lanes, of values >= 0 (0 when every lane is NaN)
+//   DH_WAVE_MAX_NAN(a)   the same of magnitudes (sign bit clear), but NaN when ANY lane is NaN
 //   DH_WAVE_MIN(a)   the smallest value of the 64 lanes, of values <= FLT_MAX (device: -max(-a), exact)
 //   DH_ROW0_MIN(a)   the smallest value of lanes 0..15, of values <= FLT_MAX
 #if DH_ON_GPU
 #define DH_WAVE_MAX(a) dh_wave_max((a)[0])
+#define DH_WAVE_MAX_NAN(a) dh_wave_max_nan((a)[0])
 #define DH_WAVE_MIN(a) (-dh_wave_max(-(a)[0]))
 #define DH_ROW0_MIN(a) dh_row_min_to_lane15((a)[0])
 #else
 #define DH_WAVE_MAX(a) dh_wave_max_lanes(a)
+#define DH_WAVE_MAX_NAN(a) dh_wave_max_nan_lanes(a)
 #define DH_WAVE_MIN(a) dh_wave_min_lanes(a, DH_WAVE)
 #define DH_ROW0_MIN(a) dh_wave_min_lanes(a, 16)
 #endif
