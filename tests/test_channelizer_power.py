@@ -10,171 +10,14 @@ Both tiers through the `ctx` fixture unless a test says otherwise:
   * end to end: a keyed CS16 composite -> channelizer (FM + DC) with power -> a DMR engine fed with the counts.
 """
 import ctypes as C
-import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+from cz_harness import (STRONG, WEAK, check_dmr_row, end_to_end_fixture, fixed, host, incs_for, make_cz, make_input, out_pushes,
+                        restate, run_lib, same, segment_table, taps_for)      # noqa: F401  (fixture)
 from digiham_amd import _capi, api, wideband
 from digiham_amd._capi import DhError
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EDGE_INCS = [0, 0x80000000, 0x7FFFFFFF, 0xFFFFFFFF, (-123456789) & 0xFFFFFFFF, 0x40000000, 0xC0000000, 1]
-
-
-class Restate:
-    def __init__(self, d):
-        libs = []
-        for name in ("cz_restate", "cz_power_restate"):
-            so = str(d / ("lib%s.so" % name))
-            subprocess.run(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, name + ".c"),
-                            "-o", so, "-lm"], check=True)
-            libs.append(C.CDLL(so))
-        self.cz, self.pw = libs
-        self.cz.cz_restate.restype = None
-        self.cz.cz_restate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
-        self.pw.cz_power_restate.restype = None
-        self.pw.cz_power_restate.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.cz.cz_phasor.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
-        a, b = C.c_float(), C.c_float()
-        self.cz.cz_phasor(0, C.byref(a), C.byref(b))          # fills the restatement's tables once, before any thread uses them
-
-    def z_rows(self, x, cf32, D, h, incs, pushes=None, retunes=None, threads=1):
-        """tests/cz_restate.c in IQ mode -> [B][n // D][2].  pushes: input lengths; retunes: {push index: {ch: inc}}."""
-        x = np.ascontiguousarray(x)
-        n = x.size // 2
-        B = len(incs)
-        pushes = pushes or [n]
-        starts = np.cumsum([0] + list(pushes[:-1])).astype(np.uint64)
-        nseg = len(pushes)
-        inc = np.zeros((nseg, B), np.uint32)
-        reset = np.zeros((nseg, B), np.uint8)
-        cur = np.array(incs, np.uint32)
-        for s in range(nseg):
-            for ch, u in (retunes or {}).get(s, {}).items():
-                cur[ch] = u
-                reset[s, ch] = 1
-            inc[s] = cur
-        h = np.ascontiguousarray(h, np.float32)
-        out = np.zeros((B, n // D, 2), np.float32)
-
-        def one(lo, hi):
-            i, r = np.ascontiguousarray(inc[:, lo:hi]), np.ascontiguousarray(reset[:, lo:hi])
-            self.cz.cz_restate(x.ctypes.data, int(cf32), n, D, h.ctypes.data, len(h), hi - lo, starts.ctypes.data, i.ctypes.data,
-                               r.ctypes.data, nseg, 0, 0, out[lo:hi].ctypes.data)
-
-        if threads <= 1:
-            one(0, B)
-        else:
-            cuts = np.linspace(0, B, min(threads, B) + 1).astype(int)
-            with ThreadPoolExecutor(threads) as ex:
-                list(ex.map(lambda k: one(int(cuts[k]), int(cuts[k + 1])), range(len(cuts) - 1)))
-        return out, reset
-
-    def power(self, z, L, open_level, close_level, hang, out_pushes, retune=None):
-        """-> power [B][n // L] float32, gate [B][n // L] uint8, counts [npush][B] uint32.  Levels and hang: a scalar, or one
-        value per push."""
-        z = np.ascontiguousarray(z, np.float32)
-        B, n = z.shape[0], z.shape[1]
-        npush = len(out_pushes)
-        assert sum(out_pushes) <= n
-        per = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (npush,)))
-        ol, cl, hg = per(open_level, np.float32), per(close_level, np.float32), per(hang, np.uint32)
-        pl = np.array(out_pushes, np.uint64)
-        rt = np.zeros((npush, B), np.uint8) if retune is None else np.ascontiguousarray(retune, np.uint8)
-        power, gate = np.zeros((B, n // L), np.float32), np.zeros((B, n // L), np.uint8)
-        counts = np.zeros((npush, B), np.uint32)
-        self.pw.cz_power_restate(z.ctypes.data, B, n, L, ol.ctypes.data, cl.ctypes.data, hg.ctypes.data, pl.ctypes.data, npush,
-                                 rt.ctypes.data, power.ctypes.data, gate.ctypes.data, counts.ctypes.data)
-        return power, gate, counts
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return Restate(tmp_path_factory.mktemp("czp"))
-
-
-def host(ctx, a):
-    return np.asarray(ctx.mem.to_numpy(a))
-
-
-def out_pushes(pushes, D):
-    """Outputs completed by each push of the given input lengths."""
-    pos, res = 0, []
-    for c in pushes:
-        res.append((pos + c) // D - pos // D)
-        pos += c
-    return res
-
-
-def make_cz(ctx, fmt, D, h, incs, output, dc, max_input, rate=1.0):
-    cz = api.Channelizer(rate, D, [u * rate / 2.0 ** 32 for u in incs], h, input=fmt, output=output, dcblock=dc, max_input=max_input, ctx=ctx)
-    for ch, u in enumerate(incs):            # exact increments (the frequency round trip above may not be)
-        assert ctx.lib.dh_channelizer_retune(cz._h, ch, int(u)) == 0
-    return cz
-
-
-def set_levels(ctx, cz, open_level, close_level, hang):
-    """Levels as float32 values, not dB."""
-    assert ctx.lib.dh_channelizer_set_squelch(cz._h, float(open_level), float(close_level), int(hang)) == 0
-
-
-def run_lib(ctx, x, fmt, D, h, incs, output, dc, L, levels, pushes=None, retunes=None, rate=1.0, cz=None, check_last=True, keep_rows=True):
-    """Push x in the given lengths.  levels: (open, close, hang) as float32 levels, or one such triple per push.
-    Returns dict(rows, power, gate: concatenated over the pushes; counts [npush][B]; first, nblk per push)."""
-    flat = np.ascontiguousarray(x).reshape(-1, 2)
-    n = len(flat)
-    pushes = pushes or [n]
-    own = cz is None
-    if own:
-        cz = make_cz(ctx, fmt, D, h, incs, output, dc, max(max(pushes), 1), rate)
-        cz.enable_power(block=L)
-    per_push = isinstance(levels[0], (tuple, list))
-    res = dict(rows=[], power=[], gate=[], counts=[], first=[], nblk=[])
-    pos = 0
-    for s, c in enumerate(pushes):
-        for ch, u in (retunes or {}).get(s, {}).items():
-            assert ctx.lib.dh_channelizer_retune(cz._h, ch, int(u)) == 0
-        set_levels(ctx, cz, *(levels[s] if per_push else levels))
-        rows, k = cz.push(np.ascontiguousarray(flat[pos:pos + c]))
-        pw, g, first = cz.power_blocks()
-        res["rows"].append(host(ctx, rows)[:, :k].copy() if keep_rows else np.zeros((len(incs), 0), np.float32))
-        res["power"].append(host(ctx, pw).copy())
-        res["gate"].append(host(ctx, g).copy())
-        res["counts"].append(host(ctx, cz.counts).view(np.uint32).copy())
-        res["first"].append(first)
-        res["nblk"].append(pw.shape[1])
-        if check_last:                          # the host arithmetic of dh_channelizer_power_last
-            j0 = pos // D
-            assert first == j0 // L and pw.shape[1] == (j0 + k) // L - j0 // L and g.shape[1] == pw.shape[1], (s, first, pw.shape)
-        pos += c
-    if own:
-        cz.close()
-    for key in ("rows", "power", "gate"):
-        res[key] = np.concatenate(res[key], axis=1)
-    res["counts"] = np.stack(res["counts"])
-    return res
-
-
-def make_input(fmt, n, seed, scale=1.0):
-    rng = np.random.default_rng(seed)
-    if fmt == "cs16":
-        return rng.integers(-30000, 30000, (n, 2)).astype(np.int16)
-    return (rng.standard_normal((n, 2)) * scale).astype(np.float32)
-
-
-def incs_for(B, seed):
-    rng = np.random.default_rng(seed)
-    extra = [int(v) for v in rng.integers(0, 1 << 32, max(B - len(EDGE_INCS), 0), dtype=np.uint64)]
-    return (EDGE_INCS + extra)[:B]
-
-
-def same(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. bit-exact
@@ -190,17 +33,17 @@ def test_bit_exact_against_restatement(ctx, restate, fmt, D, T, B, dc, L):
     n = sum(pushes)
     assert n // D == N_OUT and max(out_pushes(pushes, D)) < 1400
     x = make_input(fmt, n, D + T)
-    h = np.random.default_rng(T).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T)
     incs = incs_for(B, B)
-    z, _ = restate.z_rows(x, fmt == "cf32", D, h, incs)
+    z = restate.run(fixed(D), x, fmt == "cf32", h, incs, False, False)
     op = out_pushes(pushes, D)
     p0, _, _ = restate.power(z, L, 0.0, 0.0, 0, op)
     # levels inside the spread of the restated powers, so that gates open and close; (L = 1400 completes one block: it opens)
     lv = (np.float32(np.quantile(p0, 0.7)), np.float32(np.quantile(p0, 0.4)), 1)
     rp, rg, rc = restate.power(z, L, lv[0], lv[1], lv[2], op)
     assert rg.any() and (L == 1400 or not rg.all())
-    iq = run_lib(ctx, x, fmt, D, h, incs, "iq", False, L, lv, pushes=pushes)
-    fm = run_lib(ctx, x, fmt, D, h, incs, "fm", dc, L, lv, pushes=pushes)
+    iq = run_lib(ctx, fixed(D), x, fmt, h, incs, "iq", False, pushes=pushes, power=(L, lv))
+    fm = run_lib(ctx, fixed(D), x, fmt, h, incs, "fm", dc, pushes=pushes, power=(L, lv))
     assert same(iq["rows"], z)                                  # (what test_channelizer.py proves; the premise of this test)
     for got, what in ((iq, "iq"), (fm, "fm")):
         assert same(got["power"], rp), what
@@ -215,11 +58,11 @@ def test_iq_rows_at_any_alignment(ctx, restate, offset_floats):
     rows are only promised to be 4-byte aligned)."""
     D, T, B, L = 3, 20, 5, 37
     x = make_input("cf32", 1200, 4)
-    h = np.random.default_rng(8).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T, seed=8)
     incs = incs_for(B, 6)
-    z, _ = restate.z_rows(x, True, D, h, incs)
+    z = restate.run(fixed(D), x, True, h, incs, False, False)
     rp, rg, rc = restate.power(z, L, 0.0, 0.0, 0, [400])
-    cz = make_cz(ctx, "cf32", D, h, incs, "iq", False, 1200)
+    cz = make_cz(ctx, fixed(D), "cf32", h, incs, "iq", False, 1200)
     cz.enable_power(block=L)
     stride = 401
     buf = ctx.mem.zeros((2 * B * stride + 4,), np.float32)
@@ -238,38 +81,39 @@ def test_iq_rows_at_any_alignment(ctx, restate, offset_floats):
 def test_streaming_pushes_retune_reset(ctx, restate):
     D, T, B, L = 7, 45, 19, 13
     x = make_input("cs16", 4000, 9)
-    h = np.random.default_rng(1).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T, seed=1)
     incs = incs_for(B, 2)
-    z, _ = restate.z_rows(x, False, D, h, incs)
+    z = restate.run(fixed(D), x, False, h, incs, False, False)
     p0, _, _ = restate.power(z, L, 0.0, 0.0, 0, [4000 // D])
     lv = (np.float32(np.quantile(p0, 0.75)), np.float32(np.quantile(p0, 0.35)), 2)
-    whole = run_lib(ctx, x, "cs16", D, h, incs, "fm", True, L, lv)
+    whole = run_lib(ctx, fixed(D), x, "cs16", h, incs, "fm", True, power=(L, lv))
     pushes = [0, 1, D - 1, D, 7 * D + 3, 0, 2500, 5]
     pushes.append(4000 - sum(pushes))
     op = out_pushes(pushes, D)
-    ragged = run_lib(ctx, x, "cs16", D, h, incs, "fm", True, L, lv, pushes=pushes)          # (first / n_blocks checked per push)
+    ragged = run_lib(ctx, fixed(D), x, "cs16", h, incs, "fm", True, pushes=pushes, power=(L, lv))          # (first / n_blocks checked per push)
     assert same(ragged["power"], whole["power"]) and same(ragged["gate"], whole["gate"]) and same(ragged["rows"], whole["rows"])
     rp, rg, rc = restate.power(z, L, lv[0], lv[1], lv[2], op)
     assert same(ragged["power"], rp) and same(ragged["gate"], rg) and same(ragged["counts"], rc)
     assert (ragged["counts"][[0, 1, 2, 5]] == 0).all()         # pushes without an output
     # two retunes mid-stream (channels 3 and 11 at push 6, channel 3 again at push 8)
     ret = {6: {3: 0x12345678, 11: 0}, 8: {3: 0xFEDCBA98}}
-    zr, mask = restate.z_rows(x, False, D, h, incs, pushes=pushes, retunes=ret)
+    zr = restate.run(fixed(D), x, False, h, incs, False, False, pushes=pushes, retunes=ret)
+    mask = segment_table(len(x), incs, np.uint32, pushes, ret)[2]
     rp, rg, rc = restate.power(zr, L, lv[0], lv[1], lv[2], op, retune=mask)
     for output, dc in (("fm", True), ("iq", False)):
-        got = run_lib(ctx, x, "cs16", D, h, incs, output, dc, L, lv, pushes=pushes, retunes=ret)
+        got = run_lib(ctx, fixed(D), x, "cs16", h, incs, output, dc, pushes=pushes, retunes=ret, power=(L, lv))
         assert same(got["power"], rp) and same(got["gate"], rg) and same(got["counts"], rc), output
     # levels and hang change between pushes; the state is kept
     lvs = [(lv[0], lv[1], 2)] * 6 + [(lv[1], np.float32(0.0), 0), (lv[0], lv[0], 65535), (np.float32(0.0), np.float32(0.0), 0)]
-    got = run_lib(ctx, x, "cs16", D, h, incs, "iq", False, L, lvs, pushes=pushes)
+    got = run_lib(ctx, fixed(D), x, "cs16", h, incs, "iq", False, pushes=pushes, power=(L, lvs))
     rp, rg, rc = restate.power(z, L, [t[0] for t in lvs], [t[1] for t in lvs], [t[2] for t in lvs], op)
     assert same(got["power"], rp) and same(got["gate"], rg) and same(got["counts"], rc)
     # reset: a fresh stream, the configuration stays
-    cz = make_cz(ctx, "cs16", D, h, incs, "fm", True, 4000)
+    cz = make_cz(ctx, fixed(D), "cs16", h, incs, "fm", True, 4000)
     cz.enable_power(block=L)
-    first = run_lib(ctx, x[:3000], "cs16", D, h, incs, "fm", True, L, lv, pushes=[1000, 2000], cz=cz)
+    first = run_lib(ctx, fixed(D), x[:3000], "cs16", h, incs, "fm", True, pushes=[1000, 2000], cz=cz, power=(L, lv))
     cz.reset()
-    again = run_lib(ctx, x, "cs16", D, h, incs, "fm", True, L, lv, pushes=[4000], cz=cz)
+    again = run_lib(ctx, fixed(D), x, "cs16", h, incs, "fm", True, pushes=[4000], cz=cz, power=(L, lv))
     cz.close()
     assert same(again["power"], whole["power"]) and same(again["gate"], whole["gate"]) and same(again["counts"], whole["counts"])
     nb = first["power"].shape[1]
@@ -318,7 +162,7 @@ def test_gate_machine_in_isolation(ctx, restate, hang):
             if a == NAN:
                 x[i * L + 20, 1] = np.nan                        # outputs 20 .. 35 of the block: 16 and more from both of its ends
                 want[i] = np.nan
-        z, _ = restate.z_rows(x, True, 1, [1.0], [0])
+        z = restate.run(fixed(1), x, True, [1.0], [0], False, False)
         clean = np.repeat(np.array([a != NAN for a in sc]), L)
         assert same(z[0][clean], x[clean])
         pushes = [3 * L + 5, L - 5, 7, 10 * L, 1, nb * L - (14 * L + 8)]
@@ -327,7 +171,7 @@ def test_gate_machine_in_isolation(ctx, restate, hang):
         assert np.array_equal(rp[0], want, equal_nan=True)       # exact powers, NaN where scripted
         pg = python_gate(rp, open_level, close_level, hang)
         assert same(pg, rg), "the two readings of the specification differ"
-        got = run_lib(ctx, x, "cf32", 1, [1.0], [0], "iq", False, L, (open_level, close_level, hang), pushes=pushes)
+        got = run_lib(ctx, fixed(1), x, "cf32", [1.0], [0], "iq", False, pushes=pushes, power=(L, (open_level, close_level, hang)))
         assert same(got["power"], rp) and same(got["gate"], rg) and same(got["counts"], rc)
         assert same(got["gate"], pg)
         ref_rows.append(rg[0])
@@ -358,7 +202,7 @@ def test_block_power_of_a_tone(ctx):
                 xs = A * np.exp(2j * np.pi * ((u / 2.0 ** 32) + delta / rate) * nn)
                 x = np.stack([xs.real, xs.imag], 1)
                 x = x.astype(np.float32) if fmt == "cf32" else np.round(x * 32768.0).astype(np.int16)
-                got = run_lib(ctx, x, fmt, D, h, [u], "iq", False, L, (0.0, 0.0, 0), rate=rate)
+                got = run_lib(ctx, fixed(D), x, fmt, h, [u], "iq", False, rate=rate, power=(L, (0.0, 0.0, 0)))
                 p = got["power"][0].astype(np.float64)
                 assert len(p) == n // D // L and len(p) > first_full + 2
                 gain = abs(H(delta))
@@ -458,27 +302,13 @@ def _gated_scene(restate, D, n_rows, seconds, device, weakest_db, threads):
     """A keyed composite on a 12.5 kHz raster (all carriers key on at 0.2 s and off 0.3 s before the end, their audio starting
     at key-on; two rows are never keyed), the restatement's powers, and the precondition on the scene asserted from them."""
     L, hang, P = GATED_L, GATED_HANG, GATED_PUSH
-    rate = 48000.0 * D
-    n = int(seconds * rate)
-    half = n_rows // 2
-    raster = [(r - half) * 12500.0 for r in range(n_rows)]
-    rng = np.random.default_rng(n_rows)
-    empty = {2, n_rows - 2}
-    strong, weak = 4, 5
+    assert seconds < 2.5                                          # one call per carrier
     key = (0.2, seconds - 0.3)
-    carriers, meta, keyed = [], {}, []
-    for r in range(n_rows):
-        if r in empty:
-            continue
-        off = raster[r] + float(rng.uniform(-150, 150))
-        level = {strong: 0.0, weak: -20.0, 0: weakest_db}.get(r, float(rng.uniform(-20, -5)))
-        audio, meta[r] = wideband.dmr_audio(100 + r, n_calls=1)
+    f = end_to_end_fixture(1, D, n_rows, seconds, device, seed=7, key=key, levels={STRONG: 0.0, WEAK: -20.0, 0: weakest_db}, ysf_row=None)
+    x, h, raster, rate, n, empty, meta, keyed = f["x"], f["h"], f["raster"], f["rate"], f["n"], f["empty"], f["meta"], sorted(f["meta"])
+    for _, _, audio in f["carriers"]:
         assert len(audio) / 48000.0 <= key[1] - key[0], "the keyed interval must hold the whole generated audio"
-        carriers.append((off, level, audio))
-        keyed.append(r)
-    x = wideband.composite(D, carriers, n, seed=7, device=device, keying=[key] * len(carriers))
     xh = x if isinstance(x, np.ndarray) else x.cpu().numpy()
-    h = api.channel_taps(rate, D, 5500.0, 8000.0, 70.0)
     Tp = 16 * ((len(h) + 15) // 16)
     incs = [api.nco_increment(f, rate) for f in raster]
     n_out = n // D
@@ -486,7 +316,7 @@ def _gated_scene(restate, D, n_rows, seconds, device, weakest_db, threads):
     op = out_pushes(pushes, D)
     edges = np.cumsum([0] + op)
     # ---- the restatement, and the precondition on the scene (from the restatement's powers only)
-    z, _ = restate.z_rows(xh, False, D, h, incs, threads=threads)
+    z = restate.run(fixed(D), xh, False, h, incs, False, False, threads=threads)
     pw, _, _ = restate.power(z, L, 0.0, 0.0, 0, op)
     nb = pw.shape[1]
     F = -(-Tp // D)                                               # the filter's length in outputs
@@ -570,12 +400,7 @@ def _end_to_end_gated(ctx, oracle, restate, D, n_rows, seconds, device, weakest_
             assert counts[s, r] in (0, op[s])
         audio = np.concatenate(passed_rows[r])
         ref = oracle.chain(audio[None, :], proto=1)
-        e = np.concatenate(evs[r])
-        assert len(e) == ref["event_count"][0] and e.tobytes() == ref["events"][0, :len(e)].tobytes(), "row %d differs from the oracle" % r
-        lcs = [api.parse_lc(p) for p in e[e["type"] == 4]["payload"]]
-        assert lcs, "row %d: no LC" % r
-        assert all(l["source"] == meta[r]["src"] and l["target"] == meta[r]["dst"] for l in lcs), "row %d: wrong ids" % r
-        assert (e["type"] == 1).sum() >= meta[r]["superframes"], "row %d: fewer syncs than generated voice superframes" % r
+        check_dmr_row(r, np.concatenate(evs[r]), ref, 0, meta[r])
 
 
 def test_end_to_end_gated_small(emu_ctx, oracle, restate):
@@ -607,13 +432,13 @@ def test_thousand_channels_gpu(gpu_ctx, restate):
         x += np.stack([tone.real, tone.imag], 1).round().astype(np.int16)
     pushes = [1000003, 399997, 1000000]
     op = out_pushes(pushes, D)
-    z, _ = restate.z_rows(x, False, D, h, incs, threads=16)
+    z = restate.run(fixed(D), x, False, h, incs, False, False, threads=16)
     p0, _, _ = restate.power(z, L, 0.0, 0.0, 0, op)
     lv = (np.float32(np.quantile(p0, 0.9)), np.float32(np.quantile(p0, 0.5)), 3)
     rp, rg, rc = restate.power(z, L, lv[0], lv[1], lv[2], op)
     assert rg.any() and not rg.all() and rc.any() and not rc.all()
     for output, dc in (("fm", True), ("iq", False)):
-        got = run_lib(ctx, x, "cs16", D, h, incs, output, dc, L, lv, pushes=pushes, rate=rate, keep_rows=False)
+        got = run_lib(ctx, fixed(D), x, "cs16", h, incs, output, dc, pushes=pushes, rate=rate, keep_rows=False, power=(L, lv))
         assert same(got["power"], rp) and same(got["gate"], rg) and same(got["counts"], rc), output
 
 
@@ -629,11 +454,11 @@ def test_more_segments_than_one_grid_pass_gpu(gpu_ctx, restate, output, dc):
     op = out_pushes(pushes, D)
     assert B * (op[0] // L) > 8192 * 256 and op[0] % L and (op[0] + op[1]) % L
     x = make_input("cs16", sum(pushes), 21)
-    h = np.random.default_rng(5).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T, seed=5)
     incs = incs_for(B, 12)
-    z, _ = restate.z_rows(x, False, D, h, incs, threads=16)
+    z = restate.run(fixed(D), x, False, h, incs, False, False, threads=16)
     p0, _, _ = restate.power(z, L, 0.0, 0.0, 0, op)
     lv = (np.float32(np.quantile(p0, 0.8)), np.float32(np.quantile(p0, 0.3)), 1)
     rp, rg, rc = restate.power(z, L, lv[0], lv[1], lv[2], op)
-    got = run_lib(ctx, x, "cs16", D, h, incs, output, dc, L, lv, pushes=pushes, keep_rows=False)
+    got = run_lib(ctx, fixed(D), x, "cs16", h, incs, output, dc, pushes=pushes, keep_rows=False, power=(L, lv))
     assert same(got["power"], rp) and same(got["gate"], rg) and same(got["counts"], rc)

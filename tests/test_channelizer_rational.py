@@ -10,125 +10,15 @@ Both tiers through the `ctx` fixture unless a test says otherwise:
   * end to end: a composite at a rate that is no multiple of 48 kS/s -> channelizer (FM + DC) -> engines == the oracle.
 """
 import ctypes as C
-import os
-import subprocess
 from math import gcd
 
 import numpy as np
 import pytest
 
-from digiham_amd import _capi, api, wideband
+from cz_harness import (cfg, create, end_to_end, end_to_end_fixture, fixed, incs_for, make_cz, make_input, out_pushes, rational,
+                        restate, run_lib, taps_for)      # noqa: F401  (fixture)
+from digiham_amd import _capi, api
 from digiham_amd._capi import DhError
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EDGE_INCS = [0, 0x80000000, 0x7FFFFFFF, 0xFFFFFFFF, (-123456789) & 0xFFFFFFFF, 0x40000000, 0xC0000000, 1]
-
-
-class Restate:
-    def __init__(self, d):
-        libs = {}
-        for name in ("cz_rational_restate", "cz_restate", "cz_power_restate"):
-            so = str(d / ("lib%s.so" % name))
-            subprocess.run(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, name + ".c"),
-                            "-o", so, "-lm"], check=True)
-            libs[name] = C.CDLL(so)
-        self.rat, self.one, self.pw = libs["cz_rational_restate"], libs["cz_restate"], libs["cz_power_restate"]
-        self.rat.cz_rational_restate.restype = None
-        self.rat.cz_rational_restate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
-                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
-        self.one.cz_restate.restype = None
-        self.one.cz_restate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
-        self.pw.cz_power_restate.restype = None
-        self.pw.cz_power_restate.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-
-    def rows(self, x, cf32, L, M, h, incs, fm, dcblock, pushes=None, retunes=None):
-        """The whole stream; L = 0: tests/cz_restate.c (the integer channelizer), else tests/cz_rational_restate.c.
-        pushes: the push lengths (for retunes); retunes: {push index: {ch: inc}}."""
-        x = np.ascontiguousarray(x)
-        n, B = x.size // 2, len(incs)
-        pushes = pushes or [n]
-        starts = np.cumsum([0] + list(pushes[:-1])).astype(np.uint64)
-        nseg = len(pushes)
-        inc, reset = np.zeros((nseg, B), np.uint32), np.zeros((nseg, B), np.uint8)
-        cur = np.array(incs, np.uint32)
-        for s in range(nseg):
-            for ch, u in (retunes or {}).get(s, {}).items():
-                cur[ch] = u
-                reset[s, ch] = 1
-            inc[s] = cur
-        h = np.ascontiguousarray(h, np.float32)
-        n_out = max(L, 1) * n // M
-        out = np.zeros((B, n_out) if fm else (B, n_out, 2), np.float32)
-        tail = (starts.ctypes.data, inc.ctypes.data, reset.ctypes.data, nseg, int(fm), int(dcblock), out.ctypes.data)
-        if L:
-            self.rat.cz_rational_restate(x.ctypes.data, int(cf32), n, L, M, h.ctypes.data, len(h), B, *tail)
-        else:
-            self.one.cz_restate(x.ctypes.data, int(cf32), n, M, h.ctypes.data, len(h), B, *tail)
-        return out
-
-    def power(self, z, block, open_level, close_level, hang, out_pushes):
-        z = np.ascontiguousarray(z, np.float32)
-        B, n, npush = z.shape[0], z.shape[1], len(out_pushes)
-        per = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (npush,)))
-        ol, cl, hg = per(open_level, np.float32), per(close_level, np.float32), per(hang, np.uint32)
-        pl, rt = np.array(out_pushes, np.uint64), np.zeros((npush, B), np.uint8)
-        power, gate = np.zeros((B, n // block), np.float32), np.zeros((B, n // block), np.uint8)
-        counts = np.zeros((npush, B), np.uint32)
-        self.pw.cz_power_restate(z.ctypes.data, B, n, block, ol.ctypes.data, cl.ctypes.data, hg.ctypes.data, pl.ctypes.data, npush,
-                                 rt.ctypes.data, power.ctypes.data, gate.ctypes.data, counts.ctypes.data)
-        return power, gate, counts
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return Restate(tmp_path_factory.mktemp("czr"))
-
-
-def host(ctx, a):
-    return np.asarray(ctx.mem.to_numpy(a))
-
-
-def make_cz(ctx, fmt, L, M, h, incs, output, dc, max_input, rate=1.0):
-    cz = api.Channelizer(rate, M, [u * rate / 2.0 ** 32 for u in incs], h, input=fmt, output=output, dcblock=dc,
-                         max_input=max_input, ctx=ctx, interpolation=L)
-    for ch, u in enumerate(incs):            # exact increments (the frequency round trip above may not be)
-        assert ctx.lib.dh_channelizer_retune(cz._h, ch, int(u)) == 0
-    return cz
-
-
-def run_lib(ctx, x, fmt, L, M, h, incs, output, dc, pushes=None, retunes=None, rate=1.0, cz=None):
-    """Push x in the given lengths; returns the concatenated rows.  Every push must yield floor(L N / M) - floor(L N0 / M)."""
-    flat = np.ascontiguousarray(x).reshape(-1, 2)
-    pushes = pushes or [len(flat)]
-    own = cz is None
-    if own:
-        cz = make_cz(ctx, fmt, L, M, h, incs, output, dc, max(max(pushes), 1), rate)
-    parts, pos, Le = [], 0, max(L, 1)
-    for s, c in enumerate(pushes):
-        for ch, u in (retunes or {}).get(s, {}).items():
-            assert ctx.lib.dh_channelizer_retune(cz._h, ch, int(u)) == 0
-        rows, k = cz.push(np.ascontiguousarray(flat[pos:pos + c]))
-        assert k == Le * (pos + c) // M - Le * pos // M, (s, k)
-        parts.append(host(ctx, rows)[:, :k].copy())
-        pos += c
-    if own:
-        cz.close()
-    return np.concatenate(parts, axis=1)
-
-
-def make_input(fmt, n, seed, scale=1.0):
-    rng = np.random.default_rng(seed)
-    if fmt == "cs16":
-        return rng.integers(-30000, 30000, (n, 2)).astype(np.int16)
-    return (rng.standard_normal((n, 2)) * scale).astype(np.float32)
-
-
-def incs_for(B, seed):
-    rng = np.random.default_rng(seed)
-    extra = [int(v) for v in rng.integers(0, 1 << 32, max(B - len(EDGE_INCS), 0), dtype=np.uint64)]
-    return (EDGE_INCS + extra)[:B]
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. bit-exact
@@ -143,10 +33,10 @@ def test_bit_exact_against_restatement(ctx, restate, fmt, output, dc, L, M, T, B
     assert gcd(L, M) == 1
     n = 1500 + 3 * M
     x = make_input(fmt, n, M + T)
-    h = np.random.default_rng(T).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T)
     incs = incs_for(B, B)
-    got = run_lib(ctx, x, fmt, L, M, h, incs, output, dc)
-    ref = restate.rows(x, fmt == "cf32", L, M, h, incs, output == "fm", dc)
+    got = run_lib(ctx, rational(L, M), x, fmt, h, incs, output, dc)
+    ref = restate.run(rational(L, M), x, fmt == "cf32", h, incs, output == "fm", dc)
     assert got.shape[1] == L * n // M
     assert got.shape == ref.shape
     assert got.tobytes() == ref.tobytes()
@@ -157,33 +47,34 @@ def test_bit_exact_against_restatement(ctx, restate, fmt, output, dc, L, M, T, B
 def test_interpolation_one_is_the_integer_channelizer(ctx, restate, interp):
     fmt, output, dc, D, T, B = "cs16", "fm", True, 16, 70, 20           # an exact case of test_channelizer.py
     x = make_input(fmt, 1500 + 3 * D, D + T)
-    h = np.random.default_rng(T).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T)
     incs = incs_for(B, B)
-    got = run_lib(ctx, x, fmt, interp, D, h, incs, output, dc)
-    ref = restate.rows(x, False, 0, D, h, incs, True, dc)
+    got = run_lib(ctx, rational(interp, D), x, fmt, h, incs, output, dc)
+    ref = restate.run(fixed(D), x, False, h, incs, True, dc)
     assert got.shape == ref.shape and got.tobytes() == ref.tobytes()
 
 
 # --------------------------------------------------------------------------------------------------------------- 3. streaming
 def test_streaming_pushes_retune_reset(ctx, restate):
     L, M, T, B = 3, 8, 45, 19
+    bank = rational(L, M)
     x = make_input("cs16", 4000, 9)
-    h = np.random.default_rng(1).standard_normal(T).astype(np.float32) * 0.05
+    h = taps_for(T, seed=1)
     incs = incs_for(B, 2)
-    whole = run_lib(ctx, x, "cs16", L, M, h, incs, "fm", True)
+    whole = run_lib(ctx, bank, x, "cs16", h, incs, "fm", True)
     pushes = [0, 1, 2, 3, 7, 8 * 7 + 3, 0, 2500, 5]
     pushes.append(4000 - sum(pushes))
-    ragged = run_lib(ctx, x, "cs16", L, M, h, incs, "fm", True, pushes=pushes)
+    ragged = run_lib(ctx, bank, x, "cs16", h, incs, "fm", True, pushes=pushes)
     assert ragged.tobytes() == whole.tobytes()
-    assert whole.tobytes() == restate.rows(x, False, L, M, h, incs, True, True).tobytes()
+    assert whole.tobytes() == restate.run(bank, x, False, h, incs, True, True).tobytes()
     ret = {6: {3: 0x12345678, 11: 0}, 8: {3: 0xFEDCBA98}}
-    got = run_lib(ctx, x, "cs16", L, M, h, incs, "fm", True, pushes=pushes, retunes=ret)
-    ref = restate.rows(x, False, L, M, h, incs, True, True, pushes=pushes, retunes=ret)
+    got = run_lib(ctx, bank, x, "cs16", h, incs, "fm", True, pushes=pushes, retunes=ret)
+    ref = restate.run(bank, x, False, h, incs, True, True, pushes=pushes, retunes=ret)
     assert got.tobytes() == ref.tobytes() and got.tobytes() != whole.tobytes()
-    cz = make_cz(ctx, "cs16", L, M, h, incs, "fm", True, 4000)
-    first = run_lib(ctx, x[:3000], "cs16", L, M, h, incs, "fm", True, pushes=[1000, 2000], cz=cz)
+    cz = make_cz(ctx, bank, "cs16", h, incs, "fm", True, 4000)
+    first = run_lib(ctx, bank, x[:3000], "cs16", h, incs, "fm", True, pushes=[1000, 2000], cz=cz)
     cz.reset()
-    again = run_lib(ctx, x, "cs16", L, M, h, incs, "fm", True, pushes=[4000], cz=cz)
+    again = run_lib(ctx, bank, x, "cs16", h, incs, "fm", True, pushes=[4000], cz=cz)
     cz.close()
     assert again.tobytes() == whole.tobytes()
     assert first.tobytes() == whole[:, :first.shape[1]].tobytes()
@@ -194,11 +85,11 @@ def test_subnormal_operands_bit_exact(ctx, restate):
     """The subnormal case of test_channelizer.py at L / M = 3 / 7."""
     x = make_input("cf32", 600, 5, scale=1e-36)
     x[::7] = 0.0
-    h = np.random.default_rng(3).standard_normal(21).astype(np.float32) * 1e-3
+    h = taps_for(21, 1e-3, seed=3)
     incs = incs_for(12, 4)
     for output, dc in (("iq", False), ("fm", True)):
-        got = run_lib(ctx, x, "cf32", 3, 7, h, incs, output, dc)
-        ref = restate.rows(x, True, 3, 7, h, incs, output == "fm", dc)
+        got = run_lib(ctx, rational(3, 7), x, "cf32", h, incs, output, dc)
+        ref = restate.run(rational(3, 7), x, True, h, incs, output == "fm", dc)
         if output == "iq":
             assert (np.abs(ref[ref != 0]) < 1.1754944e-38).any(), "the case must reach subnormal outputs"
         assert got.tobytes() == ref.tobytes()
@@ -242,7 +133,7 @@ def test_rational_ddc_physics(ctx):
         for delta, stopband in ((1234.5, False), (-4000.0, False), (15000.0, True), (-40000.0, True)):
             xs = A * np.exp(2j * np.pi * ((u / 2.0 ** 32) + delta / rate) * nn)
             x = np.stack([xs.real, xs.imag], 1).astype(np.float32)
-            z = run_lib(ctx, x, "cf32", L, M, h, [u], "iq", False, rate=rate)[0]
+            z = run_lib(ctx, rational(L, M), x, "cf32", h, [u], "iq", False, rate=rate)[0]
             z = z[:, 0].astype(np.float64) + 1j * z[:, 1]
             assert len(z) == len(j)
             for p in range(L):
@@ -262,7 +153,7 @@ def test_rational_ddc_physics(ctx):
     print("FM tolerance %.3g" % tol)
     xs = A * np.exp(2j * np.pi * ((incs[1] / 2.0 ** 32) + delta / rate) * nn)
     x = np.stack([xs.real, xs.imag], 1).astype(np.float32)
-    fm = run_lib(ctx, x, "cf32", L, M, h, [incs[1]], "fm", False, rate=rate)[0].astype(np.float64)
+    fm = run_lib(ctx, rational(L, M), x, "cf32", h, [incs[1]], "fm", False, rate=rate)[0].astype(np.float64)
     first = int(np.argmax(ok)) + 2
     dev = np.abs(fm[first:] - 2 * delta / 48000.0).max()
     print("FM deviation %.3g" % dev)
@@ -272,6 +163,7 @@ def test_rational_ddc_physics(ctx):
 # ---------------------------------------------------------------------------------------------------------- 6. power and counts
 def test_power_gate_counts(ctx, restate):
     L, M, block, B = 3, 8, 16, 5
+    bank = rational(L, M)
     n = 4000
     incs = [0x60000000] + incs_for(B - 1, 6)
     rng = np.random.default_rng(8)
@@ -282,74 +174,43 @@ def test_power_gate_counts(ctx, restate):
     h = (np.hanning(98)[1:-1] * 3 / np.hanning(98).sum()).astype(np.float32)                        # every phase sums to ~1
     pushes = [300, 0, 5, 1200, 37, 900, 800, 2]
     pushes.append(n - sum(pushes))
-    op, pos = [], 0
-    for c in pushes:
-        op.append(L * (pos + c) // M - L * pos // M)
-        pos += c
+    op = out_pushes(pushes, M, L)
     levels = (np.float32(0.05), np.float32(0.02), 1)
-    z = restate.rows(x, False, L, M, h, incs, False, False)
+    z = restate.run(bank, x, False, h, incs, False, False)
     pw_ref, gate_ref, counts_ref = restate.power(z, block, *levels, op)
     assert gate_ref[0].any() and not gate_ref[0].all() and not gate_ref[1:].any(), "the fixture must key channel 0 only"
     for output, dc in (("iq", False), ("fm", True)):
-        cz = make_cz(ctx, "cs16", L, M, h, incs, output, dc, max(pushes))
-        cz.enable_power(block=block)
-        assert ctx.lib.dh_channelizer_set_squelch(cz._h, float(levels[0]), float(levels[1]), int(levels[2])) == 0
-        pw, gate, counts, pos = [], [], [], 0
-        for s, c in enumerate(pushes):
-            _, k = cz.push(x[pos:pos + c])
-            assert k == op[s]
-            p, g, first = cz.power_blocks()
-            j0 = L * pos // M
-            assert first == j0 // block and p.shape[1] == (j0 + k) // block - j0 // block
-            pw.append(host(ctx, p).copy()); gate.append(host(ctx, g).copy())
-            counts.append(host(ctx, cz.counts).view(np.uint32).copy())
-            pos += c
-        cz.close()
-        pw, gate, counts = np.concatenate(pw, 1), np.concatenate(gate, 1), np.stack(counts)
-        assert pw.shape == pw_ref.shape and pw.tobytes() == pw_ref.tobytes(), output
-        assert gate.tobytes() == gate_ref.tobytes(), output
-        assert counts.tobytes() == counts_ref.tobytes(), output
+        got = run_lib(ctx, bank, x, "cs16", h, incs, output, dc, pushes=pushes, power=(block, levels), keep_rows=False)
+        assert got["power"].shape == pw_ref.shape and got["power"].tobytes() == pw_ref.tobytes(), output
+        assert got["gate"].tobytes() == gate_ref.tobytes(), output
+        assert got["counts"].tobytes() == counts_ref.tobytes(), output
         for s in range(len(pushes)):
-            assert set(counts[s].tolist()) <= {0, op[s]}
+            assert set(got["counts"][s].tolist()) <= {0, op[s]}
     # the stride of the enable: (max_input L / M + 1) / block + 1
-    cz = make_cz(ctx, "cs16", L, M, h, incs, "iq", False, 4000)
+    cz = make_cz(ctx, bank, "cs16", h, incs, "iq", False, 4000)
     mem = ctx.mem
     need = (4000 * L // M + 1) // block + 1
     assert need > (4000 // M + 1) // block + 1
     power, gate, counts = mem.zeros((B, need), np.float32), mem.zeros((B, need), np.uint8), mem.zeros((B,), np.uint32)
     for stride, rc in ((need - 1, _capi.DH_EINVAL), (need, 0)):
-        cfg = _capi.ChannelizerPowerConfig(C.sizeof(_capi.ChannelizerPowerConfig), block, 0.0, 0.0, 0, mem.ptr(power), mem.ptr(gate),
+        pcfg = _capi.ChannelizerPowerConfig(C.sizeof(_capi.ChannelizerPowerConfig), block, 0.0, 0.0, 0, mem.ptr(power), mem.ptr(gate),
                                            mem.ptr(counts), stride)
-        assert ctx.lib.dh_channelizer_power_enable(cz._h, C.byref(cfg)) == rc, stride
+        assert ctx.lib.dh_channelizer_power_enable(cz._h, C.byref(pcfg)) == rc, stride
     cz.close()
 
 
 # -------------------------------------------------------------------------------------------------------------- 7. validation
 def test_validation(ctx):
-    lib = ctx.lib
-    inc = np.zeros(4, np.uint32)
-
-    def create(L, M, T, **kw):
-        h = np.ones(T, np.float32)
-        c = _capi.ChannelizerConfig(C.sizeof(_capi.ChannelizerConfig), 0, 4, M, h.ctypes.data_as(C.POINTER(C.c_float)), T,
-                                    inc.ctypes.data_as(C.POINTER(C.c_uint32)), 1, 2, 1, 1000, ctx.mem.stream(), L)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        hh = C.c_void_p()
-        rc = lib.dh_channelizer_create(C.byref(c), C.byref(hh))
-        if rc == 0:
-            lib.dh_channelizer_destroy(hh)
-        return rc
-
-    assert create(65, 128, 8) == _capi.DH_EINVAL
-    assert create(5, 3, 8) == _capi.DH_EINVAL                          # L > M
-    assert create(4, 6, 8) == _capi.DH_EINVAL                          # gcd 2
-    assert create(3, 8, 16384 * 3 + 1) == _capi.DH_EINVAL
-    assert create(3, 8, 16384 * 3) == 0
-    assert create(64, 1023, 8) == 0
+    rcreate = lambda L, M, T, **kw: create(ctx, cfg(ctx, interpolation=L, decimation=M, n_taps=T, taps=np.ones(T, np.float32), **kw))
+    assert rcreate(65, 128, 8) == _capi.DH_EINVAL
+    assert rcreate(5, 3, 8) == _capi.DH_EINVAL                          # L > M
+    assert rcreate(4, 6, 8) == _capi.DH_EINVAL                          # gcd 2
+    assert rcreate(3, 8, 16384 * 3 + 1) == _capi.DH_EINVAL
+    assert rcreate(3, 8, 16384 * 3) == 0
+    assert rcreate(64, 1023, 8) == 0
     old = _capi.ChannelizerConfig.interpolation.offset                 # a caller built before the field existed
-    assert create(65, 128, 8, struct_size=old) == 0
-    assert create(1, 8, 16385) == _capi.DH_EINVAL
+    assert rcreate(65, 128, 8, struct_size=old) == 0
+    assert rcreate(1, 8, 16385) == _capi.DH_EINVAL
     with pytest.raises(DhError):
         api.Channelizer(1.0, 8, [0.0], np.ones(8, np.float32), ctx=ctx, interpolation=6)
     assert api.resample_ratio(2.048e6) == (3, 128)
@@ -363,69 +224,9 @@ def test_validation(ctx):
 
 
 # -------------------------------------------------------------------------------------------------------------- 8. end to end
-def end_to_end_fixture(L, M, n_rows, seconds, device, seed=7):
-    """The composite of test_channelizer.py's _end_to_end at the capture rate 48 kS/s * M / L (tools/channelizer_model.py runs
-    its float64 model on the same): dict(rate, n, raster, x, h, meta, ysf_row, empty)."""
-    rate = 48000.0 * M / L
-    n = int(seconds * rate)
-    half = n_rows // 2
-    raster = [(r - half) * 12500.0 for r in range(n_rows)]
-    rng = np.random.default_rng(n_rows)
-    ysf_row, empty = 1, {2, n_rows - 2}
-    strong, weak = 4, 5
-    carriers, meta = [], {}
-    for r in range(n_rows):
-        if r in empty:
-            continue
-        off = raster[r] + float(rng.uniform(-150, 150))
-        level = {strong: 0.0, weak: -20.0, 0: -30.0, ysf_row: -20.0}.get(r, float(rng.uniform(-20, -5)))
-        if r == ysf_row:
-            audio = wideband.ysf_audio(100 + r, 30)
-        else:
-            audio, meta[r] = wideband.dmr_audio(100 + r, n_calls=1 if seconds < 2.5 else 2)
-            meta[r]["level_db"] = level
-        carriers.append((off, level, audio))
-    x = wideband.composite(M / L, carriers, n, seed=seed, device=device)
-    h = api.channel_taps(rate, M, 5500.0, 8000.0, 70.0, interpolation=L)
-    return dict(rate=rate, n=n, raster=raster, x=x, h=h, meta=meta, ysf_row=ysf_row, empty=empty)
-
-
-def _end_to_end(ctx, oracle, L, M, n_rows, seconds, device, seed=7):
-    """_end_to_end of test_channelizer.py at the capture rate 48 kS/s * M / L."""
-    f = end_to_end_fixture(L, M, n_rows, seconds, device, seed)
-    rate, n, raster, x, h, meta, ysf_row, empty = (f[k] for k in ("rate", "n", "raster", "x", "h", "meta", "ysf_row", "empty"))
-    cz = api.Channelizer(rate, M, raster, h, input="cs16", output="fm", dcblock=True, max_input=n, ctx=ctx, interpolation=L)
-    rows, k = cz.push(x)
-    assert k == L * n // M
-    audio = np.ascontiguousarray(host(ctx, rows)[:, :k])
-    cz.close()
-    dmr_rows = [r for r in range(n_rows) if r != ysf_row]
-    eng = api.Engine(len(dmr_rows), k, proto="dmr", ctx=ctx)
-    eng.push(ctx.mem.from_numpy(audio[dmr_rows]))
-    ev, ec = eng.events()
-    ref = oracle.chain(audio[dmr_rows], proto=1)
-    for i, r in enumerate(dmr_rows):
-        e = ev[i, :ec[i]]
-        assert ec[i] == ref["event_count"][i] and e.tobytes() == ref["events"][i, :ec[i]].tobytes(), "row %d differs from the oracle" % r
-        if r in empty:
-            assert not (e["type"] == 1).any(), "empty row %d: sync events" % r
-            continue
-        lcs = [api.parse_lc(p) for p in e[e["type"] == 4]["payload"]]
-        assert lcs, "row %d: no LC" % r
-        assert all(l["source"] == meta[r]["src"] and l["target"] == meta[r]["dst"] for l in lcs), "row %d: wrong ids" % r
-        assert (e["type"] == 1).sum() >= meta[r]["superframes"], "row %d: fewer syncs than generated voice superframes" % r
-    eng.close()
-    yeng = api.Engine(1, k, proto="ysf", ctx=ctx)
-    yeng.push(ctx.mem.from_numpy(audio[ysf_row:ysf_row + 1]))
-    yev, yec = yeng.events()
-    yref = oracle.chain(audio[ysf_row:ysf_row + 1], proto=2)
-    assert yec[0] == yref["event_count"][0] and yev[0, :yec[0]].tobytes() == yref["events"][0, :yec[0]].tobytes()
-    assert (yev[0, :yec[0]]["type"] == 16).sum() > 10, "YSF row: FICH events missing"
-    yeng.close()
-
-
 def test_end_to_end_small(emu_ctx, oracle):
-    _end_to_end(emu_ctx, oracle, 3, 50, 8, 1.5, "cpu")
+    """The scene of test_channelizer.py at the capture rate 48 kS/s * M / L."""
+    end_to_end(emu_ctx, oracle, rational(3, 50), end_to_end_fixture(3, 50, 8, 1.5, "cpu", seed=7))
 
 
 @pytest.mark.gpu
@@ -435,4 +236,4 @@ def test_end_to_end_wideband_gpu(gpu_ctx, oracle):
     device: the library passes this test with seed 8, the model's own run is outstanding).  With the device's noise of seed 7 the model itself, like
     the library, decodes a sixth LC with wrong ids in row 10 (-16.5 dB): a false decode that 2 LSB of noise tip either way
     (the CPU generator's noise of seed 7 gives five, all right), not a property of the channelizer."""
-    _end_to_end(gpu_ctx, oracle, 3, 128, 32, 4.0, "cuda", seed=8)
+    end_to_end(gpu_ctx, oracle, rational(3, 128), end_to_end_fixture(3, 128, 32, 4.0, "cuda", seed=8))

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/channelizer_model.py [--interpolation L] [--decimation M] [--rows R] [--seconds S] [--seed N] [--device cuda|cpu]
 [--raster HZ]:
-a float64 model of the rational-rate channelizer on the end-to-end fixture of tests/test_channelizer_rational.py, next to
-the library.
+a float64 model of the rational-rate channelizer on the end-to-end fixture of tests/test_channelizer_rational.py
+(tests/cz_harness.py builds it), next to the library.
 
 The model, per channel: mix the composite down by the channel's offset, convolve with each of the L phases
 h_p[k] = h[r_p + k L] of the prototype (FFT, complex128), take z[j] = (h_p * x)[n_j] with p = j mod L (DESIGN.md section
@@ -118,15 +118,14 @@ def main():
     a = ap.parse_args()
     from digiham_amd import api
     from oracle import oracle as O
-    import test_channelizer_rational as T
+    from cz_harness import end_to_end_fixture
     O.build()
     L, M = a.interpolation, a.decimation
     if a.raster:
-        import test_channelizer_raster as TR
         L = 1
-        f = TR.end_to_end_fixture(M, a.raster, a.rows, a.seconds, a.device, a.seed)
+        f = end_to_end_fixture(1, M, a.rows, a.seconds, a.device, a.seed, raster_hz=a.raster, noise_device="cpu")
     else:
-        f = T.end_to_end_fixture(L, M, a.rows, a.seconds, a.device, a.seed)
+        f = end_to_end_fixture(L, M, a.rows, a.seconds, a.device, a.seed)
     on_device = a.device != "cpu"
     x = f["x"].cpu().numpy() if on_device else f["x"]
     lib = None
