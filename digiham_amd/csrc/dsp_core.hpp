@@ -711,25 +711,41 @@ DH_HD float dh_virtual_sample(const float* tail, uint32_t tc, const float* in, u
 // `agc`: the extremes of ring slots 2 l and 2 l + 1 once more, as a per-lane value -- what the scan hands to the slicing phase in
 // registers.  Defined for the slots k0 .. k1 - 1 (the others: some value of the block, never looked at).
 struct DhAgcPair { float mn0, mx0, mn1, mx1; };
+// What the sps-10 window phase hands on in registers: the volumes (`from_win`: the scan's sources for ring slots 2 l, 2 l + 1 of a
+// run that opens its block, k0 = 0 -- S.vol_new then holds the same values, for the runs and paths that look there) and the
+// mid-symbol sums of the lane's symbols 2 l and 2 l + 1 of the run.
+struct DhWinPair { float vol0, vol1, sum0, sum1, old0, old1; };
 
 #if DH_ON_GPU
 // lane l owns ring slots 2l and 2l+1 for the prefix part; the suffix part is the same scan over the ring read
 // backwards (lane l takes slots 126-2l and 127-2l), handed back to the owning lanes -- lane 63 - l -- by four ds_bpermute
 // (until round 5 through S.mn / S.mx: four stores, a barrier, four loads, a barrier -- one LDS round trip more).  The lane's
 // results (slots 2l and 2l+1) also stay in registers: the slicing phase of a run that starts its block takes them from there.
-__device__ __forceinline__ void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc)) {
+template <bool PAIRS>                                   // PAIRS: behind the sps-10 window phase (DhWinPair; `from_win` only there)
+__device__ __forceinline__ void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc), DH_LANE_STRUCT_IN(DhWinPair, win), bool from_win) {
     const int lane = dh_fresh_lane_id_();
     const uint32_t e0 = 2u * (uint32_t) lane, e1 = e0 + 1u;
     // prefix source: old below k0, new in [k0, k1), identity above
-    const float c0 = e0 < k0 ? S.vol_old[e0] : S.vol_new[e0];
-    const float c1 = e1 < k0 ? S.vol_old[e1] : S.vol_new[e1];
+    float c0, c1;
+    if (!PAIRS) { c0 = e0 < k0 ? S.vol_old[e0] : S.vol_new[e0]; c1 = e1 < k0 ? S.vol_old[e1] : S.vol_new[e1]; }
+    else if (DH_LIKELY(from_win)) { c0 = win.vol0; c1 = win.vol1; }              // (wave-uniform; k0 = 0: nothing of the window phase's is loaded back)
+    else {
+        // (reads the compiler does not track, settled here: a tracked load's wait would be placed where the two paths join, and on
+        // the usual one it drains the window phase's stores in front of the scan)
+        c0 = dh_lds_read_b32<0>(dh_lds_addr((e0 < k0 ? S.vol_old : S.vol_new) + e0));
+        c1 = dh_lds_read_b32<0>(dh_lds_addr((e1 < k0 ? S.vol_old : S.vol_new) + e1));
+        dh_lds_reads_done(c0, c1);
+    }
     const bool v0 = e0 < k1, v1 = e1 < k1;
     const float pmn0 = v0 ? c0 : DH_FLT_MAX, pmn1 = v1 ? c1 : DH_FLT_MAX;
     const float pmx0 = v0 ? c0 : DH_FLT_MIN, pmx1 = v1 ? c1 : DH_FLT_MIN;
     float pmn = dh_vmin(pmn0, pmn1), pmx = dh_vmax(pmx0, pmx1);
     // suffix source: the old ring backwards (slots >= 100 hold the identity)
     const uint32_t r0 = 126u - e0, r1 = r0 + 1u;
-    const float o0 = S.vol_old[r0], o1 = S.vol_old[r1];
+    float o0, o1;
+    if (!PAIRS) { o0 = S.vol_old[r0]; o1 = S.vol_old[r1]; }
+    else if (DH_LIKELY(from_win)) { o0 = win.old0; o1 = win.old1; }
+    else { o0 = dh_lds_read_b32<0>(dh_lds_addr(S.vol_old + r0)); o1 = dh_lds_read_b32<0>(dh_lds_addr(S.vol_old + r1)); dh_lds_reads_done(o0, o1); }
     const float omn0 = r0 < DH_VOLUME_RB_SIZE ? o0 : DH_FLT_MAX, omn1 = r1 < DH_VOLUME_RB_SIZE ? o1 : DH_FLT_MAX;
     const float omx0 = r0 < DH_VOLUME_RB_SIZE ? o0 : DH_FLT_MIN, omx1 = r1 < DH_VOLUME_RB_SIZE ? o1 : DH_FLT_MIN;
     float smn = dh_vmin(omn0, omn1), smx = dh_vmax(omx0, omx1);
@@ -751,14 +767,20 @@ __device__ __forceinline__ void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_
     agc = r;
 }
 #else
-inline void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc)) {
+template <bool PAIRS>
+inline void dh_agc_scan(DhDspShared& S, uint32_t k0, uint32_t k1, DH_LANE_STRUCT_REF(DhAgcPair, agc), DH_LANE_STRUCT_IN(DhWinPair, win), bool from_win) {
     // plain sequential statement of the same thing (harness only)
     float pmn = DH_FLT_MAX, pmx = DH_FLT_MIN;
     for (uint32_t j = 0; j < k0; j++) { pmn = dh_fmin_(pmn, S.vol_old[j]); pmx = dh_fmax_(pmx, S.vol_old[j]); }
     for (uint32_t k = k0; k < k1; k++) {
-        pmn = dh_fmin_(pmn, S.vol_new[k]); pmx = dh_fmax_(pmx, S.vol_new[k]);
+        const float vk = !from_win ? S.vol_new[k] : (k & 1u) ? win[k >> 1].vol1 : win[k >> 1].vol0;      // (from_win: k0 = 0, slot k is symbol k of lane k / 2)
+        pmn = dh_fmin_(pmn, vk); pmx = dh_fmax_(pmx, vk);
         float smn = DH_FLT_MAX, smx = DH_FLT_MIN;
-        for (uint32_t j = k + 1; j < DH_VOLUME_RB_SIZE; j++) { smn = dh_fmin_(smn, S.vol_old[j]); smx = dh_fmax_(smx, S.vol_old[j]); }
+        for (uint32_t j = k + 1; j < DH_VOLUME_RB_SIZE; j++) {
+            // (from_win: the old ring too as the window phase handed it on -- slot j is old0 of lane (126 - j) / 2 for an even j, old1 of lane (127 - j) / 2 for an odd one)
+            const float oj = !from_win ? S.vol_old[j] : (j & 1u) ? win[(127u - j) >> 1].old1 : win[(126u - j) >> 1].old0;
+            smn = dh_fmin_(smn, oj); smx = dh_fmax_(smx, oj);
+        }
         S.mn[k] = dh_fmin_(pmn, smn); S.mx[k] = dh_fmax_(pmx, smx);
     }
     for (uint32_t l = 0; l < DH_WAVE; l++) {
@@ -1083,46 +1105,69 @@ DH_COLD void dh_exact_fir_pass(const DhDspParams& P, DhDspShared& S, uint32_t ne
     }
 }
 
+// One grid for a sps-10 run: the block after a timing step has symbol 0 at 0 and symbol q >= 1 at 10 q + step_off.  Symbol 0's ten
+// filtered samples move by step_off (+-1) in place -- all ten read, then written; word -1 of the window block is the last word of
+// the variance ring, slot 99 of row 9, which this block stores before anything reads it -- and every symbol q sits at 10 q + step_off.
+// Cold and wave-uniform: step_off != 0 only in the run that opens the block behind a timing step.  A kernel that delivers the
+// filtered samples has copied this run's out before (dh_rrc_demod_channel: the KEEPF copy precedes this call).
+DH_COLD void dh_shift_symbol0(float* fbuf, int32_t step_off) {
+    DH_LANE_VALUE(float, t);
+    DH_FOR_LANES_FRESH(lane) { DH_LV(t, lane) = fbuf[lane < 10 ? lane : 0]; }
+    DH_FOR_LANES_FRESH(lane) { if (lane < 10) fbuf[lane + step_off] = DH_LV(t, lane); }
+}
+
 // ---------------------------------------------------------------------------------------------
 // ---- P3: symbol windows (gfsk_demodulator.cpp:28-35, 82-83)
-// sps 10: two symbols per lane -- q = lane + 1 and (lanes 0..34) q = lane + 65, lane 35: symbol 0, the only one in front of the pending
-// timing step -- each read as five ds_read_b64 at compile-time offsets from one per-lane base (eight bytes from a four-byte aligned
-// address: the symbols start 40 bytes apart and a timing step moves them by four).  Ten words per lane, read in pairs, touch every
-// bank twice per 32 lanes: conflict-free.  Until the end of round 5 the two symbols of a lane were 24 symbols apart and a
-// ds_read2_b32 delivered sample i of both as a register pair for packed additions (16 vector instructions less per run): a
-// ten-word lane stride read ONE word at a time only ever reaches the sixteen banks of its parity, every read was a two-way conflict --
-// SQ_LDS_BANK_CONFLICT 4.75e8 -> 1.74e8 per launch, SQ_LDS_IDX_ACTIVE -21 %, chain -2 % (profiles/r05_a_ab_logs.txt).  Each
-// symbol's sums run in sample order, as the reference's do.  Lanes beyond the run read words of the window block that nothing will
-// look at and store nothing.
-// `fbuf`: the run's filtered samples (the window block); symbol q of the run (ring slot k0 + q) starts at q sps (+ step_off behind symbol 0).
-// Leaves S.sum[q], S.vol_new[k0 + q] and column k0 + q of the transposed ring; the caller's barrier publishes them.
+// sps 10: the slicer's pairs -- lane l (0..49) takes symbols 2 l and 2 l + 1 of the run, twenty consecutive words on the run's one
+// grid (dh_shift_symbol0), read as five ds_read_b128 at compile-time offsets from one per-lane base (dh_lds_run<20>, the sps-20
+// body's read: a twenty-word lane stride read four words at a time touches every bank once per eight lanes).  The ring takes
+// row i of both symbols, neighbouring slots, as ONE ds_write2_b32 -- ten stores per lane where the two columns took twenty -- and
+// S.sum / S.vol_new one each; the last symbol of an odd run goes word by word behind a wave-uniform branch.  The lane keeps its
+// two volumes and mid-symbol sums (DhWinPair): the scan and the slicing phase work on the same pairs and, on a run that opens its
+// block, take them from there -- the LDS copies are for the other runs and the rare paths.  Until this form a lane held symbols
+// l + 1 and l + 65 (ten ds_read_b64, twenty ring stores) and every volume and sum changed lane through LDS.  Each symbol's sums
+// run in sample order, as the reference's do.  Lanes beyond the run read words of the window block that nothing will look at and
+// store nothing.
+// `fbuf`: the run's filtered samples (the window block); sps 10: symbol q of the run (ring slot k0 + q) starts at q sps + step_off;
+// the other bodies: at q sps (+ step_off behind symbol 0).
+// Leaves S.sum[q], S.vol_new[k0 + q] and column k0 + q of the transposed ring; the caller's barrier publishes them (sps 10: its
+// stores are left in flight -- the block is one wavefront's and its LDS instructions complete in order, see the call).
+// `win` (sps 10 only): the lane's pair once more, for dh_agc_scan and dh_slice_symbols.
 template <int SPS>
-DH_HD void dh_symbol_windows(DhDspShared& S, const float* fbuf, uint32_t k0, uint32_t m, int32_t step_off, uint32_t sps, uint32_t ev_lo, uint32_t ev_hi, float sps_rcp) {
+DH_HD void dh_symbol_windows(DhDspShared& S, const float* fbuf, uint32_t k0, uint32_t m, int32_t step_off, uint32_t sps, uint32_t ev_lo, uint32_t ev_hi, float sps_rcp,
+                             DH_LANE_STRUCT_REF(DhWinPair, win)) {
 #define DH_FB(n) fbuf[n]
     if (SPS == 10 && DH_STOP_AFTER >= 3) DH_FOR_LANES_FRESH(lane) {
         const uint32_t l = (uint32_t) lane;
-        const uint32_t qa = l + 1u, qb = l < 35u ? l + 65u : 0u;
-        const bool va = qa < m, vb = l < 35u ? qb < m : l == 35u;
-        const float* srca = fbuf + (int32_t) (qa * 10u) + step_off;
-        const float* srcb = l < 35u ? srca + 640 : fbuf;
-        float v[10], w[10];
-        dh_lds_run10_pair(srca, srcb, v, w);
+        const uint32_t qa = 2u * l, qb = qa + 1u;
+        const bool vb = qb < m;                                                                            // both of the lane's symbols belong to the run
+        const float* src = l < 50u ? fbuf + (int32_t) (l * 20u) + step_off : fbuf;                        // (lanes beyond a block read symbols 0 and 1 and store nothing)
+        // (the scan's suffix source, ring slots 126 - 2 l and 127 - 2 l as they stood before this run: requested in front of the
+        // window, so that it arrives with it and the scan starts without a load of its own)
+        float x[20], v[10], w[10], old0, old1;
+        dh_lds_run20_with_pair(src, x, S.vol_old + (126u - qa), old0, old1);
+#pragma unroll
+        for (int i = 0; i < 10; i++) { v[i] = x[i]; w[i] = x[10 + i]; }
         float vola = v[0], volb = w[0];
 #pragma unroll
         for (int i = 1; i < 10; i++) { vola += v[i]; volb += w[i]; }
-        const float mida = ((v[3] + v[4]) + v[5]) + v[6], midb = ((w[3] + w[4]) + w[5]) + w[6];          // samples ev_lo .. ev_hi - 1 = 3 .. 6
+        // samples ev_lo .. ev_hi - 1 = 3 .. 6 (the first chain's steps kept apart from the second's: as one pair of chains the
+        // compiler packed them -- three v_pk_add_f32 behind six v_mov that bring the operands into register pairs)
+        float mida = v[3] + v[4]; DH_TO_VGPR(mida); mida += v[5]; DH_TO_VGPR(mida); mida += v[6]; DH_TO_VGPR(mida);
+        const float midb = ((w[3] + w[4]) + w[5]) + w[6];
         const float volume_a = dh_div_const(vola, 10.0f, sps_rcp), volume_b = dh_div_const(volb, 10.0f, sps_rcp);
-        if (va) {
-            const uint32_t ka = k0 + qa;
-            dh_lds_store_row10<0>(S.var_rb + ka, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);      // transposed ring: phase-major
-            S.sum[qa] = mida; S.vol_new[ka] = volume_a;
-        }
+        const uint32_t ka = k0 + qa;
         if (vb) {
-            const uint32_t kb = k0 + qb;
-            dh_lds_store_row10<0>(S.var_rb + kb, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9]);
-            S.sum[qb] = midb; S.vol_new[kb] = volume_b;
+            dh_lds_store_rows10_pair(S.var_rb + ka, v, w);                                                 // transposed ring: phase-major
+            dh_lds_store_pair(S.sum + qa, mida, midb); dh_lds_store_pair(S.vol_new + ka, volume_a, volume_b);
         }
-        dh_lds_stores_done();
+        if (DH_UNLIKELY((m & 1u) != 0u)) {                                                                 // (wave-uniform: the last symbol of an odd run stands alone)
+            if (qb == m) {
+                dh_lds_store_row10<0>(S.var_rb + ka, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+                S.sum[qa] = mida; S.vol_new[ka] = volume_a;
+            }
+        }
+        DH_LS(win, lane) = DhWinPair{ volume_a, volume_b, mida, midb, old0, old1 };
     }
     // sps 20 (a FIR pass holds at most 51 symbols): one symbol per lane, q = lane + 1, lane 63: symbol 0; its twenty samples as five
     // ds_read_b128 (sixteen bytes from a four-byte aligned address).  Twenty words per lane read in fours touch every bank once per
@@ -1589,7 +1634,7 @@ DH_HD int32_t dh_timing_decision(const DhDspParams& P, DhDspShared& S, DhBoundSt
 // and vote_b (2 l + 1).
 struct DhSliceSetup { bool four_levels, e_pos, width_pow2, pair_store; float T_eff, inv_width; };
 template <int SPS, int LV, bool BOUNDED>
-DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, DH_LANE_STRUCT_IN(DhAgcPair, agc), uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
+DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, DH_LANE_STRUCT_IN(DhAgcPair, agc), DH_LANE_STRUCT_IN(DhWinPair, win), uint8_t* out, uint32_t k0, uint32_t m, uint32_t ev_lo, uint32_t ev_hi,
                             const DhSliceSetup& U, uint64_t& vote_a, uint64_t& vote_b) {
     const bool four_levels = U.four_levels, e_pos = U.e_pos, width_pow2 = U.width_pow2, pair_store = U.pair_store;
     const float T_eff = U.T_eff, inv_width = U.inv_width;
@@ -1599,10 +1644,18 @@ DH_HD void dh_slice_symbols(const DhDspParams& P, DhDspShared& S, DH_LANE_STRUCT
         const uint32_t qq = va ? qa : 0u, k = k0 + qq;                            // (lanes beyond the run recompute symbols 0 / 1: in-range reads, no store)
         // (a run that starts its block: the lane's symbols 2 l, 2 l + 1 are the ring slots the AGC scan left in its registers)
         const DhAgcPair& own = DH_LS(agc, lane);
-        dh_f2 mn, mx;
-        if (k0 == 0u) { mn = dh_f2_make(own.mn0, own.mn1); mx = dh_f2_make(own.mx0, own.mx1); }
-        else { mn = dh_f2_make(S.mn[k], S.mn[k + 1u]); mx = dh_f2_make(S.mx[k], S.mx[k + 1u]); }
-        const dh_f2 sumq = dh_f2_make(S.sum[qq], S.sum[qq + 1u]);
+        // (sps 10 likewise: the lane's two mid-symbol sums are the ones the window phase left in its registers; the other runs load all
+        // three pairs and wait for them where they stand, dh_lds_pairs3_now)
+        const DhWinPair& own_win = DH_LS(win, lane);
+        dh_f2 mn, mx, sumq;
+        if (SPS == 10) {
+            if (DH_LIKELY(k0 == 0u)) { mn = dh_f2_make(own.mn0, own.mn1); mx = dh_f2_make(own.mx0, own.mx1); sumq = dh_f2_make(own_win.sum0, own_win.sum1); }
+            else dh_lds_pairs3_now(S.mn + k, S.mx + k, S.sum + qq, mn, mx, sumq);
+        } else {
+            if (k0 == 0u) { mn = dh_f2_make(own.mn0, own.mn1); mx = dh_f2_make(own.mx0, own.mx1); }
+            else { mn = dh_f2_make(S.mn[k], S.mn[k + 1u]); mx = dh_f2_make(S.mx[k], S.mx[k + 1u]); }
+            sumq = dh_f2_make(S.sum[qq], S.sum[qq + 1u]);
+        }
         const dh_f2 center = dh_f2_scale(dh_f2_add(mx, mn), 0.5f);                // (max + min) / 2.0f: the division by two is exact
         // (sps 20: the division by the window's six samples as reciprocal product + exact residual + correction, dh_div_const; tests/test_numerics.py)
         const dh_f2 average = width_pow2 ? dh_f2_scale(sumq, inv_width) : SPS == 20 ? dh_div_const2(sumq, 6.0f, inv_width)
@@ -2246,22 +2299,32 @@ DH_HD void dh_rrc_demod_channel(const DhDspParams& P, uint32_t ch, DhDspShared& 
         const bool pair_store = ((uint32_t) (uintptr_t) syms + nsym) % 2u == 0u;      // (paired slicing phases: symbols 2 l, 2 l + 1 of the run as one 16-bit store)
 
         // ---- P3: symbol windows (gfsk_demodulator.cpp:28-35, 82-83): dh_symbol_windows
-        dh_symbol_windows<SPS>(S, fbuf, k0, m, step_off, sps, ev_lo, ev_hi, sps_rcp);
-        DH_BARRIER();
+        // (sps 10: one grid first -- behind the KEEPF copy above, which delivers the samples where the FIR put them)
+        DH_LANE_STRUCT(DhWinPair, win) = {};
+        if (SPS == 10 && DH_STOP_AFTER >= 3 && DH_UNLIKELY(step_off != 0)) dh_shift_symbol0(S.xf, step_off);
+        dh_symbol_windows<SPS>(S, fbuf, k0, m, step_off, sps, ev_lo, ev_hi, sps_rcp, win);
+        // (sps 10: no drain here.  The block is one wavefront's, and a wavefront's LDS instructions complete in the order it issued them:
+        // what the scan below loads -- on a run with k0 != 0 the volumes other lanes stored -- was stored by older instructions, and
+        // the window words it stores S.mn / S.mx over have arrived in every lane's registers, dh_lds_run waits for them.  The
+        // scan's vector work runs while the window phase's twelve stores drain; the barrier behind the scan waits for both.)
+        if (SPS != 10) DH_BARRIER();
         DH_PHASE_MARK(2);
 
         dh_issue_next_window<NZ, PF_REG>(S, in, tc, p_next, pf_plain, pf_reg, pfr);
 
         // ---- P4: sliding AGC min/max as two wave scans
         DH_LANE_STRUCT(DhAgcPair, agc) = {};
-        if (DH_STOP_AFTER >= 4) dh_agc_scan(S, k0, k0 + m, agc);
-        DH_BARRIER();
+        if (DH_STOP_AFTER >= 4) dh_agc_scan<SPS == 10>(S, k0, k0 + m, agc, win, SPS == 10 && k0 == 0u);
+        // (sps 10, as above: on a run that opens its block the slicing phase takes extremes and sums from registers and loads nothing;
+        // on the others its loads of S.mn / S.mx / S.sum are younger than the stores.  Whoever next reads what these phases stored -- the
+        // timing decision, P7 -- waits for its own loads, which return behind them.)
+        if (SPS != 10) DH_BARRIER();
         DH_PHASE_MARK(3);
 
         // ---- P5: thresholds + slice (gfsk_demodulator.cpp:88-106 / fsk_demodulator.cpp:89-99): dh_slice_symbols; what it leaves in doubt: dh_settle_doubts
         if (DH_STOP_AFTER >= 5) {
             const DhSliceSetup U = { four_levels, e_pos, width_pow2, pair_store, T_eff, inv_width };
-            dh_slice_symbols<SPS, LV, BOUNDED>(P, S, agc, syms + nsym, k0, m, ev_lo, ev_hi, U, vote_a, vote_b);
+            dh_slice_symbols<SPS, LV, BOUNDED>(P, S, agc, win, syms + nsym, k0, m, ev_lo, ev_hi, U, vote_a, vote_b);
         }
         if (BOUNDED && DH_UNLIKELY((vote_a | vote_b) != 0)) {
             dh_settle_doubts<NZ>(P, S, BS, V, syms + nsym, k0, e_eff, sps, ev_lo, ev_hi, vote_a, vote_b);

@@ -272,6 +272,15 @@ template <int OFF_BYTES> __device__ __forceinline__ dh_f2 dh_lds_read_b64(uint32
     asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF_BYTES) : "memory");
     return v;
 }
+template <int OFF_BYTES> __device__ __forceinline__ float dh_lds_read_b32(uint32_t addr) {
+    float v;
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF_BYTES) : "memory");
+    return v;
+}
+// the wait that settles such reads: names their destinations (the compiler knows nothing of the reads and adds no wait of its own --
+// where a value is wanted only phases later, a wait of the compiler's at the first use would drain every LDS store issued since)
+__device__ __forceinline__ void dh_lds_reads_done(float& a, float& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b) :: "memory"); }
+__device__ __forceinline__ uint32_t dh_lds_addr(const float* p) { return (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) p; }
 template <int OFF_BYTES> __device__ __forceinline__ dh_v4f dh_lds_read_b128(uint32_t addr) {
     dh_v4f v;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF_BYTES) : "memory");
@@ -300,23 +309,36 @@ template <int N> DH_HD void dh_lds_run(const float* src, float (&v)[N]) {
     for (int i = 0; i < N; i++) v[i] = src[i];
 #endif
 }
-// The same for TWO runs of ten floats, v[i] = srca[i], w[i] = srcb[i]: ten ds_read_b64 (eight bytes from a four-byte aligned
-// address), all in flight together, ONE wait for both runs.
-DH_HD void dh_lds_run10_pair(const float* srca, const float* srcb, float (&v)[10], float (&w)[10]) {
+// dh_lds_run<20> and, requested in front of it and settled by the same wait, the two floats at `pair` (8-byte aligned): p0 =
+// pair[0], p1 = pair[1].  Device: a read the compiler does not track -- one it tracks it waits for at the first use, and where that
+// is phases later the wait drains every LDS store issued in between.
+DH_HD void dh_lds_run20_with_pair(const float* src, float (&v)[20], const float* pair, float& p0, float& p1) {
 #if DH_ON_GPU
-    const uint32_t aa = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) srca;
-    const uint32_t ab = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) srcb;
-    dh_f2 x0 = dh_lds_read_b64<0>(aa), x1 = dh_lds_read_b64<8>(aa), x2 = dh_lds_read_b64<16>(aa), x3 = dh_lds_read_b64<24>(aa), x4 = dh_lds_read_b64<32>(aa);
-    dh_f2 y0 = dh_lds_read_b64<0>(ab), y1 = dh_lds_read_b64<8>(ab), y2 = dh_lds_read_b64<16>(ab), y3 = dh_lds_read_b64<24>(ab), y4 = dh_lds_read_b64<32>(ab);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3), "+v"(y4) :: "memory");
-    v[0] = x0.x; v[1] = x0.y; v[2] = x1.x; v[3] = x1.y; v[4] = x2.x; v[5] = x2.y; v[6] = x3.x; v[7] = x3.y; v[8] = x4.x; v[9] = x4.y;
-    w[0] = y0.x; w[1] = y0.y; w[2] = y1.x; w[3] = y1.y; w[4] = y2.x; w[5] = y2.y; w[6] = y3.x; w[7] = y3.y; w[8] = y4.x; w[9] = y4.y;
+    dh_f2 q = dh_lds_read_b64<0>((uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) pair);
+    dh_lds_run<20>(src, v);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(q) :: "memory");
+    p0 = q.x; p1 = q.y;
 #else
-    for (int i = 0; i < 10; i++) { v[i] = srca[i]; w[i] = srcb[i]; }
+    dh_lds_run<20>(src, v);
+    p0 = pair[0]; p1 = pair[1];
+#endif
+}
+// Three pairs of neighbouring floats from LDS, here and now: a = (pa[0], pa[1]), b and c likewise.  Device: three ds_read2_b32 the
+// compiler does not track, in flight together, and their wait -- for a rare path that joins a usual one which loads nothing:
+// the wait for a tracked load is placed behind the join and drains, on the usual path, every LDS store still in flight.
+DH_HD void dh_lds_pairs3_now(const float* pa, const float* pb, const float* pc, dh_f2& a, dh_f2& b, dh_f2& c) {
+#if DH_ON_GPU
+    a = dh_lds_read2<0, 1>((uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) pa);
+    b = dh_lds_read2<0, 1>((uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) pb);
+    c = dh_lds_read2<0, 1>((uint32_t) (uintptr_t) (const __attribute__((address_space(3))) float*) pc);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c) :: "memory");
+#else
+    a = dh_f2_make(pa[0], pa[1]); b = dh_f2_make(pb[0], pb[1]); c = dh_f2_make(pc[0], pc[1]);
 #endif
 }
 
-// LDS stores the compiler does not track: dh_lds_stores_done() must come before the barrier that publishes them.
+// LDS stores the compiler does not track: dh_lds_stores_done() must come before the barrier that publishes them (where one does:
+// a block that is ONE wavefront's needs neither, its LDS instructions complete in the order they were issued).
 //   dh_lds_store4_at<OFF_WORDS>(base, v)   base[OFF_WORDS .. OFF_WORDS + 3] = v
 //   dh_lds_store_row10<K>(base, a0 .. a9)  base[100 i + K] = a_i: ten floats into one column of the transposed variance
 //                                          ring (row i is DH_VARIANCE_SYMBOLS = 100 words further; K = column offset)
@@ -342,9 +364,34 @@ template <int K> __device__ __forceinline__ void dh_lds_store_row10(float* base,
                     "n"(4 * K), "n"(4 * (K + 100)), "n"(4 * (K + 200)), "n"(4 * (K + 300)), "n"(4 * (K + 400)), "n"(4 * (K + 500)), "n"(4 * (K + 600)),
                     "n"(4 * (K + 700)), "n"(4 * (K + 800)), "n"(4 * (K + 900)) : "memory");
 }
+//   dh_lds_store_pair(base, a, b)          base[0] = a, base[1] = b
+//   dh_lds_store_rows10_pair(base, a, b)   base[100 i] = a[i], base[100 i + 1] = b[i]: two neighbouring columns of the ring
+// Two neighbouring words from two registers of their own: one ds_write2_b32 (offset1 = offset0 + 1).  A ds_write_b64 wants its
+// two words in an aligned register pair -- the columns' values come out of different 16-byte reads, a v_mov per pair -- and
+// an 8-byte aligned address; this form takes any registers and any dword address.  Its offsets are 8-bit dword counts: three
+// rows per base, one VALU addition per further base.
+__device__ __forceinline__ void dh_lds_store_pair(float* base, float a, float b) {
+    const uint32_t addr = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) base;
+    asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" :: "v"(addr), "v"(a), "v"(b) : "memory");
+}
+__device__ __forceinline__ void dh_lds_store_rows3_pair_(uint32_t addr, float a0, float b0, float a1, float b1, float a2, float b2) {
+    asm volatile("ds_write2_b32 %0, %1, %2 offset1:1\n\tds_write2_b32 %0, %3, %4 offset0:100 offset1:101\n\tds_write2_b32 %0, %5, %6 offset0:200 offset1:201"
+                 :: "v"(addr), "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2) : "memory");
+}
+__device__ __forceinline__ void dh_lds_store_rows10_pair(float* base, const float (&a)[10], const float (&b)[10]) {
+    const uint32_t addr = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) float*) base;
+    dh_lds_store_rows3_pair_(addr, a[0], b[0], a[1], b[1], a[2], b[2]);
+    dh_lds_store_rows3_pair_(addr + 1200u, a[3], b[3], a[4], b[4], a[5], b[5]);
+    dh_lds_store_rows3_pair_(addr + 2400u, a[6], b[6], a[7], b[7], a[8], b[8]);
+    asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" :: "v"(addr + 3600u), "v"(a[9]), "v"(b[9]) : "memory");
+}
 #else
 template <int OFF_WORDS> inline void dh_lds_store4_at(float* base, const dh_f4& v) { dh_store4(base + OFF_WORDS, v); }
 inline void dh_lds_stores_done() {}
+inline void dh_lds_store_pair(float* base, float a, float b) { base[0] = a; base[1] = b; }
+inline void dh_lds_store_rows10_pair(float* base, const float (&a)[10], const float (&b)[10]) {
+    for (int i = 0; i < 10; i++) { base[i * 100] = a[i]; base[i * 100 + 1] = b[i]; }
+}
 template <int K> inline void dh_lds_store_row10(float* base, float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, float a8, float a9) {
     const float a[10] = { a0, a1, a2, a3, a4, a5, a6, a7, a8, a9 };
     for (int i = 0; i < 10; i++) base[i * 100 + K] = a[i];

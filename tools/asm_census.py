@@ -20,6 +20,14 @@ KERNELS = OrderedDict((("dmr", "_ZN12_GLOBAL__N_17k_chainILi80ELb0ELi1ELi10ELi0E
                        ("nxdn", "_ZN12_GLOBAL__N_17k_chainILi160ELb0ELi3ELi20ELi0EE")))
 
 
+# DH_CENSUS_MORE=1: the other kernels that hold the sps-10 slicer loop as well (the chains without an RRC stage or with the FMA FIR,
+# the stand-alone slicers with and without the filter, and the two that also deliver the filtered samples)
+if os.environ.get("DH_CENSUS_MORE"):
+    KERNELS.update((("dstar", "_ZN12_GLOBAL__N_17k_chainILi0ELb0ELi5ELi10ELi0EE"), ("dmr_norrc", "_ZN12_GLOBAL__N_17k_chainILi0ELb0ELi1ELi10ELi0EE"),
+                    ("dmr_fast", "_ZN12_GLOBAL__N_17k_chainILi80ELb1ELi1ELi10ELi0EE"), ("demod0", "_ZN12_GLOBAL__N_111k_rrc_demodILi0ELb0ELi10ELi0EE"),
+                    ("demod80", "_ZN12_GLOBAL__N_111k_rrc_demodILi80ELb0ELi10ELi0EE"), ("demod80_fast", "_ZN12_GLOBAL__N_111k_rrc_demodILi80ELb1ELi10ELi0EE"),
+                    ("demod80_keepf1", "_ZN12_GLOBAL__N_111k_rrc_demodILi80ELb0ELi10ELi1EE"), ("demod80_keepf2", "_ZN12_GLOBAL__N_111k_rrc_demodILi80ELb0ELi10ELi2EE")))
+
 def kind(op):
     if op.startswith("v_mfma"): return "mfma"
     if op.startswith("v_"): return "vector"
