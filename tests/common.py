@@ -217,94 +217,3 @@ def bptc_pattern_fixture(path):
     out = np.zeros((n, 12), np.uint8)
     out[ok == 1] = z["out_ok"]
     return ok, out, z
-
-
-def run_dmr_decoder(ctx, syms, cuts, scalar, monkeypatch):
-    """Dibit streams syms[B][n] through a decoder-only DMR engine in pushes of cuts[0], cuts[1], ... symbols; pass B of the decoder
-    lane-parallel where a chunk allows it or, with `scalar`, burst after burst throughout (DH_DMR_SCALAR_PASS_B, read when the engine is
-    created) -> per channel (frame bytes, event bytes), and per push the counters' increments [(lanes[B], scalar[B])]"""
-    B, n = syms.shape
-    if scalar:
-        monkeypatch.setenv("DH_DMR_SCALAR_PASS_B", "1")
-    else:
-        monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-    eng = api.Engine(B, max(cuts), rrc="none", demod="none", proto="dmr", ctx=ctx)
-    monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-    frames, events, counts = [[] for _ in range(B)], [[] for _ in range(B)], []
-    seen = (np.zeros(B, np.int64), np.zeros(B, np.int64))
-    lo = 0
-    for c in cuts:
-        if lo >= n:
-            break
-        part = np.ascontiguousarray(syms[:, lo:lo + c])
-        lo += c
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        eng.sync()                                               # raises when the push ran into the event or frame capacity
-        f, fc = eng.frames(); e, ec = eng.events()
-        for b in range(B):
-            frames[b].append(f[b, :fc[b]].copy()); events[b].append(e[b, :ec[b]].copy())
-        now = tuple(a.astype(np.int64) for a in eng.dmr_pass_b_stats())
-        counts.append((now[0] - seen[0], now[1] - seen[1]))
-        seen = now
-    eng.close()
-    return [(np.concatenate(frames[b]).tobytes(), np.concatenate(events[b]).tobytes()) for b in range(B)], counts
-
-
-def run_dmr_symbols(ctx, streams, chunk, scalar, monkeypatch):
-    """run_dmr_decoder in pushes of `chunk` symbols (None: one push) -> per channel (frame bytes as an array, events as records), and the
-    (lane-parallel, burst-serial) chunk counts per channel over the whole run"""
-    n = streams.shape[1]
-    chunk = n if chunk is None else chunk
-    got, counts = run_dmr_decoder(ctx, streams, [chunk] * -(-n // chunk), scalar, monkeypatch)
-    return ([(np.frombuffer(f, np.uint8), np.frombuffer(e, api.EVENT_DTYPE)) for f, e in got],
-            (sum(l for l, _ in counts), sum(s for _, s in counts)))
-
-
-# ------------------------------------------------------------------ whole frames through a decoder-only engine (D-Star, POCSAG)
-def frames_fixture():
-    """tests/golden/frames_ref.npz (make_golden_frames.py): damaged D-Star radio headers and POCSAG codewords with what the
-    reference's Header::parseFromHeader / Codeword::parse made of them"""
-    import os
-    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frames_ref.npz")) as z:
-        return {k: z[k] for k in z.files}
-
-
-def event_record(sym_index, typ, a=0, b=0, payload=b""):
-    """one expected decoder event (api.EVENT_DTYPE), payload zero padded as dh_emit pads it"""
-    e = np.zeros(1, api.EVENT_DTYPE)
-    e["sym_index"], e["type"], e["a"], e["b"], e["len"] = sym_index, typ, a, b, len(payload)
-    e["payload"][0, :len(payload)] = np.frombuffer(bytes(payload), np.uint8)
-    return e
-
-
-def stack_rows(rows):
-    """rows of unequal length -> [B][n] uint8, zero padded"""
-    n = max(len(r) for r in rows)
-    return np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows]).astype(np.uint8)
-
-
-def decode_symbol_rows(ctx, proto, rows, size, pitch=None):
-    """symbol rows [B][n] through a decoder-only engine in pushes of `size` symbols (pitch = row pitch of the pushed buffer)
-    -> per channel (output bytes, events)"""
-    B, n = rows.shape
-    pitch = max(size, 64) if pitch is None else pitch
-    eng = api.Engine(B, pitch, rrc="none", demod="none", proto=proto, ctx=ctx)
-    o, e = [[] for _ in range(B)], [[] for _ in range(B)]
-    for lo in range(0, n, size):
-        m = min(size, n - lo)
-        part = np.zeros((B, pitch), np.uint8); part[:, :m] = rows[:, lo:lo + m]
-        eng.push_symbols(part, np.full(B, m, np.uint32))
-        eng.sync()                                               # raises when the push ran into the event or frame capacity
-        f, fc = eng.frames(); ev, ec = eng.events()
-        for b in range(B):
-            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
-    eng.close()
-    return [(np.concatenate(x), np.concatenate(y)) for x, y in zip(o, e)]
-
-
-def first_difference(got, want):
-    """a readable account of where two event arrays part (for assertion messages)"""
-    for i in range(min(len(got), len(want))):
-        if got[i].tobytes() != want[i].tobytes():
-            return "event %d: got %s, expected %s" % (i, got[i], want[i])
-    return "%d events, expected %d" % (len(got), len(want))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from common import assert_matches_oracle, make_channels, rel_err, rel_err_per_channel, run_engine, sha
+from dec_harness import assert_rows, expected, run_symbols
 from digiham_amd import api, synth
 
 
@@ -173,24 +174,11 @@ def test_dmr_slot_filter(ctx, oracle):
 
 def test_decoder_only_engine(ctx, oracle):
     """push_symbols: the decoder stage alone, fed dibits (what dmr_decoder sees on its stdin)."""
-    from digiham_amd import api
     for proto in ("dmr", "ysf"):
         s = [synth.dmr_stream(51, 20), synth.dmr_stream(52, 20)] if proto == "dmr" else [synth.ysf_stream(53, 6), synth.ysf_stream(54, 6)]
         n = min(len(a) for a in s)
         syms = np.stack([a[:n] for a in s])
-        eng = api.Engine(2, n, rrc="none", demod="none", proto=proto, ctx=ctx)
-        got_f, got_e = [[], []], [[], []]
-        for lo in range(0, n, 1000):
-            part = np.ascontiguousarray(syms[:, lo:lo + 1000])
-            eng.push_symbols(part, np.full(2, part.shape[1], np.uint32))
-            f, fc = eng.frames(); e, ec = eng.events()
-            for b in range(2):
-                got_f[b].append(f[b, :fc[b]].copy()); got_e[b].append(e[b, :ec[b]].copy())
-        for b in range(2):
-            d = oracle.Decoder(proto)
-            o, ev = d.process(syms[b])
-            assert (np.concatenate(got_f[b]) == o).all()
-            assert np.concatenate(got_e[b]).tobytes() == ev.tobytes()
+        assert_rows(run_symbols(ctx, proto, syms, 1000, capacity=n), expected(oracle, proto, syms), proto)
 
 
 def test_dmr_sync_loss_at_every_burst_index(ctx, oracle):
@@ -199,7 +187,6 @@ def test_dmr_sync_loss_at_every_burst_index(ctx, oracle):
     different burst -- channel c from burst c on, for 8 to 20 bursts of random dibits (sync counters run down, META_RESET, SyncPhase,
     re-acquisition somewhere inside the next chunk) -- in one push, in pushes of 1 000 symbols and in pushes of a few symbols more than
     a burst: decoder bytes and events equal the reference-shaped oracle decoder's (dmr_phase.cpp:35-47, :163-204) for every index."""
-    from digiham_amd import api
     rng = np.random.default_rng(2024)
     B, nb = 72, 150
     rows = []
@@ -213,24 +200,10 @@ def test_dmr_sync_loss_at_every_burst_index(ctx, oracle):
         rows.append(s)
     n = min(len(r) for r in rows)
     syms = np.stack([r[:n] for r in rows])
-    want = []
-    for b in range(B):
-        o, ev = oracle.Decoder("dmr").process(syms[b])
-        want.append((o, ev.tobytes()))
+    want = expected(oracle, "dmr", syms)
     for step in (n, 1000, 151):
-        eng = api.Engine(B, min(step, n), rrc="none", demod="none", proto="dmr", ctx=ctx)
-        got_f, got_e = [[] for _ in range(B)], [[] for _ in range(B)]
-        for lo in range(0, n, step):
-            part = np.ascontiguousarray(syms[:, lo:lo + step])
-            eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-            f, fc = eng.frames(); e, ec = eng.events()
-            for b in range(B):
-                got_f[b].append(f[b, :fc[b]].copy()); got_e[b].append(e[b, :ec[b]].copy())
-        for b in range(B):
-            assert (np.concatenate(got_f[b]) == want[b][0]).all(), (step, b)
-            assert np.concatenate(got_e[b]).tobytes() == want[b][1], (step, b)
-        eng.close()
-    assert any(3 in set(np.frombuffer(w[1], api.EVENT_DTYPE)["type"].tolist()) for w in want)      # META_RESETs happened
+        assert_rows(run_symbols(ctx, "dmr", syms, step, capacity=min(step, n)), want, "pushes of %d" % step)
+    assert any(3 in set(ev["type"].tolist()) for _, ev in want)      # META_RESETs happened
 
 
 def test_ysf_sync_loss_at_every_frame_index(ctx, oracle):
@@ -238,7 +211,6 @@ def test_ysf_sync_loss_at_every_frame_index(ctx, oracle):
     frame that sends it back to its SyncPhase invalidates what was decoded ahead.  Every channel loses its signal at a different frame
     (channel c from frame c on, 14 to 20 frames of random dibits), with scattered wrong dibits elsewhere (clean, repaired and Viterbi-decoded
     codewords side by side), in one push and in pushes of 1 000 and of 481 symbols: decoder bytes and events equal the oracle decoder's."""
-    from digiham_amd import api
     rng = np.random.default_rng(2025)
     B, nfr = 24, 48
     rows = []
@@ -252,24 +224,10 @@ def test_ysf_sync_loss_at_every_frame_index(ctx, oracle):
         rows.append(s)
     n = min(len(r) for r in rows)
     syms = np.stack([r[:n] for r in rows])
-    want = []
-    for b in range(B):
-        o, ev = oracle.Decoder("ysf").process(syms[b])
-        want.append((o, ev.tobytes()))
+    want = expected(oracle, "ysf", syms)
     for step in (n, 1000, 481):
-        eng = api.Engine(B, min(step, n), rrc="none", demod="none", proto="ysf", ctx=ctx)
-        got_f, got_e = [[] for _ in range(B)], [[] for _ in range(B)]
-        for lo in range(0, n, step):
-            part = np.ascontiguousarray(syms[:, lo:lo + step])
-            eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-            f, fc = eng.frames(); e, ec = eng.events()
-            for b in range(B):
-                got_f[b].append(f[b, :fc[b]].copy()); got_e[b].append(e[b, :ec[b]].copy())
-        for b in range(B):
-            assert (np.concatenate(got_f[b]) == want[b][0]).all(), (step, b)
-            assert np.concatenate(got_e[b]).tobytes() == want[b][1], (step, b)
-        eng.close()
-    assert any(20 in set(np.frombuffer(w[1], api.EVENT_DTYPE)["type"].tolist()) for w in want)     # META_RESETs happened
+        assert_rows(run_symbols(ctx, "ysf", syms, step, capacity=min(step, n)), want, "pushes of %d" % step)
+    assert any(20 in set(ev["type"].tolist()) for _, ev in want)     # META_RESETs happened
 
 
 def test_dmr_event_row_overflow_truncates_like_the_burst_serial_decoder(ctx, oracle):

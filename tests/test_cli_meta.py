@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from dec_harness import run_symbols
 from digiham_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -257,14 +258,8 @@ def _dmr_call_with_embedded(rng, lcs, cc=1, dst=1234, src=5678901):
 
 
 def _lines_from_engine(ctx, tmp_path, proto, syms):
-    eng = api.Engine(1, len(syms), rrc="none", demod="none", proto=proto, ctx=ctx)
-    batches = []
-    for lo in range(0, len(syms), 5000):                        # several decoder calls, as a pipe would deliver them
-        part = np.ascontiguousarray(syms[None, lo:lo + 5000])
-        eng.push_symbols(part, np.array([part.shape[1]], np.uint32))
-        e, ec = eng.events()
-        batches.append([e[0, i:i + 1] for i in range(ec[0])])
-    eng.close()
+    run = run_symbols(ctx, proto, syms[None], 5000, capacity=len(syms))     # several decoder calls, as a pipe would deliver them
+    batches = [[e[i:i + 1] for i in range(len(e))] for e in run.events_by_push[0]]
     exe = _meta_test(tmp_path)
     return subprocess.run([exe, proto], input=_batches(batches), capture_output=True, check=True).stdout.split(b"\n")
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from common import assert_matches_oracle, make_channels, run_engine
+from dec_harness import SymbolRun
 from digiham_amd import _capi, api, synth
 from test_monitor import PUSH, WANT, check, chunks, drive
 from test_monitor_device import same_blocks
@@ -57,39 +58,24 @@ def cuts_of(n, step):
 
 class Run:
     """a decoder-only DMR engine fed syms[B][n] in pushes of cuts[0], cuts[1], ... symbols: per channel the frames of every push, the
-    events, and the pass B counters at the end"""
+    events, and the pass B counters at the end.  scalar: pass B burst after burst (True) or lane-parallel where a chunk allows it
+    (False); None leaves DH_DMR_SCALAR_PASS_B as the process has it.  before_push(eng, k, lo) runs in front of push k."""
 
-    def __init__(self, ctx, syms, cuts, both=True, scalar=False, monkeypatch=None, before_push=None, max_syms=None, **kw):
-        B, n = syms.shape
-        if monkeypatch is not None:
-            if scalar:
-                monkeypatch.setenv("DH_DMR_SCALAR_PASS_B", "1")
-            else:
-                monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-        eng = api.Engine(B, max_syms or max(cuts), rrc="none", demod="none", proto="dmr", ctx=ctx, dmr_both_slots=both, **kw)
-        if monkeypatch is not None:
-            monkeypatch.delenv("DH_DMR_SCALAR_PASS_B", raising=False)
-        self.pushes, self.events = [[] for _ in range(B)], [[] for _ in range(B)]
-        self.stride = eng._view("frames")[1]
-        lo = 0
-        for k, c in enumerate(cuts):
-            if lo >= n:
-                break
+    def __init__(self, ctx, syms, cuts, both=True, scalar=None, before_push=None, max_syms=None, **kw):
+        env = None if scalar is None else {"DH_DMR_SCALAR_PASS_B": "1" if scalar else None}
+        with SymbolRun(ctx, "dmr", syms, cuts, capacity=max_syms or max(cuts), env=env, dmr_both_slots=both, **kw) as run:
+            self.stride = run.eng._view("frames")[1]
             if before_push is not None:
-                before_push(eng, k, lo)
-            part = np.array(syms[:, lo:lo + c])                  # (a copy: the shared streams are read-only)
-            lo += c
-            eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-            eng.sync()                                           # raises when the push ran into the event or frame capacity
-            f, fc = eng.frames(); e, ec = eng.events()
-            for b in range(B):
-                self.pushes[b].append(f[b, :fc[b]].copy()); self.events[b].append(e[b, :ec[b]].copy())
-        self.lanes, self.scalar = (a.astype(np.int64) for a in eng.dmr_pass_b_stats())
-        self.active = eng.debug_header(100 + 8).astype(np.int32)       # DS_ACTIVE_SLOT
-        self.phase = eng.debug_header(100 + 0)
-        eng.close()
-        self.frames = [np.concatenate(p).tobytes() for p in self.pushes]
-        self.ev = [np.concatenate(e).tobytes() for e in self.events]
+                before_push(run.eng, 0, 0)
+            for k in run:
+                if before_push is not None and k + 1 < len(run.plan):
+                    before_push(run.eng, k + 1, run.plan[k + 1][0])
+            self.lanes, self.scalar = (a.astype(np.int64) for a in run.eng.dmr_pass_b_stats())
+            self.active = run.eng.debug_header(100 + 8).astype(np.int32)       # DS_ACTIVE_SLOT
+            self.phase = run.eng.debug_header(100 + 0)
+        self.pushes, self.events = run.frames_by_push, run.events_by_push
+        self.frames = [f.tobytes() for f in run.frames]
+        self.ev = [e.tobytes() for e in run.events]
 
 
 def split(frame_bytes):
@@ -239,12 +225,12 @@ def test_filter_calls_and_reset(ctx, oracle):
 
 
 # ------------------------------------------------------------------ 4. both passes
-def test_both_passes(ctx, oracle, monkeypatch):
+def test_both_passes(ctx, oracle):
     syms = streams()
     want = wanted(oracle, "streams", syms)
     cuts = cuts_of(syms.shape[1], 9300)
-    run = Run(ctx, syms, cuts, monkeypatch=monkeypatch)
-    twin = Run(ctx, syms, cuts, scalar=True, monkeypatch=monkeypatch)
+    run = Run(ctx, syms, cuts, scalar=False)
+    twin = Run(ctx, syms, cuts, scalar=True)
     assert_both(run, want, 3, "lanes")
     assert run.frames == twin.frames and run.ev == twin.ev
     assert (twin.lanes == 0).all() and (twin.scalar > 0).all()
@@ -378,22 +364,20 @@ def test_errors_and_default(ctx, oracle):
 def test_outpack(ctx):
     syms = streams()
     B = syms.shape[0]
-    eng = api.Engine(B, 5000, rrc="none", demod="none", proto="dmr", ctx=ctx, dmr_both_slots=True)
     pack = api.OutPack(4 * B, 4096, 1 << 16, ctx=ctx)
     want = []
-    for k in range(2):
-        eng.push_symbols(np.array(syms[:, 5000 * k:5000 * (k + 1)]), np.full(B, 5000, np.uint32))
-        pack.append(eng, user=k)
-        (f, fc), (e, ec) = eng.frames(), eng.events()
-        want += [(b, k, f[b, :fc[b]].tobytes(), e[b, :ec[b]].tobytes()) for b in range(B) if fc[b] or ec[b]]
-    header, entries, events, frames = pack.read()
+    with SymbolRun(ctx, "dmr", syms[:, :10000], 5000, capacity=5000, dmr_both_slots=True) as run:
+        for k in run:
+            pack.append(run.eng, user=k)
+            got = [(b, k, run.frames_by_push[b][k].tobytes(), run.events_by_push[b][k].tobytes()) for b in range(B)]
+            want += [g for g in got if g[2] or g[3]]
+        header, entries, events, frames = pack.read()
     assert pack.rc == 0 and header["dropped"] == 0 and len(entries) == len(want) >= B
     assert (entries["n_frame_bytes"] % REC == 0).all() and entries["n_frame_bytes"].sum() > 20 * REC
     got = [(blk["channel"], blk["user"], blk["frames"].tobytes(), blk["events"].tobytes())
            for blk in api._packed_blocks(entries, events, frames, "user", "tag")]
     assert got == want
     pack.close()
-    eng.close()
 
 
 class Three:

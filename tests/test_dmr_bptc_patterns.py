@@ -25,7 +25,8 @@ import os
 import numpy as np
 import pytest
 
-from common import BPTC_CLASSES, BPTC_PATTERN_SEED, bptc_pattern_fixture, bptc_patterns, npz_digest, run_dmr_symbols
+from common import BPTC_CLASSES, BPTC_PATTERN_SEED, bptc_pattern_fixture, bptc_patterns, npz_digest
+from dec_harness import expected, is_emu, run_dmr_pass_b
 from digiham_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,10 +110,6 @@ SYNCS = [np.array(synth.DMR_SYNC[k], np.uint8) for k in ("bs_data", "ms_data")]
 LEAD0 = 29
 
 
-def _is_emu(ctx):
-    return type(ctx.mem).__name__ == "NumpyMemory"
-
-
 def _slot_type_dibits():
     """[256][10]: Golay(20,8) of cc << 4 | dt as ten dibits, first on top (dmr_phase.cpp:236-245)"""
     w = np.array([synth.block_encode("golay_20_8", v) for v in range(256)], np.uint32)
@@ -192,8 +189,8 @@ def _check_events_by_rule(pat, ev, lead, idx, dt, cc, what):
     assert (e["b"] == dt[m]).all() and (e["len"] == 0).all(), what
 
 
-def test_vectors_as_data_bursts(ctx, oracle, pat, monkeypatch):
-    emu = _is_emu(ctx)
+def test_vectors_as_data_bursts(ctx, oracle, pat):
+    emu = is_emu(ctx)
     B = 8 if emu else 64
     idx = _pick(pat, 40 if emu else None)
     assert set(pat["cls"][idx].tolist()) == set(range(len(BPTC_CLASSES))) and (emu or len(idx) == len(pat["ok"]))
@@ -201,9 +198,10 @@ def test_vectors_as_data_bursts(ctx, oracle, pat, monkeypatch):
     K = vidx.shape[1]
     assert K > 64                                                 # more than the chunk behind the sync search: pass B goes lane-parallel
     assert len({int(l) % 2 for l in leads}) == 2 and len(set(leads.tolist())) == min(B, 32)
-    want = [oracle.Decoder("dmr").process(row) for row in streams]
+    want = expected(oracle, "dmr", streams)
 
-    got, (lanes, serial) = run_dmr_symbols(ctx, streams, None, False, monkeypatch)
+    run, counts = run_dmr_pass_b(ctx, streams, None, False)
+    got, (lanes, serial) = run.results, counts.sum(axis=0)
     assert (lanes > 0).all() and (serial == 1).all(), (lanes, serial)   # only the chunk behind the search is taken burst after burst
     for b in range(B):
         _check_events_by_rule(pat, got[b][1], int(leads[b]), vidx[b], dt[b], cc[b], "channel %d" % b)
@@ -211,13 +209,15 @@ def test_vectors_as_data_bursts(ctx, oracle, pat, monkeypatch):
         assert got[b][1].tobytes() == want[b][1].tobytes(), "channel %d: events differ from the oracle's" % b
         assert len(got[b][0]) == 0 == len(want[b][0]), "channel %d: frame bytes from data bursts" % b
 
-    forced, (lanes, serial) = run_dmr_symbols(ctx, streams, None, True, monkeypatch)
+    run, counts = run_dmr_pass_b(ctx, streams, None, True)
+    forced, (lanes, serial) = run.results, counts.sum(axis=0)
     assert (lanes == 0).all() and (serial > 1).all()
     for b in range(B):
         assert forced[b][1].tobytes() == got[b][1].tobytes() and len(forced[b][0]) == 0, "channel %d: the burst-serial pass B differs" % b
 
     sub = slice(0, B if emu else 8)                               # bursts straddle the pushes
-    pushed, (lanes, serial) = run_dmr_symbols(ctx, streams[sub], 997, False, monkeypatch)
+    run, counts = run_dmr_pass_b(ctx, streams[sub], 997, False)
+    pushed, (lanes, serial) = run.results, counts.sum(axis=0)
     assert (lanes > 0).all()
     for b in range(sub.stop):
         assert pushed[b][1].tobytes() == got[b][1].tobytes() and len(pushed[b][0]) == 0, "channel %d: pushes of 997 symbols differ" % b

@@ -16,8 +16,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from common import assert_matches_oracle, run_dmr_decoder as run_decoder, run_engine
-from digiham_amd import api, synth
+from common import assert_matches_oracle, run_engine
+from dec_harness import assert_rows, run_dmr_pass_b
+from digiham_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEEDS = (611, 612, 613, 614)             # regular behind their first chunk (test_seeds_are_regular_for_the_serial_machine)
@@ -67,14 +68,13 @@ def push_plan(kind, n):
 
 
 @pytest.mark.parametrize("two_slots", [False, True])
-def test_seeds_are_regular_for_the_serial_machine(emu_ctx, two_slots, monkeypatch):
+def test_seeds_are_regular_for_the_serial_machine(emu_ctx, two_slots):
     """The noise-free streams as the burst-serial pass sees them: one SYNC or EMB event for every burst on the grid, the only reset
     events at the very first burst (the TACT that tells the slot).  Seeds that fail here cannot carry the counter conditions below."""
     syms = dibits(two_slots, False)
-    got, counts = run_decoder(emu_ctx, syms, [syms.shape[1]], True, monkeypatch)
-    assert sum(int(l.sum()) for l, _ in counts) == 0          # the switch holds: no chunk went lane-parallel
-    for b, (_, ev) in enumerate(got):
-        ev = np.frombuffer(ev, api.EVENT_DTYPE)
+    run, counts = run_dmr_pass_b(emu_ctx, syms, [syms.shape[1]], True)
+    assert counts[:, 0].sum() == 0                            # the switch holds: no chunk went lane-parallel
+    for b, ev in enumerate(run.events):
         first = int(ev["sym_index"][0])
         burst = (ev["sym_index"].astype(np.int64) - first) // 144
         assert ((ev["sym_index"] - first) % 144 == 0).all()
@@ -86,27 +86,25 @@ def test_seeds_are_regular_for_the_serial_machine(emu_ctx, two_slots, monkeypatc
 
 @pytest.mark.parametrize("noisy", [False, True])
 @pytest.mark.parametrize("two_slots", [False, True])
-def test_decoder_only_engine(ctx, two_slots, noisy, monkeypatch):
+def test_decoder_only_engine(ctx, two_slots, noisy):
     syms = dibits(two_slots, noisy)
-    want = [(o.tobytes(), ev.tobytes()) for o, ev in decoded(two_slots, noisy)]
+    want = decoded(two_slots, noisy)
     fell_back = 0
     for kind in (63, 64, 65, 128, 129, "ragged"):
         cuts = push_plan(kind, syms.shape[1])
-        got, counts = run_decoder(ctx, syms, cuts, False, monkeypatch)
-        forced, forced_counts = run_decoder(ctx, syms, cuts, True, monkeypatch)
-        for b in range(len(SEEDS)):
-            assert got[b][0] == want[b][0], (kind, SEEDS[b], "frames differ from the oracle's")
-            assert got[b][1] == want[b][1], (kind, SEEDS[b], "events differ from the oracle's")
-            assert got[b] == forced[b], (kind, SEEDS[b], "differs from the serial pass")
-        assert sum(int(l.sum()) for l, _ in forced_counts) == 0
-        lanes = sum(l for l, _ in counts); scalar = sum(s for _, s in counts)
-        assert (lanes + scalar == sum(s for _, s in forced_counts)).all()      # the same chunks either way
+        got, counts = run_dmr_pass_b(ctx, syms, cuts, False)
+        forced, forced_counts = run_dmr_pass_b(ctx, syms, cuts, True)
+        assert_rows(got, want, ["pushes of %s, seed %d, against the oracle" % (kind, s) for s in SEEDS])
+        assert_rows(forced, got.results, ["pushes of %s, seed %d, the serial pass against the lane-parallel" % (kind, s) for s in SEEDS])
+        assert forced_counts[:, 0].sum() == 0
+        lanes, scalar = counts.sum(axis=0)
+        assert (lanes + scalar == forced_counts[:, 1].sum(axis=0)).all()       # the same chunks either way
         if noisy:
             assert (lanes > 0).all()
             fell_back += int(scalar.sum()) - len(SEEDS)
         else:
             assert (scalar == 1).all(), (kind, scalar)         # the chunk behind the sync search; every other chunk lane-parallel
-            assert (counts[0][1] == 1).all()                   # ... which is the first chunk of the first push
+            assert (counts[0, 1] == 1).all()                   # ... which is the first chunk of the first push
             assert (lanes >= syms.shape[1] // (144 * 64)).all()
     if noisy:
         assert fell_back > 0                                   # the wrong dibits did make irregular chunks, and those agree as well

@@ -17,7 +17,7 @@ symbols, and with the burst-serial pass B.
 import numpy as np
 import pytest
 
-from common import run_dmr_symbols
+from dec_harness import expected, run_dmr_pass_b
 from digiham_amd import synth
 
 EV_SYNC, EV_META_RESET, EV_SLOTTYPE, EV_EMB = 1, 3, 7, 8
@@ -117,18 +117,17 @@ def _streams(per_channel, leads):
     return out
 
 
-def _check(ctx, oracle, monkeypatch, streams, leads, expect, sync_b, chunks, lanes_in):
+def _check(ctx, oracle, streams, leads, expect, sync_b, chunks, lanes_in):
     """expect[c]: {burst: wrong bits of its sync word} for the bursts that carry a full sync word.  Runs the streams in one push and in
     the given pushes, lane-parallel and burst-serial, and holds every run to the oracle and the SYNC events to the construction."""
-    B = len(streams)
-    want = [oracle.Decoder("dmr").process(row) for row in streams]
+    want = expected(oracle, "dmr", streams)
     for chunk in (None,) + tuple(chunks):
         for scalar in (False, True):
-            got, (lanes, serial) = run_dmr_symbols(ctx, streams, chunk, scalar, monkeypatch)
+            run, counts = run_dmr_pass_b(ctx, streams, chunk, scalar)
+            lanes, serial = counts.sum(axis=0)
             what = "pushes of %s, %s pass B" % (chunk, "burst-serial" if scalar else "lane-parallel")
             assert (lanes == 0).all() if scalar else (chunk not in lanes_in or (lanes > 0).all()), (what, lanes, serial)
-            for c in range(B):
-                frames, ev = got[c]
+            for c, (frames, ev) in enumerate(run.results):
                 sync = {int(e["sym_index"]): int(e["b"]) for e in ev[ev["type"] == EV_SYNC]}
                 exp = {leads[c] + 144 * k: sync_b[c] for k, w in expect[c].items() if w <= 3}
                 assert sync == exp, "%s, channel %d: SYNC events at other bursts than those with at most 3 wrong bits: %s" % (
@@ -140,7 +139,7 @@ def _check(ctx, oracle, monkeypatch, streams, leads, expect, sync_b, chunks, lan
     return want
 
 
-def test_search_locks_at_three_wrong_bits_not_at_four(ctx, oracle, monkeypatch):
+def test_search_locks_at_three_wrong_bits_not_at_four(ctx, oracle):
     """Noise lead, a burst whose sync word has 4 wrong bits, one with 3, three clean ones -- for each of the four patterns and i = 0..47.
     The search (dh_dmr_sync_type on the planes) walks over the first burst: the first event of the channel is at the second."""
     rng = np.random.default_rng(50)
@@ -153,7 +152,7 @@ def test_search_locks_at_three_wrong_bits_not_at_four(ctx, oracle, monkeypatch):
             per_channel.append(b); leads.append(LEAD0 + len(leads) % 32)
             expect.append({0: 4, 1: 3, 2: 0, 3: 0, 4: 0}); sync_b.append(1 if name.endswith("data") else 2)
     streams = _streams(per_channel, leads)
-    _check(ctx, oracle, monkeypatch, streams, leads, expect, sync_b, (97,), lanes_in=(97,))
+    _check(ctx, oracle, streams, leads, expect, sync_b, (97,), lanes_in=(97,))
 
 
 def _word_plan(n_slots_of_words):
@@ -162,7 +161,7 @@ def _word_plan(n_slots_of_words):
 
 
 @pytest.mark.parametrize("family", ["bs", "ms"])
-def test_locked_data_bursts_at_the_limit(ctx, oracle, monkeypatch, family):
+def test_locked_data_bursts_at_the_limit(ctx, oracle, family):
     """Idle bursts on both slots; every third burst of a slot (bursts 4, 5 of every six) carries a damaged data sync word, weights
     ascending.  The decoder stays locked throughout, and every burst -- sync or not -- has its slot type parsed."""
     name = family + "_data"
@@ -181,14 +180,14 @@ def test_locked_data_bursts_at_the_limit(ctx, oracle, monkeypatch, family):
         assert sorted(set(exp.values())) == [0, 1, 2, 3, 4, 5]
         per_channel.append(b); leads.append(LEAD0 + 9 * c); expect.append(exp)
     streams = _streams(per_channel, leads)
-    want = _check(ctx, oracle, monkeypatch, streams, leads, expect, [1] * 4, (1000, 97), lanes_in=(None, 1000, 97))
+    want = _check(ctx, oracle, streams, leads, expect, [1] * 4, (1000, 97), lanes_in=(None, 1000, 97))
     for c in range(4):
         st = want[c][1][want[c][1]["type"] == EV_SLOTTYPE]
         assert (st["sym_index"] == leads[c] + 144 * np.arange(K)).all() and (st["b"] == 9).all() and (st["payload"][:, 0] == CC).all()
 
 
 @pytest.mark.parametrize("family", ["bs", "ms"])
-def test_locked_voice_superframes_at_the_limit(ctx, oracle, monkeypatch, family):
+def test_locked_voice_superframes_at_the_limit(ctx, oracle, family):
     """Voice superframes on both slots; burst A of each carries a damaged voice sync word (weights ascending, dealt out over the two
     slots), bursts B..F a clean EMB.  A burst A without sync costs a count and no more: the superframe goes on, voice bytes come out."""
     name = family + "_voice"
@@ -210,7 +209,7 @@ def test_locked_voice_superframes_at_the_limit(ctx, oracle, monkeypatch, family)
         assert sorted(set(exp.values())) == [0, 1, 2, 3, 4, 5]
         per_channel.append(b); leads.append(LEAD0 + 1 + 14 * c); expect.append(exp)
     streams = _streams(per_channel, leads)
-    want = _check(ctx, oracle, monkeypatch, streams, leads, expect, [2] * 2, (1000, 97), lanes_in=(None, 1000, 97))
+    want = _check(ctx, oracle, streams, leads, expect, [2] * 2, (1000, 97), lanes_in=(None, 1000, 97))
     for c in range(2):
         assert len(want[c][0]) == 27 * (K // 2)                    # slot 0 speaks from its first burst to its last
         emb = want[c][1][want[c][1]["type"] == EV_EMB]

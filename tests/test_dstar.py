@@ -12,8 +12,9 @@ import os
 import numpy as np
 import pytest
 
-from digiham_amd import api, synth
+from digiham_amd import synth
 from common import assert_matches_oracle, run_engine
+from dec_harness import assert_rows, expected, run_symbols, stack_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EV_HEADER, EV_VOICE_START, EV_SYNC_VOICE, EV_MESSAGE, EV_SIMPLE, EV_FRAME_SYNC, EV_META_RESET = range(64, 71)
@@ -51,18 +52,6 @@ def test_oracle_header_known_answers(oracle):
         assert not oracle.dstar_header_parse(synth.dstar_header_bits(bytes(bad)))[0]
 
 
-def _decode_bits(ctx, bits, chunk):
-    eng = api.Engine(1, max(chunk, 64), rrc="none", demod="none", proto="dstar", ctx=ctx)
-    o, e = [], []
-    for lo in range(0, len(bits), chunk):
-        part = np.ascontiguousarray(bits[None, lo:lo + chunk])
-        eng.push_symbols(part, np.full(1, part.shape[1], np.uint32))
-        f, fc = eng.frames(); ev, ec = eng.events()
-        o.append(f[0, :fc[0]].copy()); e.append(ev[0, :ec[0]].copy())
-    eng.close()
-    return np.concatenate(o), np.concatenate(e)
-
-
 def _headers(ev):
     h = ev[ev["type"] == EV_HEADER]
     return [(int(a["b"]), bytes(a["payload"][:24]) + bytes(b["payload"][:17])) for a, b in zip(h[0::2], h[1::2])]
@@ -73,7 +62,8 @@ def test_decoder_on_bits_matches_oracle(ctx, oracle, seed):
     clean, infos = synth.dstar_stream(seed, 8)
     noisy, _ = synth.dstar_stream(seed, 8, ber=0.004)                  # corrected headers, missed syncs, broken slow data
     for stream in (clean, noisy):
-        out, ev = oracle.Decoder("dstar").process(stream)
+        want = expected(oracle, "dstar", stream[None])
+        out, ev = want[0]
         if stream is clean:                                            # the stream says what it should: headers, messages, voice
             heads = _headers(ev)
             for i in infos:
@@ -92,9 +82,7 @@ def test_decoder_on_bits_matches_oracle(ctx, oracle, seed):
             assert bytes(out) == b"".join(bytes(v) for t in sent for v in t)
             assert (ev["type"] == EV_META_RESET).sum() >= sum(i["kind"] != 6 for i in infos)
         for chunk in (len(stream), 1000, 97):
-            go, ge = _decode_bits(ctx, stream, chunk)
-            assert len(go) == len(out) and (go == out).all()
-            assert ge.tobytes() == ev.tobytes()
+            assert_rows(run_symbols(ctx, "dstar", stream[None], chunk), want, "pushes of %d" % chunk)
 
 
 def test_decoder_on_noise_and_sync_storms(ctx, oracle):
@@ -108,12 +96,11 @@ def test_decoder_on_noise_and_sync_storms(ctx, oracle):
                   np.array(synth.DSTAR_TERMINATOR, np.uint8)]
     parts += [np.array([1, 0] * 16 + synth.DSTAR_FRAME_SYNC, np.uint8), h[:500]]
     stream = np.concatenate(parts)
-    out, ev = oracle.Decoder("dstar").process(stream)
+    want = expected(oracle, "dstar", stream[None])
+    ev = want[0][1]
     assert (ev["type"] == EV_VOICE_START).sum() >= 5 and (ev["type"] == EV_META_RESET).sum() >= 5
     for chunk in (len(stream), 4096, 661):
-        go, ge = _decode_bits(ctx, stream, chunk)
-        assert len(go) == len(out) and (go == out).all()
-        assert ge.tobytes() == ev.tobytes()
+        assert_rows(run_symbols(ctx, "dstar", stream[None], chunk), want, "pushes of %d" % chunk)
 
 
 def test_full_chain_fsk_sps10(ctx, oracle):
@@ -143,81 +130,32 @@ def test_tiny_empty_and_ragged_pushes(ctx, oracle):
     # decoder-only engine fed 1 .. 7 bits at a time through a header and the first superframe
     rng = np.random.default_rng(8)
     stream = np.concatenate([rng.integers(0, 2, 50).astype(np.uint8), synth.dstar_transmission(rng, n_superframes=1)[0]])
-    out, ev = oracle.Decoder("dstar").process(stream)
-    eng = api.Engine(1, 64, rrc="none", demod="none", proto="dstar", ctx=ctx)
-    o, e, lo, k = [], [], 0, 0
-    while lo < len(stream):
-        n = [1, 7, 0, 3, 5, 2][k % 6]; k += 1
-        part = np.zeros((1, 64), np.uint8); part[0, :min(n, len(stream) - lo)] = stream[lo:lo + n]
-        eng.push_symbols(part, np.full(1, min(n, len(stream) - lo), np.uint32))
-        lo += n
-        f, fc = eng.frames(); evs, ec = eng.events()
-        o.append(f[0, :fc[0]].copy()); e.append(evs[0, :ec[0]].copy())
-    eng.close()
-    go, ge = np.concatenate(o), np.concatenate(e)
-    assert len(go) == len(out) and (go == out).all() and ge.tobytes() == ev.tobytes()
-    assert (ev["type"] == EV_HEADER).sum() >= 2
+    want = expected(oracle, "dstar", [stream])
+    assert_rows(run_symbols(ctx, "dstar", [stream], [1, 7, 0, 3, 5, 2], cycle=True, pitch=64), want)
+    assert (want[0][1]["type"] == EV_HEADER).sum() >= 2
 
 
 def test_decoder_only_rows_at_odd_addresses(ctx, oracle):
     """Three channels in a symbol buffer with an odd row pitch: the packed fast path funnel-shifts unaligned rows."""
     streams = [synth.dstar_stream(s, 4)[0] for s in (41, 42, 43)]
     n = min(len(s) for s in streams)
-    chunk, pitch = 1501, 1503
-    eng = api.Engine(3, pitch, rrc="none", demod="none", proto="dstar", ctx=ctx)
-    got_o, got_e = [[] for _ in range(3)], [[] for _ in range(3)]
-    for lo in range(0, n, chunk):
-        part = np.zeros((3, pitch), np.uint8)
-        cnt = np.zeros(3, np.uint32)
-        for b in range(3):
-            seg = streams[b][lo:min(lo + chunk, n)]
-            part[b, :len(seg)] = seg; cnt[b] = len(seg)
-        eng.push_symbols(part, cnt)
-        f, fc = eng.frames(); ev, ec = eng.events()
-        for b in range(3):
-            got_o[b].append(f[b, :fc[b]].copy()); got_e[b].append(ev[b, :ec[b]].copy())
-    eng.close()
-    for b in range(3):
-        out, ev = oracle.Decoder("dstar").process(streams[b][:n])
-        go, ge = np.concatenate(got_o[b]), np.concatenate(got_e[b])
-        assert len(out) > 0 and len(go) == len(out) and (go == out).all() and ge.tobytes() == ev.tobytes()
+    rows = [s[:n] for s in streams]
+    want = expected(oracle, "dstar", rows)
+    assert all(len(out) > 0 for out, _ in want)
+    assert_rows(run_symbols(ctx, "dstar", rows, 1501, pitch=1503), want)
 
 
 # ------------------------------------------------------------------ the five-frame fast path of the voice phase, by construction
 VOICE_AT = 64 + 15 + 660                       # dstar_transmission: bit sync, frame sync, header; then 96-bit frames
 
 
-def _decode_rows(ctx, rows, sizes, pitch=None):
-    """rows [B][n] through a decoder-only engine in pushes of the given sizes (cycled); pitch = row pitch of the pushed buffer"""
-    B, n = rows.shape
-    pitch = max(max(sizes), 64) if pitch is None else pitch
-    eng = api.Engine(B, pitch, rrc="none", demod="none", proto="dstar", ctx=ctx)
-    o, e, lo, k = [[] for _ in range(B)], [[] for _ in range(B)], 0, 0
-    while lo < n:
-        m = min(sizes[k % len(sizes)], n - lo); k += 1
-        part = np.zeros((B, pitch), np.uint8); part[:, :m] = rows[:, lo:lo + m]
-        eng.push_symbols(part, np.full(B, m, np.uint32))
-        lo += m
-        f, fc = eng.frames(); ev, ec = eng.events()
-        for b in range(B):
-            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(x) for x in o], [np.concatenate(x) for x in e]
-
-
 def _assert_rows_match(ctx, oracle, rows, pushes, pitch=None):
-    want = [oracle.Decoder("dstar").process(r) for r in rows]
+    """rows [B][n] in pushes of each of the given lists of sizes (cycled); pitch = row pitch of the pushed buffer"""
+    want = expected(oracle, "dstar", rows)
     for sizes in pushes:
-        out, ev = _decode_rows(ctx, rows, sizes, pitch)
-        for b, (wo, we) in enumerate(want):
-            assert len(out[b]) == len(wo) and (out[b] == wo).all(), (sizes[:2], b)
-            assert ev[b].tobytes() == we.tobytes(), (sizes[:2], b)
+        run = run_symbols(ctx, "dstar", rows, sizes, cycle=True, pitch=max(max(sizes), 64) if pitch is None else pitch)
+        assert_rows(run, want, "pushes of %s" % sizes[:2])
     return want
-
-
-def _stack(rows):
-    n = max(len(r) for r in rows)
-    return np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows]).astype(np.uint8)
 
 
 def test_end_pattern_at_every_frame_of_the_fast_path(ctx, oracle):
@@ -232,7 +170,7 @@ def test_end_pattern_at_every_frame_of_the_fast_path(ctx, oracle):
         at = VOICE_AT + 96 * (21 + idx) + 72
         tail = term[24:] if half else term
         rows[k % 4] += [b[:at], tail, rng.integers(0, 2, int(rng.integers(150, 400))).astype(np.uint8)]
-    rows = _stack([np.concatenate(r) for r in rows])
+    rows = stack_rows([np.concatenate(r) for r in rows])
     want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [4096], [997]))
     ev = np.concatenate([e for _, e in want])
     assert ((ev["type"] == EV_META_RESET) & (ev["b"] == 0)).sum() >= 40 and (ev["type"] == EV_MESSAGE).sum() >= 40
@@ -252,7 +190,7 @@ def test_symbols_with_bit_1_set_in_every_byte_lane_of_a_batch(ctx, oracle):
             b[VOICE_AT + 96 * (21 * k + 1) + 8 * lane + lane % 8] |= 2
             b[VOICE_AT + 96 * (21 * k + 11) + 8 * (lane * 7 % 60) + 7 - lane % 8] |= 2
         rows.append(np.concatenate([rng.integers(0, 2, 40 + c).astype(np.uint8), b, rng.integers(0, 2, 300).astype(np.uint8)]))
-    rows = _stack(rows)
+    rows = stack_rows(rows)
     assert (rows > 1).sum() == 4 * 30
     want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [5000]))
     assert all(len(o) // 9 >= 16 * 21 - 2 for o, _ in want)                 # the calls went through to their ends
@@ -267,7 +205,7 @@ def test_fast_path_at_the_end_of_a_push_at_every_row_misalignment(ctx, oracle):
         b, _, _ = synth.dstar_transmission(rng, my="MIS%d" % c, n_superframes=9, message="misaligned row %d" % c)
         rows.append(np.concatenate([rng.integers(0, 2, 33 + 5 * c).astype(np.uint8), b, rng.integers(0, 2, 200).astype(np.uint8)]))
     sizes = [515 + d + 96 * k for k in range(3) for d in range(4)]
-    want = _assert_rows_match(ctx, oracle, _stack(rows), (sizes, sizes[::-1], [s + 96 for s in sizes[5:] + sizes[:5]]), pitch=811)
+    want = _assert_rows_match(ctx, oracle, stack_rows(rows), (sizes, sizes[::-1], [s + 96 for s in sizes[5:] + sizes[:5]]), pitch=811)
     assert all(len(o) // 9 >= 9 * 21 - 2 and (e["type"] == EV_MESSAGE).sum() >= 4 for o, e in want)
 
 
@@ -282,7 +220,7 @@ def test_superframe_that_begins_without_sync_collects_slow_data_only(ctx, oracle
         b, _, voice = synth.dstar_transmission(rng, my="LATE%d" % c, message="late entry %d" % c, n_superframes=3, with_header=False, inline_header=False)
         sent.append(np.concatenate(voice[21:]))                            # 20 data frames and the first due sync frame are heard, not written
         rows.append(np.concatenate([np.zeros(50 + 3 * c, np.uint8), b, rng.integers(0, 2, 300).astype(np.uint8)]))
-    rows = _stack(rows)
+    rows = stack_rows(rows)
     want = _assert_rows_match(ctx, oracle, rows, ([rows.shape[1]], [1000], [97]))
     for (o, e), v in zip(want, sent):
         start = e[e["type"] == EV_VOICE_START]

@@ -28,7 +28,8 @@ from itertools import permutations
 import numpy as np
 import pytest
 
-from common import decode_symbol_rows, event_record, first_difference, frames_fixture, npz_digest, stack_rows
+from common import npz_digest
+from dec_harness import assert_rows, event_record, expected, frames_fixture, is_emu, run_symbols, stack_rows
 from digiham_amd import api, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -331,15 +332,10 @@ def _hold(ctx, oracle, radios, pushes=PUSHES):
     for r, row in zip(radios, rows):
         r.check(row)                                                 # before any decoder runs
     for size, pitch in pushes:
-        got = decode_symbol_rows(ctx, "dstar", rows, rows.shape[1] if size is None else size, pitch)
-        for b, ((out, ev), (wo, we)) in enumerate(zip(got, want)):
-            assert len(out) == len(wo) and (out == wo).all(), (size, b, len(out) // 9, len(wo) // 9)
-            assert ev.tobytes() == we.tobytes(), (size, b, first_difference(ev, we))
-    if type(ctx.mem).__name__ == "NumpyMemory":
-        for b, (row, (wo, we)) in enumerate(zip(rows, want)):
-            out, ev = oracle.Decoder("dstar").process(row)
-            assert len(out) == len(wo) and (out == wo).all(), b
-            assert ev.tobytes() == we.tobytes(), (b, first_difference(ev, we))
+        run = run_symbols(ctx, "dstar", rows, size, pitch=max(size or rows.shape[1], 64) if pitch is None else pitch)
+        assert_rows(run, want, "pushes of %s" % size)
+    if is_emu(ctx):
+        assert_rows(expected(oracle, "dstar", rows), want, "the oracle")
     seen = Counter()
     for r in radios:
         seen.update(r.seen)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from common import npz_digest, sha
+from dec_harness import run_symbols, tier
 from digiham_amd import api, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,18 +105,7 @@ LEAD = 29
 
 def _run_symbols(ctx, proto, streams, chunk=None):
     """streams [B][n] dibits (or bits) -> per-channel event arrays of a decoder-only engine."""
-    B, n = streams.shape
-    chunk = n if chunk is None else chunk
-    eng = api.Engine(B, chunk, rrc="none", demod="none", proto=proto, ctx=ctx)
-    evs = [[] for _ in range(B)]
-    for lo in range(0, n, chunk):
-        part = np.ascontiguousarray(streams[:, lo:lo + chunk])
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        e, ec = eng.events()
-        for b in range(B):
-            evs[b].append(e[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(e) for e in evs]
+    return run_symbols(ctx, proto, streams, chunk, capacity=chunk or streams.shape[1]).events
 
 
 def _dmr_streams(bursts, B):
@@ -138,26 +128,22 @@ def _events_at(ev, typ, end):
     return {int(e["sym_index"]): e for e in sel}
 
 
-def _size(ctx, full, small):
-    return small if type(ctx.mem).__name__ == "NumpyMemory" else full
-
-
 def test_slottype_events_vs_reference(ctx, oracle, gold):
     """Every 20-bit slot-type word (all 2^20 with -m gpu) in a data burst: the SLOTTYPE event carries what the reference's
     SlotType::parse / getDataType / getColorCode give (dmr_phase.cpp:244-249, slottype.cpp:9-22)."""
     v, h = gold
     o, c = oracle.Elements("oracle").dmr_slottype(np.arange(1 << 20))
     assert sha(o, c) == h["dmr_slottype_all_2^20"]      # the expectation below IS the reference's table
-    step = _size(ctx, 1, 509)
+    step = tier(ctx, 1, 509)
     words = np.arange(0, 1 << 20, step, dtype=np.uint32)
     words = words[:len(words) // 64 * 64]
-    B = _size(ctx, 1024, 4)
+    B = tier(ctx, 1024, 4)
     rng = np.random.default_rng(6)
     bursts = rng.integers(0, 4, (len(words), 144)).astype(np.uint8)
     st = _to_dibits(_bits(words, 20))
     bursts[:, 61:66], bursts[:, 90:95], bursts[:, 66:90] = st[:, :5], st[:, 5:], BS_DATA
     streams, K = _dmr_streams(bursts, B)
-    evs = _run_symbols(ctx, "dmr", streams, chunk=_size(ctx, None, 20000))
+    evs = _run_symbols(ctx, "dmr", streams, chunk=tier(ctx, None, 20000))
     n_ok = 0
     for b in range(B):
         got = _events_at(evs[b], api_ev("DMR_SLOTTYPE"), LEAD + 144 * K)
@@ -206,8 +192,8 @@ def test_emb_events_vs_reference(ctx, oracle, gold):
     v, h = gold
     o, c = oracle.Elements("oracle").dmr_emb(np.arange(1 << 16))
     assert sha(o, c) == h["dmr_emb_all_2^16"]
-    words = np.arange(0, 1 << 16, _size(ctx, 1, 131), dtype=np.uint32)
-    B = _size(ctx, 256, 2)
+    words = np.arange(0, 1 << 16, tier(ctx, 1, 131), dtype=np.uint32)
+    B = tier(ctx, 256, 2)
     words = words[:len(words) // (2 * B) * 2 * B]
     rng = np.random.default_rng(7)
     S = len(words) // 2
@@ -221,7 +207,7 @@ def test_emb_events_vs_reference(ctx, oracle, gold):
         mids[:, 0, 4:20] = rng.integers(0, 4, (S, 16))
         sfs.append(_voice_superframes(mids, rng))
     streams, K = _dmr_streams(_interleave_slots(*sfs), B)
-    evs = _run_symbols(ctx, "dmr", streams, chunk=_size(ctx, None, 20000))
+    evs = _run_symbols(ctx, "dmr", streams, chunk=tier(ctx, None, 20000))
     per = S // B
     n_ok = 0
     for b in range(B):
@@ -253,9 +239,9 @@ def test_embedded_lc_events_vs_reference(ctx, gold):
     nine bytes appears at the LCSS-stop burst exactly where EmbeddedCollector::getLc succeeded (embedded.cpp:20-94,
     dmr_phase.cpp:136-164).  A first superframe leaves `prev` in the collector, as the golden script did."""
     v, _ = gold
-    n = _size(ctx, len(v["elc_out"]) // 64 * 64, 0)
+    n = tier(ctx, len(v["elc_out"]) // 64 * 64, 0)
     idx = np.arange(n) if n else np.concatenate([np.arange(0, 4096, 171), np.arange(4096, 6144, 37)])[:80]
-    B = _size(ctx, 64, 2)
+    B = tier(ctx, 64, 2)
     idx = idx[:len(idx) // (2 * B) * 2 * B]
     rng = np.random.default_rng(8)
     LCSS = {0: [], 1: [2], 2: [1, 2], 3: [1, 3, 2], 4: [1, 3, 3, 2], 5: [1, 3, 3, 3, 2]}
@@ -269,7 +255,7 @@ def test_embedded_lc_events_vs_reference(ctx, gold):
         sfs[s].append(_voice_superframes(np.stack([pm, tm]), rng))
         stop_burst[(j // 2, s)] = (i, nf)
     streams, K = _dmr_streams(_interleave_slots(np.concatenate(sfs[0]), np.concatenate(sfs[1])), B)
-    evs = _run_symbols(ctx, "dmr", streams, chunk=_size(ctx, None, 20000))
+    evs = _run_symbols(ctx, "dmr", streams, chunk=tier(ctx, None, 20000))
     per = len(idx) // 2 // B
     n_ok = 0
     for b in range(B):
@@ -295,8 +281,8 @@ def test_fich_events_vs_reference(ctx, gold):
     frames: a FICH event with the reference's 32-bit word appears exactly at the frames the reference decodes
     (ysf_phase.cpp:60-66, fich.cpp:12-52)."""
     v, _ = gold
-    n = _size(ctx, len(v["fich_in"]), 96)
-    B = _size(ctx, 64, 2)
+    n = tier(ctx, len(v["fich_in"]), 96)
+    B = tier(ctx, 64, 2)
     idx = (np.arange(n) * (len(v["fich_in"]) // n))[:n // B * B]
     rng = np.random.default_rng(9)
     frames = rng.integers(0, 4, (len(idx), 480)).astype(np.uint8)
@@ -305,7 +291,7 @@ def test_fich_events_vs_reference(ctx, gold):
     K = len(idx) // B
     lead = np.broadcast_to(rng.integers(0, 4, LEAD).astype(np.uint8), (B, LEAD))
     streams = np.concatenate([lead, frames.reshape(B, K * 480), np.zeros((B, 500), np.uint8)], axis=1)
-    evs = _run_symbols(ctx, "ysf", streams, chunk=_size(ctx, None, 30000))
+    evs = _run_symbols(ctx, "ysf", streams, chunk=tier(ctx, None, 30000))
     n_ok = 0
     for b in range(B):
         got = _events_at(evs[b], api_ev("YSF_FICH"), LEAD + 480 * K)
@@ -321,8 +307,8 @@ def test_pocsag_codeword_events_vs_reference(ctx, gold):
     """The reference's Codeword::parse vectors as the 16 codewords of consecutive batches: a CODEWORD event with the
     reference's corrected word appears exactly where Codeword::parse succeeded (pocsag_phase.cpp:54-57, codeword.cpp:9-31)."""
     v, _ = gold
-    n = _size(ctx, len(v["cw_in"]), 256)
-    B = _size(ctx, 16, 2)
+    n = tier(ctx, len(v["cw_in"]), 256)
+    B = tier(ctx, 16, 2)
     idx = (np.arange(n) * (len(v["cw_in"]) // n))[:n // (16 * B) * 16 * B]
     sync = np.array(synth._bits_of(synth.POCSAG_SYNC, 32), np.uint8)
     K = len(idx) // B // 16                                   # batches per channel
@@ -354,8 +340,8 @@ def test_dstar_header_events_vs_reference(ctx, gold):
     (dstar_phase.cpp:39-54, header.cpp:22-54)."""
     v, _ = gold
     raw = np.unpackbits(v["dh_in_bits"], axis=1)[:, :660]
-    n = _size(ctx, len(raw) // 64 * 64, 24)
-    B = _size(ctx, 64, 2)
+    n = tier(ctx, len(raw) // 64 * 64, 24)
+    B = tier(ctx, 64, 2)
     idx = (np.arange(n) * (len(raw) // n))[:n // B * B]
     K = len(idx) // B
     hsync = np.array([0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 1, 1, 0, 1, 1, 0, 0, 1, 0, 1, 0, 0, 0, 0], np.uint8)     # dstar_phase.hpp:18
@@ -392,8 +378,8 @@ def test_tact_slot_tracking_vs_reference(ctx, gold):
     drive the TDMA slot of every burst: the `a` field of each burst's SLOTTYPE event must follow dmr_phase.cpp:65-95 fed
     with the REFERENCE's TACT outcome for that CACH."""
     v, _ = gold
-    n = _size(ctx, 4096, 128)
-    B = _size(ctx, 16, 2)
+    n = tier(ctx, 4096, 128)
+    B = tier(ctx, 16, 2)
     K = n // B
     rng = np.random.default_rng(12)
     idx = v["cach_sample_idx"][:n]

@@ -9,7 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from digiham_amd import api, synth
+from dec_harness import run_symbols
+from digiham_amd import synth
 from oracle import meta as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -217,14 +218,8 @@ def _dstar_stream(rng):
 
 
 def _product_lines(ctx, exe, proto, syms, chunk):
-    eng = api.Engine(1, len(syms), rrc="none", demod="none", proto=proto, ctx=ctx)
-    batches = b""
-    for lo in range(0, len(syms), chunk):
-        part = np.ascontiguousarray(syms[None, lo:lo + chunk])
-        eng.push_symbols(part, np.array([part.shape[1]], np.uint32))
-        e, ec = eng.events()
-        batches += np.uint32(ec[0]).tobytes() + e[0, :ec[0]].tobytes()
-    eng.close()
+    run = run_symbols(ctx, proto, syms[None], chunk, capacity=len(syms))
+    batches = b"".join(np.uint32(len(e)).tobytes() + e.tobytes() for e in run.events_by_push[0])
     return subprocess.run([exe, proto], input=batches, capture_output=True, check=True).stdout.split(b"\n")[:-1]
 
 

@@ -15,8 +15,9 @@ import os
 import numpy as np
 import pytest
 
-from digiham_amd import api, synth, _taps
+from digiham_amd import synth, _taps
 from common import assert_matches_oracle, nxdn_digests, run_engine
+from dec_harness import assert_rows, expected, run_symbols, stack_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -67,18 +68,6 @@ def test_cai_test_patterns_form_a_vcall_superframe(oracle, nx):
     assert [int(e["a"]) for e in ev[ev["type"] == 33]] == [0, 1, 2, 3]
 
 
-def _decode_symbols(ctx, s, chunk):
-    eng = api.Engine(1, max(chunk, 16), rrc="none", demod="none", proto="nxdn", ctx=ctx)
-    o, e = [], []
-    for lo in range(0, len(s), chunk):
-        part = np.ascontiguousarray(s[None, lo:lo + chunk])
-        eng.push_symbols(part, np.full(1, part.shape[1], np.uint32))
-        f, fc = eng.frames(); ev, ec = eng.events()
-        o.append(f[0, :fc[0]].copy()); e.append(ev[0, :ec[0]].copy())
-    eng.close()
-    return np.concatenate(o), np.concatenate(e)
-
-
 @pytest.mark.parametrize("seed", [3, 4])
 def test_decoder_on_dibits_matches_oracle(ctx, oracle, seed):
     s = synth.nxdn_stream(seed, 40)
@@ -87,26 +76,11 @@ def test_decoder_on_dibits_matches_oracle(ctx, oracle, seed):
     hit = rng.random(len(s)) < 0.01                  # dibit errors: FEC, CRC failures, lost sync words
     noisy[hit] ^= rng.integers(1, 4, int(hit.sum())).astype(np.uint8)
     for stream in (s, noisy):
-        out, ev = oracle.Decoder("nxdn").process(stream)
+        want = expected(oracle, "nxdn", stream[None])
+        out, ev = want[0]
         assert len(out) > 0 and (ev["type"] == 34).sum() > 0
         for chunk in (len(stream), 1000, 193):
-            go, ge = _decode_symbols(ctx, stream, chunk)
-            assert len(go) == len(out) and (go == out).all()
-            assert ge.tobytes() == ev.tobytes()
-
-
-def _decode_rows(ctx, rows, chunk):
-    B, n = rows.shape
-    eng = api.Engine(B, max(min(chunk, n), 16), rrc="none", demod="none", proto="nxdn", ctx=ctx)
-    o, e = [[] for _ in range(B)], [[] for _ in range(B)]
-    for lo in range(0, n, chunk):
-        part = np.ascontiguousarray(rows[:, lo:lo + chunk])
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        f, fc = eng.frames(); ev, ec = eng.events()
-        for b in range(B):
-            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(x) for x in o], [np.concatenate(x) for x in e]
+            assert_rows(run_symbols(ctx, "nxdn", stream[None], chunk, capacity=max(chunk, 16)), want, "pushes of %d" % chunk)
 
 
 @pytest.fixture(scope="module")
@@ -126,9 +100,8 @@ def mixed(oracle):
         loss.append((6 + k, 1 + 2 * k % 9))
         s, st, _ = synth.nxdn_mixed_stream(600 + k, 30, accept, lead_in=20 + k, loss=loss[-1], voice_only=True)
         rows.append(s); starts.append(st)
-    n = max(len(r) for r in rows)
-    rows = np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows])
-    want = [oracle.Decoder("nxdn").process(r) for r in rows]
+    rows = stack_rows(rows)
+    want = expected(oracle, "nxdn", rows)
     return rows, starts, loss, inside, want
 
 
@@ -166,11 +139,8 @@ def test_mixed_streams_match_oracle(ctx, mixed, chunk):
     """Decoder bytes, events and counts of the 36 mixed channels equal the oracle decoder's, in one push and in pushes that
     leave every number of whole frames (and, with 200, every offset) in hand."""
     rows, _, _, _, want = mixed
-    out, ev = _decode_rows(ctx, rows, rows.shape[1] if chunk is None else chunk)
-    for b, (wo, we) in enumerate(want):
-        assert len(out[b]) == len(wo) and (out[b] == wo).all(), "channel %d: decoder bytes" % b
-        assert len(ev[b]) == len(we), "channel %d: %d events, oracle %d" % (b, len(ev[b]), len(we))
-        assert ev[b].tobytes() == we.tobytes(), "channel %d: events" % b
+    n = rows.shape[1]
+    assert_rows(run_symbols(ctx, "nxdn", rows, chunk, capacity=max(min(chunk or n, n), 16)), want, "pushes of %s" % chunk)
 
 
 def test_full_chain_narrow_rrc_sps20_mixed_frames(ctx, oracle):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from common import npz_digest
+from dec_harness import assert_rows, first_differing_frame, run_symbols, tier
 from digiham_amd import api, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -35,10 +36,6 @@ def nxe():
 @pytest.fixture(scope="module")
 def nx():
     return np.load(os.path.join(HERE, "golden", "nxdn_ref.npz"))
-
-
-def _size(ctx, full, small):
-    return small if type(ctx.mem).__name__ == "NumpyMemory" else full
 
 
 def _miscorrected(v, name):
@@ -136,38 +133,22 @@ class _Channel:
         return s
 
 
-def _run(ctx, streams, chunk):
-    B, n = streams.shape
-    chunk = n if chunk is None else chunk
-    eng = api.Engine(B, max(chunk, 16), rrc="none", demod="none", proto="nxdn", ctx=ctx)
-    out, evs = [[] for _ in range(B)], [[] for _ in range(B)]
-    for lo in range(0, n, chunk):
-        part = np.ascontiguousarray(streams[:, lo:lo + chunk])
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        f, fc = eng.frames(); e, ec = eng.events()
-        for b in range(B):
-            out[b].append(f[b, :fc[b]].copy()); evs[b].append(e[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(o) for o in out], [np.concatenate(e) for e in evs]
-
-
 def _check(ctx, chans, chunk):
     """push the channels' streams and hold events and voice bytes to the model; returns all expected events"""
     lead = np.random.default_rng(5).integers(0, 4, LEAD).astype(np.uint8)
     K = len(chans[0].rows)
     assert all(len(c.rows) == K for c in chans)
-    out, evs = _run(ctx, np.stack([c.stream(lead) for c in chans]), chunk)
+    streams = np.stack([c.stream(lead) for c in chans])
+    run = run_symbols(ctx, "nxdn", streams, chunk, capacity=max(chunk or streams.shape[1], 16))
     end = LEAD + 192 * K
-    for b, c in enumerate(chans):
-        got, exp = evs[b][evs[b]["sym_index"] < end], np.concatenate(c.ev)
-        if got.tobytes() != exp.tobytes():
-            for k in range(min(len(got), len(exp))):
-                assert got[k].tobytes() == exp[k].tobytes(), "channel %d push %s frame %d: got %s, reference %s" % (
-                    b, chunk, (int(exp[k]["sym_index"]) - LEAD) // 192, got[k], exp[k])
-            assert len(got) == len(exp), "channel %d push %s: %d events, the reference's results give %d" % (b, chunk, len(got), len(exp))
+    got, want, what = [], [], []
+    for c, out, ev in zip(chans, run.frames, run.events):
         voice = np.concatenate(c.out) if c.out else np.zeros(0, np.uint8)
-        assert len(out[b]) >= len(voice) and (out[b][:len(voice)] == voice).all(), "channel %d push %s: voice bytes" % (b, chunk)
-        assert len(out[b]) - len(voice) <= 36                                # (at most the zero padding's first frame)
+        assert len(out) - len(voice) <= 36, "push %s: voice bytes" % chunk   # (at most the zero padding's first frame)
+        got.append((out[:len(voice)], ev[ev["sym_index"] < end]))
+        want.append((voice, np.concatenate(c.ev)))
+        what.append("push %s frame %s" % (chunk, first_differing_frame(got[-1][1], want[-1][1], LEAD, 192)))
+    assert_rows(got, want, what)
     return np.concatenate([np.concatenate(c.ev) for c in chans])
 
 
@@ -206,20 +187,20 @@ def test_sacch_events_vs_reference(ctx, nxe, chunk):
     the reference's CRC passed, with its structure index and five bytes -- 127 of them miscorrections that only the
     reference's tie rules reproduce; SACCH_SF events as SacchSuperframeCollector gives them for those results."""
     n = len(nxe["sacch_in"])
-    idx = np.arange(n) if _size(ctx, True, False) else np.arange(3, n, 4)
-    exp = _check(ctx, _sacch_channels(nxe, idx, _size(ctx, 16, 2)), chunk)
+    idx = np.arange(n) if tier(ctx, True, False) else np.arange(3, n, 4)
+    exp = _check(ctx, _sacch_channels(nxe, idx, tier(ctx, 16, 2)), chunk)
     assert (exp["type"] == EV_SACCH).sum() >= 4 * nxe["sacch_ok"][idx].sum() > 0
-    assert _miscorrected(nxe, "sacch")[idx].sum() >= _size(ctx, 100, 25)
-    assert (exp["type"] == EV_SACCH_SF).sum() >= _size(ctx, 5, 1) and not (exp["type"] == EV_FACCH1).any()
+    assert _miscorrected(nxe, "sacch")[idx].sum() >= tier(ctx, 100, 25)
+    assert (exp["type"] == EV_SACCH_SF).sum() >= tier(ctx, 5, 1) and not (exp["type"] == EV_FACCH1).any()
 
 
 def test_no_sacch_event_without_superframe_sacch(ctx, nxe):
     """SACCHs the reference accepts, under LICHs whose functional channel is not the superframe SACCH (0 and 3; voice or
     FACCH1 blocks): the 30 dibits are skipped, no SACCH or SACCH_SF event (nxdn_phase.cpp:104)."""
-    acc = np.nonzero(nxe["sacch_ok"])[0][:_size(ctx, 160, 40)]
+    acc = np.nonzero(nxe["sacch_ok"])[0][:tier(ctx, 160, 40)]
     fill = [(d, (False, None)) for d in nxe["filler_facch1_in"]]
     chans, rng = [], np.random.default_rng(22)
-    for groups in _split(acc, _size(ctx, 4, 2), 5):
+    for groups in _split(acc, tier(ctx, 4, 2), 5):
         c = _Channel()
         for g in groups:
             for lich in (0x46, 0x5E, 0x40, 0x42, 0x5C):
@@ -266,12 +247,12 @@ def test_facch1_events_vs_reference(ctx, nxe, chunk):
     where the reference's CRC-12 passed, with the block index and its 12 bytes (40 of them miscorrections); the voice
     block of a mixed frame comes out as its 18 descrambled bytes."""
     n = len(nxe["facch1_in"])
-    idx = np.arange(n) if _size(ctx, True, False) else np.arange(1, n, 4)
-    exp = _check(ctx, _facch1_channels(nxe, idx, _size(ctx, 16, 2)), chunk)
+    idx = np.arange(n) if tier(ctx, True, False) else np.arange(1, n, 4)
+    exp = _check(ctx, _facch1_channels(nxe, idx, tier(ctx, 16, 2)), chunk)
     fa = exp[exp["type"] == EV_FACCH1]
     n_ok = int(nxe["facch1_ok"][idx].sum())
     assert (fa["a"] == 0).sum() >= 4 * n_ok > 0 and (fa["a"] == 1).sum() >= 4 * n_ok
-    assert _miscorrected(nxe, "facch1")[idx].sum() >= _size(ctx, 30, 8)
+    assert _miscorrected(nxe, "facch1")[idx].sum() >= tier(ctx, 30, 8)
 
 
 # ------------------------------------------------------------------ LICH
@@ -285,7 +266,7 @@ def test_lich_events_and_governing_lich_vs_reference(ctx, oracle, nx, nxe):
         assert [oracle.nxdn_lich(r, "ref") for r in lich_in] == list(lich_out)
     s_acc, f_acc = np.nonzero(nxe["sacch_ok"])[0], np.nonzero(nxe["facch1_ok"])[0]
     chans, after_failure, rng = [], set(), np.random.default_rng(24)
-    for b in range(_size(ctx, 16, 2)):
+    for b in range(tier(ctx, 16, 2)):
         order = np.random.default_rng(40 + b).permutation(len(lich_in))
         c = _Channel()
         c.frame(_lich8(0x56), 0x56, nxe["sacch_in"][s_acc[b]], (True, nxe["sacch_out"][s_acc[b]]), [_voice(rng), _voice(rng)])

@@ -10,8 +10,9 @@ import os
 import numpy as np
 import pytest
 
-from digiham_amd import api, synth
+from digiham_amd import synth
 from common import assert_matches_oracle, run_engine
+from dec_harness import assert_rows, expected, run_symbols, stack_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,18 +33,6 @@ def test_product_bch_matches_the_reference_vectors(ctx, gold):
     assert (ok == gold["bch_ok"]).all() and (np.where(ok == 1, out, 0) == gold["bch_out"]).all()
 
 
-def _decode_bits(ctx, bits, chunk):
-    eng = api.Engine(1, max(chunk, 64), rrc="none", demod="none", proto="pocsag", ctx=ctx)
-    o, e = [], []
-    for lo in range(0, len(bits), chunk):
-        part = np.ascontiguousarray(bits[None, lo:lo + chunk])
-        eng.push_symbols(part, np.full(1, part.shape[1], np.uint32))
-        f, fc = eng.frames(); ev, ec = eng.events()
-        o.append(f[0, :fc[0]].copy()); e.append(ev[0, :ec[0]].copy())
-    eng.close()
-    return np.concatenate(o), np.concatenate(e)
-
-
 @pytest.mark.parametrize("seed", [3, 4])
 def test_decoder_on_bits_matches_oracle(ctx, oracle, seed):
     bits, sent = synth.pocsag_stream(seed, 8)
@@ -52,14 +41,12 @@ def test_decoder_on_bits_matches_oracle(ctx, oracle, seed):
     hit = rng.random(len(bits)) < 0.004                # bit errors: BCH corrections, dropped messages, lost sync words
     noisy[hit] ^= 1
     for stream in (bits, noisy):
-        out, ev = oracle.Decoder("pocsag").process(stream)
-        lines = bytes(out).decode("latin1").split("\n")
+        want = expected(oracle, "pocsag", stream[None])
+        lines = bytes(want[0][0]).decode("latin1").split("\n")
         if stream is bits:                             # most pages come out verbatim (a transmission right behind another is missed)
             assert sum(("address:%d;message:%s" % (a, t)) in lines for a, f, t in sent) >= len(sent) // 2
         for chunk in (len(stream), 1000, 97):
-            go, ge = _decode_bits(ctx, stream, chunk)
-            assert len(go) == len(out) and (go == out).all()
-            assert ge.tobytes() == ev.tobytes()
+            assert_rows(run_symbols(ctx, "pocsag", stream[None], chunk), want, "pushes of %d" % chunk)
 
 
 def test_full_chain_fsk_inverted_sps40(ctx, oracle):
@@ -75,20 +62,6 @@ def test_full_chain_fsk_inverted_sps40(ctx, oracle):
     for chunks in ([n], [48000, 12345]):
         res = run_engine(ctx, x, "pocsag", chunks, rrc="none", demod="fsk", sps=40, invert=True)
         assert_matches_oracle(res, ref, len(x), "pocsag %s" % chunks[:1])
-
-
-def _decode_rows(ctx, rows, chunk):
-    B, n = rows.shape
-    eng = api.Engine(B, max(chunk, 64), rrc="none", demod="none", proto="pocsag", ctx=ctx)
-    o, e = [[] for _ in range(B)], [[] for _ in range(B)]
-    for lo in range(0, n, chunk):
-        part = np.ascontiguousarray(rows[:, lo:lo + chunk])
-        eng.push_symbols(part, np.full(B, part.shape[1], np.uint32))
-        f, fc = eng.frames(); ev, ec = eng.events()
-        for b in range(B):
-            o[b].append(f[b, :fc[b]].copy()); e[b].append(ev[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(x) for x in o], [np.concatenate(x) for x in e]
 
 
 def _transmission(words, missed_sync=(), odd=()):
@@ -138,20 +111,16 @@ def _edge_streams():
     words = [synth.POCSAG_IDLE] * 2 + page(8 * 4711 + 1, 3, text(40))
     for odd in ((3,), (3, 17, 30), (32 * 3 + 5,), (32 * 4 + 9, 32 * 5 + 1), (1, 32 * 3 + 31, 32 * 6)):
         rows.append(np.concatenate([_transmission(words, odd=odd), gap()]))
-    n = max(len(r) for r in rows)
-    return np.stack([np.concatenate([r, np.zeros(n - len(r), np.uint8)]) for r in rows]).astype(np.uint8)
+    return stack_rows(rows)
 
 
 def test_decoder_edges_match_oracle(ctx, oracle):
     rows = _edge_streams()
-    want = [oracle.Decoder("pocsag").process(r) for r in rows]
+    want = expected(oracle, "pocsag", rows)
     lines = [bytes(o).decode("latin1").split("\n") for o, _ in want]
     assert len(lines[0]) - 1 >= 1 and len(lines[1]) - 1 >= 6               # pages came out (only function 3 yields text, message.cpp:27-72)
     assert max(len(l) for l in lines[1]) >= 77 + len("address:8;message:")
     for missed in range(4):                                                  # 1..3 missed sync words: the later pages still arrive; 4: fewer
         assert len(lines[4 + missed]) - 1 >= 5 if missed < 3 else len(lines[4 + missed]) < len(lines[4])
     for chunk in (rows.shape[1], 1000, 97, 33):
-        out, ev = _decode_rows(ctx, rows, chunk)
-        for b, (wo, we) in enumerate(want):
-            assert len(out[b]) == len(wo) and (out[b] == wo).all(), (chunk, b)
-            assert ev[b].tobytes() == we.tobytes(), (chunk, b)
+        assert_rows(run_symbols(ctx, "pocsag", rows, chunk), want, "pushes of %d" % chunk)

@@ -22,7 +22,8 @@ from collections import Counter
 import numpy as np
 import pytest
 
-from common import decode_symbol_rows, event_record, first_difference, frames_fixture, npz_digest, stack_rows
+from common import npz_digest
+from dec_harness import assert_rows, event_record, expected, frames_fixture, is_emu, run_symbols, stack_rows
 from digiham_amd import api, synth
 from test_pocsag import _transmission
 
@@ -255,16 +256,11 @@ def _hold(ctx, oracle, pagers, pushes=PUSHES):
     assert rows.shape[0] <= 8 and rows.shape[1] <= 25000 and rows.max() <= 1
     for p, r in zip(pagers, rows):
         p.check_search(r)                                            # before any decoder runs
+    want = [(p.output(), p.events()) for p in pagers]
     for size in pushes:
-        got = decode_symbol_rows(ctx, "pocsag", rows, rows.shape[1] if size is None else size)
-        for b, (p, (out, ev)) in enumerate(zip(pagers, got)):
-            assert bytes(out) == bytes(p.output()), (size, b, bytes(out)[-200:], bytes(p.output())[-200:])
-            assert ev.tobytes() == p.events().tobytes(), (size, b, first_difference(ev, p.events()))
-    if type(ctx.mem).__name__ == "NumpyMemory":
-        for b, (p, r) in enumerate(zip(pagers, rows)):
-            out, ev = oracle.Decoder("pocsag").process(r)
-            assert bytes(out) == bytes(p.output()), b
-            assert ev.tobytes() == p.events().tobytes(), (b, first_difference(ev, p.events()))
+        assert_rows(run_symbols(ctx, "pocsag", rows, size, pitch=max(size or rows.shape[1], 64)), want, "pushes of %s" % size)
+    if is_emu(ctx):
+        assert_rows(expected(oracle, "pocsag", rows), want, "the oracle")
     seen = Counter()
     for p in pagers:
         seen.update(p.seen)

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from common import assert_matches_oracle, npz_digest, run_engine
+from dec_harness import assert_rows, first_differing_frame, run_symbols, tier
 from digiham_amd import api, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,10 +50,6 @@ def yse():
 def gold():
     with np.load(os.path.join(HERE, "golden", "elements_ref.npz")) as z:
         return {k: z[k] for k in ("fich_in", "fich_out", "fich_data")}
-
-
-def _size(ctx, full, small):
-    return small if type(ctx.mem).__name__ == "NumpyMemory" else full
 
 
 # ------------------------------------------------------------------ the fixture itself
@@ -235,42 +232,17 @@ class _Channel:
 def _run(ctx, streams, chunk=None, pitch=None, aligned=False):
     """streams (one row of dibits per channel) through a decoder-only engine in pushes of `chunk` symbols; pitch = row pitch
     of the pushed buffer; aligned: the buffer's first row starts at a multiple of 16 bytes (host memory only)"""
-    B, n = len(streams), max(len(s) for s in streams)
-    chunk = n if chunk is None else chunk
-    pitch = max(chunk, 64) if pitch is None else pitch
-    eng = api.Engine(B, pitch, rrc="none", demod="none", proto="ysf", ctx=ctx)
-    out, evs = [[] for _ in range(B)], [[] for _ in range(B)]
-    for lo in range(0, n, chunk):
-        raw = np.zeros(B * pitch + 16, np.uint8)
-        off = (-raw.ctypes.data) & 15 if aligned else 0
-        part = raw[off:off + B * pitch].reshape(B, pitch)
-        cnt = np.zeros(B, np.uint32)
-        for b, s in enumerate(streams):
-            seg = s[lo:lo + chunk]
-            part[b, :len(seg)] = seg; cnt[b] = len(seg)
-        eng.push_symbols(part, cnt)
-        f, fc = eng.frames(); e, ec = eng.events()
-        for b in range(B):
-            out[b].append(f[b, :fc[b]].copy()); evs[b].append(e[b, :ec[b]].copy())
-    eng.close()
-    return [np.concatenate(o) for o in out], [np.concatenate(e) for e in evs]
+    if pitch is None:
+        pitch = max(chunk or max(len(s) for s in streams), 64)
+    return run_symbols(ctx, "ysf", streams, chunk, pitch=pitch, aligned=aligned)
 
 
 def _check(ctx, chans, chunk, pitch=None, aligned=False):
     """push the channels' streams and hold events and output bytes to the model; returns all expected events"""
     lead = np.random.default_rng(5).integers(0, 4, 64).astype(np.uint8)
-    out, evs = _run(ctx, [c.stream(lead) for c in chans], chunk, pitch, aligned)
-    for b, c in enumerate(chans):
-        got, exp = evs[b], c.events()
-        if got.tobytes() != exp.tobytes():
-            for k in range(min(len(got), len(exp))):
-                assert got[k].tobytes() == exp[k].tobytes(), "channel %d push %s frame %d: got %s, reference %s" % (
-                    b, chunk, (int(exp[k]["sym_index"]) - c.lead) // 480, got[k], exp[k])
-            assert len(got) == len(exp), "channel %d push %s: %d events, the reference's results give %d" % (b, chunk, len(got), len(exp))
-        want = c.bytes()
-        if len(out[b]) != len(want) or (out[b] != want).any():
-            k = int(np.nonzero(out[b][:min(len(want), len(out[b]))] != want[:min(len(want), len(out[b]))])[0][:1].sum())
-            assert False, "channel %d push %s: %d output bytes, expected %d; first difference at byte %d" % (b, chunk, len(out[b]), len(want), k)
+    run = _run(ctx, [c.stream(lead) for c in chans], chunk, pitch, aligned)
+    what = ["push %s frame %s" % (chunk, first_differing_frame(got, c.events(), c.lead, 480)) for got, c in zip(run.events, chans)]
+    assert_rows(run, [(c.bytes(), c.events()) for c in chans], what)
     return np.concatenate([c.events() for c in chans])
 
 
@@ -363,9 +335,9 @@ def test_dch_events_vs_reference(ctx, yse, gold, chunk):
     de-whitened bytes; FICH and MODE events and the 40 voice bytes of every frame.  The push sizes make the decode-ahead take
     1, 2, 3, 5, 16 and 16 + 1 frames; 37 symbols a push leaves every frame to a push of its own with most of it carried."""
     n = len(yse["dch_in"])
-    idx = np.arange(n) if _size(ctx, True, False) else np.arange(2, n, 3)
+    idx = np.arange(n) if tier(ctx, True, False) else np.arange(2, n, 3)
     assert sorted(set(yse["dch_src"][idx])) == [0, 1, 2, 3, 4]
-    chans = _dch_channels(yse, gold, idx, _size(ctx, 16, 3))
+    chans = _dch_channels(yse, gold, idx, tier(ctx, 16, 3))
     if chunk in WANT_CHUNKS:
         sizes = set(_chunk_sizes(len(chans[0].rows) * 480 + LEAD + 200, LEAD, chunk))
         assert WANT_CHUNKS[chunk] <= sizes, sizes
@@ -434,22 +406,22 @@ def test_single_dibit_at_every_position_and_alignment(ctx, yse, gold):
     P = _Parts(yse, gold, 34)
     fs, ds = np.nonzero(yse["fichx_src"] == 1)[0], np.nonzero(yse["dch_src"] == 1)[0]
     assert (yse["fichx_pos"][fs] == yse["dch_pos"][ds]).all() and (yse["fichx_pat"][fs] == yse["dch_pat"][ds]).all()
-    keep = np.ones(300, bool) if _size(ctx, True, False) else np.isin(yse["dch_pos"][ds], [0, 13, 14, 15, 16, 17, 18, 86, 87, 88, 89, 90, 91, 92, 95, 99])
+    keep = np.ones(300, bool) if tier(ctx, True, False) else np.isin(yse["dch_pos"][ds], [0, 13, 14, 15, 16, 17, 18, 86, 87, 88, 89, 90, 91, 92, 95, 99])
     pitch = 300 * 480 + 301
     assert pitch % 2 == 1
-    wants = _size(ctx, list(range(16)), [0, 1, 7, 15])
+    wants = tier(ctx, list(range(16)), [0, 1, 7, 15])
     # row b starts b * pitch bytes behind a multiple of 16: a lead-in of (want - b * pitch) & 15 dibits puts the first frame `want`
     # dibits behind one.  (With an odd pitch no 16 rows have both every lead-in and every alignment, so on the GPU 16 more rows
     # take the lead-ins 0..15 in order.)
-    leads = [(want - b * pitch) & 15 for b, want in enumerate(wants)] + _size(ctx, list(range(16)), [])
+    leads = [(want - b * pitch) & 15 for b, want in enumerate(wants)] + tier(ctx, list(range(16)), [])
     chans = []
     for lead in leads:
         c = _Channel(lead)
         for f, d in zip(fs[keep], ds[keep]):
             P.v2_frame(c, P.fichx(f), d)
         chans.append(c)
-    assert {(lead + b * pitch) & 15 for b, lead in enumerate(leads)} >= set(wants) and set(leads) >= set(_size(ctx, range(16), []))
-    exp = _check(ctx, chans, None, pitch=pitch, aligned=_size(ctx, False, True))
+    assert {(lead + b * pitch) & 15 for b, lead in enumerate(leads)} >= set(wants) and set(leads) >= set(tier(ctx, range(16), []))
+    exp = _check(ctx, chans, None, pitch=pitch, aligned=tier(ctx, False, True))
     assert (exp["type"] == EV_FICH).sum() == len(chans) * keep.sum()
     assert (exp["type"] == EV_DCH).sum() == len(chans) * yse["dch_ok"][ds[keep]].sum() < len(chans) * keep.sum()
 
@@ -465,12 +437,12 @@ def test_header_csd_vs_reference(ctx, yse, gold):
     P = _Parts(yse, gold, 35)
     v = yse
     acc, rej = np.nonzero(v["csd_ok"] == 1)[0], np.nonzero(v["csd_ok"] == 0)[0]
-    step = _size(ctx, 1, 12)
+    step = tier(ctx, 1, 12)
     combos = []
     for k in range(0, max(len(acc), len(rej)), step):
         a, a2, r, r2 = acc[k % len(acc)], acc[(k + 7) % len(acc)], rej[k % len(rej)], rej[(k + 5) % len(rej)]
         combos += [(a, a2), (a, r), (r, a), (r, r2)]
-    B = _size(ctx, 8, 2)
+    B = tier(ctx, 8, 2)
     chans, n38 = [], 0
     dch_ok = np.nonzero((v["dch_ok"] == 1) & (v["dch_src"] >= 1))[0]
     for b in range(B):
@@ -506,7 +478,7 @@ def test_header_csd_vs_reference(ctx, yse, gold):
         assert (hd["a"] == 0).sum() == 2 * len(combos) // 4 == (hd["a"] == 1).sum()
         assert {int(b) for b in exp["b"][exp["type"] == EV_META_RESET]} == {1, 2}
     sizes = [sum(len(o) for o in c.out) for c in chans]
-    assert n38 >= _size(ctx, 20, 6) and all(s > 0 for s in sizes)
+    assert n38 >= tier(ctx, 20, 6) and all(s > 0 for s in sizes)
 
 
 # ------------------------------------------------------------------ V/D2 voice blocks
@@ -528,7 +500,7 @@ def test_v2_voice_majority_vote(ctx, yse, gold):
     keeps the two triplets straddling de-interleave rows).  The expected 7 bytes come from the AMBE bits
     given to the encoder and the wrong bits injected, never from a decoder."""
     P = _Parts(yse, gold, 36)
-    cases = _v2_cases(_size(ctx, False, True))
+    cases = _v2_cases(tier(ctx, False, True))
     C = len(cases)
     clean = np.nonzero(yse["dch_src"] == 0)[0]
     chans, seen = [], set()
@@ -570,9 +542,9 @@ def test_v1_and_full_rate_bytes(ctx, yse, gold):
     and mixed; expected bytes straight from the dibits."""
     P = _Parts(yse, gold, 38)
     chans = []
-    for b in range(_size(ctx, 8, 2)):
+    for b in range(tier(ctx, 8, 2)):
         c = _Channel()
-        kinds = [0] * 5 + [3] * 5 + [1] * 3 + list(P.rng.choice([0, 1, 3], _size(ctx, 40, 12)))
+        kinds = [0] * 5 + [3] * 5 + [1] * 3 + list(P.rng.choice([0, 1, 3], tier(ctx, 40, 12)))
         for k, dt in enumerate(kinds):
             c.frame(P.fich(1, int(dt), k + b), P.random_payload())
         chans.append(c)
@@ -592,7 +564,7 @@ def test_sync_count_and_relock(ctx, yse, gold):
     rng = np.random.default_rng(40)
     dch_ok = np.nonzero(yse["dch_ok"] == 1)[0]
     chans = []
-    for b in range(_size(ctx, 6, 2)):
+    for b in range(tier(ctx, 6, 2)):
         c = _Channel()
         plan = [3, 4, 3, 0, 4, 4, 4, 0, 0, 3, 4, 4, 4, 4, 2, 0, 0, 0, 4, 0, 4, 0, 4, 4, 4, 0]
         for k, nwrong in enumerate(plan):
@@ -679,13 +651,9 @@ def test_mixed_streams_walk_the_whole_frame_machine(mixed):
 def test_mixed_streams_match_oracle(ctx, mixed, chunk):
     """the 36 mixed streams (a fixed six of them on the emulation: a loss, scattered errors, the two at the sync limit)
     through decoder-only engines, whole and in pushes of 1000, 481 and 37 symbols: bytes and events equal the oracle's"""
-    pick = _size(ctx, list(range(36)), [0, 1, 2, 3, 4, 11])
+    pick = tier(ctx, list(range(36)), [0, 1, 2, 3, 4, 11])
     streams = [mixed[i][0] for i in pick]
-    out, evs = _run(ctx, streams, chunk)
-    for b, i in enumerate(pick):
-        _, _, want, ev, _ = mixed[i]
-        assert len(out[b]) == len(want) and (out[b] == want).all(), "stream %d push %s: output bytes" % (i, chunk)
-        assert evs[b].tobytes() == ev.tobytes(), "stream %d push %s: events" % (i, chunk)
+    assert_rows(_run(ctx, streams, chunk), [mixed[i][2:4] for i in pick], ["stream %d push %s" % (i, chunk) for i in pick])
 
 
 def test_mixed_stream_through_the_full_chain(ctx, oracle, mixed):
