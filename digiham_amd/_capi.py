@@ -127,6 +127,7 @@ def _signatures():
         "dh_debug_mfma_f16": i(vp, vp, vp, vp, sz, vp),
         "dh_debug_f16_split": i(vp, vp, vp, sz, C.c_float, vp),
         "dh_debug_copy": i(vp, vp, sz, vp),
+        "dh_debug_seam_probe": i(C.c_int, vp, vp, sz, vp), "dh_debug_seam_probe_words": i(C.c_int, P(sz), P(sz)),
         "dh_engine_create": i(P(EngineConfig), P(vp)), "dh_engine_destroy": (None, [vp]),
         "dh_engine_reset": i(vp), "dh_engine_set_slot_filter": i(vp, u32),
         "dh_engine_reset_channel": i(vp, u32), "dh_engine_reset_channels": i(vp, vp), "dh_engine_set_slot_filter_channel": i(vp, u32, u32),
@@ -164,6 +165,14 @@ def _signatures():
         "dh_outpack_device": i(vp, P(vp), P(vp), P(vp), P(vp)),
     }
 
+
+# the ops of dh_debug_seam_probe, in the order of enum dh_probe_op (include/digiham_amd.h)
+PROBE_OPS = {name: i for i, name in enumerate(
+    """VMIN VMAX MIN3_ABS MAX3_ABS MAX_ABS_GROUPS5 MUL_UNIFORM SQRT_UPPER DIV_CONST2 F2_MAC F2_MAC_FAST F2_MAC_PAIR_LO F2_MAC_PAIR_HI
+    F2_MAC_PAIR_FAST_LO F2_MAC_PAIR_FAST_HI F2_FMA F2_SCALE F16_SPLIT4_PLAIN WAVE_MAX WAVE_MAX_NAN WAVE_MIN ROW0_MIN ROW_SUM5_PAIR
+    AGC_SCAN AGC_SCAN_PAIRS LDS_RUN20 LDS_RUN40 LDS_RUN20_WITH_PAIR LDS_PAIRS3_NOW LDS_READS LDS_STORE4_AT LDS_STORE4_AT_PLAIN
+    LDS_STORE_ROW10_0 LDS_STORE_ROW10_1000 LDS_STORE_ROW10_2000 LDS_STORE_ROW10_3000 LDS_STORE_PAIR LDS_STORE_ROWS10_PAIR
+    LV_READ LV_DOWN LS_WRITE_READ LS_GATHER LANES_BELOW STATE BITS""".split())}
 
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = list(SIGNATURES)

@@ -227,6 +227,24 @@ class Context:
         self._call("dh_debug_f16_split", self.mem.ptr(d), self.mem.ptr(h1), self.mem.ptr(h2), n, float(scale), self.mem.stream())
         return self.mem.to_numpy(h1).view(np.float16), self.mem.to_numpy(h2).view(np.float16)
 
+    def seam_probe_words(self, op):
+        """(input words, output words) per case of a seam-probe op (dh_debug_seam_probe_words)."""
+        a, b = C.c_size_t(), C.c_size_t()
+        self._call("dh_debug_seam_probe_words", int(op), C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def debug_seam_probe(self, op, words):
+        """One primitive of the kernels' device / CPU layer run alone (dh_debug_seam_probe): words uint32 [cases][in_words(op)],
+        one wavefront per case; returns uint32 [cases][out_words(op)].  Words the probe does not write come back as 0xA5A5A5A5."""
+        nin, nout = self.seam_probe_words(op)
+        w = np.ascontiguousarray(words, np.uint32)
+        if w.ndim != 2 or w.shape[1] != nin:
+            raise ValueError("Context.debug_seam_probe: op %d takes [cases][%d] words, got %s" % (op, nin, w.shape))
+        d = self.mem.from_numpy(w)
+        out = self.mem.from_numpy(np.full((w.shape[0], nout), 0xA5A5A5A5, np.uint32))
+        self._call("dh_debug_seam_probe", int(op), self.mem.ptr(d), self.mem.ptr(out), w.shape[0], self.mem.stream())
+        return self.mem.to_numpy(out, np.uint32).reshape(w.shape[0], nout)
+
     def dvfilter(self, x, state=None):
         """x: int16 [B][n] numpy; returns (y, state) with state a device array [B][22] to carry on."""
         a = np.ascontiguousarray(x, np.int16)

@@ -25,6 +25,7 @@
 //   int  dh_be_div_gain(const float* in, float* out, size_t n, int narrow, void* stream);
 //   int  dh_be_div_const(const float* in, float* out, size_t n, unsigned divisor, void* stream);
 //   int  dh_be_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* stream);
+//   int  dh_be_seam_probe(int op, const uint32_t* in, uint32_t* out, size_t cases, void* stream);                  (seam_probe_core.hpp)
 // and the other launches of the four later handles, each listed at the head of its section below:
 //   dh_be_cz_window / dh_be_cz_fm / dh_be_cz_power                                         the channelizer
 //   dh_be_preroll_append / dh_be_preroll_gather                                            the pre-roll ring
@@ -193,6 +194,18 @@ int dh_debug_mfma_f16(const uint16_t* a, const uint16_t* b, const float* c, floa
 int dh_debug_f16_split(const float* in, uint16_t* h1, uint16_t* h2, size_t n, float scale, void* s) {
     if ((!in || !h1 || !h2) && n) return DH_EINVAL;
     return dh_be_f16_split(in, h1, h2, n, scale, s);
+}
+int dh_debug_seam_probe_words(int op, size_t* in_words, size_t* out_words) {
+    DhProbeShape w;
+    if (!dh_probe_shape(op, w)) return DH_EINVAL;
+    if (in_words) *in_words = w.in_words;
+    if (out_words) *out_words = w.out_words;
+    return DH_OK;
+}
+int dh_debug_seam_probe(int op, const uint32_t* in, uint32_t* out, size_t cases, void* s) {
+    DhProbeShape w;
+    if (!dh_probe_shape(op, w) || ((!in || !out) && cases)) return DH_EINVAL;
+    return dh_be_seam_probe(op, in, out, cases, s);
 }
 
 int dh_debug_copy(const void* src, void* dst, size_t n_bytes, void* s) {

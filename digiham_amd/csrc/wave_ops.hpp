@@ -136,6 +136,11 @@ DH_HD float dh_sqrt_upper(float x) {
 //   dh_fmin_ / dh_fmax_(a, b)   `if (b < a) a = b`, the reference's own statement: a NaN b is skipped, a NaN a stays
 //   dh_vmin / dh_vmax(a, b)     v_min_f32 / v_max_f32: the operand that is not NaN -- for a NaN ENTRY b exactly what
 //                               `if (v < min) min = v` does -- at one VALU instruction where compare + select cost two
+//                               (a QUIET NaN, that is.  The kernels run in IEEE mode, where v_min_f32 / v_max_f32 / v_min3_f32 and
+//                               their DPP forms answer a SIGNALLING NaN operand with a quiet NaN instead of skipping it -- measured
+//                               through the seam probe on an MI355X: all 115 rows of the operand table with one, none skipped; a
+//                               wave reduction then drops that NaN at its next step, unless the step was the last.  The operands
+//                               here are sums, differences and earlier minima, never raw samples: arithmetic results, quiet.)
 //   dh_min3_abs(a, b, c)        min(|a|, |b|, |c|) in one instruction (v_min3_f32).  Callers that must notice a NaN
 //                               distance make sure ALL THREE are NaN then (they are: every distance of a symbol hangs
 //                               on the same average and extremes) -- see P5
@@ -506,9 +511,9 @@ __device__ __forceinline__ float dh_row_min_to_lane15(float v) {
 }
 #else
 inline float dh_wave_max_lanes(const float (&a)[DH_WAVE][1]) {
-    float m = 0.0f;
-    for (int l = 0; l < DH_WAVE; l++) m = __builtin_fmaxf(m, a[l][0]);
-    return m;
+    float m = 0.0f; bool any = false;
+    for (int l = 0; l < DH_WAVE; l++) { m = __builtin_fmaxf(m, a[l][0]); any |= a[l][0] == a[l][0]; }
+    return any ? m : __builtin_nanf("");
 }
 inline float dh_wave_max_nan_lanes(const float (&a)[DH_WAVE][1]) {
     uint32_t m = 0;
@@ -517,13 +522,18 @@ inline float dh_wave_max_nan_lanes(const float (&a)[DH_WAVE][1]) {
     return r.f;
 }
 inline float dh_wave_min_lanes(const float (&a)[DH_WAVE][1], int lanes) {
-    float m = DH_FLT_MAX;
-    for (int l = 0; l < lanes; l++) m = dh_fmin_(m, a[l][0]);
-    return m;
+    float m = DH_FLT_MAX; bool any = false;
+    for (int l = 0; l < lanes; l++) { m = dh_fmin_(m, a[l][0]); any |= a[l][0] == a[l][0]; }
+    return any ? m : __builtin_nanf("");
 }
 #endif
-// Reductions of a DH_LANE_ARRAY(float, a, 1), wave-uniform results; NaN lanes are skipped, except by DH_WAVE_MAX_NAN:
-//   DH_WAVE_MAX(a)   the largest value of the 64 lanes, of values >= 0 (0 when every lane is NaN)
+// Reductions of a DH_LANE_ARRAY(float, a, 1), wave-uniform results; NaN lanes are skipped, except by DH_WAVE_MAX_NAN.  When EVERY
+// lane they look at is NaN there is nothing to skip to and the three skipping ones give NaN (v_max_f32 / v_min_f32 of two NaNs; until
+// the seam probe ran them alone the restatements gave their seeds, 0 and FLT_MAX, and DH_WAVE_MAX's statement said 0).  No caller
+// depends on it: the sps-10 votes keep lanes that hold no phase at FLT_MAX (dsp_core.hpp: `own`, "lanes 10 .. 15 hold FLT_MAX"),
+// and where all 64 lanes hold phases (a run-time sps of 64 or more) a NaN interval clears its lane's bit in v_ok, which every
+// verdict that looks at the minimum requires to be full.
+//   DH_WAVE_MAX(a)   the largest value of the 64 lanes, of values >= 0
 //   DH_WAVE_MAX_NAN(a)   the same of magnitudes (sign bit clear), but NaN when ANY lane is NaN
 //   DH_WAVE_MIN(a)   the smallest value of the 64 lanes, of values <= FLT_MAX (device: -max(-a), exact)
 //   DH_ROW0_MIN(a)   the smallest value of lanes 0..15, of values <= FLT_MAX

@@ -703,6 +703,74 @@ int dh_debug_f16_split(const float* d_in, uint16_t* d_h1, uint16_t* d_h2, size_t
  * streaming rate, which is what a kernel that mostly reads (the chain kernels) can be priced against. */
 int dh_debug_copy(const void* d_src, void* d_dst, size_t n_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The seam probe: ONE primitive of the kernels' device / CPU layer (dh_portable.hpp, wave_ops.hpp) or one hand-scheduled piece
+ * (dh_agc_scan) run alone, one wavefront per case, on operands the caller chooses.  Not part of any path: the parity tests hold
+ * the device form and its CPU restatement to the primitive's written statement through it (tests/test_seam_primitives.py).
+ *
+ * Case c reads d_in + c * in_words(op) and writes d_out + c * out_words(op) (32-bit words; dh_debug_seam_probe_words).  Input:
+ * four header words (the case's wave-uniform operands, h0 .. h3), then the lanes' words, word i of lane l at [4 + 64 i + l].
+ * Output: word i of lane l at [64 i + l], unless stated.  Floats travel as bit patterns.  L = lane words in -> lane words out.
+ *
+ *   VMIN, VMAX                 L 2 -> 1    dh_vmin / dh_vmax(w0, w1)
+ *   MIN3_ABS, MAX3_ABS         L 3 -> 1    dh_min3_abs / dh_max3_abs(w0, w1, w2)
+ *   MAX_ABS_GROUPS5            L 20 -> 1   dh_max_abs_groups<5>, group g = words 4 g .. 4 g + 3
+ *   MUL_UNIFORM                L 1 -> 1    dh_mul_uniform(h0, w0)
+ *   SQRT_UPPER                 L 1 -> 1    dh_sqrt_upper(w0)
+ *   DIV_CONST2                 L 2 -> 2    dh_div_const2((w0, w1), d = h0, r = h1)
+ *   F2_MAC, F2_MAC_FAST        L 5 -> 2    dh_f2_mac<false / true>(c = w0, w = (w1, w2), acc = (w3, w4))
+ *   F2_MAC_PAIR_LO / _HI, F2_MAC_PAIR_FAST_LO / _HI
+ *                              L 4 -> 2    dh_f2_mac_pair<FAST, HALF>(cc = (h0, h1), w = (w0, w1), acc = (w2, w3))
+ *   F2_FMA                     L 6 -> 2    dh_f2_fma((w0, w1), (w2, w3), (w4, w5))
+ *   F2_SCALE                   L 3 -> 2    dh_f2_scale((w0, w1), w2)
+ *   F16_SPLIT4_PLAIN           L 4 -> 4    dh_f16_split4_plain((w0 .. w3), scale = h0): h1 as two words (halves 0|1, 2|3), then h2
+ *   WAVE_MAX, WAVE_MAX_NAN, WAVE_MIN, ROW0_MIN
+ *                              L 1, ONE output word: the reduction of the lanes' w0
+ *   ROW_SUM5_PAIR              L 2 -> 2    dh_row_sum5_pair(s = w0, q = w1)
+ *   AGC_SCAN, AGC_SCAN_PAIRS   L 10 -> 8   dh_agc_scan<false / true>, h0 = k0, h1 = k1 (k0 < k1 <= 100), h2 = from_win (PAIRS and
+ *                                          k0 = 0 only); w0, w1 = vol_old[l], [64 + l]; w2, w3 = vol_new[l], [64 + l]; w4 .. w9 = the
+ *                                          lane's DhWinPair (vol0, vol1, sum0, sum1, old0, old1).  Out: S.mn[l], S.mn[64 + l], S.mx[l],
+ *                                          S.mx[64 + l] (0xA5A5A5A5 where the scan wrote nothing), then the lane's DhAgcPair
+ *   The LDS movers work on a block of 5 632 words that holds the bits 0x3F000000 + (h0 & 0xFFFF) + i in word i; w0 = the lane's
+ *   base in words (at most 1 720).  A lane's j-th stored value is 0x4B000000 + 64 l + j.
+ *   LDS_RUN20, LDS_RUN40       L 1 -> 20 / 40     dh_lds_run<20 / 40>
+ *   LDS_RUN20_WITH_PAIR        L 2 -> 22          dh_lds_run20_with_pair, the pair at word w1 & ~1: v[0 .. 19], p0, p1
+ *   LDS_PAIRS3_NOW             L 3 -> 6           dh_lds_pairs3_now at w0, w1, w2: a.x, a.y, b.x, b.y, c.x, c.y
+ *   LDS_READS                  L 2 -> 6           ds_read2_b32 at w0; ds_read_b64 at w1 & ~1; two ds_read_b32 at w0, w0 + 1
+ *   LDS_STORE4_AT (_PLAIN)     L 1, out = the block afterwards: dh_lds_store4_at<0, G, 2 G, 3 G, 4 G>, values j = 0 .. 19,
+ *                                                 G = 272 (the padded window) / 256 (_PLAIN)
+ *   LDS_STORE_ROW10_0 / _1000 / _2000 / _3000     L 1, out = the block: dh_lds_store_row10<K>, values j = 0 .. 9
+ *   LDS_STORE_PAIR             L 1, out = the block: dh_lds_store_pair, values 0, 1
+ *   LDS_STORE_ROWS10_PAIR      L 1, out = the block: dh_lds_store_rows10_pair, a = values 0 .. 9, b = values 10 .. 19
+ *   LV_READ                    L 1 -> 1    word k of the output = DH_LV_READ(w0, k)
+ *   LV_DOWN                    L 1 -> 4    DH_LV_DOWN(w0, lane, d) for d = 0, 1, 5, 63
+ *   LS_WRITE_READ              L 4 -> 5    struct (a = w1, b = w2); for k = 0 .. 63: m0 = 0x00A50000 + k, DH_LS_WRITE(a, k, w3 of lane k),
+ *                                          m0 read back, then DH_LV_READ(w0, 63 - k) and DH_LS_READ(a, k).  Out: a afterwards; the
+ *                                          DH_LS_READs (word k); the DH_LV_READs (word k); b; what m0 held behind each write (word k)
+ *   LS_GATHER                  L 3 -> 1    DH_LS_GATHER(a = w1, lane w2 & 63)
+ *   LANES_BELOW                L 0 -> 1    DH_LANES_BELOW(h0 | h1 << 32, lane)
+ *   STATE                      L 2 -> 3    DhState: load(w0); out word 0 of lane k = get(k); eight set(w1 of lane 2 i & 63, w1 of lane
+ *                                          2 i + 1); out word 1 = store(); out word 2 = store_words(first = h0 & 63, n = h1): n words
+ *   BITS                       L 2 -> 5    x = w0 | w1 << 32: dh_brev32(w0), dh_ffs64(x), dh_top64(x) (~0 for x = 0), dh_popc32(w0), dh_popc64(x)
+ *
+ * DH_EINVAL for an op that does not exist; DH_OK for cases == 0.
+ * ---------------------------------------------------------------------- */
+enum dh_probe_op {
+    DH_PROBE_VMIN = 0, DH_PROBE_VMAX, DH_PROBE_MIN3_ABS, DH_PROBE_MAX3_ABS, DH_PROBE_MAX_ABS_GROUPS5, DH_PROBE_MUL_UNIFORM, DH_PROBE_SQRT_UPPER,
+    DH_PROBE_DIV_CONST2, DH_PROBE_F2_MAC, DH_PROBE_F2_MAC_FAST, DH_PROBE_F2_MAC_PAIR_LO, DH_PROBE_F2_MAC_PAIR_HI, DH_PROBE_F2_MAC_PAIR_FAST_LO,
+    DH_PROBE_F2_MAC_PAIR_FAST_HI, DH_PROBE_F2_FMA, DH_PROBE_F2_SCALE, DH_PROBE_F16_SPLIT4_PLAIN,
+    DH_PROBE_WAVE_MAX, DH_PROBE_WAVE_MAX_NAN, DH_PROBE_WAVE_MIN, DH_PROBE_ROW0_MIN, DH_PROBE_ROW_SUM5_PAIR,
+    DH_PROBE_AGC_SCAN, DH_PROBE_AGC_SCAN_PAIRS,
+    DH_PROBE_LDS_RUN20, DH_PROBE_LDS_RUN40, DH_PROBE_LDS_RUN20_WITH_PAIR, DH_PROBE_LDS_PAIRS3_NOW, DH_PROBE_LDS_READS,
+    DH_PROBE_LDS_STORE4_AT, DH_PROBE_LDS_STORE4_AT_PLAIN, DH_PROBE_LDS_STORE_ROW10_0, DH_PROBE_LDS_STORE_ROW10_1000, DH_PROBE_LDS_STORE_ROW10_2000,
+    DH_PROBE_LDS_STORE_ROW10_3000, DH_PROBE_LDS_STORE_PAIR, DH_PROBE_LDS_STORE_ROWS10_PAIR,
+    DH_PROBE_LV_READ, DH_PROBE_LV_DOWN, DH_PROBE_LS_WRITE_READ, DH_PROBE_LS_GATHER, DH_PROBE_LANES_BELOW, DH_PROBE_STATE, DH_PROBE_BITS,
+    DH_PROBE_OP_COUNT
+};
+int dh_debug_seam_probe(int op, const uint32_t* d_in, uint32_t* d_out, size_t cases, void* stream);
+/* words per case of an op (host only; either pointer may be NULL) */
+int dh_debug_seam_probe_words(int op, size_t* in_words, size_t* out_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import re
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "digiham_amd", "csrc")
 LAYER = ("dh_portable.hpp", "wave_ops.hpp")
-CORE = tuple(sorted(f for f in os.listdir(CSRC) if f.endswith("_core.hpp")))      # all ten; what is left of DH_DEVICE_BUILD in them stands at namespace scope, around a CPU restatement
+CORE = tuple(sorted(f for f in os.listdir(CSRC) if f.endswith("_core.hpp")))      # all eleven; what is left of DH_DEVICE_BUILD in them stands at namespace scope, around a CPU restatement
 
 
 def _code_lines(text):

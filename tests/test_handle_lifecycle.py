@@ -122,7 +122,8 @@ SYMBOLS = [
     "dh_bch_31_21", "dh_bptc_196_96", "dh_channelizer_create", "dh_channelizer_destroy", "dh_channelizer_phasor",
     "dh_channelizer_power_enable", "dh_channelizer_power_last", "dh_channelizer_push", "dh_channelizer_push_host",
     "dh_channelizer_reset", "dh_channelizer_retune", "dh_channelizer_set_squelch", "dh_copy_to_device", "dh_copy_to_host", "dh_crc16",
-    "dh_debug_copy", "dh_debug_div_const", "dh_debug_div_gain", "dh_debug_f16_split", "dh_debug_mfma_f16", "dh_device_alloc",
+    "dh_debug_copy", "dh_debug_div_const", "dh_debug_div_gain", "dh_debug_f16_split", "dh_debug_mfma_f16", "dh_debug_seam_probe",
+    "dh_debug_seam_probe_words", "dh_device_alloc",
     "dh_device_count", "dh_device_free", "dh_dvfilter_s16", "dh_engine_create", "dh_engine_debug_header", "dh_engine_destroy",
     "dh_engine_events", "dh_engine_filtered", "dh_engine_frames", "dh_engine_push", "dh_engine_push_host", "dh_engine_push_host_ragged",
     "dh_engine_push_ragged", "dh_engine_push_symbols", "dh_engine_read_events", "dh_engine_read_filtered", "dh_engine_read_frames",
