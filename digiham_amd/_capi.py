@@ -17,6 +17,9 @@ PROTO = {"none": 0, None: 0, "dmr": 1, "ysf": 2, "nxdn": 3, "pocsag": 4, "dstar"
 FLAG_FAST_FIR, FLAG_KEEP_FILTERED, FLAG_FSK_INVERT, FLAG_NO_EVENTS, FLAG_ORDERED_TIMING, FLAG_SPLIT_STAGES = 1, 2, 4, 8, 16, 32
 FLAG_EXACT_SYMBOLS, FLAG_EXACT_FIR, FLAG_OVERLAP_PUSHES, FLAG_ONE_LAUNCH = 64, 128, 256, 512
 FLAG_DMR_BOTH_SLOTS = 0x400
+FLAG_CALL_DIGEST = 0x800                   # DH_FLAG_CALL_DIGEST: the event rows leave as call records ("Call digest", include/digiham_amd.h)
+EV_CALL = 96                               # DH_EV_CALL
+CALL_RECORD_BYTES = {"dmr": 16, "nxdn": 8, "ysf": 21}
 DMR_SLOT_RECORD_BYTES = 28                 # DH_DMR_SLOT_RECORD_BYTES: 27 payload bytes and the slot
 
 
@@ -102,6 +105,10 @@ class DhError(RuntimeError):
         names = {-1: "DH_EINVAL", -2: "DH_ENOMEM", -3: "DH_EDEVICE", -4: "DH_ENODEV", -5: "DH_ECAPACITY"}
         super().__init__("%s failed: %s %s" % (what, names.get(code, code), detail))
         self.code = code
+
+
+class DhInvalid(DhError, ValueError):
+    """a DH_EINVAL that names the Python arguments that caused it"""
 
 
 def _signatures():

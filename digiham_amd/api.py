@@ -79,6 +79,43 @@ def parse_lc(payload):
             "source": d[6] << 16 | d[7] << 8 | d[8], "data": d[2:9]}
 
 
+_CALL_SYNC = {"dmr": (None, "data", "voice", "unknown"), "nxdn": (None, "voice")}
+_CALL_TYPE = {"dmr": (None, "group", "direct"), "nxdn": (None, "conference", "individual")}
+_YSF_MODE = (None, "V1", "FR data", "DN", "VW")
+
+
+def _ysf_string(raw):
+    """ten raw bytes cut at the first blank or newline (treatYsfString, ysf_phase.cpp:351-361); nothing left: None"""
+    raw = bytes(raw)
+    for c in (b"\n", b" "):
+        at = raw.find(c)
+        if at >= 0:
+            raw = raw[:at]
+    return raw.decode("latin-1") if raw.strip(b"\0") else None
+
+
+def parse_call(proto, event):
+    """The call record an EV_CALL event carries (DH_FLAG_CALL_DIGEST; include/digiham_amd.h, "Call digest"), as a dict.
+    "dmr": {"changed": (slot, ...) from the event's `a`, "slots": [per slot {"sync", "type", "source", "target"}]};
+    "nxdn": {"changed": (0,), "sync", "type", "source", "destination"}; "ysf": {"changed": (0,), "mode", "target", "source"},
+    the strings cut at the first blank or newline as treatYsfString does.  A field of zeros reads as None, and so does a DMR
+    slot whose record is all zeros."""
+    if int(event["type"]) != _capi.EV_CALL or int(event["len"]) != _capi.CALL_RECORD_BYTES[proto]:
+        raise ValueError("parse_call: not a %s EV_CALL event: type %d, len %d" % (proto, int(event["type"]), int(event["len"])))
+    d = bytes(bytearray(event["payload"]))
+    changed = tuple(i for i in range(2) if int(event["a"]) >> i & 1)
+    num = lambda b: int.from_bytes(b, "big") or None
+    name = lambda table, i: table[i] if i < len(table) else "unknown"
+    if proto == "dmr":
+        return {"changed": changed, "slots": [{"sync": name(_CALL_SYNC["dmr"], d[8 * s]), "type": name(_CALL_TYPE["dmr"], d[8 * s + 1]),
+                                               "source": num(d[8 * s + 2:8 * s + 5]), "target": num(d[8 * s + 5:8 * s + 8])}
+                                              if any(d[8 * s:8 * s + 8]) else None for s in range(2)]}
+    if proto == "nxdn":
+        return {"changed": changed, "sync": name(_CALL_SYNC["nxdn"], d[0]), "type": name(_CALL_TYPE["nxdn"], d[1]),
+                "source": num(d[2:4]), "destination": num(d[4:6])}
+    return {"changed": changed, "mode": name(_YSF_MODE, d[0]), "target": _ysf_string(d[1:11]), "source": _ysf_string(d[11:21])}
+
+
 def _check(rc, what, lib):
     if rc != 0:
         raise DhError(rc, what, lib.dh_last_error().decode(errors="replace"))
@@ -301,23 +338,33 @@ class Engine(_Handle):
 
     def __init__(self, n_channels, max_samples, rrc="wide", demod="gfsk", sps=10, proto="dmr", fast_fir=False,
                  keep_filtered=False, invert=False, events=True, slot_filter=3, ctx=None, device=0, ordered_timing=False, split_stages=False,
-                 taps=None, gain=None, exact_symbols=False, exact_fir=False, overlap_pushes=False, one_launch=False, dmr_both_slots=False):
+                 taps=None, gain=None, exact_symbols=False, exact_fir=False, overlap_pushes=False, one_launch=False, dmr_both_slots=False,
+                 call_digest=False):
         """rrc = "custom" takes the caller's coefficient table: `taps` (nZeros + 1 floats, any shape) and `gain`, as
         Digiham::RrcFilter::RrcFilter(nZeros, gain, coeffs[]) does (include/rrc_filter.hpp:12).
         dmr_both_slots (proto "dmr" only): the voice of both timeslots leaves as 28-byte slot-tagged records
-        (DH_FLAG_DMR_BOTH_SLOTS; dmr_split_slots takes them apart)."""
+        (DH_FLAG_DMR_BOTH_SLOTS; dmr_split_slots takes them apart).
+        call_digest (proto "dmr", "ysf" or "nxdn", with events, without overlap_pushes; anything else is the library's DH_EINVAL,
+        raised as a DhError that is a ValueError too): every push ends with the k_call_digest launch, and events() are the
+        digested rows -- an EV_CALL where the channel's call record changed (parse_call), the pass-through events, nothing else
+        (DH_FLAG_CALL_DIGEST; include/digiham_amd.h, "Call digest")."""
         flags = (_capi.FLAG_FAST_FIR if fast_fir else 0) | (_capi.FLAG_KEEP_FILTERED if keep_filtered else 0) | \
                 (_capi.FLAG_FSK_INVERT if invert else 0) | (0 if events else _capi.FLAG_NO_EVENTS) | \
                 (_capi.FLAG_ORDERED_TIMING if ordered_timing else 0) | (_capi.FLAG_SPLIT_STAGES if split_stages else 0) | \
                 (_capi.FLAG_EXACT_SYMBOLS if exact_symbols else 0) | (_capi.FLAG_EXACT_FIR if exact_fir else 0) | \
                 (_capi.FLAG_OVERLAP_PUSHES if overlap_pushes else 0) | (_capi.FLAG_ONE_LAUNCH if one_launch else 0) | \
-                (_capi.FLAG_DMR_BOTH_SLOTS if dmr_both_slots else 0)
+                (_capi.FLAG_DMR_BOTH_SLOTS if dmr_both_slots else 0) | (_capi.FLAG_CALL_DIGEST if call_digest else 0)
         custom = dict(struct_size=_capi.EngineConfig.rrc_taps.offset)     # the layout before the custom-filter fields: every library version takes it
         if rrc == "custom":
             t = np.ascontiguousarray(taps, np.float32).ravel()                # copied by dh_engine_create
             custom = dict(rrc_taps=t.ctypes.data_as(C.POINTER(C.c_float)), rrc_nzeros=len(t) - 1, rrc_gain=float(gain))
-        self._open(ctx, device, _capi.EngineConfig, n_channels=n_channels, max_samples=max_samples, rrc=_capi.RRC[rrc],
-                   demod=_capi.DEMOD[demod], sps=sps, proto=_capi.PROTO[proto], flags=flags, slot_filter=slot_filter, **custom)
+        try:
+            self._open(ctx, device, _capi.EngineConfig, n_channels=n_channels, max_samples=max_samples, rrc=_capi.RRC[rrc],
+                       demod=_capi.DEMOD[demod], sps=sps, proto=_capi.PROTO[proto], flags=flags, slot_filter=slot_filter, **custom)
+        except DhError as e:
+            if call_digest and e.code == _capi.DH_EINVAL:
+                raise _capi.DhInvalid(e.code, "Engine(call_digest=True, proto=%r, events=%r, overlap_pushes=%r)" % (proto, events, overlap_pushes)) from None
+            raise
         self.B, self.max_samples = n_channels, max_samples
         self.has_demod, self.has_proto = _capi.DEMOD[demod] != 0, _capi.PROTO[proto] != 0
         self.keep_filtered = (keep_filtered or rrc == "custom") and _capi.RRC[rrc] != 0
@@ -748,6 +795,9 @@ class Monitor(_Handle):
     dmr_both_slots=True: the DMR engine is created with it, and the `frames` of a "dmr" block are 28-byte slot-tagged
     records (dmr_split_slots) -- both calls of a two-slot channel instead of the one that holds the decoder's output.
 
+    call_digest=True: the DMR, YSF and NXDN engines are created with it; the `events` of their blocks are the digested rows
+    (Engine; parse_call reads an EV_CALL).
+
     on_close=None | "default" (CLOSE_DEFAULT) | {family: (hits, dist)}: naming on close.  In the round in which an
     unassigned channel closes, before its scanner state is reset, H = the sum of `hits` and D = the smallest `best_dist`
     over each family's patterns are read from scanner.stats().  A family with hits != 0, H >= hits and D <= dist is
@@ -762,7 +812,8 @@ class Monitor(_Handle):
     evidence stays below its family's thresholds; under CLOSE_DEFAULT, NXDN is never named on close."""
 
     def __init__(self, n_channels, max_samples, depth=96000, lead=480, confirm=2, release=4,
-                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, dmr_both_slots=False, on_close=None):
+                 protos=("dmr", "ysf", "nxdn", "dstar", "pocsag"), ctx=None, device=0, dmr_both_slots=False, on_close=None,
+                 call_digest=False):
         self._resolve(ctx, device)
         self.B, self.max_samples, self.depth = int(n_channels), int(max_samples), int(depth)
         self.lead, self.confirm, self.release = int(lead), int(confirm), int(release)
@@ -774,7 +825,7 @@ class Monitor(_Handle):
         self.stage = self.ctx.mem.zeros((self.B, self.max_samples), np.float32)
         for p in self.protos:
             self.engines[p] = Engine(self.B, self.max_samples, proto=p, ctx=self.ctx, dmr_both_slots=bool(dmr_both_slots) and p == "dmr",
-                                     **SCAN_FRONTS[PROTO_FRONT[p]])
+                                     call_digest=bool(call_digest) and p in _capi.CALL_RECORD_BYTES, **SCAN_FRONTS[PROTO_FRONT[p]])
         self._clear()
 
     def _clear(self):

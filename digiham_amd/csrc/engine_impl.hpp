@@ -52,6 +52,10 @@ inline int make_layout(const dh_engine_config& c, Layout& L) {
     if (c.demod != DH_DEMOD_NONE && c.demod != DH_DEMOD_FSK2 && c.demod != DH_DEMOD_GFSK4) return DH_EINVAL;
     if (c.proto < DH_PROTO_NONE || c.proto > DH_PROTO_SCAN) return DH_EINVAL;
     if ((c.flags & DH_FLAG_DMR_BOTH_SLOTS) && c.proto != DH_PROTO_DMR) return DH_EINVAL;
+    // the call digest folds the events of the three protocols whose identity is a handful of numbers; it rewrites the event row
+    // behind the push's last launch on the engine's stream, so it needs the row and one stream
+    if ((c.flags & DH_FLAG_CALL_DIGEST) && ((c.proto != DH_PROTO_DMR && c.proto != DH_PROTO_YSF && c.proto != DH_PROTO_NXDN) ||
+                                            (c.flags & (DH_FLAG_NO_EVENTS | DH_FLAG_OVERLAP_PUSHES)))) return DH_EINVAL;
     if (c.demod != DH_DEMOD_NONE && (c.sps < 3 || c.sps > DH_MAX_SPS)) return DH_EINVAL;
     if (c.demod == DH_DEMOD_NONE && c.rrc == DH_RRC_NONE && c.proto == DH_PROTO_NONE) return DH_EINVAL;
     L.B = c.n_channels; L.max_samples = c.max_samples; L.sps = c.demod ? c.sps : 1;
@@ -119,6 +123,7 @@ inline void fill_taps(int rrc, P& p) {
 //   dh_be_rrc_generic(be, const DhRrcGenParams&);
 //   dh_be_rrc_hist(be, float* hist, const float* in, size_t in_stride, uint32_t n, const uint32_t* n_per, uint32_t nz, uint32_t B);
 //   dh_be_decoder(be, const DhDecParams&, int proto);
+//   dh_be_call_digest(be, const DhDigestParams&, int proto);                   (digest_core.hpp)
 //   dh_be_init_state(be, uint32_t* dsp_state, size_t state_words, uint32_t tail0, uint32_t* dec_state, uint32_t slot_filter, uint32_t B);
 //   dh_be_set_slot_filter(be, uint32_t* dec_state, uint32_t filter, uint32_t B);
 // and dh_be_reset_channels(BE&, const DhResetChannels&) (a barrier inside: engine.hip has the gfx950 one, monitor_core.hpp
@@ -179,7 +184,7 @@ struct Engine {
     DhFecTables* tables = nullptr;
     uint32_t last_n = 0;
     // kernel arguments: what the configuration fixes is filled once (configure()), a push adds its input and its counts
-    DhDspParams dsp{}; DhRrcParams rrcp{}; DhRrcGenParams gen{}; DhDecParams dec{};
+    DhDspParams dsp{}; DhRrcParams rrcp{}; DhRrcGenParams gen{}; DhDecParams dec{}; DhDigestParams dig{};
     bool fast = false;                                           // DH_FLAG_FAST_FIR (with fused_keep: which floats the one launch delivers)
     float* custom_taps = nullptr;                                // DH_RRC_CUSTOM: device copy of the caller's table
     uint32_t* tapfrag = nullptr;                                 // split-f16 FIR of the wide filter: per-lane tap fragments (dh_f16_tap_fragments)
@@ -269,6 +274,8 @@ struct Engine {
         dec.out = frames; dec.out_stride = L.out_cap; dec.out_cap = L.out_cap; dec.out_count = frame_count;
         dec.events = events; dec.ev_stride = L.ev_cap; dec.ev_cap = L.ev_cap; dec.ev_count = ev_count;
         dec.overflow = overflow; dec.T = tables; dec.n_channels = L.B;
+        dig.events = events; dig.ev_stride = L.ev_cap; dig.ev_cap = L.ev_cap; dig.ev_count = ev_count;
+        dig.state = dec_state; dig.state_stride = DH_DEC_STATE_WORDS; dig.n_channels = L.B;
         const char* scalar_b = getenv("DH_DMR_SCALAR_PASS_B");         // "1": the DMR decoder's pass B burst by burst for every chunk (A/B runs, tests)
         dec.dmr_scalar_pass_b = scalar_b && atoi(scalar_b) > 0 ? 1u : 0u;
     }
@@ -370,6 +377,8 @@ struct Engine {
         }
         be.timing_mark(2);
         if (L.proto && L.demod && !decoder_done) rc |= dh_be_decoder(be, dec, L.proto);
+        // DH_FLAG_CALL_DIGEST: behind the push's last launch (the chain, its fix-up launch, or the decoder's own)
+        if (L.flags & DH_FLAG_CALL_DIGEST) rc |= dh_be_call_digest(be, dig, L.proto);
         be.timing_mark(3);
         be.timing_next();
         return rc ? DH_EDEVICE : DH_OK;
@@ -393,7 +402,9 @@ struct Engine {
         if (!L.proto || L.demod || !d_syms || !d_count) return DH_EINVAL;
         last_counts = nullptr;
         dec.syms = d_syms; dec.sym_stride = stride; dec.sym_count = d_count;
-        return dh_be_decoder(be, dec, L.proto) ? DH_EDEVICE : DH_OK;
+        int rc = dh_be_decoder(be, dec, L.proto);
+        if (L.flags & DH_FLAG_CALL_DIGEST) rc |= dh_be_call_digest(be, dig, L.proto);
+        return rc ? DH_EDEVICE : DH_OK;
     }
 
     int check_overflow() {

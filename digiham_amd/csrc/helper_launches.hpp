@@ -5,8 +5,8 @@
 // launcher that states the grid that wrapper assumes, the empty-launch early-out and the stream.  Both are compiled by both
 // builds and end in dh_launch (the launch vocabulary: dh_portable.hpp), so the index maps, grid clamps and grid-stride loops
 // below are what the CPU tests execute.  The helper kernels of a handle stand in the same form at the end of the core header
-// that owns their bodies (kernels_core.hpp, channelizer_core.hpp, preroll_core.hpp, monitor_core.hpp, outpack_core.hpp,
-// seam_probe_core.hpp);
+// that owns their bodies (kernels_core.hpp, digest_core.hpp, channelizer_core.hpp, preroll_core.hpp, monitor_core.hpp,
+// outpack_core.hpp, seam_probe_core.hpp);
 // these here have no such header, and their launches need the two hooks below from the build that includes them.
 //
 // Not written once: the kernels whose device form needs barriers over LDS staging, matrix-core tiles or wave votes (k_chain,

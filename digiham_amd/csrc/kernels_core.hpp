@@ -9,6 +9,7 @@
 #include "channelizer_core.hpp"
 #include "preroll_core.hpp"
 #include "decoder_core.hpp"
+#include "digest_core.hpp"
 
 // ---- engine state initialisation: what the reference's constructors leave behind ------------
 DH_HD void dh_init_state_channel(uint32_t* dsp_state, size_t state_words, uint32_t tail0,

@@ -155,6 +155,57 @@ enum { DH_PROTO_NONE = 0, DH_PROTO_DMR = 1, DH_PROTO_YSF = 2, DH_PROTO_NXDN = 3,
  * ---------------------------------------------------------------------- */
 #define DH_DMR_SLOT_RECORD_BYTES 28
 
+#define DH_FLAG_CALL_DIGEST     0x800 /* proto DH_PROTO_DMR, DH_PROTO_YSF or DH_PROTO_NXDN only, and neither with DH_FLAG_NO_EVENTS nor with
+                                         DH_FLAG_OVERLAP_PUSHES (DH_EINVAL otherwise, before anything is allocated): every push ends with one more
+                                         launch, k_call_digest, that folds the channel's events into its call record and rewrites the event row in
+                                         place ("Call digest" below).  Off: the raw events, no extra launch, allocation or state word. */
+
+/* ----------------------------------------------------------------------
+ * Call digest (DH_FLAG_CALL_DIGEST).  Own specification; the updates are those of the reference's MetaCollectors on their
+ * identity fields (src/dmr_decoder/dmr_meta.cpp:11-179 with its call sites dmr_phase.cpp:80, :109-114, :178-184, :196-202,
+ * :279-282, :304-339 and lc.cpp:26-43; src/nxdn_decoder/nxdn_meta.cpp:52-75 with nxdn_phase.cpp:51, :115-121, :141, :157;
+ * src/ysf_decoder/ysf_meta.cpp:47-93 with ysf_phase.cpp:73-163, :270-287), as include/digiham/{dmr,nxdn,ysf}_meta.hpp replay them.
+ *
+ * Records.  Every channel owns one call record in its decoder state.  It is zero after create and after any reset
+ * (dh_engine_reset, _reset_channel, _reset_channels); a reset raises no event.
+ *   DMR, 16 bytes, slot s at bytes [8 s, 8 s + 8): byte 0 sync (0 none, 1 data, 2 voice, 3 any other sync type), byte 1 type
+ *     (0 none, 1 group, 2 direct), bytes 2-4 source, bytes 5-7 target (24 bits each, big endian).
+ *   NXDN, 8 bytes: byte 0 sync (0 none, 1 voice), byte 1 type (0 none, 1 conference, 2 individual), bytes 2-3 source, bytes
+ *     4-5 destination (big endian), bytes 6-7 zero.
+ *   YSF, 21 bytes: byte 0 mode (0 none, otherwise 1 + (b & 3) of the MODE event), bytes 1-10 target, bytes 11-20 source (the
+ *     ten raw bytes as carried).
+ *
+ * Fold.  The raw events of a push are visited in row order; each applies one update.
+ *   DMR, s = a & 1.  SYNC: sync of s = b (1, 2; anything else: 3), and if len > 0 && payload[0], type, source and target of s
+ *     become 0.  SLOT_RESET (either b): all four fields of s become 0.  META_RESET: both slots become 0.  SOFT_RESET: type,
+ *     source and target of s become 0.  LC with len >= 9 and opcode group (0) or unit-to-unit (3): type = 1 or 2, target =
+ *     payload bytes 3-5, source = payload bytes 6-8 (Digiham::Dmr::Lc).  Every other event leaves the record alone.
+ *   NXDN.  SYNC_VOICE: sync = 1.  SACCH_SF with len >= 9 and (payload[0] & 0x3F) == 1 (VCALL): type from payload[2] >> 5
+ *     (1 conference -> 1, 4 individual -> 2, others 0), source = payload bytes 3-4, destination = bytes 5-6.  META_RESET: all 0.
+ *   YSF.  MODE: mode = 1 + (b & 3).  DCH with len >= 10: a = 0 sets target = payload[0, 10), a = 1 sets source.  HEADER_DCH with
+ *     len >= 20 and a = 0: target = payload[0, 10), source = payload[10, 20).  META_RESET: all 0.
+ *
+ * Output.  Every raw event yields at most one output event at its place, order kept (a stable compaction):
+ *   - the update changed a byte of the record: one DH_EV_CALL event, sym_index the raw event's, a = which parts changed (DMR:
+ *     bit s for slot s, so a META_RESET may give 3; NXDN and YSF: 1), b = 0, len = 16, 8 or 21, payload = the whole record
+ *     after the update, 0 beyond len;
+ *   - otherwise the event is copied bit for bit if it is a pass-through event -- DMR: LC whose opcode is a talker-alias block
+ *     or GPS info (4 .. 8: LC_TALKER_ALIAS_HDR .. LC_GPS_INFO of include/digiham/lc.hpp); YSF: DCH with a >= 2, HEADER_DCH with
+ *     a = 1; NXDN: none;
+ *   - otherwise it is dropped (EMB, SLOTTYPE, BPTC, FICH, LICH, SACCH fragments, FACCH1, and every event that repeats what the
+ *     record already says).
+ *
+ * Properties.  The new count never exceeds the old one (row capacities are unchanged); no byte beyond the new count is
+ * defined.  Concatenated over a stream, the digested events do not depend on how the stream is cut into pushes: the record
+ * carries over.  A row the decoder truncated (DH_ECAPACITY) is digested as far as it was kept.  Frames, symbols, statistics
+ * and the slot filter are untouched.  Combines freely with DH_FLAG_DMR_BOTH_SLOTS, DH_FLAG_SPLIT_STAGES and decoder-only
+ * engines (dh_engine_push_symbols); dh_engine_events, dh_engine_read_events and dh_outpack_append see the digested row.
+ * (dh_monitor creates its engines itself and has no field for the flag: its configuration struct keeps its size.)
+ * ---------------------------------------------------------------------- */
+#define DH_CALL_RECORD_DMR_BYTES 16
+#define DH_CALL_RECORD_NXDN_BYTES 8
+#define DH_CALL_RECORD_YSF_BYTES 21
+
 typedef struct {
     uint32_t struct_size;     /* = sizeof(dh_engine_config) */
     int32_t  device;          /* HIP device ordinal */
@@ -214,7 +265,10 @@ enum {
     DH_EV_DSTAR_HEADER = 64, DH_EV_DSTAR_VOICE_START = 65, DH_EV_DSTAR_SYNC_VOICE = 66, DH_EV_DSTAR_MESSAGE = 67,
     DH_EV_DSTAR_SIMPLE = 68, DH_EV_DSTAR_FRAME_SYNC = 69, DH_EV_DSTAR_META_RESET = 70,
     /* protocol scan: a sync pattern found (sym_index = its first symbol, a = DH_SCAN_* pattern, b = distance, len = 0) */
-    DH_EV_SCAN_HIT = 80
+    DH_EV_SCAN_HIT = 80,
+    /* call digest (DH_FLAG_CALL_DIGEST): the channel's call record changed (a = parts changed, len = 16 / 8 / 21 for DMR / NXDN /
+     * YSF, payload = the record after the change) */
+    DH_EV_CALL = 96
 };
 
 /* ----------------------------------------------------------------------
