@@ -40,7 +40,10 @@ class ChannelizerConfig(C.Structure):
 class ChannelizerPowerConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("block", C.c_uint32), ("open_level", C.c_float), ("close_level", C.c_float),
                 ("hang_blocks", C.c_uint32), ("d_power", C.c_void_p), ("d_gate", C.c_void_p), ("d_counts", C.c_void_p),
-                ("stride", C.c_size_t)]
+                ("stride", C.c_size_t), ("d_ferr", C.c_void_p)]
+
+
+CHANNELIZER_POWER_CONFIG_V1_SIZE = ChannelizerPowerConfig.d_ferr.offset      # DH_CHANNELIZER_POWER_CONFIG_V1_SIZE
 
 
 class PrerollConfig(C.Structure):

@@ -1185,6 +1185,18 @@ def raster_bins(freqs_hz, input_rate, raster_hz):
     return bins
 
 
+def frequency_error_hz(ferr, gate, output_rate):
+    """Per channel, how far off its channel the carrier sits, in Hz: the median of ferr * output_rate / 2 over the columns
+    whose gate byte is 1, NaN where there is none.  ferr, gate: host arrays [B][n] (Channelizer.ferr_blocks() and
+    power_blocks() of one or more pushes, copied to the host).  The value to subtract is what Channelizer.retune takes:
+    retune(ch, channel frequency + error)."""
+    f = np.asarray(ferr, np.float64) * (float(output_rate) / 2.0)
+    g = np.asarray(gate) == 1
+    if f.ndim != 2 or f.shape != g.shape:
+        raise ValueError("frequency_error_hz: ferr %s and gate %s must be [B][n] both" % (f.shape, g.shape))
+    return np.array([np.median(row[m]) if m.any() else np.nan for row, m in zip(f, g)], np.float64)
+
+
 class Channelizer(_Handle):
     """One wideband complex stream -> one row per channel at input_rate * interpolation / decimation (dh_channelizer; the
     arithmetic is specified in digiham_amd/csrc/channelizer_core.hpp).  interpolation is 1 unless the capture rate is no
@@ -1198,7 +1210,8 @@ class Channelizer(_Handle):
     same bank for about n_taps / K times less matrix work; needs interpolation = 1.  Without it (the general case) each
     channel may sit anywhere.
     enable_power(...) adds per-channel block power and a squelch gate: after every push `counts` (device uint32 [B]) is what
-    Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed."""
+    Engine.push(rows, n=n_out, counts=cz.counts) takes, and power_blocks() the blocks that push completed; with ferr=True
+    also ferr_blocks(), how far off its channel each carrier sits (frequency_error_hz)."""
     _kind = "dh_channelizer"
 
     def __init__(self, input_rate, decimation, freqs_hz, taps, input="cs16", output="fm", dcblock=True, max_input=1 << 20,
@@ -1223,26 +1236,28 @@ class Channelizer(_Handle):
         self.out_stride = self.max_input * self.L // self.D + 1
         self.rows = mem.zeros((self.B, self.out_stride) if output == "fm" else (self.B, self.out_stride, 2), np.float32)
         self._keep = None
-        self.block, self.power, self.gate, self.counts = 0, None, None, None
+        self.block, self.power, self.gate, self.counts, self.ferr = 0, None, None, None, None
 
     @staticmethod
     def _level(db):
         return 0.0 if db is None else float(10.0 ** (float(db) / 10.0))
 
-    def enable_power(self, block=480, open_db=None, close_db=None, hang_blocks=0):
+    def enable_power(self, block=480, open_db=None, close_db=None, hang_blocks=0, ferr=False):
         """Block power over `block` outputs and the squelch gate (before the first push, or right after reset()).  Levels in dB
         relative to |z|^2 = 1 -- a full-scale CS16 tone through unity-gain taps is 0 dB; None: level 0.0 (with both None
-        every channel passes: power only)."""
+        every channel passes: power only).  ferr: also the frequency-error blocks (ferr_blocks(), frequency_error_hz)."""
         mem, block = self.ctx.mem, int(block)
         if block < 1:
             raise DhError(_capi.DH_EINVAL, "dh_channelizer_power_enable", "block < 1")
         stride = self.out_stride // block + 1
         power, gate = mem.zeros((self.B, stride), np.float32), mem.zeros((self.B, stride), np.uint8)
         counts = mem.zeros((self.B,), np.uint32)
+        fe = mem.zeros((self.B, stride), np.float32) if ferr else None
         cfg = _capi.ChannelizerPowerConfig(C.sizeof(_capi.ChannelizerPowerConfig), block, self._level(open_db), self._level(close_db),
-                                           int(hang_blocks), mem.ptr(power), mem.ptr(gate), mem.ptr(counts), stride)
+                                           int(hang_blocks), mem.ptr(power), mem.ptr(gate), mem.ptr(counts), stride,
+                                           mem.ptr(fe) if ferr else None)
         self._call("dh_channelizer_power_enable", C.byref(cfg))
-        self.block, self.power, self.gate, self.counts = block, power, gate, counts
+        self.block, self.power, self.gate, self.counts, self.ferr = block, power, gate, counts, fe
 
     def set_squelch(self, open_db, close_db, hang_blocks):
         self._call("dh_channelizer_set_squelch", self._level(open_db), self._level(close_db), int(hang_blocks))
@@ -1252,6 +1267,15 @@ class Channelizer(_Handle):
         first, n = C.c_uint64(0), C.c_size_t(0)
         self._call("dh_channelizer_power_last", C.byref(first), C.byref(n))
         return self.power[:, :n.value], self.gate[:, :n.value], first.value
+
+    def ferr_blocks(self):
+        """(ferr[:, :n], first_block) of the last push, a device array: column i is block first_block + i, in units of half
+        the output rate (frequency_error_hz).  Needs enable_power(ferr=True)."""
+        first, n = C.c_uint64(0), C.c_size_t(0)
+        self._call("dh_channelizer_power_last", C.byref(first), C.byref(n))
+        if self.ferr is None:
+            raise DhError(_capi.DH_EINVAL, "Channelizer.ferr_blocks", "enable_power(ferr=True) first")
+        return self.ferr[:, :n.value], first.value
 
     def reset(self):
         self._call("dh_channelizer_reset")

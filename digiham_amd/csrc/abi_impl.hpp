@@ -312,12 +312,16 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
     DhCzPowerParams pw{};                               // what power_enable() and set_squelch() fix; a push adds its outputs and its position
     uint32_t* d_pstate = nullptr;                       // [B][DH_CZ_PSTATE_WORDS]
     uint64_t pw_first = 0; size_t pw_n = 0;             // blocks completed by the last push
+    // frequency-error blocks (d_ferr of the power configuration); fe.ferr = null: off, nothing allocated and nothing launched
+    DhCzFerrParams fe{};
+    float* d_fstate = nullptr;                          // [B][2][4]: two copies of a channel's (Ar, Ai, z[j-1])
+    uint32_t fe_copy = 0;                               // the copy the next launch reads; it writes the other one
 
     size_t in_bytes() const { return cf32 ? 8u : 4u; }
     uint64_t outputs(uint64_t n) const { return (uint64_t) L * n / D; }         // outputs that exist after n input samples
     size_t bank() const { return (size_t) 2 * tpad * ncols; }
     int clear() {
-        cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0;
+        cur = 0; prev_n = 0; n0 = 0; pw_first = 0; pw_n = 0; fe_copy = 0;
         return bufs.zero_all() ? DH_EDEVICE : DH_OK;
     }
     // a channel's word from the caller's value: the increment, or (a two's-complement int32) the bin reduced into [0, K)
@@ -414,7 +418,10 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         return DH_OK;
     }
     int power_enable(const dh_channelizer_power_config& c) {
-        if (c.struct_size < sizeof(dh_channelizer_power_config) || c.block < 1 || c.block > 65536 || !c.d_power || !c.d_gate || !c.d_counts ||
+        // d_ferr was appended to the struct: a caller built against the older header passes the older size, and the field is
+        // then not read
+        const bool v1 = c.struct_size == DH_CHANNELIZER_POWER_CONFIG_V1_SIZE;
+        if ((!v1 && c.struct_size != sizeof(dh_channelizer_power_config)) || c.block < 1 || c.block > 65536 || !c.d_power || !c.d_gate || !c.d_counts ||
             c.stride < ((size_t) outputs(max_input) + 1) / c.block + 1 || n0 != 0)
             return DH_EINVAL;
         const int rc = set_squelch(c.open_level, c.close_level, c.hang_blocks);
@@ -422,6 +429,11 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         const size_t words = (size_t) DH_CZ_PSTATE_WORDS * B;
         if (!d_pstate && !bufs.alloc(d_pstate, words, dh::ZERO_PER_CHANNEL)) return DH_ENOMEM;
         if (be.zero(d_pstate, sizeof(uint32_t) * words)) return DH_EDEVICE;
+        float* d_ferr = v1 ? nullptr : c.d_ferr;
+        const size_t fwords = (size_t) DH_CZ_FSTATE_WORDS * B;
+        if (d_ferr && !d_fstate && !bufs.alloc(d_fstate, fwords, dh::ZERO_PER_CHANNEL)) return DH_ENOMEM;
+        if (d_ferr && be.zero(d_fstate, sizeof(float) * fwords)) return DH_EDEVICE;
+        fe.ferr = d_ferr; fe.stride = c.stride; fe.B = B; fe.L = c.block; fe.fm = fm; fe_copy = 0;
         pw.pstate = d_pstate; pw.power = c.d_power; pw.gate = c.d_gate; pw.counts = c.d_counts; pw.stride = c.stride;
         pw.B = B; pw.L = c.block; pw.fm = fm; pw.inv = (float) (1.0 / (double) c.block);
         pw_first = 0; pw_n = 0;
@@ -434,7 +446,14 @@ struct dh_channelizer : dh_state {                      // (clear() and retune()
         pw.n_blocks = (uint32_t) ((j0 + no) / pw.L - j0 / pw.L);
         pw.nseg = no ? (uint32_t) (((uint64_t) pw.pos0 + no + pw.L - 1) / pw.L) : 0u;
         pw_first = j0 / pw.L; pw_n = pw.n_blocks;
-        return dh_be_cz_power(pw, stream) ? DH_EDEVICE : DH_OK;
+        if (dh_be_cz_power(pw, stream)) return DH_EDEVICE;
+        if (!fe.ferr || !no) return DH_OK;
+        // the frequency-error blocks of the same segments, from one copy of the state into the other
+        fe.z = pw.z; fe.z_stride = out_stride; fe.pos0 = pw.pos0; fe.n_out = no; fe.nseg = pw.nseg;
+        fe.fin = d_fstate + 4u * fe_copy; fe.fout = d_fstate + 4u * (fe_copy ^ 1u);
+        if (dh_be_cz_ferr(fe, stream)) return DH_EDEVICE;
+        fe_copy ^= 1u;
+        return DH_OK;
     }
     int push(const void* in, size_t n_in, float* out, size_t out_stride, size_t* n_out, bool host) {
         if (!n_out) return DH_EINVAL;

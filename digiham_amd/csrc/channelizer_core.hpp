@@ -122,6 +122,36 @@
 // segment in order and writes either a power value or the carried S; (6) dh_cz_gate_channel, one channel per lane: the
 // recurrence over the blocks this push completed, the gate bytes, counts[b] and the state.
 //
+// ---- Frequency-error blocks (optional; d_ferr of dh_channelizer_power_enable).  The specification; tests/cz_ferr_restate.c
+// restates it from this text alone.  Everything not mentioned is as for block power: blocks are indexed by the global output
+// index j since create / reset, so push boundaries do not move block boundaries. ----
+//   ABI       dh_channelizer_power_config ends in float* d_ferr ([n_channels][stride], the caller's device memory, like
+//             d_power).  struct_size = DH_CHANNELIZER_POWER_CONFIG_V1_SIZE (the struct up to d_ferr): the field is not read,
+//             whatever bytes follow, and the feature is off.  struct_size = the whole struct: d_ferr = NULL is off.  Every other
+//             struct_size is DH_EINVAL.  Off means off: nothing more is allocated, launched or written than without the field.
+//   w         for output j of channel b with p = z_b[j-1]:  a = zr pr, c = zi pi, d = zi pr, e = zr pi;  wr = a + c,
+//             wi = d - e -- what dh_cz_fm_item computes, every product and sum rounded.  z is the rotated output, the same value
+//             in both output modes and in all three kinds of bank; z[-1] = 0 after create and reset.
+//   Chains    Ar and Ai start at +0 at the beginning of every block; Ar = Ar + wr[j], Ai = Ai + wi[j] in increasing j: ONE
+//             chain each, no split accumulators, no tree.  A push that ends inside a block leaves (Ar, Ai) and z[j] in the
+//             channel's state and the next push continues the same chains.
+//   Value     when output (m + 1) L - 1 has been added: ferr[b][m] = dh_fe_atan2f_over_pi(Ai, Ar) (frontend_core.hpp);
+//             (0, 0) -> 0, infinities and NaN propagate as its operations have them.  The unit is half the output rate:
+//             Hz = ferr * output_rate / 2.  Column i of d_ferr after a push is block first_block + i of
+//             dh_channelizer_power_last, as for d_power.  It is the |z|^2-weighted mean frequency of the block: strong
+//             samples dominate, and an empty channel gives noise around 0.
+//   Retune    of channel b zeroes its Ar, Ai and carried z.  The block in progress keeps its index; its value is the chain
+//             over the outputs after the retune.  Reset zeroes everything and keeps the configuration.
+//   Carried z the stage keeps its own previous z in both modes (in IQ mode nothing writes words 0 and 1 of the FM state, and
+//             in FM mode dh_cz_tail_channel has overwritten them with this push's last z before this stage runs).
+//   Power     power, gate, counts, the rows and dh_channelizer_power_last are byte for byte what they are without d_ferr.
+// Work per push with d_ferr set and outputs completed, after (5) and (6): (7) dh_cz_ferr_segment, one lane per (channel, block
+// segment of this push) with dh_cz_power_segment's item map and loads.  The state is [B][2][4] floats: two copies of
+// (Ar, Ai, z re, z im) per channel, so that DeviceBuffers::zero_row clears exactly channel b's eight words; a push
+// reads one copy and writes the other, the host alternating them by the parity of the pushes that launched the stage: the
+// lane of segment 0 reads the carried words in the same launch in which the lane of the last segment writes the new ones,
+// and nothing orders the two.  A push with no outputs launches nothing and keeps the parity.
+//
 // Work per push (host code in abi_impl.hpp): (1) dh_cz_window_item -- the window [H = T'-1 history samples ++ the new ones]
 // as complex floats; (2) the GEMM + rotation, tiled over 128 output instants x 64 channels (k_cz_gemm; host body
 // dh_cz_output); FM mode then (3) dh_cz_fm_item, one output per lane, and (4) dh_cz_tail_channel, one channel per lane:
@@ -139,6 +169,7 @@
 #define DH_CZ_TBITS 12            // the two phasor tables: 4096 entries each
 #define DH_CZ_STATE_WORDS 4       // per channel: z[j-1] (re, im), x_prev, y_prev of the DC blocker
 #define DH_CZ_PSTATE_WORDS 4      // per channel, only with power enabled (an array of its own): S (float bits), open, quiet, S of this push
+#define DH_CZ_FSTATE_WORDS 8      // per channel, only with d_ferr set (an array of its own): two copies of (Ar, Ai, z[j-1] re, im)
 #define DH_CZ_MAX_L 64            // interpolation: phases of a rational rate
 #define DH_CZ_MAX_RASTER 16384    // raster: K, the steps per input rate
 #define DH_CZ_MAX_FOLD_P 64       // raster: T <= 64 K ...
@@ -436,6 +467,81 @@ DH_HD void dh_cz_gate_channel(const DhCzPowerParams& P, uint32_t b) {
     P.counts[b] = any ? P.n_out : 0u;
 }
 
+// ---- frequency-error blocks (the specification in the header comment) ---------------------------------------------------
+struct DhCzFerrParams {
+    const float* z;               // as in DhCzPowerParams
+    size_t z_stride;
+    const float* fin;             // the state copy this push reads: channel b's (Ar, Ai, z[j-1] re, im) at fin + b DH_CZ_FSTATE_WORDS
+    float* fout;                  // ... and the copy it writes, the same way
+    float* ferr;                  // [B][stride]: column i = block first + i of this push
+    size_t stride;
+    uint32_t pos0;                // j0 mod L
+    uint32_t n_out, nseg, B, L;
+    int fm;
+};
+
+// output z after p = z[j-1]: w = z conj(p) as in dh_cz_fm_item, added to the two chains; z is the next output's p
+DH_HD void dh_cz_ferr_step(float zr, float zi, float& pr, float& pi, float& Ar, float& Ai) {
+    const float a = zr * pr, c = zi * pi, d = zi * pr, e = zr * pi;
+    const float wr = a + c, wi = d - e;
+    Ar = Ar + wr; Ai = Ai + wi;
+    pr = zr; pi = zi;
+}
+
+// segment s of channel b, the rows [r0, r1) of the push as in dh_cz_power_segment; its first p is the carried z (s = 0) or
+// row r0 - 1 of this push.  The products do not depend on the chains: the loads and they run ahead of the dependent adds.
+DH_HD void dh_cz_ferr_segment(const DhCzFerrParams& P, uint32_t b, uint32_t s) {
+    const uint32_t end = (s + 1u) * P.L - P.pos0;                       // row after the block's last output
+    const uint32_t r0 = s ? s * P.L - P.pos0 : 0u, r1 = dh_min(end, P.n_out);
+    float Ar = 0.0f, Ai = 0.0f, pr = 0.0f, pi = 0.0f;
+    if (s == 0u) {
+        const DhCzF4 c = *(const DhCzF4*) (P.fin + (size_t) b * DH_CZ_FSTATE_WORDS);
+        if (P.pos0) { Ar = c.v[0]; Ai = c.v[1]; }
+        pr = c.v[2]; pi = c.v[3];
+    }
+    uint32_t r = r0;
+    if (P.fm) {                   // lanes on consecutive channels: 8-byte loads, 512 contiguous bytes per wave instruction
+        const size_t step = 2 * (size_t) P.B;
+        const float* p = P.z + 2 * ((size_t) r0 * P.B + b);
+        if (s) { const DhCzF2 v = *(const DhCzF2*) (p - step); pr = v.v[0]; pi = v.v[1]; }
+        for (; r + 8 <= r1; r += 8, p += 8 * step) {                    // eight loads in flight ahead of the chains
+            DhCzF2 v[8];
+            for (int e = 0; e < 8; e++) v[e] = *(const DhCzF2*) (p + e * step);
+            for (int e = 0; e < 8; e++) dh_cz_ferr_step(v[e].v[0], v[e].v[1], pr, pi, Ar, Ai);
+        }
+        for (; r < r1; r++, p += step) { const DhCzF2 v = *(const DhCzF2*) p; dh_cz_ferr_step(v.v[0], v.v[1], pr, pi, Ar, Ai); }
+    } else {                      // each lane along its own contiguous segment of its row
+        const float* p = P.z + 2 * ((size_t) b * P.z_stride + r0);
+        const bool al8 = ((uintptr_t) p & 7u) == 0;
+        if (s) {
+            if (al8) { const DhCzF2 v = *(const DhCzF2*) (p - 2); pr = v.v[0]; pi = v.v[1]; }
+            else { pr = p[-2]; pi = p[-1]; }
+        }
+        if (al8) {
+            if (((uintptr_t) p & 8u) && r < r1) { const DhCzF2 v = *(const DhCzF2*) p; dh_cz_ferr_step(v.v[0], v.v[1], pr, pi, Ar, Ai); r++; p += 2; }
+            for (; r + 16 <= r1; r += 16, p += 32) {                    // eight 16-byte loads in flight: one 128-byte line
+                DhCzF4 v[8];
+                for (int e = 0; e < 8; e++) v[e] = *(const DhCzF4*) (p + 4 * e);
+                for (int e = 0; e < 8; e++) { dh_cz_ferr_step(v[e].v[0], v[e].v[1], pr, pi, Ar, Ai); dh_cz_ferr_step(v[e].v[2], v[e].v[3], pr, pi, Ar, Ai); }
+            }
+            for (; r + 2 <= r1; r += 2, p += 4) {
+                const DhCzF4 v = *(const DhCzF4*) p;
+                dh_cz_ferr_step(v.v[0], v.v[1], pr, pi, Ar, Ai); dh_cz_ferr_step(v.v[2], v.v[3], pr, pi, Ar, Ai);
+            }
+        }
+        for (; r < r1; r++, p += 2) dh_cz_ferr_step(p[0], p[1], pr, pi, Ar, Ai);           // the last output, or rows that are only 4-byte aligned
+    }
+    const bool complete = end <= P.n_out;
+    if (complete) P.ferr[(size_t) b * P.stride + s] = dh_fe_atan2f_over_pi(Ai, Ar);
+    // The carry goes to the other copy of the state (fout), never to the one the lane of segment 0 reads in this same launch
+    // (fin): nothing orders the two lanes.  The host swaps the copies for the next push.
+    if (s + 1u == P.nseg) {
+        DhCzF4 c;
+        c.v[0] = complete ? 0.0f : Ar; c.v[1] = complete ? 0.0f : Ai; c.v[2] = pr; c.v[3] = pi;
+        *(DhCzF4*) (P.fout + (size_t) b * DH_CZ_FSTATE_WORDS) = c;
+    }
+}
+
 // ---- host side: the phasor tables and the rotated taps (computed once per create / retune, then uploaded) ---------------
 // coarse ++ fine, [2][4096][2] floats
 inline const float* dh_cz_host_tables() {
@@ -551,4 +657,25 @@ static int dh_be_cz_fm(const float* zbuf, float* state, float* out, size_t out_s
 static int dh_be_cz_power(const DhCzPowerParams& P, void* stream) {
     if (P.nseg && dh_launch(k_cz_power, dim3(grid_for((size_t) P.B * P.nseg, 256)), dim3(256), 0, stream, "k_cz_power", P)) return DH_EDEVICE;
     return dh_launch(k_cz_gate, dim3((P.B + DH_WAVE - 1) / DH_WAVE), dim3(DH_WAVE), 0, stream, "k_cz_gate", P) ? DH_EDEVICE : DH_OK;
+}
+
+// ---------------------------------------------------------------- frequency-error blocks (after the launches above: they
+// stay the text they were)
+namespace {
+
+// one lane per (channel, block segment of this push), k_cz_power's item map: FM mode lanes on consecutive channels of zbuf,
+// IQ mode lanes on consecutive segments of one channel's row
+__global__ __launch_bounds__(256) void k_cz_ferr(const DhCzFerrParams P) {
+    const size_t n = (size_t) P.B * P.nseg;
+    for (size_t t = (size_t) blockIdx.x * 256u + threadIdx.x; t < n; t += (size_t) gridDim.x * 256u) {
+        const uint32_t b = (uint32_t) (P.fm ? t % P.B : t / P.nseg), s = (uint32_t) (P.fm ? t / P.B : t % P.nseg);
+        dh_cz_ferr_segment(P, b, s);
+    }
+}
+
+}  // namespace
+
+// only for a push with outputs (nseg != 0)
+static int dh_be_cz_ferr(const DhCzFerrParams& P, void* stream) {
+    return dh_launch(k_cz_ferr, dim3(grid_for((size_t) P.B * P.nseg, 256)), dim3(256), 0, stream, "k_cz_ferr", P) ? DH_EDEVICE : DH_OK;
 }

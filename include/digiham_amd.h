@@ -480,7 +480,22 @@ typedef struct {
     uint8_t*  d_gate;              /* [n_channels][stride] */
     uint32_t* d_counts;            /* [n_channels] */
     size_t   stride;               /* >= (max_input * L / decimation + 1) / block + 1 */
+    float*    d_ferr;              /* [n_channels][stride] frequency-error blocks (below); NULL: off */
 } dh_channelizer_power_config;
+/* Frequency-error blocks (optional; bit for bit specified in channelizer_core.hpp): how far off its channel a carrier sits.
+ * d_ferr was appended to the struct.  struct_size = DH_CHANNELIZER_POWER_CONFIG_V1_SIZE (a caller built against the older
+ * header): the field is not read, whatever bytes follow, and the feature is off.  struct_size = sizeof(the struct): d_ferr =
+ * NULL is off -- nothing more is allocated, launched or written than before -- and otherwise every push that completes
+ * outputs launches one more kernel, and column i of d_ferr is block *first_block + i of dh_channelizer_power_last, as for
+ * d_power.  Any other struct_size is DH_EINVAL.
+ * Value: with w[j] = z[j] conj(z[j-1]) (the discriminator's product, z[-1] = 0 after create / reset), Ar and Ai the in-order
+ * sums of re w and im w over the block from +0, ferr = atan2(Ai, Ar) / pi with dh_frontend_s16's polynomial; (0, 0) -> 0.
+ * The unit is half the output rate: Hz = ferr * output_rate / 2.  It is the |z|^2-weighted mean frequency of the block:
+ * strong samples dominate, an empty channel gives noise around 0.  The same value in both output modes and all three kinds
+ * of bank.  A push that ends inside a block carries (Ar, Ai) and its last z; a retune zeroes the channel's sums and carried z
+ * (the block in progress keeps its index and holds the outputs after the retune); a reset zeroes all of them.  Power, gate,
+ * counts and the rows are byte for byte what they are without d_ferr. */
+#define DH_CHANNELIZER_POWER_CONFIG_V1_SIZE offsetof(dh_channelizer_power_config, d_ferr)
 int  dh_channelizer_power_enable(dh_channelizer* c, const dh_channelizer_power_config* cfg);
 /* new levels and hang from the next push on; the gates' state is kept.  DH_EINVAL before the enable */
 int  dh_channelizer_set_squelch(dh_channelizer* c, float open_level, float close_level, uint32_t hang_blocks);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/channelizer_rate.py [--out FILE] [--pushes K] [--config a|b|c|c-short|all] [--interpolation L] [--power L]
-[--lib PATH --tag NAME] [--raster]: throughput of dh_channelizer on cuda:0.
+[--ferr] [--lib PATH --tag NAME] [--raster]: throughput of dh_channelizer on cuda:0.
 
 Configurations, taps = api.channel_taps(rate, D, 6.5 kHz, 12 kHz, 60 dB):
   (a) 2.4 MS/s CS16, D = 50, 192 channels on a 12.5 kHz raster, 10 s of input per push;
@@ -20,6 +20,12 @@ and in "fm" + DC-blocker mode (+ the discriminator and the recurrence).  Reporte
 the real-time factor, and the GEMM's TFLOP/s counted as 8 B T' n_out over the whole push, with its fraction of the
 157.3 TF f32 matrix peak.  One JSON line per (config, mode).  --power L adds the modes "iq+power" and "fm+power": the same
 with block power over L outputs and the gate enabled (k_cz_power reads 8 bytes per output and channel once more; k_cz_gate).
+--ferr (with --power L) adds "iq+ferr" and "fm+ferr": power and the frequency-error blocks (k_cz_ferr reads the same bytes
+again).  The lines of profiles/channelizer_ferr_rate.jsonl ("Frequency-error blocks measured"): the
+feature off against the parent in ONE process, run(...) of this file called in turn with the parent's and the new library
+(tags parent_1, new_1, parent_2, new_2; configuration a, iq and fm), then --config all --power 480 --ferr --modes "" --tag on;
+the kernel times: rocprofv3 --kernel-trace --stats -- python tools/channelizer_rate.py --config all --power 480 --ferr
+--modes "", in a run of its own.
 --lib PATH times another build of the library (tools/build_variant.sh) instead of the package's, --tag labels its lines.
 --raster (configurations a and b: their channels sit on 12.5 kHz steps, K = rate / 12.5 kHz) times every (config, mode) four
 times in this process, alternating: fixed offsets, raster, fixed offsets, raster (tags fixed_1, raster_1, fixed_2,
@@ -66,6 +72,8 @@ def run(name, c, mode, pushes, warmup=2, power=0, ctx=None, tag=None, raster_hz=
     cz = api.Channelizer(rate, D, freqs, h, input="cs16", output=mode, dcblock=(mode == "fm"), max_input=n, ctx=ctx, **rational)
     if label.endswith("+power"):
         cz.enable_power(block=power, open_db=-40.0, close_db=-43.0, hang_blocks=2)
+    if label.endswith("+ferr"):
+        cz.enable_power(block=power, open_db=-40.0, close_db=-43.0, hang_blocks=2, ferr=True)
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randint(-2000, 2000, (n, 2), generator=g, device="cuda", dtype=torch.int32).to(torch.int16)
     times = []
@@ -82,7 +90,7 @@ def run(name, c, mode, pushes, warmup=2, power=0, ctx=None, tag=None, raster_hz=
     flop = 8.0 * B * tpad * n_out
     tf = flop / (ms * 1e-3) / 1e12
     extra = {"tag": tag} if tag else {}
-    if label.endswith("+power"):
+    if label.endswith("+power") or label.endswith("+ferr"):
         extra.update(block=power, power_read_mb=round(8.0 * B * n_out / 1e6, 1))
     if L > 1:
         extra.update(L=L)
@@ -106,7 +114,10 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--tag", default=None)
     ap.add_argument("--raster", action="store_true")
+    ap.add_argument("--ferr", action="store_true")
     a = ap.parse_args()
+    if a.ferr and not a.power:
+        ap.error("--ferr needs --power L: the frequency-error blocks are the power blocks")
     names = ["a", "b"] if a.config == "all" else [a.config]
     if a.raster and (a.interpolation > 1 or any(CONFIGS[n].get("L", 1) > 1 for n in names)):
         ap.error("--raster needs interpolation = 1: configurations a and b, no --interpolation")
@@ -115,7 +126,7 @@ def main():
     if a.lib:
         from digiham_amd import _capi, api
         ctx = api.Context(lib=_capi.load(a.lib))
-    modes = [m for m in a.modes.split(",") if m] + (["iq+power", "fm+power"] if a.power else [])
+    modes = [m for m in a.modes.split(",") if m] + (["iq+power", "fm+power"] if a.power else []) + (["iq+ferr", "fm+ferr"] if a.ferr else [])
     for name in names:
         for mode in modes:
             cfg = dict(CONFIGS[name], L=a.interpolation) if a.interpolation else CONFIGS[name]
